@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s (pixels x spp) of the radiance integrator on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config C]
+  python bench.py --gpus N --steps K --warmup W [--config C] [--full] [--dump-outputs DIR]
   (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, config).
+Everything else it can measure or check (per-launch kernel times and the two rooflines, the machine probes, all_in_flight,
+cpu_baseline, the plausibility guard on the frame) runs only with --full.  --dump-outputs DIR writes what the timed steps
+computed after they end: DIR/frame.npy, the (H, W, 3) float32 radiance sum of the K passes that rank 0 assembles (DIR/tiles.npy,
+this rank's tile buffer, under --emulate-world).  An output above 48 MiB (configs[4]'s 2160p frame) is written as a fixed, seeded
+sample of its pixels with their indices (DIR/<name>_rows.npy, float64).  Scene, camera and per-pass seeds depend only on the arguments.
 
 Workload (default --config 2) = BASELINE.json configs[2], the configuration the metric is quoted on: Cornell room
 + 69,564-triangle "bunny" stand-in with the specular-reflection BRDF, 1920x1080, NEE on, the reference's camera.
@@ -14,12 +21,12 @@ A STEP is one full-frame PASS of the hot path: every pixel of the frame runs `sp
 submitted in render calls of AT MOST the config's own pass count (configs[2]: 8), back to back — the shape PathTracer::Render
 has: its NUM_MULTI_SAMPLE passes are all a render call can keep in flight.  --steps 20 is therefore 8 + 8 + 4 (the line says
 so: config.render_calls); the figure for all K passes submitted as ONE call (more streams in flight than the config can have)
-is measured after the timed region and reported separately as all_in_flight, never as value.  With N GPUs the
+is measured after the timed region (--full) and reported separately as all_in_flight, never as value.  With N GPUs the
 frame's 8x8 tiles are dealt round-robin to the ranks (total work fixed -> "strong" scaling); after the K timed steps
 the finished tiles are gathered to rank 0 with ONE collective (RCCL over xGMI) and de-interleaved — that exchange is
 inside the timed region.  value = W*H*spp_per_pass*K / seconds / 1e6, whole job, inputs resident in HBM.
 
-Also on the JSON line:
+Also on the JSON line, with --full:
   roofline     — for the dominant kernel (wf_trace, the traversal kernel).  The kernel is bound by vector-ALU issue,
                  not by HBM (no dense contraction -> no MFMA; its working set is cache resident), so the roofline is a
                  VALU one: achieved = lane-operations per second = (active-lane VALU instructions per sample, from the
@@ -150,6 +157,24 @@ def load_pmc(config):
     return None
 
 
+DUMP_BYTES_MAX = 48 << 20       # all files of one --dump-outputs together (npy headers aside); 1080p frames fit whole
+
+
+def dump_output(out_dir, name, t):
+    """Write the float32 device tensor t as out_dir/<name>.npy.  Above DUMP_BYTES_MAX it is cut to rows of its last axis and a fixed,
+    seeded sample of those rows is written instead, with their indices as out_dir/<name>_rows.npy (float64: exact)."""
+    import numpy as np
+    a = t.cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    if a.nbytes > DUMP_BYTES_MAX:
+        rows = a.reshape(-1, a.shape[-1])
+        k = DUMP_BYTES_MAX // (rows.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], k, replace=False))
+        np.save(os.path.join(out_dir, name + "_rows.npy"), idx.astype(np.float64))
+        a = rows[idx]
+    np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -163,7 +188,12 @@ def main():
     ap.add_argument("--rank", type=int, default=0)
     ap.add_argument("--all-in-flight", action="store_true", help="submit all --steps passes as ONE render call (more passes in flight than the config has; not the config's shape)")
     ap.add_argument("--no-all-in-flight-extra", action="store_true", help="skip the extra all-in-flight measurement after the timed region")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: per-launch kernel times "
+                    "and rooflines, machine probes, all_in_flight, cpu_baseline, the plausibility guard on the frame")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed steps computed to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[args.config]
     W, H = cfg["W"], cfg["H"]
     spp = args.spp or cfg["spp"]
@@ -239,8 +269,9 @@ def main():
             gather_tiles(warm.tiles if backend == "nccl" else warm.tiles.cpu(), rank, world)
         del warm
     barrier()
-    scene.render_timings(reset=True)
-    scene.enable_trace_timing(16384)         # HIP events around every wf_trace and wf_shade launch, on the launch stream
+    if args.full:
+        scene.render_timings(reset=True)
+        scene.enable_trace_timing(16384)     # HIP events around every wf_trace and wf_shade launch, on the launch stream
     t_sum_ms = t_max_ms = s_sum_ms = s_max_ms = 0.0
     t_launches = s_launches = iters = 0
     t0 = time.perf_counter()
@@ -248,10 +279,11 @@ def main():
         t.render()
         if i > 0:
             trs[0].tiles.add_(t.tiles)
-        # per-launch kernel times of this call (reading the events blocks only on work that has already drained)
-        a, n, m = scene.trace_timing(); t_sum_ms += a; t_launches += n; t_max_ms = max(t_max_ms, m)
-        a, n, m = scene.shade_timing(); s_sum_ms += a; s_launches += n; s_max_ms = max(s_max_ms, m)
-        iters += int(scene.last_iterations())
+        if args.full:
+            # per-launch kernel times of this call (reading the events blocks only on work that has already drained)
+            a, n, m = scene.trace_timing(); t_sum_ms += a; t_launches += n; t_max_ms = max(t_max_ms, m)
+            a, n, m = scene.shade_timing(); s_sum_ms += a; s_launches += n; s_max_ms = max(s_max_ms, m)
+            iters += int(scene.last_iterations())
     tiles = trs[0].tiles
     if world > 1 and backend != "nccl":                      # rehearsal: gloo gathers host tensors
         g = gather_tiles(tiles.cpu(), rank, world)
@@ -266,7 +298,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    kern_ms = scene.render_timings(reset=True)
+    if args.dump_outputs and rank == 0:
+        dump_output(args.dump_outputs, "tiles" if args.emulate_world else "frame", tiles if args.emulate_world else frame)
 
     if rank == 0:
         samples = float(W) * H * spp * args.steps           # whole job
@@ -285,103 +318,105 @@ def main():
         if args.emulate_world:
             out["emulated"] = {"world": args.emulate_world, "rank": args.rank, "seconds": dt,
                                "note": "only this rank's share of the tile split was rendered, on one GPU; value = that share's samples / its time"}
-        roof = {"kernel": "wf_trace", "bound": "valu", "unit": "Glane-op/s", "peak": VALU_PEAK_GLOPS,
-                "achieved": None, "frac": None, "traffic": None}
-        roof_s = {"kernel": "wf_shade", "bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS, "achieved": None, "frac": None, "traffic": None}
-        pmc = load_pmc(args.config)
-        pmc_src = None
-        if pmc:
-            pmc_src = "%s (%s)" % (pmc.get("_path"), pmc.get("collected_with", ""))
-        if t_launches > 0:
-            k_ms = t_sum_ms / t_launches
-            spl = call_samples / t_launches                      # samples' worth of rays one launch advances
-            roof.update({"kernel_ms_avg": k_ms, "kernel_ms_max": t_max_ms, "launches_timed": int(t_launches), "kernel_ms_sum": t_sum_ms,
-                         "samples_per_launch": spl, "bounce_iterations": iters,
-                         "pipeline_ms_per_step": (float(np.sum(kern_ms)) / args.steps) if len(kern_ms) else None})
-            k = (pmc or {}).get("kernels", {}).get("wf_trace")
-            if k:
-                lane_ops = k["valu_lane_ops_per_sample"] * spl           # per launch
-                roof["achieved"] = lane_ops / (k_ms * 1e-3) / 1e9
-                roof["frac"] = roof["achieved"] / VALU_PEAK_GLOPS
-                roof["valu_lane_ops_per_sample"] = k["valu_lane_ops_per_sample"]
-                roof["valu_lane_utilisation"] = k.get("valu_lane_utilisation")
-                roof["valu_issue_frac"] = (k["valu_insts_per_sample"] * spl * 64.0 / (k_ms * 1e-3) / 1e9) / VALU_PEAK_GLOPS
-                roof["traffic"] = k["hbm_bytes_per_sample"] * spl         # HBM-side bytes per launch (fabric requests; Infinity-Cache hits included)
-                roof["hbm_frac"] = roof["traffic"] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-                roof["l2_hit_rate"] = k.get("l2_hit_rate")
-                roof["pmc_source"] = pmc_src
-                # the counters are per-sample figures from a separate profiled run; say what that run was next to what this one is
-                roof["pmc_samples_profiled"] = pmc.get("samples_profiled"); roof["pmc_note"] = pmc.get("note")
-                roof["live"] = {"spp_per_pass": spp, "steps": args.steps}
-            # algorithmic bytes of the REFERENCE traversal (40 B per node fetched + 36 B per triangle test, counted
-            # by the instrumented oracle on this scene and frame) over this kernel's time.  Not a bandwidth: see the docstring.
-            try:
-                tc = json.load(open(os.path.join(ROOT, "tests", "golden", "traversal_counters.json")))[cfg["counters"]]
-                bps = (40.0 * tc["nodes_fetched"] + 36.0 * tc["tri_tests"]) / tc["paths"]
-                eff = spl * bps / (k_ms * 1e-3) / 1e9
-                out["vs_reference_algorithm"] = {"reference_traversal_bytes_per_sample": bps, "effective_GBps": eff,
-                                                 "ratio_to_hbm_peak": eff / HBM_PEAK_GBS,
-                                                 "note": "speed-up over a bandwidth-perfect execution of the reference's traversal "
-                                                         "(brute force on degenerate rays, camera ray re-traced per sample); not a bandwidth"}
-            except (KeyError, OSError):
-                pass
-        if s_launches > 0:
-            ks_ms = s_sum_ms / s_launches
-            spl_s = call_samples / s_launches
-            roof_s.update({"kernel_ms_avg": ks_ms, "kernel_ms_max": s_max_ms, "launches_timed": int(s_launches), "kernel_ms_sum": s_sum_ms,
-                           "samples_per_launch": spl_s})
-            # every wf_shade* kernel of the profiled run (the schedule variants are separate kernels), per sample
-            ks = [v for n, v in (pmc or {}).get("kernels", {}).items() if n.startswith("wf_shade") and "hbm_bytes_per_sample" in v]
-            if ks:
-                bps = sum(v["hbm_bytes_per_sample"] for v in ks)
-                lops = sum(v.get("valu_lane_ops_per_sample", 0.0) for v in ks)
-                insts = sum(v.get("valu_insts_per_sample", 0.0) for v in ks)
-                roof_s["traffic"] = bps * spl_s                              # HBM-side bytes per launch
-                roof_s["achieved"] = roof_s["traffic"] / (ks_ms * 1e-3) / 1e9
-                roof_s["frac"] = roof_s["achieved"] / HBM_PEAK_GBS
-                roof_s["hbm_bytes_per_sample"] = bps
-                roof_s["valu_lane_ops_per_sample"] = lops
-                roof_s["valu_lane_utilisation"] = (lops / (64.0 * insts)) if insts else None
-                roof_s["valu_frac"] = lops * spl_s / (ks_ms * 1e-3) / 1e9 / VALU_PEAK_GLOPS
-                roof_s["pmc_source"] = pmc_src
-        if not args.no_probes:
-            try:
-                roof["hbm_peak_measured_triad_GBps"] = ptamd.triad_gbps(1 << 30, 10, dev.index or 0)
-                r, g = ptamd.valu_rate(0, 4, 20000, dev.index or 0)
-                roof["valu_peak_measured"] = {"op": "v_fma_f32, 4 waves/SIMD", "Glane_op_per_s": r * 64 / 1e9, "clock_ghz": g,
-                                              "clocks_per_wave_inst_per_simd": 1024.0 * g * 1e9 / r}
-                if roof.get("achieved"):
-                    roof["frac_of_measured_peak"] = roof["achieved"] / (r * 64 / 1e9)
-                if roof_s.get("achieved"):
-                    roof_s["hbm_peak_measured_triad_GBps"] = roof["hbm_peak_measured_triad_GBps"]
-                    roof_s["frac_of_measured_triad"] = roof_s["achieved"] / roof["hbm_peak_measured_triad_GBps"]
-            except Exception as e:      # probes never fail the bench
-                roof["probe_error"] = str(e)
-        out["roofline"] = roof
-        out["roofline_shade"] = roof_s
-        if world == 1 and len(calls) > 1 and not args.no_all_in_flight_extra and not args.emulate_world:
-            # what the same K passes take when they are all in flight together (the previous rounds' bench line); NOT the config's shape
-            one = TileRenderer(scene, cam, params(args.warmup, args.steps), dev)
-            one.work.zero_(); one.tiles.zero_()
-            torch.cuda.synchronize(dev)
-            t1 = time.perf_counter()
-            one.render()
-            torch.cuda.synchronize(dev)
-            d1 = time.perf_counter() - t1
-            out["all_in_flight"] = {"value": samples / d1 / 1e6, "unit": "Msamples/s", "passes_in_flight": args.steps, "ms_per_step": d1 * 1e3 / args.steps,
-                                    "note": "all %d passes submitted as one render call: more streams in flight than the config's %d passes allow" % (args.steps, cfg["passes"])}
-            del one
-        if world == 1 and not args.no_cpu_baseline and not args.emulate_world:
-            ncores = min(len(os.sched_getaffinity(0)), 16)      # the box's CPU share for one GPU
-            out["cpu_baseline"] = cpu_baseline(cfg, nodes, tris, ncores)
-        if not args.emulate_world:
-            # a cheap sanity guard on the timed output (not a parity test): finite, plausible brightness
-            m = float(torch.nan_to_num(frame, nan=0.0).mean().item()) / args.steps
-            nan_px = int(torch.isnan(frame).any(-1).sum().item())
-            if not (0.05 < m < 5.0) or bool(torch.isinf(frame).any().item()):
-                raise SystemExit(f"bench output implausible (mean {m})")
-            if nan_px:      # the reference's NaN pixels (0/0 in its own BxDF arithmetic, reproduced bit for bit; tests/test_gpu_parity.py)
-                out["config"]["nan_pixels"] = nan_px
+        if args.full:
+            kern_ms = scene.render_timings(reset=True)
+            roof = {"kernel": "wf_trace", "bound": "valu", "unit": "Glane-op/s", "peak": VALU_PEAK_GLOPS,
+                    "achieved": None, "frac": None, "traffic": None}
+            roof_s = {"kernel": "wf_shade", "bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS, "achieved": None, "frac": None, "traffic": None}
+            pmc = load_pmc(args.config)
+            pmc_src = None
+            if pmc:
+                pmc_src = "%s (%s)" % (pmc.get("_path"), pmc.get("collected_with", ""))
+            if t_launches > 0:
+                k_ms = t_sum_ms / t_launches
+                spl = call_samples / t_launches                      # samples' worth of rays one launch advances
+                roof.update({"kernel_ms_avg": k_ms, "kernel_ms_max": t_max_ms, "launches_timed": int(t_launches), "kernel_ms_sum": t_sum_ms,
+                             "samples_per_launch": spl, "bounce_iterations": iters,
+                             "pipeline_ms_per_step": (float(np.sum(kern_ms)) / args.steps) if len(kern_ms) else None})
+                k = (pmc or {}).get("kernels", {}).get("wf_trace")
+                if k:
+                    lane_ops = k["valu_lane_ops_per_sample"] * spl           # per launch
+                    roof["achieved"] = lane_ops / (k_ms * 1e-3) / 1e9
+                    roof["frac"] = roof["achieved"] / VALU_PEAK_GLOPS
+                    roof["valu_lane_ops_per_sample"] = k["valu_lane_ops_per_sample"]
+                    roof["valu_lane_utilisation"] = k.get("valu_lane_utilisation")
+                    roof["valu_issue_frac"] = (k["valu_insts_per_sample"] * spl * 64.0 / (k_ms * 1e-3) / 1e9) / VALU_PEAK_GLOPS
+                    roof["traffic"] = k["hbm_bytes_per_sample"] * spl         # HBM-side bytes per launch (fabric requests; Infinity-Cache hits included)
+                    roof["hbm_frac"] = roof["traffic"] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                    roof["l2_hit_rate"] = k.get("l2_hit_rate")
+                    roof["pmc_source"] = pmc_src
+                    # the counters are per-sample figures from a separate profiled run; say what that run was next to what this one is
+                    roof["pmc_samples_profiled"] = pmc.get("samples_profiled"); roof["pmc_note"] = pmc.get("note")
+                    roof["live"] = {"spp_per_pass": spp, "steps": args.steps}
+                # algorithmic bytes of the REFERENCE traversal (40 B per node fetched + 36 B per triangle test, counted
+                # by the instrumented oracle on this scene and frame) over this kernel's time.  Not a bandwidth: see the docstring.
+                try:
+                    tc = json.load(open(os.path.join(ROOT, "tests", "golden", "traversal_counters.json")))[cfg["counters"]]
+                    bps = (40.0 * tc["nodes_fetched"] + 36.0 * tc["tri_tests"]) / tc["paths"]
+                    eff = spl * bps / (k_ms * 1e-3) / 1e9
+                    out["vs_reference_algorithm"] = {"reference_traversal_bytes_per_sample": bps, "effective_GBps": eff,
+                                                     "ratio_to_hbm_peak": eff / HBM_PEAK_GBS,
+                                                     "note": "speed-up over a bandwidth-perfect execution of the reference's traversal "
+                                                             "(brute force on degenerate rays, camera ray re-traced per sample); not a bandwidth"}
+                except (KeyError, OSError):
+                    pass
+            if s_launches > 0:
+                ks_ms = s_sum_ms / s_launches
+                spl_s = call_samples / s_launches
+                roof_s.update({"kernel_ms_avg": ks_ms, "kernel_ms_max": s_max_ms, "launches_timed": int(s_launches), "kernel_ms_sum": s_sum_ms,
+                               "samples_per_launch": spl_s})
+                # every wf_shade* kernel of the profiled run (the schedule variants are separate kernels), per sample
+                ks = [v for n, v in (pmc or {}).get("kernels", {}).items() if n.startswith("wf_shade") and "hbm_bytes_per_sample" in v]
+                if ks:
+                    bps = sum(v["hbm_bytes_per_sample"] for v in ks)
+                    lops = sum(v.get("valu_lane_ops_per_sample", 0.0) for v in ks)
+                    insts = sum(v.get("valu_insts_per_sample", 0.0) for v in ks)
+                    roof_s["traffic"] = bps * spl_s                              # HBM-side bytes per launch
+                    roof_s["achieved"] = roof_s["traffic"] / (ks_ms * 1e-3) / 1e9
+                    roof_s["frac"] = roof_s["achieved"] / HBM_PEAK_GBS
+                    roof_s["hbm_bytes_per_sample"] = bps
+                    roof_s["valu_lane_ops_per_sample"] = lops
+                    roof_s["valu_lane_utilisation"] = (lops / (64.0 * insts)) if insts else None
+                    roof_s["valu_frac"] = lops * spl_s / (ks_ms * 1e-3) / 1e9 / VALU_PEAK_GLOPS
+                    roof_s["pmc_source"] = pmc_src
+            if not args.no_probes:
+                try:
+                    roof["hbm_peak_measured_triad_GBps"] = ptamd.triad_gbps(1 << 30, 10, dev.index or 0)
+                    r, g = ptamd.valu_rate(0, 4, 20000, dev.index or 0)
+                    roof["valu_peak_measured"] = {"op": "v_fma_f32, 4 waves/SIMD", "Glane_op_per_s": r * 64 / 1e9, "clock_ghz": g,
+                                                  "clocks_per_wave_inst_per_simd": 1024.0 * g * 1e9 / r}
+                    if roof.get("achieved"):
+                        roof["frac_of_measured_peak"] = roof["achieved"] / (r * 64 / 1e9)
+                    if roof_s.get("achieved"):
+                        roof_s["hbm_peak_measured_triad_GBps"] = roof["hbm_peak_measured_triad_GBps"]
+                        roof_s["frac_of_measured_triad"] = roof_s["achieved"] / roof["hbm_peak_measured_triad_GBps"]
+                except Exception as e:      # probes never fail the bench
+                    roof["probe_error"] = str(e)
+            out["roofline"] = roof
+            out["roofline_shade"] = roof_s
+            if world == 1 and len(calls) > 1 and not args.no_all_in_flight_extra and not args.emulate_world:
+                # what the same K passes take when they are all in flight together (the previous rounds' bench line); NOT the config's shape
+                one = TileRenderer(scene, cam, params(args.warmup, args.steps), dev)
+                one.work.zero_(); one.tiles.zero_()
+                torch.cuda.synchronize(dev)
+                t1 = time.perf_counter()
+                one.render()
+                torch.cuda.synchronize(dev)
+                d1 = time.perf_counter() - t1
+                out["all_in_flight"] = {"value": samples / d1 / 1e6, "unit": "Msamples/s", "passes_in_flight": args.steps, "ms_per_step": d1 * 1e3 / args.steps,
+                                        "note": "all %d passes submitted as one render call: more streams in flight than the config's %d passes allow" % (args.steps, cfg["passes"])}
+                del one
+            if world == 1 and not args.no_cpu_baseline and not args.emulate_world:
+                ncores = min(len(os.sched_getaffinity(0)), 16)      # the box's CPU share for one GPU
+                out["cpu_baseline"] = cpu_baseline(cfg, nodes, tris, ncores)
+            if not args.emulate_world:
+                # a cheap sanity guard on the timed output (not a parity test): finite, plausible brightness
+                m = float(torch.nan_to_num(frame, nan=0.0).mean().item()) / args.steps
+                nan_px = int(torch.isnan(frame).any(-1).sum().item())
+                if not (0.05 < m < 5.0) or bool(torch.isinf(frame).any().item()):
+                    raise SystemExit(f"bench output implausible (mean {m})")
+                if nan_px:      # the reference's NaN pixels (0/0 in its own BxDF arithmetic, reproduced bit for bit; tests/test_gpu_parity.py)
+                    out["config"]["nan_pixels"] = nan_px
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -28,7 +28,7 @@ run() {
   if [ -n "$envs" ]; then IFS=, read -ra kv <<< "$envs"; E+=("${kv[@]}"); fi
   echo "== $leg $*" | tee -a "$LOG"
   local out
-  out=$(env "${E[@]}" timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-probes "$@" 2>> "$LOG") || { echo "ab.sh: leg '$leg $*' failed (see $LOG)" | tee -a "$LOG"; exit 3; }
+  out=$(env "${E[@]}" timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-probes "$@" 2>> "$LOG") || { echo "ab.sh: leg '$leg $*' failed (see $LOG)" | tee -a "$LOG"; exit 3; }
   echo "$out" >> "$LOG"
   echo "$out" | python3 -c "
 import sys, json

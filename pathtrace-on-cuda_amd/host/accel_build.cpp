@@ -8,8 +8,9 @@
 // two children that overlap completely (25.8 node records + 8.4 triangle tests per ray on the
 // 69,576-triangle scene, with a heavy tail).  So the kernels traverse a second tree:
 //
-//   * a binned-SAH BVH over the individual triangles (longest useful axis, 32 bins, leaves of
-//     <= 2 triangles), emitted as the same 64-byte two-child records (pt_device.h);
+//   * a binned-SAH BVH over the individual triangles (32 bins on the centroid per axis and on the
+//     triangle's size, leaves of <= 2 triangles), emitted as the same 64-byte two-child records
+//     (pt_device.h); PTAMD_TREE=0 builds the earlier centroid-only tree;
 //   * its boxes are padded by 2^-16 relative (+ tiny absolute) so that, with the slab test's own
 //     slack, no triangle Triangle::hit can accept is ever culled;
 //   * every triangle record carries its index in the reference's order (the tie rule and the
@@ -37,7 +38,7 @@
 
 namespace {
 
-struct Item { float mn[3], mx[3]; int tri; };
+struct Item { float mn[3], mx[3]; int tri; float lsz; };      // lsz: log2 of the box diagonal (size key of the size-aware build)
 struct BN { float mn[3], mx[3]; int l, r, first, count; };
 
 struct Builder {
@@ -128,6 +129,90 @@ struct Builder {
         nodes[me].l = l; nodes[me].r = r; nodes[me].count = 0;
         return me;
     }
+
+    // ---- the size-aware build (default; PTAMD_TREE=0 keeps build() above) ----
+    // Centroid binning treats a big triangle as a point: a wall's centroid lies in the middle of the room, so SAH files it
+    // with the mesh and its box inflates subtrees deep inside the mesh.  Here every node also weighs splits a centroid does
+    // not represent: the items binned on log2 of their box diagonal, i.e. large against small at every bin edge (binning on
+    // box min / box max per axis as well was measured: no better, tools/tree_lab.cpp).  The cost counts what wf_trace pays: a
+    // leaf is one pair-record test whatever it holds, so a subtree of n items is charged per leaf, ceil(n / maxLeaf).  No
+    // item is ever duplicated (every triangle stays reachable exactly once).
+    static constexpr int kKeys = 4;            // 0-2 centroid (x2) per axis, 3 log2 of the box diagonal
+    static constexpr int kBins = 32;
+    static float key(const Item& x, int k) { return k < 3 ? x.mn[k] + x.mx[k] : x.lsz; }
+    int leaves_of(int c) const { return (c + maxLeaf - 1) / maxLeaf; }
+
+    int build_sized(int lo, int hi, int depth)
+    {
+        const int me = (int)nodes.size();
+        nodes.emplace_back();
+        if (depth > maxDepth) maxDepth = depth;
+        float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+        float kmn[kKeys], kmx[kKeys];
+        for (int k = 0; k < kKeys; k++) { kmn[k] = FLT_MAX; kmx[k] = -FLT_MAX; }
+        for (int i = lo; i < hi; i++) {
+            const Item& x = items[i];
+            for (int a = 0; a < 3; a++) { mn[a] = std::min(mn[a], x.mn[a]); mx[a] = std::max(mx[a], x.mx[a]); }
+            for (int k = 0; k < kKeys; k++) { const float v = key(x, k); kmn[k] = std::min(kmn[k], v); kmx[k] = std::max(kmx[k], v); }
+        }
+        memcpy(nodes[me].mn, mn, 12); memcpy(nodes[me].mx, mx, 12);
+        const int n = hi - lo;
+        if (n <= maxLeaf) { nodes[me].first = lo; nodes[me].count = n; nodes[me].l = nodes[me].r = -1; return me; }
+        int mid = -1;
+        const bool forceMedian = depth + ceil_log2((n + maxLeaf - 1) / maxLeaf) >= kAccelMaxDepth - 1;
+        if (!forceMedian) {
+            float best = FLT_MAX; int bk = -1, bsp = -1;
+            for (int k = 0; k < kKeys; k++) {
+                const float ext = kmx[k] - kmn[k];
+                if (!(ext > 0.f)) continue;
+                const float sc = kBins / ext;
+                int cnt[kBins] = {0}; float bmn[kBins][3], bmx[kBins][3];
+                for (int j = 0; j < kBins; j++) for (int a = 0; a < 3; a++) { bmn[j][a] = FLT_MAX; bmx[j][a] = -FLT_MAX; }
+                for (int i = lo; i < hi; i++) {
+                    const Item& x = items[i];
+                    const int j = std::min(kBins - 1, (int)((key(x, k) - kmn[k]) * sc));
+                    cnt[j]++;
+                    for (int a = 0; a < 3; a++) { bmn[j][a] = std::min(bmn[j][a], x.mn[a]); bmx[j][a] = std::max(bmx[j][a], x.mx[a]); }
+                }
+                float ra[kBins]; int rc[kBins];
+                float am[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, aM[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX}; int c = 0;
+                for (int j = kBins - 1; j > 0; j--) {
+                    c += cnt[j];
+                    for (int a = 0; a < 3; a++) { am[a] = std::min(am[a], bmn[j][a]); aM[a] = std::max(aM[a], bmx[j][a]); }
+                    ra[j] = c ? area(am, aM) : 0.f; rc[j] = c;
+                }
+                float lm[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, lM[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX}; c = 0;
+                for (int j = 0; j < kBins - 1; j++) {
+                    c += cnt[j];
+                    for (int a = 0; a < 3; a++) { lm[a] = std::min(lm[a], bmn[j][a]); lM[a] = std::max(lM[a], bmx[j][a]); }
+                    if (!c || !rc[j + 1]) continue;
+                    const float cost = area(lm, lM) * (float)leaves_of(c) + ra[j + 1] * (float)leaves_of(rc[j + 1]);
+                    if (cost < best) { best = cost; bk = k; bsp = j; }
+                }
+            }
+            if (bk >= 0) {
+                const float k0 = kmn[bk], sc = kBins / (kmx[bk] - kmn[bk]);
+                auto it = std::partition(items.begin() + lo, items.begin() + hi, [&](const Item& x) {
+                    return std::min(kBins - 1, (int)((key(x, bk) - k0) * sc)) <= bsp;
+                });
+                mid = (int)(it - items.begin());
+                if (mid == lo || mid == hi) mid = -1;
+            }
+        }
+        if (mid < 0) {
+            int ax = 0;
+            if (kmx[1] - kmn[1] > kmx[ax] - kmn[ax]) ax = 1;
+            if (kmx[2] - kmn[2] > kmx[ax] - kmn[ax]) ax = 2;
+            mid = (lo + hi) / 2;
+            std::nth_element(items.begin() + lo, items.begin() + mid, items.begin() + hi, [ax](const Item& a, const Item& b) {
+                return (a.mn[ax] + a.mx[ax]) < (b.mn[ax] + b.mx[ax]);
+            });
+        }
+        const int l = build_sized(lo, mid, depth + 1);
+        const int r = build_sized(mid, hi, depth + 1);
+        nodes[me].l = l; nodes[me].r = r; nodes[me].count = 0;
+        return me;
+    }
 };
 
 inline float as_float(int32_t i) { float f; memcpy(&f, &i, 4); return f; }
@@ -164,9 +249,16 @@ void pt_build_accel(const PtBVHNode* rnodes, int n_rnodes, const PtTriangle* tri
             it.mx[a] = std::max(t.V0[a], std::max(t.V1[a], t.V2[a]));
         }
         it.tri = i;
+        const float d0 = it.mx[0] - it.mn[0], d1 = it.mx[1] - it.mn[1], d2 = it.mx[2] - it.mn[2];
+        it.lsz = 0.5f * std::log2(std::max(d0 * d0 + d1 * d1 + d2 * d2, 1e-30f));
     }
+    // PTAMD_TREE=0: the centroid-SAH tree with the largest-area 4-wide collapse (A/B only: the tree steers the search, it
+    // cannot change a result).  Read at every upload, so one process can build both.
+    const char* te = getenv("PTAMD_TREE");
+    const bool sized = !(te && atoi(te) == 0);
     b.nodes.reserve((size_t)n_tris * 2);
-    b.build(0, n_tris, 0);
+    if (sized) b.build_sized(0, n_tris, 0);
+    else b.build(0, n_tris, 0);
     out.depth = b.maxDepth;
 
     // triangle test records in tree order
@@ -248,6 +340,11 @@ void pt_build_accel(const PtBVHNode* rnodes, int n_rnodes, const PtTriangle* tri
     int quadDepth = 0;
     struct Emit {
         Builder& b; std::vector<Q4>& quad; float absPad; int& maxDepth;
+        // with a depth cap (size-aware tree): a child whose subtree would end below kQuadDepthCap even if every level below it
+        // were collapsed two binary levels at a time (height[] = binary levels under a node) is opened here first, the deepest
+        // first; the rest of the four slots go by largest area.  Opening both children of a node that fits always fits, so the
+        // 4-wide tree stays within the cap whenever the binary tree is at most 2 * (kQuadDepthCap + 1) levels deep.
+        const std::vector<int>* height;             // null: no cap (PTAMD_TREE=0)
         int run(int bnode, int depth)
         {
             if (depth > maxDepth) maxDepth = depth;
@@ -255,12 +352,20 @@ void pt_build_accel(const PtBVHNode* rnodes, int n_rnodes, const PtTriangle* tri
             ch[nc++] = b.nodes[(size_t)bnode].l; ch[nc++] = b.nodes[(size_t)bnode].r;
             while (nc < 4) {
                 int pick = -1; float pa = -1.f;
-                for (int k = 0; k < nc; k++) {
-                    const BN& c = b.nodes[(size_t)ch[k]];
-                    if (c.count > 0) continue;
-                    const float ar = Builder::area(c.mn, c.mx);
-                    if (ar > pa) { pa = ar; pick = k; }
+                if (height) {
+                    int ph = 0;
+                    for (int k = 0; k < nc; k++) {
+                        const int h = (*height)[(size_t)ch[k]];
+                        if (h > 0 && depth + (h + 1) / 2 > kQuadDepthCap && h > ph) { ph = h; pick = k; }
+                    }
                 }
+                if (pick < 0)
+                    for (int k = 0; k < nc; k++) {
+                        const BN& c = b.nodes[(size_t)ch[k]];
+                        if (c.count > 0) continue;
+                        const float ar = Builder::area(c.mn, c.mx);
+                        if (ar > pa) { pa = ar; pick = k; }
+                    }
                 if (pick < 0) break;
                 const BN& c = b.nodes[(size_t)ch[pick]];
                 const int l = c.l, r = c.r;
@@ -340,7 +445,10 @@ void pt_build_accel(const PtBVHNode* rnodes, int n_rnodes, const PtTriangle* tri
         q.d[5] = q.d[6] = q.d[7] = (uint32_t)~0;
         for (int a = 0; a < 3; a++) { q.d[8 + a] = 0u | (255u << 8) | (255u << 16) | (255u << 24); q.d[11 + a] = qh[a]; }
     } else {
-        Emit em{b, quad, absPad, quadDepth};
+        std::vector<int> height(b.nodes.size(), 0);      // a child's index is above its parent's
+        for (size_t i = b.nodes.size(); i-- > 0;)
+            if (b.nodes[i].count == 0) height[i] = 1 + std::max(height[(size_t)b.nodes[i].l], height[(size_t)b.nodes[i].r]);
+        Emit em{b, quad, absPad, quadDepth, sized ? &height : nullptr};
         em.run(0, 0);
     }
     // Renumber: the first kQuadTopBfs nodes in breadth-first order — every ray walks them, and wf_trace keeps a prefix of

@@ -6,6 +6,8 @@
 
 constexpr int kQuadTopBfs = 1024;       // leading quad nodes numbered breadth-first (wf_trace stages a prefix of them in LDS)
 constexpr int kAccelMaxDepth = 32;       // == ptd::kStackDepth; the builder never exceeds it
+constexpr int kQuadDepthCap = 12;        // deepest 4-wide level the size-aware collapse aims for: wf_drain walks the 4-wide tree only while
+                                         // 3 * quad_depth + 2 fits its 40-entry stack (csrc/pt_wavefront.hip: kDrainQuadStack)
 
 struct PtAccel {
     std::vector<float> wide;             // n_wide x 16 floats (two child boxes + two refs)

@@ -3,7 +3,8 @@
 #   tools/ab.sh TAG [--no-tests] LEG [LEG ...]
 # LEG = name[:ENV=VAL[,ENV=VAL...]]   name "main" = the library in tree, anything else = pathtrace-on-cuda_amd/build/libptamd_<name>.so
 #       (tools/build_variant.sh); the ENV=VAL pairs are exported for that leg only (PTAMD_* scheduling knobs).
-# Runs the GPU parity suite first (unless --no-tests), then per leg: configs[2] twice, configs[1], configs[3] and one rank of an 8-way split once.
+# Runs the GPU parity suite first (unless --no-tests), then per leg: configs[2] twice, configs[1], configs[3], configs[4] and one rank of an
+# 8-way split once.
 # Everything (stderr included) goes to gpurun_out/<TAG>.log; a leg that yields no JSON line aborts the run with a non-zero status.
 set -euo pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$(dirname "$(readlink -f "$0")")")}"
@@ -40,4 +41,5 @@ print(round(d['value'], 1), 'Msamples/s  ms/step', round(d['ms_per_step'], 1), '
 for rep in 1 2; do for n in "$@"; do run "$n"; done; done
 for n in "$@"; do run "$n" --config 1; done
 for n in "$@"; do run "$n" --config 3; done
+for n in "$@"; do run "$n" --config 4; done
 for n in "$@"; do run "$n" --emulate-world 8 --rank 0; done

@@ -212,6 +212,60 @@ PT_API int  pt_gather_frame(PtComm* c, const float* d_tiles, const PtCamera* cam
 PT_API int  pt_render_split(PtScene* s, const PtCamera* cam, const PtParams* prm, PtComm* c, float* h_accum_rgb);
 
 /* ----------------------------------------------------------------------------------
+ * First-hit feature buffers ("AOVs") and a feature-guided denoiser (new: the reference has neither).
+ * Opt-in and separate from the render: they read only the scene's immutable data, never a render's state, and leave every
+ * frame of pt_render / pt_render_tiles / pt_render_split as it is.
+ *
+ * pt_render_aov: for every pixel of the FULL frame, the camera ray of the first path of each pass first_pass + j of the call
+ *   (j = 0 .. passes-1; the ray pt_dbg_pixel_dir reproduces, origin cam->pos, t_max 999999), traced to its closest hit.
+ *   Writes pt_aov_floats() floats, 8 per pixel, row-major (d_aov[(py*W + px)*8 + k]), float32 sums in pass order and one
+ *   IEEE division at the end:
+ *     k 0..2  sum of the hit material's albedo / passes          (a miss adds 0)
+ *     k 3..5  sum of the ray-facing shading normal / passes      (not renormalised; a miss adds 0)
+ *     k 6     sum of t over the hitting samples / their number   (0 if none)
+ *     k 7     hits / passes                                      (coverage)
+ *   d_prim (may be NULL): int32 per pixel, the primitive the ray of pass first_pass hit (triangles, then spheres, as
+ *   pt_dbg_raycast's out_prim), -1 for a miss.  Only prm->passes and prm->first_pass are read: rank, world, spp_per_pass and
+ *   the bounce settings are ignored, the buffer is always the whole frame.  Asynchronous on `hip_stream`; d_aov 16-byte aligned.
+ * pt_aov: the same into host buffers (h_prim may be NULL), synchronous.
+ *
+ * pt_denoise: edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with albedo demodulation, guided by the AOVs.
+ *   d_rgb is a row-major W*H*3 frame as pt_render returns it (the sum over passes of per-pass means, NaN pixels allowed);
+ *   d_out receives a frame of the same shape and scale (pt_tonemap_u8(out, sample_cnt) works unchanged).  Definition:
+ *     c_p = rgb_p / sample_cnt;  div_p = albedo_p where > 1e-3, else 1 (per channel; 1 without demodulation);  e_p = c_p / div_p
+ *     finite_p = all three components of c_p (after an iteration: of e_p) are finite
+ *     iteration i = 0 .. L-1, step s = 2^i, taps q = p + s*(dx, dy), dx, dy in -2..2, inside the frame and finite_q:
+ *       w = h(dx) h(dy) exp(-E),  h = (1/16, 1/4, 3/8, 1/4, 1/16),  w = 0 exactly when E > 80
+ *       E = |e_p - e_q|^2 / (sigma_color^2 4^-i)   (left out when !finite_p)
+ *         + |n_p - n_q|^2 / sigma_normal^2          (n = AOV 3..5)
+ *         + |z_p - z_q| / (sigma_depth max(z_p, z_q)) (z = AOV 6; 0 when both are 0)
+ *     e_p <- sum w e_q / sum w (kept when sum w = 0: a NaN pixel with a finite neighbour becomes finite, a NaN never spreads)
+ *     out_p = e_p * div_p * sample_cnt after L iterations;  L = 0 copies d_rgb bit for bit.
+ *   d_work: pt_denoise_work_bytes(W, H) bytes; d_aov and d_work 16-byte aligned; d_out must not overlap d_rgb, d_aov or d_work,
+ *   and the inputs are not modified.  Asynchronous on `hip_stream`.
+ * pt_denoise_host: the same on host buffers, on HIP device `device`, synchronous.
+ * Bad arguments (NULL pointers, W or H < 2, sample_cnt <= 0, iterations outside 0..12, a sigma <= 0, overlapping buffers)
+ * return PT_ERR_INVALID before any HIP call.
+ * -------------------------------------------------------------------------------- */
+typedef struct PtDenoiseParams {
+    int32_t iterations;       /* L, 0..12 (default 5: steps 1..16, a 125-pixel footprint) */
+    float   sigma_color;      /* default 16 (chosen on 4-pass x 1-spp frames) */
+    float   sigma_normal;     /* default 0.1 */
+    float   sigma_depth;      /* default 0.1 (relative depth difference) */
+    int32_t demodulate;       /* 1: filter colour / albedo, remodulate afterwards (default) */
+} PtDenoiseParams;
+
+PT_API int64_t pt_aov_floats(const PtCamera* cam);                /* W * H * 8, or -1 */
+PT_API int  pt_render_aov(PtScene* s, const PtCamera* cam, const PtParams* prm, float* d_aov, int32_t* d_prim, void* hip_stream);
+PT_API int  pt_aov(PtScene* s, const PtCamera* cam, const PtParams* prm, float* h_aov, int32_t* h_prim);
+PT_API void pt_denoise_params_default(PtDenoiseParams* p);
+PT_API int64_t pt_denoise_work_bytes(int32_t W, int32_t H);         /* 48 * W * H, or -1 */
+PT_API int  pt_denoise(const float* d_rgb, const float* d_aov, int32_t W, int32_t H, int32_t sample_cnt, const PtDenoiseParams* p,
+                       float* d_out, void* d_work, void* hip_stream);
+PT_API int  pt_denoise_host(int32_t device, const float* h_rgb, const float* h_aov, int32_t W, int32_t H, int32_t sample_cnt,
+                            const PtDenoiseParams* p, float* h_out);
+
+/* ----------------------------------------------------------------------------------
  * (a12,a13) Output + camera helpers (host).
  * pt_tonemap_u8 = exportImage (srcs/pathtracer.cu:94-112): /SampleCnt, ACESFilm
  *   (include/CudaUtil.cuh:383-391), ConverToUint8 (include/image.h:5-8).

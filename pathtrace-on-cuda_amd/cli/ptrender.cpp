@@ -15,17 +15,19 @@ static void usage()
     std::cout <<
         "usage: ptrender [--scene cornell|standin|standin4] [--obj FILE --obj-scale S --obj-translate X,Y,Z]\n"
         "                [--glass-sphere] [--width W] [--height H] [--passes N] [--spp N] [--depth N]\n"
-        "                [--lat-lon N] [--device D] [--no-progressive] [--raw FILE]\n"
+        "                [--lat-lon N] [--device D] [--no-progressive] [--raw FILE] [--denoise FILE.png] [--aov FILE]\n"
         "                [--world N --rank R --id-file PATH [--job-tag T]]   (one process per GPU; rank 0 writes the frame;\n"
         "                 T = a number the ranks of this job share and other jobs do not, default: the parent process id)\n"
         "Writes temp.png (per pass) and result.png in the current directory, like PathTracer::Render.\n"
         "--raw FILE: also writes the float accumulation buffer (W*H*3 float32) there after every pass (viewer hook).\n"
+        "--denoise FILE.png: also writes the frame denoised with the first-hit feature buffers (rank 0, after the final frame).\n"
+        "--aov FILE: also writes those feature buffers (W*H*8 float32: albedo.rgb normal.xyz depth coverage) there.\n"
         "Defaults: scene cornell, 1920x1080, 8 passes x 64 spp, depth 8.\n";
 }
 
 int main(int argc, char** argv)
 {
-    std::string scene = "cornell", obj, rawPath;
+    std::string scene = "cornell", obj, rawPath, denoisePath, aovPath;
     float objScale = 1.f; float objT[3] = {0, 0, 0};
     int W = 1920, H = 1080, passes = 8, spp = 64, depth = 8, latlon = 187, device = 0;
     bool glass = false, progressive = true;
@@ -47,6 +49,8 @@ int main(int argc, char** argv)
         else if (a == "--device") device = atoi(next());
         else if (a == "--no-progressive") progressive = false;
         else if (a == "--raw") rawPath = next();
+        else if (a == "--denoise") denoisePath = next();
+        else if (a == "--aov") aovPath = next();
         else if (a == "--world") world = atoi(next());
         else if (a == "--rank") rank = atoi(next());
         else if (a == "--id-file") idFile = next();
@@ -80,6 +84,7 @@ int main(int argc, char** argv)
     PathTracer tracer;
     tracer.params.passes = passes; tracer.params.spp_per_pass = spp; tracer.params.max_bounce = depth;
     tracer.device = device; tracer.progressive = progressive; tracer.raw_path = rawPath;
+    tracer.denoise_path = denoisePath; tracer.aov_path = aovPath;
     tracer.rank = rank; tracer.world = world; tracer.id_file = idFile; tracer.job_tag = jobTag;
     tracer.Render(camera, &bvh);
     const double samples = (double)W * H * passes * spp;

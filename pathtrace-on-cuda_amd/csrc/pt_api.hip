@@ -30,6 +30,8 @@ hipError_t ptk_dbg_sincos(const float*, int, float*, hipStream_t);
 hipError_t ptk_dbg_ray_setup(const float*, int, float*, hipStream_t);
 hipError_t ptk_dbg_pixel_dir(const ptd::DevCamera*, const int*, int, float*, hipStream_t);
 hipError_t ptk_dbg_nee(const ptd::DevScene*, const float*, int, float*, hipStream_t);
+hipError_t ptk_aov(const ptd::DevScene*, const ptd::DevCamera*, int, int, float*, int*, hipStream_t);
+hipError_t ptk_denoise(const float*, const float*, int, int, int, int, float, float, float, int, float*, void*, hipStream_t);
 size_t ptk_wf_work_bytes(size_t nUnits, int traceBlocks);
 int ptk_wf_cohorts(size_t nUnits);
 const float* ptk_wf_staging(void* work);
@@ -611,6 +613,133 @@ int pt_dbg_trace_timeline(PtScene* s, int64_t* out3n, int32_t n_launches)
 }
 
 PT_API int pt_enable_counters(PtScene* s, int32_t on) { if (!s) return PT_ERR_INVALID; s->count_next = on != 0; return PT_OK; }
+
+// ---- first-hit feature buffers and the denoiser (pt_denoise.hip) --------------------------
+static const int64_t kMaxPixels = (int64_t)1 << 28;      // keeps every per-pixel float offset (x 8) inside int64 and the pixel index inside int
+
+static int aov_args(const PtCamera* cam, const PtParams* prm)
+{
+    if (!cam || !prm) { pt_set_error("NULL camera/params"); return PT_ERR_INVALID; }
+    if (cam->W < 2 || cam->H < 2 || (int64_t)cam->W * cam->H > kMaxPixels) { pt_set_error("frame %dx%d out of range", cam->W, cam->H); return PT_ERR_INVALID; }
+    if (prm->passes < 1 || prm->first_pass < 0) { pt_set_error("bad params: passes=%d first_pass=%d", prm->passes, prm->first_pass); return PT_ERR_INVALID; }
+    if ((long long)cam->W * cam->H * (long long)(prm->first_pass + prm->passes) > 0x7fffffffLL) {
+        pt_set_error("offset + SampleIDX*W*H overflows int (srcs/pathtracer.cu:71)");
+        return PT_ERR_INVALID;
+    }
+    return PT_OK;
+}
+
+int64_t pt_aov_floats(const PtCamera* cam)
+{
+    if (!cam || cam->W < 2 || cam->H < 2 || (int64_t)cam->W * cam->H > kMaxPixels) { pt_set_error("pt_aov_floats: bad camera"); return -1; }
+    return (int64_t)cam->W * cam->H * 8;
+}
+
+int pt_render_aov(PtScene* s, const PtCamera* cam, const PtParams* prm, float* d_aov, int32_t* d_prim, void* hip_stream)
+{
+    if (!s || !d_aov) { pt_set_error("pt_render_aov: NULL argument"); return PT_ERR_INVALID; }
+    if ((uintptr_t)d_aov % 16) { pt_set_error("pt_render_aov: d_aov is not 16-byte aligned"); return PT_ERR_INVALID; }
+    int rc = aov_args(cam, prm);
+    if (rc) return rc;
+    ptd::DevCamera c;
+    fill_camera(cam, c);
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(ptk_aov(&s->dev, &c, prm->first_pass, prm->passes, d_aov, d_prim, (hipStream_t)hip_stream));
+    return PT_OK;
+}
+
+int pt_aov(PtScene* s, const PtCamera* cam, const PtParams* prm, float* h_aov, int32_t* h_prim)
+{
+    if (!s || !h_aov) { pt_set_error("pt_aov: NULL argument"); return PT_ERR_INVALID; }
+    int rc = aov_args(cam, prm);
+    if (rc) return rc;
+    const size_t n = (size_t)cam->W * cam->H;
+    HIPCHK(hipSetDevice(s->device));
+    float* d_aov = nullptr; int32_t* d_prim = nullptr;
+    auto body = [&]() -> int {
+        HIPCHK(hipMalloc((void**)&d_aov, n * 32));
+        if (h_prim) HIPCHK(hipMalloc((void**)&d_prim, n * 4));
+        int r = pt_render_aov(s, cam, prm, d_aov, d_prim, nullptr);
+        if (r) return r;
+        HIPCHK(hipMemcpy(h_aov, d_aov, n * 32, hipMemcpyDeviceToHost));
+        if (h_prim) HIPCHK(hipMemcpy(h_prim, d_prim, n * 4, hipMemcpyDeviceToHost));
+        return PT_OK;
+    };
+    rc = body();
+    (void)hipFree(d_aov); (void)hipFree(d_prim);
+    return rc;
+}
+
+int64_t pt_denoise_work_bytes(int32_t W, int32_t H)
+{
+    if (W < 2 || H < 2 || (int64_t)W * H > kMaxPixels) { pt_set_error("pt_denoise_work_bytes: frame %dx%d out of range", W, H); return -1; }
+    return (int64_t)W * H * 48;
+}
+
+static bool overlaps(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+static int denoise_args(const void* rgb, const void* aov, int32_t W, int32_t H, int32_t sample_cnt, const PtDenoiseParams* p,
+                        const void* out, const void* work, bool device)
+{
+    if (!rgb || !aov || !p || !out || (device && !work)) { pt_set_error("pt_denoise: NULL argument"); return PT_ERR_INVALID; }
+    if (W < 2 || H < 2 || (int64_t)W * H > kMaxPixels) { pt_set_error("pt_denoise: frame %dx%d out of range", W, H); return PT_ERR_INVALID; }
+    if (sample_cnt <= 0) { pt_set_error("pt_denoise: sample_cnt %d <= 0", sample_cnt); return PT_ERR_INVALID; }
+    if (p->iterations < 0 || p->iterations > 12) { pt_set_error("pt_denoise: iterations %d outside 0..12", p->iterations); return PT_ERR_INVALID; }
+    if (!(p->sigma_color > 0.f) || !(p->sigma_normal > 0.f) || !(p->sigma_depth > 0.f) ||
+        !std::isfinite(p->sigma_color) || !std::isfinite(p->sigma_normal) || !std::isfinite(p->sigma_depth)) {
+        pt_set_error("pt_denoise: sigmas must be finite and > 0"); return PT_ERR_INVALID;
+    }
+    const size_t n = (size_t)W * H;
+    if (overlaps(out, n * 12, rgb, n * 12) || overlaps(out, n * 12, aov, n * 32) || (work && overlaps(out, n * 12, work, n * 48))) {
+        pt_set_error("pt_denoise: the output overlaps an input or the work buffer"); return PT_ERR_INVALID;
+    }
+    if (device && (((uintptr_t)aov % 16) || ((uintptr_t)work % 16) || overlaps(work, n * 48, rgb, n * 12) || overlaps(work, n * 48, aov, n * 32))) {
+        pt_set_error("pt_denoise: d_aov / d_work not 16-byte aligned, or d_work overlaps an input"); return PT_ERR_INVALID;
+    }
+    return PT_OK;
+}
+
+int pt_denoise(const float* d_rgb, const float* d_aov, int32_t W, int32_t H, int32_t sample_cnt, const PtDenoiseParams* p,
+               float* d_out, void* d_work, void* hip_stream)
+{
+    const int rc = denoise_args(d_rgb, d_aov, W, H, sample_cnt, p, d_out, d_work, true);
+    if (rc) return rc;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    if (p->iterations == 0) { HIPCHK(hipMemcpyAsync(d_out, d_rgb, (size_t)W * H * 12, hipMemcpyDeviceToDevice, stream)); return PT_OK; }
+    HIPCHK(ptk_denoise(d_rgb, d_aov, W, H, sample_cnt, p->iterations, p->sigma_color, p->sigma_normal, p->sigma_depth,
+                       p->demodulate ? 1 : 0, d_out, d_work, stream));
+    return PT_OK;
+}
+
+int pt_denoise_host(int32_t device, const float* h_rgb, const float* h_aov, int32_t W, int32_t H, int32_t sample_cnt,
+                    const PtDenoiseParams* p, float* h_out)
+{
+    int rc = denoise_args(h_rgb, h_aov, W, H, sample_cnt, p, h_out, nullptr, false);
+    if (rc) return rc;
+    const size_t n = (size_t)W * H;
+    HIPCHK(hipSetDevice(device));
+    char* d = nullptr;      // one allocation: rgb | aov | out | work
+    auto body = [&]() -> int {
+        HIPCHK(hipMalloc((void**)&d, n * (12 + 32 + 12 + 48) + 64));
+        float* d_rgb = (float*)d;
+        float* d_aov = (float*)(d + ((n * 12 + 15) & ~(size_t)15));
+        float* d_out = (float*)((char*)d_aov + n * 32);
+        void* d_work = (char*)d_aov + ((n * 44 + 15) & ~(size_t)15);
+        HIPCHK(hipMemcpy(d_rgb, h_rgb, n * 12, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_aov, h_aov, n * 32, hipMemcpyHostToDevice));
+        int r = pt_denoise(d_rgb, d_aov, W, H, sample_cnt, p, d_out, d_work, nullptr);
+        if (r) return r;
+        HIPCHK(hipMemcpy(h_out, d_out, n * 12, hipMemcpyDeviceToHost));
+        return PT_OK;
+    };
+    rc = body();
+    (void)hipFree(d);
+    return rc;
+}
 
 // ---- parity hooks ------------------------------------------------------------------------
 int pt_dbg_raycast(PtScene* s, const float* rays8, int32_t n, float* out_hits29, int32_t* out_prim)

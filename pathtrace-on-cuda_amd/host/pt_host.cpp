@@ -40,6 +40,17 @@ void pt_params_default(PtParams* p)
     p->world = 1;
 }
 
+// Denoiser defaults (include/pt_api.h: pt_denoise).  The sigmas were chosen by the CPU experiment of DESIGN.md section 9.
+void pt_denoise_params_default(PtDenoiseParams* p)
+{
+    if (!p) return;
+    p->iterations = 5;
+    p->sigma_color = 16.f;
+    p->sigma_normal = 0.1f;
+    p->sigma_depth = 0.1f;
+    p->demodulate = 1;
+}
+
 // exportImage (srcs/pathtracer.cu:94-112): c = raw / SampleCnt (vec3::operator/=, which
 // multiplies by a reciprocal taken in double, include/CudaVector.cuh:151-158), ACESFilm
 // (include/CudaUtil.cuh:383-391), ConverToUint8 = (uchar)(v * 255.99f) (include/image.h:5-8).

@@ -145,5 +145,16 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
     std::cout << "Delta time : " << std::chrono::duration_cast<std::chrono::milliseconds>(clk::now() - t0).count() << " (ms)" << std::endl;
     exportImage(img, raw.data(), "result.png", H, W, params.passes);
     write_raw(raw_path, raw);
+    if (!denoise_path.empty() || !aov_path.empty()) {
+        // the call's passes: first_pass .. first_pass + passes - 1, the same pixels the frame sums (whole frame, also in a split)
+        std::vector<float> aov((size_t)W * H * 8);
+        check(pt_aov(scene, &cam, &params, aov.data(), nullptr), "pt_aov");
+        write_raw(aov_path, aov);
+        if (!denoise_path.empty()) {
+            std::vector<float> den(raw.size());
+            check(pt_denoise_host(device, raw.data(), aov.data(), W, H, params.passes, &denoise_params, den.data()), "pt_denoise_host");
+            exportImage(img, den.data(), denoise_path.c_str(), H, W, params.passes);
+        }
+    }
     pt_scene_destroy(scene);
 }

@@ -87,7 +87,7 @@ public:
     PtParams params;                        // defaults = the reference's #defines
     int device = 0;
     bool progressive = true;                // rewrite temp.png after every pass (srcs/pathtracer.cu:245)
-    PathTracer() { pt_params_default(&params); }
+    PathTracer() { pt_params_default(&params); pt_denoise_params_default(&denoise_params); }
     void Render(Camera& camera, BVH* bvh);  // writes temp.png / result.png in the CWD; GPU error -> message + exit(99)
     double last_render_ms = 0.0;            // kernel time of the last Render (sum over passes)
     // Viewer hook (new; the reference's viewer only sees temp.png, srcs/renderer.cpp:283-293): when non-empty, the float accumulation
@@ -100,4 +100,9 @@ public:
     int rank = 0, world = 1;
     std::string id_file;
     unsigned long long job_tag = 0;
+    // Feature buffers and denoiser (new; include/pt_api.h: pt_render_aov, pt_denoise), rank 0 only, after the final frame: when
+    // non-empty, the first-hit AOVs of the call's passes are taken and `denoise_path` receives the denoised frame, tone-mapped
+    // like result.png; `aov_path` receives the raw AOV buffer (W*H*8 float32, row-major).  Empty: nothing changes.
+    std::string denoise_path, aov_path;
+    PtDenoiseParams denoise_params;
 };

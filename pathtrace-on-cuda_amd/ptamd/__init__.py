@@ -41,6 +41,13 @@ class PtParams(C.Structure):
                 ("rank", C.c_int32), ("world", C.c_int32)]
 
 
+class PtDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_int32)]
+
+
+AOV_FLOATS = 8        # floats per pixel of pt_render_aov: albedo.rgb | normal.xyz | depth | coverage
+
 _lib = None
 
 # every symbol include/pt_api.h declares: (name, restype, argtypes)
@@ -104,6 +111,13 @@ API = [
     ("pt_set_drain_threshold", C.c_int, [_P, C.c_int32]),
     ("pt_set_shade_rounds", C.c_int, [_P, C.c_int32]),
     ("pt_set_early_shade", C.c_int, [_P, C.c_int32]),
+    ("pt_aov_floats", C.c_int64, [C.POINTER(PtCamera)]),
+    ("pt_render_aov", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), _P, _P, _P]),
+    ("pt_aov", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), _P, _P]),
+    ("pt_denoise_params_default", None, [C.POINTER(PtDenoiseParams)]),
+    ("pt_denoise_work_bytes", C.c_int64, [C.c_int32, C.c_int32]),
+    ("pt_denoise", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PtDenoiseParams), _P, _P, _P]),
+    ("pt_denoise_host", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PtDenoiseParams), _P]),
 ]
 
 
@@ -348,6 +362,19 @@ class Scene:
         _check(lib().pt_dbg_trace_timeline(self._h, _ptr(raw), -int(n_launches)), "pt_dbg_trace_timeline")
         return raw
 
+    def aov(self, cam, prm):
+        """First-hit feature buffers of the passes prm.first_pass .. + prm.passes - 1 (include/pt_api.h: pt_render_aov), synchronous:
+        ((H, W, 8) float32 albedo.rgb | normal.xyz | depth | coverage, (H, W) int32 primitive of the first pass's ray, -1 = miss)."""
+        out = np.zeros((cam.H, cam.W, AOV_FLOATS), np.float32)
+        prim = np.zeros((cam.H, cam.W), np.int32)
+        _check(lib().pt_aov(self._h, C.byref(cam), C.byref(prm), _ptr(out), _ptr(prim)), "pt_aov")
+        return out, prim
+
+    def render_aov(self, cam, prm, d_aov_ptr, d_prim_ptr=0, stream_ptr=0):
+        """Device-resident pt_render_aov into raw device pointers (d_prim_ptr 0 = none), enqueued on the given stream."""
+        _check(lib().pt_render_aov(self._h, C.byref(cam), C.byref(prm), C.c_void_p(d_aov_ptr), C.c_void_p(d_prim_ptr or None),
+                                   C.c_void_p(stream_ptr)), "pt_render_aov")
+
     def raycast(self, rays8):
         rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
         n = rays8.shape[0]
@@ -373,6 +400,52 @@ def work_bytes(cam, prm):
 
 def untile(d_gathered_ptr, cam, world, d_frame_ptr, stream_ptr=0):
     _check(lib().pt_untile(C.c_void_p(d_gathered_ptr), C.byref(cam), world, C.c_void_p(d_frame_ptr), C.c_void_p(stream_ptr)), "pt_untile")
+
+
+def aov_floats(cam):
+    n = lib().pt_aov_floats(C.byref(cam))
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def denoise_params(**kw):
+    """PtDenoiseParams: pt_denoise_params_default, then the given fields (iterations, sigma_color, sigma_normal, sigma_depth,
+    demodulate)."""
+    p = PtDenoiseParams()
+    lib().pt_denoise_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"unknown denoise parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def denoise_work_bytes(W, H):
+    n = lib().pt_denoise_work_bytes(W, H)
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def denoise(rgb, aov, sample_cnt, device=0, **params):
+    """pt_denoise_host: (H, W, 3) frame as Scene.render returns it + (H, W, 8) AOVs -> denoised (H, W, 3) float32 of the same scale."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    aov = np.ascontiguousarray(aov, np.float32)
+    H, W = rgb.shape[:2]
+    if rgb.shape != (H, W, 3) or aov.shape != (H, W, AOV_FLOATS):
+        raise ValueError(f"shapes {rgb.shape} / {aov.shape}: want (H, W, 3) and (H, W, {AOV_FLOATS})")
+    out = np.zeros_like(rgb)
+    p = denoise_params(**params)
+    _check(lib().pt_denoise_host(device, _ptr(rgb), _ptr(aov), W, H, int(sample_cnt), C.byref(p), _ptr(out)), "pt_denoise_host")
+    return out
+
+
+def denoise_device(d_rgb_ptr, d_aov_ptr, W, H, sample_cnt, d_out_ptr, d_work_ptr, stream_ptr=0, **params):
+    """pt_denoise on raw device pointers (d_work: denoise_work_bytes(W, H) bytes), enqueued on the given stream."""
+    p = denoise_params(**params)
+    _check(lib().pt_denoise(C.c_void_p(d_rgb_ptr), C.c_void_p(d_aov_ptr), W, H, int(sample_cnt), C.byref(p), C.c_void_p(d_out_ptr),
+                            C.c_void_p(d_work_ptr), C.c_void_p(stream_ptr)), "pt_denoise")
 
 
 class Comm:

@@ -266,6 +266,62 @@ PT_API int  pt_denoise_host(int32_t device, const float* h_rgb, const float* h_a
                             const PtDenoiseParams* p, float* h_out);
 
 /* ----------------------------------------------------------------------------------
+ * Per-pixel variance across passes, an error estimate, render-to-target (new: the reference has none of them).
+ * Opt-in and beside the render: these calls only READ what a render left behind, and leave every frame as it is.
+ *
+ * Contract of the work buffer (new): after pt_render_tiles(s, cam, prm, d_tiles, d_work, stream) the start of d_work holds the
+ *   per-pass means the frame was summed from — prm->passes x pt_tiles_floats(cam, prm) float32, pass-major, each pass in the
+ *   layout of d_tiles (value = pixelColor / spp_per_pass, srcs/pathtracer.cu:81; padding pixels of ragged edge tiles and of tiles
+ *   past the last one are exactly 0) — in both render modes, valid until d_work is next written.  d_tiles is their sum in pass
+ *   order starting from 0.
+ * Why passes: the reference draws ONE jittered direction per pixel per pass and sends all spp_per_pass paths down it
+ *   (srcs/pathtracer.cu:74-80), so the samples inside a pass are not independent; the per-pass means are.
+ *
+ * pt_accumulate_passes: folds those means into running moments, per float, S = their sum and M2 = the sum of their squared
+ *   deviations from their mean, in the layout of d_tiles (pt_tiles_floats() floats each; pt_gather_frame / pt_untile move them
+ *   unchanged).  cam / prm are those of the render (prm->passes means are read; rank / world as rendered); n_before = passes
+ *   folded in so far (0: d_sum and d_m2 are overwritten, not read).  For pass k = n_before + 1, ... with mean m, IEEE float32:
+ *     S_prev = S;  S = S_prev + m                                                  (k = 1: S = 0 + m)
+ *     k >= 2:  d1 = m - S_prev / (k - 1);  d2 = m - S / k;  M2 = M2 + d1 * d2      (k = 1: M2 = 0)
+ *   Welford's update with the means taken from S: S is bit for bit the frame pt_render_tiles returns for the same passes in one
+ *   call, however they were split over calls.  Non-finite means propagate (the reference produces NaN pixels).
+ * pt_variance: d_var = max(M2, 0) * n / (n - 1), the estimated variance of S, i.e. of the frame value pt_render returns
+ *   (rounding can leave M2 a hair below 0 on a converged pixel; a NaN M2 stays NaN).  n_passes >= 2; any float count.
+ * pt_error_estimate: whole-buffer figures over the pixels of this rank's tiles that lie inside the frame (hence cam and
+ *   prm->rank / world; prm->passes is not read) and whose S and M2 are all finite.  Per-pixel terms in float32 as written below, summed
+ *   in float64 in a fixed order (per-block partial sums in d_scratch, added up on the host; no atomics): two calls return the
+ *   same bits.  The only call here that waits for the stream (it reads the partial sums back).
+ * Buffers are caller-owned; 16-byte aligned ones are read and written with 16-byte accesses (others work, slower).  Everything is
+ * enqueued on `hip_stream` on the current device.  Bad arguments (NULL, n_before < 0, n_passes < 2, camera / params that
+ * pt_tiles_floats rejects) return PT_ERR_INVALID before any HIP call.
+ *
+ * pt_render_converge: host convenience like pt_render (whole frame, world = 1, synchronous).  Renders batches of prm->passes
+ *   passes (first_pass advancing from prm->first_pass), folds each batch, estimates after each batch once two passes are in,
+ *   and stops after the first batch whose rel_rms <= target_rel_rms, or at max_passes (>= 2; the last batch is shortened to
+ *   fit, and prm->first_pass + max_passes must respect the seed limit of pt_render).  h_accum_rgb[W*H*3] = S, bit for bit what
+ *   pt_render returns for passes = *passes_done (divide by it: pt_tonemap_u8(out, *passes_done)); h_var_rgb (may be NULL) =
+ *   pt_variance of it; *est = the last estimate.  A batch costs a pipeline drain and a 40 KB read-back: measured at
+ *   1080p on 8 passes x 256 spp, batches of 1 / 4 / 8 passes take 1.48 / 1.10 / 1.00 x the time of one pt_render call (DESIGN.md
+ *   section 10) — use batches of 8 (4 if the finer stopping grain is worth 10 %), never 1; a tile-split version would need the
+ *   ranks to agree on when to stop and is not provided (the three calls above take any rank / world).
+ * -------------------------------------------------------------------------------- */
+typedef struct PtErrorEstimate {
+    double rel_rms;           /* sqrt( sum Var_i / sum S_i^2 ) over the floats of the pixels used: the expected relative RMS error of the frame */
+    double mean_rel_se;       /* mean over the pixels used of sqrt((Var_r + Var_g) + Var_b) / (((|S_r| + |S_g|) + |S_b|) + 0.03 n):
+                                 rel_rms is dominated by whatever is brightest, this figure weighs every pixel alike */
+    int64_t pixels, skipped;  /* pixels used; in-frame pixels left out because S or M2 is not finite */
+} PtErrorEstimate;
+
+PT_API int  pt_accumulate_passes(const void* d_work, const PtCamera* cam, const PtParams* prm, int32_t n_before,
+                                 float* d_sum, float* d_m2, void* hip_stream);
+PT_API int  pt_variance(const float* d_m2, int64_t n_floats, int32_t n_passes, float* d_var, void* hip_stream);
+PT_API int64_t pt_error_scratch_bytes(int64_t n_floats);           /* 40 * min(1024, ceil(n_floats / 3072)), or -1 (n_floats < 1) */
+PT_API int  pt_error_estimate(const float* d_sum, const float* d_m2, const PtCamera* cam, const PtParams* prm, int32_t n_passes,
+                              void* d_scratch, PtErrorEstimate* h_out, void* hip_stream);
+PT_API int  pt_render_converge(PtScene* s, const PtCamera* cam, const PtParams* prm, double target_rel_rms, int32_t max_passes,
+                               float* h_accum_rgb, float* h_var_rgb, int32_t* passes_done, PtErrorEstimate* est);
+
+/* ----------------------------------------------------------------------------------
  * (a12,a13) Output + camera helpers (host).
  * pt_tonemap_u8 = exportImage (srcs/pathtracer.cu:94-112): /SampleCnt, ACESFilm
  *   (include/CudaUtil.cuh:383-391), ConverToUint8 (include/image.h:5-8).

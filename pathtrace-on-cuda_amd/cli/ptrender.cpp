@@ -16,18 +16,23 @@ static void usage()
         "usage: ptrender [--scene cornell|standin|standin4] [--obj FILE --obj-scale S --obj-translate X,Y,Z]\n"
         "                [--glass-sphere] [--width W] [--height H] [--passes N] [--spp N] [--depth N]\n"
         "                [--lat-lon N] [--device D] [--no-progressive] [--raw FILE] [--denoise FILE.png] [--aov FILE]\n"
+        "                [--target-error E [--max-passes N] [--variance FILE]]\n"
         "                [--world N --rank R --id-file PATH [--job-tag T]]   (one process per GPU; rank 0 writes the frame;\n"
         "                 T = a number the ranks of this job share and other jobs do not, default: the parent process id)\n"
         "Writes temp.png (per pass) and result.png in the current directory, like PathTracer::Render.\n"
         "--raw FILE: also writes the float accumulation buffer (W*H*3 float32) there after every pass (viewer hook).\n"
         "--denoise FILE.png: also writes the frame denoised with the first-hit feature buffers (rank 0, after the final frame).\n"
         "--aov FILE: also writes those feature buffers (W*H*8 float32: albedo.rgb normal.xyz depth coverage) there.\n"
+        "--target-error E: renders batches of --passes passes until the frame's estimated relative RMS error is <= E or --max-passes\n"
+        "  (default 8 batches) are in, prints the passes used and the estimates; --variance FILE: the per-pixel variance of the frame\n"
+        "  (W*H*3 float32).  Single process only; result.png and --denoise use the passes actually rendered.\n"
         "Defaults: scene cornell, 1920x1080, 8 passes x 64 spp, depth 8.\n";
 }
 
 int main(int argc, char** argv)
 {
-    std::string scene = "cornell", obj, rawPath, denoisePath, aovPath;
+    std::string scene = "cornell", obj, rawPath, denoisePath, aovPath, variancePath;
+    double targetError = 0.0; int maxPasses = 0;
     float objScale = 1.f; float objT[3] = {0, 0, 0};
     int W = 1920, H = 1080, passes = 8, spp = 64, depth = 8, latlon = 187, device = 0;
     bool glass = false, progressive = true;
@@ -51,6 +56,9 @@ int main(int argc, char** argv)
         else if (a == "--raw") rawPath = next();
         else if (a == "--denoise") denoisePath = next();
         else if (a == "--aov") aovPath = next();
+        else if (a == "--target-error") targetError = atof(next());
+        else if (a == "--max-passes") maxPasses = atoi(next());
+        else if (a == "--variance") variancePath = next();
         else if (a == "--world") world = atoi(next());
         else if (a == "--rank") rank = atoi(next());
         else if (a == "--id-file") idFile = next();
@@ -59,6 +67,8 @@ int main(int argc, char** argv)
         else { std::cerr << "unknown option " << a << "\n"; usage(); return 2; }
     }
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && idFile.empty())) { std::cerr << "--world N needs 0 <= --rank < N and --id-file PATH\n"; return 2; }
+    if ((maxPasses != 0 || !variancePath.empty()) && !(targetError > 0.0)) { std::cerr << "--max-passes and --variance need --target-error E > 0\n"; return 2; }
+    if (targetError > 0.0 && (world > 1 || (maxPasses != 0 && maxPasses < 2))) { std::cerr << "--target-error is single-process and needs --max-passes >= 2\n"; return 2; }
     const int kind = scene == "cornell" ? 0 : scene == "standin" ? 1 : scene == "standin4" ? 2 : -1;
     if (kind < 0) { std::cerr << "unknown scene " << scene << "\n"; return 2; }
 
@@ -85,8 +95,13 @@ int main(int argc, char** argv)
     tracer.params.passes = passes; tracer.params.spp_per_pass = spp; tracer.params.max_bounce = depth;
     tracer.device = device; tracer.progressive = progressive; tracer.raw_path = rawPath;
     tracer.denoise_path = denoisePath; tracer.aov_path = aovPath;
+    tracer.target_error = targetError; tracer.max_passes = maxPasses; tracer.variance_path = variancePath;
     tracer.rank = rank; tracer.world = world; tracer.id_file = idFile; tracer.job_tag = jobTag;
     tracer.Render(camera, &bvh);
+    if (targetError > 0.0) {      // kernel_ms below would be the last batch only
+        std::cout << "{\"passes_done\": " << tracer.passes_done << "}" << std::endl;
+        return 0;
+    }
     const double samples = (double)W * H * passes * spp;
     std::cout << "{\"msamples_per_s_kernel\": " << samples / (tracer.last_render_ms * 1e-3) / 1e6 << ", \"kernel_ms\": " << tracer.last_render_ms << "}" << std::endl;
     return 0;

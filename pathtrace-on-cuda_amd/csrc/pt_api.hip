@@ -32,6 +32,11 @@ hipError_t ptk_dbg_pixel_dir(const ptd::DevCamera*, const int*, int, float*, hip
 hipError_t ptk_dbg_nee(const ptd::DevScene*, const float*, int, float*, hipStream_t);
 hipError_t ptk_aov(const ptd::DevScene*, const ptd::DevCamera*, int, int, float*, int*, hipStream_t);
 hipError_t ptk_denoise(const float*, const float*, int, int, int, int, float, float, float, int, float*, void*, hipStream_t);
+hipError_t ptk_stats_fold(const float*, int, long long, int, float*, float*, hipStream_t);
+hipError_t ptk_stats_variance(const float*, long long, int, float*, hipStream_t);
+int ptk_stats_blocks(long long);
+int ptk_stats_partial_bytes(void);
+hipError_t ptk_stats_estimate(const float*, const float*, long long, int, int, int, int, int, int, int, void*, hipStream_t);
 size_t ptk_wf_work_bytes(size_t nUnits, int traceBlocks);
 int ptk_wf_cohorts(size_t nUnits);
 const float* ptk_wf_staging(void* work);
@@ -738,6 +743,120 @@ int pt_denoise_host(int32_t device, const float* h_rgb, const float* h_aov, int3
     };
     rc = body();
     (void)hipFree(d);
+    return rc;
+}
+
+// ---- moments over passes, error estimate, render-to-target (pt_stats.hip) -----------------
+int pt_accumulate_passes(const void* d_work, const PtCamera* cam, const PtParams* prm, int32_t n_before, float* d_sum, float* d_m2,
+                         void* hip_stream)
+{
+    if (!d_work || !d_sum || !d_m2) { pt_set_error("pt_accumulate_passes: NULL argument"); return PT_ERR_INVALID; }
+    if (n_before < 0 || (prm && (long long)n_before + prm->passes > 0x7fffffffLL)) { pt_set_error("pt_accumulate_passes: bad n_before %d", n_before); return PT_ERR_INVALID; }
+    ptd::DevParams d;
+    const int rc = fill_params(cam, prm, d);
+    if (rc) return rc;
+    const long long perPass = (long long)d.n_tiles_local * ptd::kTilePixels * 3;
+    // both render modes leave the per-pass means at the start of the work buffer (pt_render_tiles: what sum_passes reads)
+    HIPCHK(ptk_stats_fold(ptk_wf_staging(const_cast<void*>(d_work)), d.passes, perPass, n_before, d_sum, d_m2, (hipStream_t)hip_stream));
+    return PT_OK;
+}
+
+int pt_variance(const float* d_m2, int64_t n_floats, int32_t n_passes, float* d_var, void* hip_stream)
+{
+    if (!d_m2 || !d_var || n_floats < 1 || n_passes < 2) { pt_set_error("pt_variance: NULL buffer, n_floats < 1 or n_passes < 2"); return PT_ERR_INVALID; }
+    HIPCHK(ptk_stats_variance(d_m2, n_floats, n_passes, d_var, (hipStream_t)hip_stream));
+    return PT_OK;
+}
+
+int64_t pt_error_scratch_bytes(int64_t n_floats)
+{
+    if (n_floats < 1) { pt_set_error("pt_error_scratch_bytes: n_floats < 1"); return -1; }
+    const int64_t nb = (n_floats + 3071) / 3072;
+    return (nb > 1024 ? 1024 : nb) * ptk_stats_partial_bytes();
+}
+
+int pt_error_estimate(const float* d_sum, const float* d_m2, const PtCamera* cam, const PtParams* prm, int32_t n_passes,
+                      void* d_scratch, PtErrorEstimate* h_out, void* hip_stream)
+{
+    if (!d_sum || !d_m2 || !d_scratch || !h_out) { pt_set_error("pt_error_estimate: NULL argument"); return PT_ERR_INVALID; }
+    if (n_passes < 2) { pt_set_error("pt_error_estimate: n_passes %d < 2", n_passes); return PT_ERR_INVALID; }
+    if (!cam || !prm) { pt_set_error("NULL camera/params"); return PT_ERR_INVALID; }
+    PtParams p = *prm; p.passes = 1; p.first_pass = 0;      // only the geometry of the split is read
+    ptd::DevParams d;
+    const int rc = fill_params(cam, &p, d);
+    if (rc) return rc;
+    const long long n = (long long)d.n_tiles_local * ptd::kTilePixels * 3;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    HIPCHK(ptk_stats_estimate(d_sum, d_m2, n, n_passes, cam->W, cam->H, d.tiles_x, d.n_tiles_total, d.rank, d.world, d_scratch, stream));
+    struct Partial { double var, s2, se; long long pixels, skipped; };
+    std::vector<Partial> part((size_t)ptk_stats_blocks(n));
+    if ((int)sizeof(Partial) != ptk_stats_partial_bytes()) { pt_set_error("pt_error_estimate: partial layout mismatch"); return PT_ERR_INVALID; }
+    HIPCHK(hipMemcpyAsync(part.data(), d_scratch, part.size() * sizeof(Partial), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    double var = 0.0, s2 = 0.0, se = 0.0; long long pixels = 0, skipped = 0;
+    for (const Partial& q : part) { var += q.var; s2 += q.s2; se += q.se; pixels += q.pixels; skipped += q.skipped; }      // block order
+    h_out->rel_rms = std::sqrt(var / s2);
+    h_out->mean_rel_se = se / (double)pixels;
+    h_out->pixels = pixels; h_out->skipped = skipped;
+    return PT_OK;
+}
+
+int pt_render_converge(PtScene* s, const PtCamera* cam, const PtParams* prm, double target_rel_rms, int32_t max_passes,
+                       float* h_accum_rgb, float* h_var_rgb, int32_t* passes_done, PtErrorEstimate* est)
+{
+    if (!s || !prm || !h_accum_rgb || !passes_done || !est) { pt_set_error("pt_render_converge: NULL argument"); return PT_ERR_INVALID; }
+    if (max_passes < 2 || !(target_rel_rms >= 0.0)) { pt_set_error("pt_render_converge: max_passes %d < 2 or target not >= 0", max_passes); return PT_ERR_INVALID; }
+    PtParams p = *prm; p.rank = 0; p.world = 1;
+    if (p.passes < 1) { pt_set_error("pt_render_converge: batch of %d passes", p.passes); return PT_ERR_INVALID; }
+    if (p.passes > max_passes) p.passes = max_passes;
+    const int batch = p.passes;
+    const int64_t nt = pt_tiles_floats(cam, &p);
+    int64_t wb = pt_work_bytes(cam, &p);
+    PtParams all = p; all.passes = max_passes;              // the seed limit for the last pass that may be rendered
+    if (nt < 0 || wb < 0 || pt_tiles_floats(cam, &all) < 0) return PT_ERR_INVALID;
+    if (max_passes % batch) {                               // the shortened last batch
+        PtParams q = p; q.passes = max_passes % batch;
+        const int64_t w2 = pt_work_bytes(cam, &q);
+        if (w2 < 0) return PT_ERR_INVALID;
+        if (w2 > wb) wb = w2;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    float *d_tiles = nullptr, *d_sum = nullptr, *d_m2 = nullptr, *d_frame = nullptr; void *d_work = nullptr, *d_scratch = nullptr;
+    const size_t frameBytes = (size_t)cam->W * cam->H * 12;
+    auto body = [&]() -> int {
+        HIPCHK(hipMalloc((void**)&d_tiles, (size_t)nt * 4));
+        HIPCHK(hipMalloc((void**)&d_sum, (size_t)nt * 4));
+        HIPCHK(hipMalloc((void**)&d_m2, (size_t)nt * 4));
+        HIPCHK(hipMalloc(&d_work, (size_t)wb));
+        HIPCHK(hipMalloc(&d_scratch, (size_t)pt_error_scratch_bytes(nt)));
+        HIPCHK(hipMalloc((void**)&d_frame, frameBytes));
+        int done = 0;
+        while (done < max_passes) {
+            p.first_pass = prm->first_pass + done;
+            p.passes = max_passes - done < batch ? max_passes - done : batch;
+            int r = pt_render_tiles(s, cam, &p, d_tiles, d_work, nullptr);
+            if (!r) r = pt_accumulate_passes(d_work, cam, &p, done, d_sum, d_m2, nullptr);
+            if (r) return r;
+            done += p.passes;
+            if (done < 2) continue;
+            r = pt_error_estimate(d_sum, d_m2, cam, &p, done, d_scratch, est, nullptr);
+            if (r) return r;
+            if (est->rel_rms <= target_rel_rms) break;
+        }
+        *passes_done = done;
+        int r = pt_untile(d_sum, cam, 1, d_frame, nullptr);
+        if (r) return r;
+        HIPCHK(hipMemcpy(h_accum_rgb, d_frame, frameBytes, hipMemcpyDeviceToHost));
+        if (h_var_rgb) {
+            r = pt_variance(d_m2, nt, done, d_tiles, nullptr);      // d_tiles is free by now
+            if (!r) r = pt_untile(d_tiles, cam, 1, d_frame, nullptr);
+            if (r) return r;
+            HIPCHK(hipMemcpy(h_var_rgb, d_frame, frameBytes, hipMemcpyDeviceToHost));
+        }
+        return PT_OK;
+    };
+    const int rc = body();
+    (void)hipFree(d_tiles); (void)hipFree(d_sum); (void)hipFree(d_m2); (void)hipFree(d_work); (void)hipFree(d_scratch); (void)hipFree(d_frame);
     return rc;
 }
 

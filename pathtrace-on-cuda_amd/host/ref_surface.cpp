@@ -110,6 +110,7 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
     cam.fovy_deg = camera.fovy; cam.aspect = camera.aspect; cam.W = W; cam.H = H;
 
     std::vector<float> raw((size_t)W * H * 3, 0.f), pass((size_t)W * H * 3);
+    PtParams shown = params;      // the passes the frame holds: the export, the AOVs and the denoiser follow it
     const auto t0 = clk::now();
     last_render_ms = 0.0;
     if (world > 1) {
@@ -125,6 +126,18 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
         float ms = 0.f; pt_last_render_ms(scene, &ms); last_render_ms = ms;
         pt_comm_destroy(comm);
         if (rank != 0) { pt_scene_destroy(scene); return; }
+    } else if (target_error > 0.0) {
+        // batches of params.passes passes until the frame's own error estimate reaches the target
+        const int cap = max_passes > 0 ? max_passes : 8 * params.passes;
+        std::vector<float> var(variance_path.empty() ? 0 : raw.size());
+        PtErrorEstimate est;
+        check(pt_render_converge(scene, &cam, &params, target_error, cap, raw.data(), var.empty() ? nullptr : var.data(), &passes_done, &est),
+              "pt_render_converge");
+        float ms = 0.f; pt_last_render_ms(scene, &ms); last_render_ms = ms;      // the last batch
+        std::cout << "Converge : passes " << passes_done << " of at most " << cap << ", rel_rms " << est.rel_rms << " (target " << target_error
+                  << "), mean_rel_se " << est.mean_rel_se << ", pixels " << est.pixels << ", skipped " << est.skipped << std::endl;
+        write_raw(variance_path, var);
+        shown.passes = passes_done;
     } else if (progressive) {
         // one call per pass, summed in pass order: bit-identical to a single multi-pass call, and temp.png
         // can be rewritten after every pass as the reference does (srcs/pathtracer.cu:236-246)
@@ -142,18 +155,19 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
         check(pt_render(scene, &cam, &params, raw.data()), "pt_render");
         float ms = 0.f; pt_last_render_ms(scene, &ms); last_render_ms = ms;
     }
+    passes_done = shown.passes;
     std::cout << "Delta time : " << std::chrono::duration_cast<std::chrono::milliseconds>(clk::now() - t0).count() << " (ms)" << std::endl;
-    exportImage(img, raw.data(), "result.png", H, W, params.passes);
+    exportImage(img, raw.data(), "result.png", H, W, shown.passes);
     write_raw(raw_path, raw);
     if (!denoise_path.empty() || !aov_path.empty()) {
         // the call's passes: first_pass .. first_pass + passes - 1, the same pixels the frame sums (whole frame, also in a split)
         std::vector<float> aov((size_t)W * H * 8);
-        check(pt_aov(scene, &cam, &params, aov.data(), nullptr), "pt_aov");
+        check(pt_aov(scene, &cam, &shown, aov.data(), nullptr), "pt_aov");
         write_raw(aov_path, aov);
         if (!denoise_path.empty()) {
             std::vector<float> den(raw.size());
-            check(pt_denoise_host(device, raw.data(), aov.data(), W, H, params.passes, &denoise_params, den.data()), "pt_denoise_host");
-            exportImage(img, den.data(), denoise_path.c_str(), H, W, params.passes);
+            check(pt_denoise_host(device, raw.data(), aov.data(), W, H, shown.passes, &denoise_params, den.data()), "pt_denoise_host");
+            exportImage(img, den.data(), denoise_path.c_str(), H, W, shown.passes);
         }
     }
     pt_scene_destroy(scene);

@@ -105,4 +105,12 @@ public:
     // like result.png; `aov_path` receives the raw AOV buffer (W*H*8 float32, row-major).  Empty: nothing changes.
     std::string denoise_path, aov_path;
     PtDenoiseParams denoise_params;
+    // Render to a target (new; include/pt_api.h: pt_render_converge), single process only: when target_error > 0 the frame is
+    // rendered in batches of params.passes passes until the estimated relative RMS error is <= target_error or max_passes
+    // (0 = 8 batches) are in; one line reports the passes used and both estimates, `variance_path` (when non-empty) receives
+    // the per-pixel variance of the frame (W*H*3 float32, row-major), and result.png / the denoiser use passes_done.
+    double target_error = 0.0;
+    int max_passes = 0;
+    std::string variance_path;
+    int passes_done = 0;                    // passes in the frame of the last Render
 };

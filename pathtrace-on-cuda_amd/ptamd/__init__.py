@@ -46,6 +46,10 @@ class PtDenoiseParams(C.Structure):
                 ("demodulate", C.c_int32)]
 
 
+class PtErrorEstimate(C.Structure):
+    _fields_ = [("rel_rms", C.c_double), ("mean_rel_se", C.c_double), ("pixels", C.c_int64), ("skipped", C.c_int64)]
+
+
 AOV_FLOATS = 8        # floats per pixel of pt_render_aov: albedo.rgb | normal.xyz | depth | coverage
 
 _lib = None
@@ -118,6 +122,12 @@ API = [
     ("pt_denoise_work_bytes", C.c_int64, [C.c_int32, C.c_int32]),
     ("pt_denoise", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PtDenoiseParams), _P, _P, _P]),
     ("pt_denoise_host", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PtDenoiseParams), _P]),
+    ("pt_accumulate_passes", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32, _P, _P, _P]),
+    ("pt_variance", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
+    ("pt_error_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("pt_error_estimate", C.c_int, [_P, _P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32, _P, C.POINTER(PtErrorEstimate), _P]),
+    ("pt_render_converge", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_double, C.c_int32, _P, _P, C.POINTER(C.c_int32),
+                                     C.POINTER(PtErrorEstimate)]),
 ]
 
 
@@ -375,6 +385,39 @@ class Scene:
         _check(lib().pt_render_aov(self._h, C.byref(cam), C.byref(prm), C.c_void_p(d_aov_ptr), C.c_void_p(d_prim_ptr or None),
                                    C.c_void_p(stream_ptr)), "pt_render_aov")
 
+    def render_stats(self, cam, prm):
+        """Whole frame with its per-pixel variance across the call's passes (prm.passes >= 2), synchronous: one pt_render_tiles,
+        pt_accumulate_passes, pt_variance and two pt_untile.  Returns ((H, W, 3) float32 frame — bit for bit what render()
+        returns — and (H, W, 3) float32 estimated variance of it).  torch provides the device buffers."""
+        import torch
+        p = PtParams.from_buffer_copy(prm)
+        p.rank, p.world = 0, 1
+        n = tiles_floats(cam, p)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            tiles = torch.empty((3, n), dtype=torch.float32, device=dev)          # frame tiles | S | M2 (then the variance)
+            work = torch.empty(work_bytes(cam, p), dtype=torch.uint8, device=dev)
+            frames = torch.empty((2, cam.H, cam.W, 3), dtype=torch.float32, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            self.render_tiles(cam, p, tiles[0].data_ptr(), work.data_ptr(), st)
+            accumulate_passes(work.data_ptr(), cam, p, 0, tiles[1].data_ptr(), tiles[2].data_ptr(), st)
+            variance(tiles[2].data_ptr(), n, p.passes, tiles[0].data_ptr(), st)
+            untile(tiles[1].data_ptr(), cam, 1, frames[0].data_ptr(), st)
+            untile(tiles[0].data_ptr(), cam, 1, frames[1].data_ptr(), st)
+            out = frames.cpu().numpy()
+        return out[0], out[1]
+
+    def render_converge(self, cam, prm, target_rel_rms, max_passes):
+        """pt_render_converge: batches of prm.passes passes until the estimated relative RMS error is <= target_rel_rms or
+        max_passes are in.  Returns (frame (H, W, 3) float32 = the sum over passes_done passes, variance of it (H, W, 3),
+        passes_done, dict(rel_rms, mean_rel_se, pixels, skipped))."""
+        rgb = np.zeros((cam.H, cam.W, 3), np.float32)
+        var = np.zeros((cam.H, cam.W, 3), np.float32)
+        done, est = C.c_int32(0), PtErrorEstimate()
+        _check(lib().pt_render_converge(self._h, C.byref(cam), C.byref(prm), float(target_rel_rms), int(max_passes), _ptr(rgb), _ptr(var),
+                                        C.byref(done), C.byref(est)), "pt_render_converge")
+        return rgb, var, done.value, _estimate_dict(est)
+
     def raycast(self, rays8):
         rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
         n = rays8.shape[0]
@@ -446,6 +489,38 @@ def denoise_device(d_rgb_ptr, d_aov_ptr, W, H, sample_cnt, d_out_ptr, d_work_ptr
     p = denoise_params(**params)
     _check(lib().pt_denoise(C.c_void_p(d_rgb_ptr), C.c_void_p(d_aov_ptr), W, H, int(sample_cnt), C.byref(p), C.c_void_p(d_out_ptr),
                             C.c_void_p(d_work_ptr), C.c_void_p(stream_ptr)), "pt_denoise")
+
+
+def _estimate_dict(e):
+    return dict(rel_rms=e.rel_rms, mean_rel_se=e.mean_rel_se, pixels=e.pixels, skipped=e.skipped)
+
+
+def accumulate_passes(d_work_ptr, cam, prm, n_before, d_sum_ptr, d_m2_ptr, stream_ptr=0):
+    """pt_accumulate_passes on raw device pointers: folds the prm.passes per-pass means the last render_tiles(cam, prm, ..., d_work)
+    left in d_work into the running moments S, M2 (tiles_floats(cam, prm) floats each); n_before = passes folded in so far."""
+    _check(lib().pt_accumulate_passes(C.c_void_p(d_work_ptr), C.byref(cam), C.byref(prm), int(n_before), C.c_void_p(d_sum_ptr),
+                                      C.c_void_p(d_m2_ptr), C.c_void_p(stream_ptr)), "pt_accumulate_passes")
+
+
+def variance(d_m2_ptr, n_floats, n_passes, d_var_ptr, stream_ptr=0):
+    """pt_variance on raw device pointers: d_var = max(M2, 0) * n / (n - 1), the estimated variance of S."""
+    _check(lib().pt_variance(C.c_void_p(d_m2_ptr), int(n_floats), int(n_passes), C.c_void_p(d_var_ptr), C.c_void_p(stream_ptr)), "pt_variance")
+
+
+def error_scratch_bytes(n_floats):
+    n = lib().pt_error_scratch_bytes(int(n_floats))
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def error_estimate(d_sum_ptr, d_m2_ptr, cam, prm, n_passes, d_scratch_ptr, stream_ptr=0):
+    """pt_error_estimate on raw device pointers (d_scratch: error_scratch_bytes(tiles_floats(cam, prm)) bytes); waits for the
+    stream.  Returns dict(rel_rms, mean_rel_se, pixels, skipped)."""
+    e = PtErrorEstimate()
+    _check(lib().pt_error_estimate(C.c_void_p(d_sum_ptr), C.c_void_p(d_m2_ptr), C.byref(cam), C.byref(prm), int(n_passes),
+                                   C.c_void_p(d_scratch_ptr), C.byref(e), C.c_void_p(stream_ptr)), "pt_error_estimate")
+    return _estimate_dict(e)
 
 
 class Comm:

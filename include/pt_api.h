@@ -322,6 +322,53 @@ PT_API int  pt_render_converge(PtScene* s, const PtCamera* cam, const PtParams* 
                                float* h_accum_rgb, float* h_var_rgb, int32_t* passes_done, PtErrorEstimate* est);
 
 /* ----------------------------------------------------------------------------------
+ * A pixel window or any list of tiles without the full frame (new: the reference renders whole frames only).
+ * Opt-in: every call above is as it was.  A tile is the 8x8 tile of the tile split, numbered row-major over the FULL frame
+ * (tile t covers pixels x = 8 (t % tiles_x) .., y = 8 (t / tiles_x) .., tiles_x = ceil(W / 8)).  Seeds depend on the pixel, the
+ * pass and the full frame's W, H only, so a pixel has the same value whichever call renders it.
+ *
+ * pt_render_tile_list: renders the n_tiles tiles whose numbers are in the HOST array h_tiles, in any order, for passes
+ *   prm->first_pass .. first_pass + passes - 1.  Output is list-major in the layout of pt_render_tiles:
+ *     d_tiles[((i * 64) + (ty*8+tx)) * 3 + c] for list position i, pt_tile_list_floats(n_tiles) floats; value = sum over the
+ *   call's passes of the per-pass mean starting from 0, pixels outside the frame exactly 0 — bit for bit the floats tile
+ *   h_tiles[i] has in pt_render_tiles' buffer.  Checked on the host before any HIP call, else PT_ERR_INVALID: n_tiles >= 1,
+ *   every entry in [0, tiles_x * tiles_y), no entry twice, prm->rank == 0 && prm->world == 1 (a caller splits a frame by making
+ *   lists).  The list is copied into a buffer the scene owns (grown on demand, in stream order) and has been read when the call
+ *   returns.  Otherwise pt_render_tiles' contract: one render at a time per scene, BLOCKING as mode 1 is, all GPU work on
+ *   `hip_stream`; pt_last_render_ms and pt_last_iterations report it.
+ *   Render mode: a list is always rendered by the queue-driven pipeline.  pt_set_mode(0), PTAMD_MODE=0, pt_enable_counters,
+ *   pt_enable_trace_timing and the PTAMD_TSTAT diagnostics do not apply to it and are left as they are for the next pt_render_tiles
+ *   (both modes give the same bits, so nothing is lost).
+ *   Work buffer: d_work is scratch of pt_tile_list_work_bytes() bytes, and the contract of the section above holds for it —
+ *   after the call its start holds the per-pass means, prm->passes x n_tiles x 192 float32, pass-major, each pass in list order
+ *   in the layout of d_tiles, valid until d_work is next written.
+ * pt_tile_list_work_bytes: what the render of that many tiles needs, not the full frame's figure: the pipeline's need depends
+ *   on the number of work units only, so this is pt_work_bytes of any frame that has n_tiles tiles (8 n_tiles x 8 pixels, say)
+ *   with the same prm — a part proportional to n_tiles x passes plus a fixed part sized by the resident traversal grid (1 tile x
+ *   8 passes: 88.9 MB, against 7.94 GB for 1080p x 8 passes).  -1 for arguments pt_render_tile_list would reject.
+ * pt_tiles_of_window (host only): the tiles that overlap the half-open pixel window [x0, x1) x [y0, y1), ascending.  Returns
+ *   their number and writes at most `cap` of them (h_tiles may be NULL when cap is 0); a window that is empty, inverted or not
+ *   inside the frame returns PT_ERR_INVALID.
+ * pt_untile_list: scatters a list-major tile buffer into d_out, a row-major (y1 - y0) x (x1 - x0) x 3 buffer that stands for
+ *   that window of the frame.  Pure copy, bit for bit.  Pixels of the window that no listed tile covers are NOT written, and
+ *   pixels of listed tiles outside the window are dropped: with the whole frame as the window this re-renders a region into a
+ *   frame one already has.  Entries are checked as above (a tile listed twice is merely written twice).  The call waits for
+ *   `hip_stream` once (until the list has been read from h_tiles); the copy itself is asynchronous on it.
+ * pt_render_window: host convenience like pt_render, synchronous; h_rgb[(y1 - y0) * (x1 - x0) * 3] is the window, bit for bit
+ *   pt_render(...)[y0:y1, x0:x1].  prm->rank / world are ignored as pt_render ignores them.
+ * No list variants of pt_render_aov (full frame, 2.9 ms at 1080p), of the denoiser or of the moments calls.
+ * -------------------------------------------------------------------------------- */
+PT_API int64_t pt_tile_list_floats(int32_t n_tiles);                /* 192 * n_tiles, or -1 */
+PT_API int64_t pt_tile_list_work_bytes(const PtCamera* cam, const PtParams* prm, int32_t n_tiles);
+PT_API int  pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, const int32_t* h_tiles, int32_t n_tiles,
+                                float* d_tiles, void* d_work, void* hip_stream);
+PT_API int32_t pt_tiles_of_window(const PtCamera* cam, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t* h_tiles, int32_t cap);
+PT_API int  pt_untile_list(const float* d_tiles, const int32_t* h_tiles, int32_t n_tiles, const PtCamera* cam,
+                           int32_t x0, int32_t y0, int32_t x1, int32_t y1, float* d_out, void* hip_stream);
+PT_API int  pt_render_window(PtScene* s, const PtCamera* cam, const PtParams* prm, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                             float* h_rgb);
+
+/* ----------------------------------------------------------------------------------
  * (a12,a13) Output + camera helpers (host).
  * pt_tonemap_u8 = exportImage (srcs/pathtracer.cu:94-112): /SampleCnt, ACESFilm
  *   (include/CudaUtil.cuh:383-391), ConverToUint8 (include/image.h:5-8).

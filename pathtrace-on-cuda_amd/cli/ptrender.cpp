@@ -16,7 +16,7 @@ static void usage()
         "usage: ptrender [--scene cornell|standin|standin4] [--obj FILE --obj-scale S --obj-translate X,Y,Z]\n"
         "                [--glass-sphere] [--width W] [--height H] [--passes N] [--spp N] [--depth N]\n"
         "                [--lat-lon N] [--device D] [--no-progressive] [--raw FILE] [--denoise FILE.png] [--aov FILE]\n"
-        "                [--target-error E [--max-passes N] [--variance FILE]]\n"
+        "                [--target-error E [--max-passes N] [--variance FILE]] [--window X0,Y0,X1,Y1]\n"
         "                [--world N --rank R --id-file PATH [--job-tag T]]   (one process per GPU; rank 0 writes the frame;\n"
         "                 T = a number the ranks of this job share and other jobs do not, default: the parent process id)\n"
         "Writes temp.png (per pass) and result.png in the current directory, like PathTracer::Render.\n"
@@ -26,6 +26,9 @@ static void usage()
         "--target-error E: renders batches of --passes passes until the frame's estimated relative RMS error is <= E or --max-passes\n"
         "  (default 8 batches) are in, prints the passes used and the estimates; --variance FILE: the per-pixel variance of the frame\n"
         "  (W*H*3 float32).  Single process only; result.png and --denoise use the passes actually rendered.\n"
+        "--window X0,Y0,X1,Y1: renders only the half-open pixel window [X0, X1) x [Y0, Y1) of the frame (the 8x8 tiles that overlap it);\n"
+        "  temp.png, result.png and --raw are the window, pixel for pixel the crop of the full frame's.  Single process, and not with\n"
+        "  --denoise, --aov or --target-error.\n"
         "Defaults: scene cornell, 1920x1080, 8 passes x 64 spp, depth 8.\n";
 }
 
@@ -36,6 +39,7 @@ int main(int argc, char** argv)
     float objScale = 1.f; float objT[3] = {0, 0, 0};
     int W = 1920, H = 1080, passes = 8, spp = 64, depth = 8, latlon = 187, device = 0;
     bool glass = false, progressive = true;
+    int win[4] = {0, 0, 0, 0}; bool windowed = false;
     int rank = 0, world = 1; std::string idFile; unsigned long long jobTag = (unsigned long long)getppid();
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -59,6 +63,7 @@ int main(int argc, char** argv)
         else if (a == "--target-error") targetError = atof(next());
         else if (a == "--max-passes") maxPasses = atoi(next());
         else if (a == "--variance") variancePath = next();
+        else if (a == "--window") { if (sscanf(next(), "%d,%d,%d,%d", &win[0], &win[1], &win[2], &win[3]) != 4) { usage(); return 2; } windowed = true; }
         else if (a == "--world") world = atoi(next());
         else if (a == "--rank") rank = atoi(next());
         else if (a == "--id-file") idFile = next();
@@ -69,6 +74,8 @@ int main(int argc, char** argv)
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && idFile.empty())) { std::cerr << "--world N needs 0 <= --rank < N and --id-file PATH\n"; return 2; }
     if ((maxPasses != 0 || !variancePath.empty()) && !(targetError > 0.0)) { std::cerr << "--max-passes and --variance need --target-error E > 0\n"; return 2; }
     if (targetError > 0.0 && (world > 1 || (maxPasses != 0 && maxPasses < 2))) { std::cerr << "--target-error is single-process and needs --max-passes >= 2\n"; return 2; }
+    if (windowed && (world > 1 || !denoisePath.empty() || !aovPath.empty() || targetError > 0.0)) { std::cerr << "--window is single-process and does not go with --denoise, --aov or --target-error\n"; return 2; }
+    if (windowed && (win[0] < 0 || win[1] < 0 || win[2] > W || win[3] > H || win[0] >= win[2] || win[1] >= win[3])) { std::cerr << "--window X0,Y0,X1,Y1 needs 0 <= X0 < X1 <= width and 0 <= Y0 < Y1 <= height\n"; return 2; }
     const int kind = scene == "cornell" ? 0 : scene == "standin" ? 1 : scene == "standin4" ? 2 : -1;
     if (kind < 0) { std::cerr << "unknown scene " << scene << "\n"; return 2; }
 
@@ -96,13 +103,14 @@ int main(int argc, char** argv)
     tracer.device = device; tracer.progressive = progressive; tracer.raw_path = rawPath;
     tracer.denoise_path = denoisePath; tracer.aov_path = aovPath;
     tracer.target_error = targetError; tracer.max_passes = maxPasses; tracer.variance_path = variancePath;
+    if (windowed) { tracer.window_x0 = win[0]; tracer.window_y0 = win[1]; tracer.window_x1 = win[2]; tracer.window_y1 = win[3]; }
     tracer.rank = rank; tracer.world = world; tracer.id_file = idFile; tracer.job_tag = jobTag;
     tracer.Render(camera, &bvh);
     if (targetError > 0.0) {      // kernel_ms below would be the last batch only
         std::cout << "{\"passes_done\": " << tracer.passes_done << "}" << std::endl;
         return 0;
     }
-    const double samples = (double)W * H * passes * spp;
+    const double samples = (windowed ? (double)(win[2] - win[0]) * (win[3] - win[1]) : (double)W * H) * passes * spp;
     std::cout << "{\"msamples_per_s_kernel\": " << samples / (tracer.last_render_ms * 1e-3) / 1e6 << ", \"kernel_ms\": " << tracer.last_render_ms << "}" << std::endl;
     return 0;
 }

@@ -42,7 +42,7 @@ int ptk_wf_cohorts(size_t nUnits);
 const float* ptk_wf_staging(void* work);
 int ptk_wf_stack_capacity(void);
 hipError_t ptk_wf_render(int, const ptd::DevScene*, const ptd::DevCamera*, const ptd::DevParams*, void*, int, uint32_t*, hipStream_t, hipStream_t*,
-                         hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t*, int*, hipEvent_t*, int, int*, int, int, void*, int);
+                         hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t*, int*, hipEvent_t*, int, int*, int, int, void*, int, const int32_t*);
 }
 
 void pt_set_error(const char* fmt, ...);   // pt_host.cpp
@@ -66,6 +66,8 @@ struct PtScene {
     void* d_lights = nullptr; void* d_spheres = nullptr; void* d_core = nullptr;
     unsigned int* d_unit_counter = nullptr;
     void* d_counters = nullptr;
+    int32_t* d_tile_list = nullptr;      // the tile numbers of the pt_render_tile_list call in flight (grown on demand)
+    int64_t tile_list_cap = 0;           // entries allocated
     int64_t bytes = 0;
     int n_lights = 0;
     int max_depth = 0;
@@ -315,7 +317,7 @@ void pt_scene_destroy(PtScene* s)
 {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    void* p[] = {s->d_nodes, s->d_quad, s->d_tri, s->d_tripair, s->d_leafbox, s->d_surf, s->d_lights, s->d_spheres, s->d_core, s->d_unit_counter, s->d_counters};
+    void* p[] = {s->d_nodes, s->d_quad, s->d_tri, s->d_tripair, s->d_leafbox, s->d_surf, s->d_lights, s->d_spheres, s->d_core, s->d_unit_counter, s->d_counters, s->d_tile_list};
     for (void* q : p) if (q) (void)hipFree(q);
     for (int i = 0; i < PtScene::kEvRing; i++) for (int j = 0; j < 2; j++) if (s->ev[i][j]) (void)hipEventDestroy(s->ev[i][j]);
     if (s->h_poll) (void)hipHostFree(s->h_poll);
@@ -417,7 +419,7 @@ int pt_render_tiles(PtScene* s, const PtCamera* cam, const PtParams* prm, float*
         HIPCHK(ptk_wf_render(s->device, &s->dev, &c, &d, d_work, kTraceBlocks, s->h_poll, stream, s->xstreams,
                              s->ev[slot][0], s->ev[slot][1], s->ev_fork, s->ev_join, &iters,
                              s->trace_ev.empty() ? nullptr : s->trace_ev.data(), (int)s->trace_ev.size() / 3, s->trace_ev_used, s->drain_below, s->shade_rounds,
-                             kTraceStat ? s->d_counters : nullptr, s->early_below));
+                             kTraceStat ? s->d_counters : nullptr, s->early_below, nullptr));
         s->last_iters = iters;
         s->ev_count++;
         HIPCHK(ptk_sum_passes(ptk_wf_staging(d_work), d.passes, perPass, d_tiles, stream));
@@ -436,6 +438,82 @@ int pt_render_tiles(PtScene* s, const PtCamera* cam, const PtParams* prm, float*
     HIPCHK(hipEventRecord(s->ev[slot][1], stream));
     s->ev_count++;
     HIPCHK(ptk_sum_passes((const float*)d_work, d.passes, perPass, d_tiles, stream));
+    return PT_OK;
+}
+
+// ---- a list of tiles instead of a rank's fixed share (csrc/pt_region.hip has the window helpers and the scatter) ----------------
+// DevParams of a list render: a world of one whose "frame" has n_tiles tiles — the pipeline only counts units; the pixels come from the list
+static int fill_list_params(const PtCamera* cam, const PtParams* prm, int32_t n_tiles, ptd::DevParams& d)
+{
+    const int rc = fill_params(cam, prm, d);
+    if (rc) return rc;
+    if (prm->rank != 0 || prm->world != 1) { pt_set_error("a tile list is rendered with rank 0 of world 1 (split a frame by making lists): rank=%d world=%d", prm->rank, prm->world); return PT_ERR_INVALID; }
+    if (n_tiles < 1 || n_tiles > d.n_tiles_total) { pt_set_error("n_tiles=%d: a list holds 1 .. %d tiles of a %dx%d frame", n_tiles, d.n_tiles_total, cam->W, cam->H); return PT_ERR_INVALID; }
+    d.n_tiles_local = n_tiles;
+    d.n_units = n_tiles * prm->passes;      // <= the full frame's, which fill_params has bounded
+    return PT_OK;
+}
+
+int64_t pt_tile_list_floats(int32_t n_tiles)
+{
+    if (n_tiles < 1) { pt_set_error("pt_tile_list_floats: n_tiles=%d", n_tiles); return -1; }
+    return (int64_t)n_tiles * ptd::kTilePixels * 3;
+}
+
+int64_t pt_tile_list_work_bytes(const PtCamera* cam, const PtParams* prm, int32_t n_tiles)
+{
+    ptd::DevParams d;
+    if (fill_list_params(cam, prm, n_tiles, d)) return -1;
+    const int64_t means = (int64_t)d.n_tiles_local * ptd::kTilePixels * 3 * 4 * prm->passes;
+    const int64_t wave = (int64_t)ptk_wf_work_bytes((size_t)d.n_units, kTraceBlocks);
+    return means > wave ? means : wave;
+}
+
+int pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, const int32_t* h_tiles, int32_t n_tiles,
+                        float* d_tiles, void* d_work, void* hip_stream)
+{
+    if (!s || !h_tiles || !d_tiles || !d_work) { pt_set_error("pt_render_tile_list: NULL argument"); return PT_ERR_INVALID; }
+    ptd::DevParams d;
+    int rc = fill_list_params(cam, prm, n_tiles, d);
+    if (rc) return rc;
+    {
+        std::vector<bool> seen((size_t)d.n_tiles_total, false);
+        for (int32_t i = 0; i < n_tiles; i++) {
+            const int32_t t = h_tiles[i];
+            if (t < 0 || t >= d.n_tiles_total) { pt_set_error("pt_render_tile_list: entry %d is tile %d, the frame has tiles 0 .. %d", i, t, d.n_tiles_total - 1); return PT_ERR_INVALID; }
+            if (seen[(size_t)t]) { pt_set_error("pt_render_tile_list: tile %d is listed twice (entry %d)", t, i); return PT_ERR_INVALID; }
+            seen[(size_t)t] = true;
+        }
+    }
+    if (s->n_lights < 1) {
+        pt_set_error("scene has no emissive triangle: the reference's `curand(s) %% Nl` is undefined (include/CudaUtil.cuh:235)");
+        return PT_ERR_NO_LIGHT;
+    }
+    ptd::DevCamera c;
+    fill_camera(cam, c);
+
+    hipStream_t stream = (hipStream_t)hip_stream;
+    HIPCHK(hipSetDevice(s->device));
+    if (s->tile_list_cap < n_tiles) {
+        // the previous list render on this scene has drained (one render at a time per scene), so nothing reads the old buffer
+        if (s->d_tile_list) { HIPCHK(hipFree(s->d_tile_list)); s->d_tile_list = nullptr; s->tile_list_cap = 0; }
+        const int64_t cap = n_tiles < 1024 ? 1024 : n_tiles;
+        HIPCHK(hipMalloc((void**)&s->d_tile_list, (size_t)cap * 4));
+        s->tile_list_cap = cap;
+    }
+    // stream-ordered before wf_init_list; the render below returns only once it has drained, so h_tiles is not read after the call
+    HIPCHK(hipMemcpyAsync(s->d_tile_list, h_tiles, (size_t)n_tiles * 4, hipMemcpyHostToDevice, stream));
+    const int slot = s->ev_count % PtScene::kEvRing;
+    int iters = 0;
+    s->trace_ev_per = 0;
+    for (int k = 0; k < 4; k++) s->trace_ev_used[k] = 0;
+    // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply)
+    HIPCHK(ptk_wf_render(s->device, &s->dev, &c, &d, d_work, kTraceBlocks, s->h_poll, stream, s->xstreams,
+                         s->ev[slot][0], s->ev[slot][1], s->ev_fork, s->ev_join, &iters, nullptr, 0, s->trace_ev_used,
+                         s->drain_below, s->shade_rounds, nullptr, s->early_below, s->d_tile_list));
+    s->last_iters = iters;
+    s->ev_count++;
+    HIPCHK(ptk_sum_passes(ptk_wf_staging(d_work), d.passes, (long long)d.n_tiles_local * ptd::kTilePixels * 3, d_tiles, stream));
     return PT_OK;
 }
 

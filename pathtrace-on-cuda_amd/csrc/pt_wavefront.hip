@@ -151,6 +151,44 @@ void wf_init(DevScene sc, DevCamera cam, DevParams prm, WfBuf b, uint32_t nStrea
     block_append<kLists>(e, ids, c, l, top);
 }
 
+// wf_init_list: wf_init with the tile of local index lt taken from a list (pt_render_tile_list: any n_tiles_local tiles of the frame, in
+// any order) instead of the fixed share lt * world + rank — the one line that differs.  A kernel of its own, with the list as an extra
+// argument and wf_init left as it is: this is the only place of the pipeline that turns a stream into a pixel, from here on a stream is
+// its slot, so wf_trace, wf_shade and wf_drain (and the argument blocks they get by value) are the same for both.
+__global__ __launch_bounds__(256)
+void wf_init_list(DevScene sc, DevCamera cam, DevParams prm, WfBuf b, uint32_t nStreams, const int32_t* __restrict__ tileList)
+{
+    const uint32_t sid = blockIdx.x * 256u + threadIdx.x;
+    bool live = false, camShort = false;
+    if (sid < nStreams) {
+        const uint32_t unit = (uint32_t)prm.unit_base + (sid >> 6), lane = sid & 63;
+        const int pass_rel = (int)(unit / (uint32_t)prm.n_tiles_local);
+        const int lt = (int)(unit % (uint32_t)prm.n_tiles_local);
+        const int tile = tileList[lt];
+        const int tx = tile % prm.tiles_x, ty = tile / prm.tiles_x;
+        const int px = tx * kTile + (int)(lane & 7), py = ty * kTile + (int)(lane >> 3);
+        const int pass = prm.first_pass + pass_rel;
+        live = (tile < prm.n_tiles_total) && (px < cam.W) && (py < cam.H);
+        if (live) {
+            init_stream(cam, prm, b, sid, px, py, pass);
+            const float4 d0 = b.ray_d[0][sid];
+            camShort = ray_is_short(sc, f3(cam.pos[0], cam.pos[1], cam.pos[2]), f3(d0.x, d0.y, d0.z), 3.0e38f);
+        } else {
+            b.staging[3 * (size_t)sid + 0] = 0.f; b.staging[3 * (size_t)sid + 1] = 0.f; b.staging[3 * (size_t)sid + 2] = 0.f;
+        }
+    }
+    // the camera ray: queued by class like every other ray (a pixel that looks past the mesh has a short ray)
+    const bool shortRay = live && camShort;
+    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1: the last entry of a queue array
+    const bool e[kLists] = {live, live && !shortRay, false, false, shortRay, false, false};
+    uint32_t* const c[kLists] = {&b.cnt[0].nActive, &b.cnt[0].nRays[0][0], &b.cnt[0].nRays[1][0], &b.cnt[0].nRays[2][0],
+                                 &b.cnt[0].nRays[0][kShortWord], &b.cnt[0].nRays[1][kShortWord], &b.cnt[0].nRays[2][kShortWord]};
+    uint32_t* const l[kLists] = {b.active[0], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
+    const uint32_t ids[kLists] = {sid, sid, sid, sid, sid, sid, sid};
+    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
+    block_append<kLists>(e, ids, c, l, top);
+}
+
 // ---------------------------------------------------------------------------------------
 // wf_trace: persistent closest-hit kernel with lane refill.
 // Shadow rays (kinds 1 and 2, queue indices >= nPath): the ray only decides whether the closest hit is the sampled light point
@@ -993,7 +1031,7 @@ static const WfTuning& wf_tuning()
 static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::DevCamera* cam, ptd::DevParams prm,
                              ptd::WfBuf b, int traceBlocks, uint32_t* h_cnt, hipStream_t stream,
                              hipEvent_t* trace_ev, int trace_ev_pairs, int* trace_ev_used, int drainBelow, int shadeRounds, int* iters_out, unsigned long long* traceStat,
-                             hipStream_t aux, hipEvent_t* evOvl, int earlyBelow)
+                             hipStream_t aux, hipEvent_t* evOvl, int earlyBelow, const int32_t* tileList)
 {
     using namespace ptd;
     hipError_t e;
@@ -1001,7 +1039,8 @@ static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::Dev
     const size_t nStreams = (size_t)prm.n_units * 64;
     if ((e = hipMemsetAsync(b.cnt, 0, 3 * kWfSlotBytes, stream)) != hipSuccess) return e;
     const int nb = (int)((nStreams + 255) / 256);
-    hipLaunchKernelGGL(wf_init, dim3(nb), dim3(256), 0, stream, *sc, *cam, prm, b, (uint32_t)nStreams);
+    if (tileList) hipLaunchKernelGGL(wf_init_list, dim3(nb), dim3(256), 0, stream, *sc, *cam, prm, b, (uint32_t)nStreams, tileList);
+    else hipLaunchKernelGGL(wf_init, dim3(nb), dim3(256), 0, stream, *sc, *cam, prm, b, (uint32_t)nStreams);
     const int ovfStride = traceBlocks * 256;
     const int tb = traceBlocks < nb ? traceBlocks : nb;
     // every sample needs at most max_bounce + (max_refract + 2) bounces, +1 iteration to retire
@@ -1095,15 +1134,18 @@ static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::Dev
     return hipSuccess;
 }
 
-// Runs the whole pipeline for one pt_render_tiles call.  `stream` is the caller's stream;
+// Runs the whole pipeline for one pt_render_tiles / pt_render_tile_list call.  `stream` is the caller's stream;
 // `xstreams` are up to 3 extra streams owned by the scene; `h_cnt` holds one pinned poll word
 // (64 B apart) per cohort.  ev_begin/ev_end bracket the whole render on `stream`.  trace_ev:
 // optional event triples (before wf_trace, after it, after wf_shade), split evenly between cohorts; trace_ev_used[c] = triples used by cohort c.
+// tileList (device, prm->n_tiles_local global tile numbers; nullptr = the fixed share of prm->rank / world): every cohort's streams
+// are set up by wf_init_list from it; nothing else of the pipeline differs.
 // Blocks the host until the render has drained.
 hipError_t ptk_wf_render(int device, const ptd::DevScene* sc, const ptd::DevCamera* cam, const ptd::DevParams* prm,
                          void* work, int traceBlocks, uint32_t* h_cnt, hipStream_t stream, hipStream_t* xstreams,
                          hipEvent_t ev_begin, hipEvent_t ev_end, hipEvent_t ev_fork, hipEvent_t* ev_join, int* iters_out,
-                         hipEvent_t* trace_ev, int trace_ev_pairs, int* trace_ev_used, int drainBelow, int shadeRounds, void* traceStat, int earlyBelow)
+                         hipEvent_t* trace_ev, int trace_ev_pairs, int* trace_ev_used, int drainBelow, int shadeRounds, void* traceStat, int earlyBelow,
+                         const int32_t* tileList)
 {
     using namespace ptd;
     const size_t nUnits = (size_t)prm->n_units;
@@ -1134,7 +1176,7 @@ hipError_t ptk_wf_render(int device, const ptd::DevScene* sc, const ptd::DevCame
         hipStream_t aux = (C == 1) ? xstreams[0] : nullptr;
         auto job = [=, &rc, &iters]() {
             hipEvent_t evOvl[4] = {ev_fork, ev_join[0], ev_join[1], ev_join[2]};
-            rc[(size_t)c] = run_cohort(device, sc, cam, cp, b, traceBlocks, h_cnt + 16 * c, cs, tev, evPer, used, drainBelow, shadeRounds, &iters[(size_t)c], (unsigned long long*)traceStat, aux, evOvl, earlyBelow);
+            rc[(size_t)c] = run_cohort(device, sc, cam, cp, b, traceBlocks, h_cnt + 16 * c, cs, tev, evPer, used, drainBelow, shadeRounds, &iters[(size_t)c], (unsigned long long*)traceStat, aux, evOvl, earlyBelow, tileList);
         };
         if (C == 1) job(); else th.emplace_back(job);
     }

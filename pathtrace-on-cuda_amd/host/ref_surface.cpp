@@ -90,7 +90,10 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
     using clk = std::chrono::system_clock;
     std::cout << "Camera : " << camera.Screen_W << " x " << camera.Screen_H << std::endl;
     const int W = (int)camera.Screen_W, H = (int)camera.Screen_H;
-    Image img(W, H, 3);
+    const bool windowed = window_x1 > window_x0;
+    // what is exported: the frame, or the window of it that is rendered
+    const int outW = windowed ? window_x1 - window_x0 : W, outH = windowed ? window_y1 - window_y0 : H;
+    Image img(outW, outH, 3);
     LoadFromBVH(bvh);
     std::cout << "Tree on GPU Size : " << CudaBVH.size() << std::endl;
     std::cout << "Prim on GPU Size : " << CudaPrims.size() << std::endl;
@@ -109,7 +112,11 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
     cam.right[0] = r.x; cam.right[1] = r.y; cam.right[2] = r.z;
     cam.fovy_deg = camera.fovy; cam.aspect = camera.aspect; cam.W = W; cam.H = H;
 
-    std::vector<float> raw((size_t)W * H * 3, 0.f), pass((size_t)W * H * 3);
+    std::vector<float> raw((size_t)outW * outH * 3, 0.f), pass((size_t)outW * outH * 3);
+    auto render = [&](const PtParams& p, float* out) {
+        if (windowed) check(pt_render_window(scene, &cam, &p, window_x0, window_y0, window_x1, window_y1, out), "pt_render_window");
+        else check(pt_render(scene, &cam, &p, out), "pt_render");
+    };
     PtParams shown = params;      // the passes the frame holds: the export, the AOVs and the denoiser follow it
     const auto t0 = clk::now();
     last_render_ms = 0.0;
@@ -143,21 +150,21 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
         // can be rewritten after every pass as the reference does (srcs/pathtracer.cu:236-246)
         for (int i = 0; i < params.passes; i++) {
             PtParams p = params; p.passes = 1; p.first_pass = params.first_pass + i;
-            check(pt_render(scene, &cam, &p, pass.data()), "pt_render");
+            render(p, pass.data());
             float ms = 0.f; pt_last_render_ms(scene, &ms); last_render_ms += ms;
             for (size_t k = 0; k < raw.size(); k++) raw[k] += pass[k];
             std::cout << "Sample " << i << " : Delta time : "
                       << std::chrono::duration_cast<std::chrono::milliseconds>(clk::now() - t0).count() << " (ms)" << std::endl;
-            exportImage(img, raw.data(), "temp.png", H, W, i + 1);
+            exportImage(img, raw.data(), "temp.png", outH, outW, i + 1);
             write_raw(raw_path, raw);
         }
     } else {
-        check(pt_render(scene, &cam, &params, raw.data()), "pt_render");
+        render(params, raw.data());
         float ms = 0.f; pt_last_render_ms(scene, &ms); last_render_ms = ms;
     }
     passes_done = shown.passes;
     std::cout << "Delta time : " << std::chrono::duration_cast<std::chrono::milliseconds>(clk::now() - t0).count() << " (ms)" << std::endl;
-    exportImage(img, raw.data(), "result.png", H, W, shown.passes);
+    exportImage(img, raw.data(), "result.png", outH, outW, shown.passes);
     write_raw(raw_path, raw);
     if (!denoise_path.empty() || !aov_path.empty()) {
         // the call's passes: first_pass .. first_pass + passes - 1, the same pixels the frame sums (whole frame, also in a split)

@@ -113,4 +113,8 @@ public:
     int max_passes = 0;
     std::string variance_path;
     int passes_done = 0;                    // passes in the frame of the last Render
+    // Render region (new; include/pt_api.h: pt_render_window), single process only and without the denoiser, the AOVs or a target:
+    // when window_x1 > window_x0 only the half-open pixel window is rendered (the 8x8 tiles that overlap it, not the frame) and
+    // temp.png, result.png and raw_path hold the window — the pixels are those of the full frame's render, bit for bit.
+    int window_x0 = 0, window_y0 = 0, window_x1 = 0, window_y1 = 0;
 };

@@ -128,6 +128,12 @@ API = [
     ("pt_error_estimate", C.c_int, [_P, _P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32, _P, C.POINTER(PtErrorEstimate), _P]),
     ("pt_render_converge", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_double, C.c_int32, _P, _P, C.POINTER(C.c_int32),
                                      C.POINTER(PtErrorEstimate)]),
+    ("pt_tile_list_floats", C.c_int64, [C.c_int32]),
+    ("pt_tile_list_work_bytes", C.c_int64, [C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32]),
+    ("pt_render_tile_list", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), _P, C.c_int32, _P, _P, _P]),
+    ("pt_tiles_of_window", C.c_int32, [C.POINTER(PtCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
+    ("pt_untile_list", C.c_int, [_P, _P, C.c_int32, C.POINTER(PtCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    ("pt_render_window", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
 ]
 
 
@@ -418,6 +424,34 @@ class Scene:
                                         C.byref(done), C.byref(est)), "pt_render_converge")
         return rgb, var, done.value, _estimate_dict(est)
 
+    def render_tile_list_device(self, cam, prm, tiles, d_tiles_ptr, d_work_ptr, stream_ptr=0):
+        """Device-resident render of the listed tiles (global tile numbers, any order; raw device pointers: tile_list_floats(n)
+        floats, tile_list_work_bytes(cam, prm, n) bytes), enqueued on the given stream; blocks until the render has drained
+        (include/pt_api.h: pt_render_tile_list)."""
+        t = _tile_list(tiles)
+        _check(lib().pt_render_tile_list(self._h, C.byref(cam), C.byref(prm), _ptr(t), t.size, C.c_void_p(d_tiles_ptr),
+                                         C.c_void_p(d_work_ptr), C.c_void_p(stream_ptr)), "pt_render_tile_list")
+
+    def render_tile_list(self, cam, prm, tiles):
+        """The listed tiles, synchronous: (n, 8, 8, 3) float32, [i, ty, tx] = pixel (tx, ty) of tile tiles[i]; pixels outside
+        the frame are 0.  torch provides the device buffers."""
+        import torch
+        t = _tile_list(tiles)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            out = torch.empty(tile_list_floats(t.size), dtype=torch.float32, device=dev)
+            work = torch.empty(tile_list_work_bytes(cam, prm, t.size), dtype=torch.uint8, device=dev)
+            self.render_tile_list_device(cam, prm, t, out.data_ptr(), work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            return out.cpu().numpy().reshape(t.size, TILE, TILE, 3)
+
+    def render_window(self, cam, prm, window):
+        """The pixel window (x0, y0, x1, y1), half-open, synchronous: (y1 - y0, x1 - x0, 3) float32, bit for bit
+        render(cam, prm)[y0:y1, x0:x1]; only the tiles that overlap the window are rendered."""
+        x0, y0, x1, y1 = (int(v) for v in window)
+        out = np.zeros((max(y1 - y0, 0), max(x1 - x0, 0), 3), np.float32)
+        _check(lib().pt_render_window(self._h, C.byref(cam), C.byref(prm), x0, y0, x1, y1, _ptr(out)), "pt_render_window")
+        return out
+
     def raycast(self, rays8):
         rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
         n = rays8.shape[0]
@@ -443,6 +477,45 @@ def work_bytes(cam, prm):
 
 def untile(d_gathered_ptr, cam, world, d_frame_ptr, stream_ptr=0):
     _check(lib().pt_untile(C.c_void_p(d_gathered_ptr), C.byref(cam), world, C.c_void_p(d_frame_ptr), C.c_void_p(stream_ptr)), "pt_untile")
+
+
+def _tile_list(tiles):
+    return np.ascontiguousarray(tiles, np.int32).reshape(-1)
+
+
+def tiles_of_window(cam, window):
+    """Global numbers (row-major over the full frame, ascending) of the 8x8 tiles that overlap the half-open pixel window
+    (x0, y0, x1, y1); raises for a window that is empty or not inside the frame."""
+    x0, y0, x1, y1 = (int(v) for v in window)
+    n = lib().pt_tiles_of_window(C.byref(cam), x0, y0, x1, y1, None, 0)
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    out = np.zeros(n, np.int32)
+    lib().pt_tiles_of_window(C.byref(cam), x0, y0, x1, y1, _ptr(out), n)
+    return out
+
+
+def tile_list_floats(n_tiles):
+    n = lib().pt_tile_list_floats(int(n_tiles))
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def tile_list_work_bytes(cam, prm, n_tiles):
+    n = lib().pt_tile_list_work_bytes(C.byref(cam), C.byref(prm), int(n_tiles))
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def untile_list(d_tiles_ptr, tiles, cam, window, d_out_ptr, stream_ptr=0):
+    """Scatter a list-major tile buffer into the row-major buffer of a window of the frame (raw device pointers); pixels of the
+    window that no listed tile covers are left as they are (include/pt_api.h: pt_untile_list)."""
+    t = _tile_list(tiles)
+    x0, y0, x1, y1 = (int(v) for v in window)
+    _check(lib().pt_untile_list(C.c_void_p(d_tiles_ptr), _ptr(t), t.size, C.byref(cam), x0, y0, x1, y1, C.c_void_p(d_out_ptr),
+                                C.c_void_p(stream_ptr)), "pt_untile_list")
 
 
 def aov_floats(cam):

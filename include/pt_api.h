@@ -369,6 +369,46 @@ PT_API int  pt_render_window(PtScene* s, const PtCamera* cam, const PtParams* pr
                              float* h_rgb);
 
 /* ----------------------------------------------------------------------------------
+ * A batch of camera views in one pipeline run (new: the reference renders one camera per call).
+ * Opt-in: every call above is as it was.  Many small frames of one scene (a turntable, multi-view data, thumbnails) rendered one
+ * after the other are bound by launch latency: the number of bounce iterations of a render does not fall with its size.  The
+ * streams of all views of a batch share the iterations of ONE render.
+ *
+ * pt_render_views: renders the n_views cameras in the HOST array h_cams, for passes first .. first + prm->passes - 1 of each view,
+ *   first = h_first_pass[v] (HOST array of n_views entries), or prm->first_pass for every view when h_first_pass is NULL.
+ *   Cameras: all share W and H; pos, forward, up, right, fovy_deg and aspect are free per view.
+ *   Output is view-major: d_tiles[v * T + ...], T = pt_tiles_floats(cam, world 1), pt_views_floats() floats in all.  View v's slice is
+ *   bit for bit the buffer pt_render_tiles(s, &h_cams[v], prm with first_pass = first of v, rank 0, world 1) writes, padding pixels
+ *   of ragged tiles exactly 0, so pt_untile(d_tiles + v * T, &h_cams[v], 1, frame_v, stream) assembles view v's frame.
+ *   Work buffer: d_work is scratch of pt_views_work_bytes() bytes, and the contract of the moments section holds for it — after
+ *   the call its start holds the per-pass means, prm->passes x n_views x T float32, pass-major, within a pass view-major in the
+ *   layout of d_tiles, valid until d_work is next written: a caller can fold moments per view from it.
+ *   Checked on the host before any HIP call, else PT_ERR_INVALID: n_views >= 1, no NULL pointer, equal W, H >= 2 across the views,
+ *   prm->rank == 0 && prm->world == 1, every h_first_pass[v] >= 0, the seed limit of pt_render_tiles for every view's
+ *   first + passes, and a stream count a single frame of that many tiles may have: n_views x tiles x passes work units within
+ *   pt_render_tiles' own limit and 64 x that below 2^31.
+ *   Otherwise pt_render_tile_list's contract: BLOCKING as mode 1 is, one render at a time per scene, all GPU work on `hip_stream`,
+ *   always the queue-driven pipeline (pt_set_mode(0), pt_enable_counters and the PTAMD_TSTAT diagnostics do not apply and are
+ *   left as set for the next pt_render_tiles; pt_enable_trace_timing does apply); pt_last_render_ms and pt_last_iterations report
+ *   it.  pt_set_shade_rounds, pt_set_drain_threshold and pt_set_early_shade act on the batch's stream count as on a frame's.  The
+ *   cameras and first passes are copied into buffers the scene owns (grown on demand, in stream order) and have been read when
+ *   the call returns.
+ * pt_views_floats: n_views * pt_tiles_floats(cam0, world 1), or -1.
+ * pt_views_work_bytes: pt_work_bytes of a frame that has n_views x tiles tiles (8 tiles_x x 8 tiles_y n_views pixels, say) with the
+ *   same prm, as pt_tile_list_work_bytes: the pipeline's need depends on the number of work units only.  -1 for arguments
+ *   pt_render_views would reject.
+ * pt_render_views_host: host convenience like pt_render, synchronous; h_rgb[n_views x H x W x 3], view v = pt_render of h_cams[v].
+ * Out of scope: views of different sizes, views x tile lists, a tile split of a batch over ranks, view variants of pt_render_aov
+ * and the denoiser (call them per view).
+ * -------------------------------------------------------------------------------- */
+PT_API int64_t pt_views_floats(const PtCamera* cam0, int32_t n_views);
+PT_API int64_t pt_views_work_bytes(const PtCamera* cam0, const PtParams* prm, int32_t n_views);
+PT_API int  pt_render_views(PtScene* s, const PtCamera* h_cams, int32_t n_views, const PtParams* prm, const int32_t* h_first_pass,
+                            float* d_tiles, void* d_work, void* hip_stream);
+PT_API int  pt_render_views_host(PtScene* s, const PtCamera* h_cams, int32_t n_views, const PtParams* prm, const int32_t* h_first_pass,
+                                 float* h_rgb);
+
+/* ----------------------------------------------------------------------------------
  * (a12,a13) Output + camera helpers (host).
  * pt_tonemap_u8 = exportImage (srcs/pathtracer.cu:94-112): /SampleCnt, ACESFilm
  *   (include/CudaUtil.cuh:383-391), ConverToUint8 (include/image.h:5-8).

@@ -42,7 +42,8 @@ int ptk_wf_cohorts(size_t nUnits);
 const float* ptk_wf_staging(void* work);
 int ptk_wf_stack_capacity(void);
 hipError_t ptk_wf_render(int, const ptd::DevScene*, const ptd::DevCamera*, const ptd::DevParams*, void*, int, uint32_t*, hipStream_t, hipStream_t*,
-                         hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t*, int*, hipEvent_t*, int, int*, int, int, void*, int, const int32_t*);
+                         hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t*, int*, hipEvent_t*, int, int*, int, int, void*, int, const int32_t*,
+                         const ptd::DevCamera*, const int32_t*, const float4*);
 }
 
 void pt_set_error(const char* fmt, ...);   // pt_host.cpp
@@ -68,6 +69,9 @@ struct PtScene {
     void* d_counters = nullptr;
     int32_t* d_tile_list = nullptr;      // the tile numbers of the pt_render_tile_list call in flight (grown on demand)
     int64_t tile_list_cap = 0;           // entries allocated
+    void* d_views = nullptr;             // the cameras of the pt_render_views call in flight (grown on demand): origins (float4) | DevCamera | first pass (int32), view_cap of each
+    int64_t view_cap = 0;                // views allocated
+    std::vector<char> h_views;           // host image of d_views (the source of its stream-ordered copy)
     int64_t bytes = 0;
     int n_lights = 0;
     int max_depth = 0;
@@ -317,7 +321,7 @@ void pt_scene_destroy(PtScene* s)
 {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    void* p[] = {s->d_nodes, s->d_quad, s->d_tri, s->d_tripair, s->d_leafbox, s->d_surf, s->d_lights, s->d_spheres, s->d_core, s->d_unit_counter, s->d_counters, s->d_tile_list};
+    void* p[] = {s->d_nodes, s->d_quad, s->d_tri, s->d_tripair, s->d_leafbox, s->d_surf, s->d_lights, s->d_spheres, s->d_core, s->d_unit_counter, s->d_counters, s->d_tile_list, s->d_views};
     for (void* q : p) if (q) (void)hipFree(q);
     for (int i = 0; i < PtScene::kEvRing; i++) for (int j = 0; j < 2; j++) if (s->ev[i][j]) (void)hipEventDestroy(s->ev[i][j]);
     if (s->h_poll) (void)hipHostFree(s->h_poll);
@@ -419,7 +423,7 @@ int pt_render_tiles(PtScene* s, const PtCamera* cam, const PtParams* prm, float*
         HIPCHK(ptk_wf_render(s->device, &s->dev, &c, &d, d_work, kTraceBlocks, s->h_poll, stream, s->xstreams,
                              s->ev[slot][0], s->ev[slot][1], s->ev_fork, s->ev_join, &iters,
                              s->trace_ev.empty() ? nullptr : s->trace_ev.data(), (int)s->trace_ev.size() / 3, s->trace_ev_used, s->drain_below, s->shade_rounds,
-                             kTraceStat ? s->d_counters : nullptr, s->early_below, nullptr));
+                             kTraceStat ? s->d_counters : nullptr, s->early_below, nullptr, nullptr, nullptr, nullptr));
         s->last_iters = iters;
         s->ev_count++;
         HIPCHK(ptk_sum_passes(ptk_wf_staging(d_work), d.passes, perPass, d_tiles, stream));
@@ -510,11 +514,148 @@ int pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, co
     // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply)
     HIPCHK(ptk_wf_render(s->device, &s->dev, &c, &d, d_work, kTraceBlocks, s->h_poll, stream, s->xstreams,
                          s->ev[slot][0], s->ev[slot][1], s->ev_fork, s->ev_join, &iters, nullptr, 0, s->trace_ev_used,
-                         s->drain_below, s->shade_rounds, nullptr, s->early_below, s->d_tile_list));
+                         s->drain_below, s->shade_rounds, nullptr, s->early_below, s->d_tile_list, nullptr, nullptr, nullptr));
     s->last_iters = iters;
     s->ev_count++;
     HIPCHK(ptk_sum_passes(ptk_wf_staging(d_work), d.passes, (long long)d.n_tiles_local * ptd::kTilePixels * 3, d_tiles, stream));
     return PT_OK;
+}
+
+// ---- a batch of cameras in one pipeline run -----------------------------------------------------------------------------------------
+// DevParams of a batch: a world of one whose "frame" has n_views x tiles tiles (tiles_x / tiles_y / n_tiles_total stay those of one view:
+// wf_init_views turns a local tile into (view, tile of the view) with them) — the pipeline only counts units.  first_pass: the
+// largest of the batch, so that fill_params' seed limit covers every view (W and H are shared).
+static int fill_views_params(const PtCamera* cam0, const PtParams* prm, int32_t n_views, int32_t max_first_pass, ptd::DevParams& d)
+{
+    if (!cam0 || !prm) { pt_set_error("NULL camera/params"); return PT_ERR_INVALID; }
+    if (n_views < 1) { pt_set_error("n_views=%d: a batch holds at least one view", n_views); return PT_ERR_INVALID; }
+    PtParams p = *prm; p.first_pass = max_first_pass;
+    const int rc = fill_params(cam0, &p, d);
+    if (rc) return rc;
+    if (prm->rank != 0 || prm->world != 1) { pt_set_error("a batch of views is rendered with rank 0 of world 1: rank=%d world=%d", prm->rank, prm->world); return PT_ERR_INVALID; }
+    // what a single frame of that many tiles may have: fill_params' own limit on the units, and 64 streams per unit below 2^31
+    // (bit 31 of a ray-queue entry is the resume flag)
+    const long long units = (long long)n_views * d.n_tiles_total * prm->passes;
+    if (units > 0x7fffffffLL || units * 64 >= (1LL << 31)) {
+        pt_set_error("%d views x %d tiles x %d passes: too many work units for one pipeline run (64 x units must stay below 2^31)", n_views, d.n_tiles_total, prm->passes);
+        return PT_ERR_INVALID;
+    }
+    d.n_tiles_local = n_views * d.n_tiles_total;
+    d.n_units = (int)units;
+    return PT_OK;
+}
+
+int64_t pt_views_floats(const PtCamera* cam0, int32_t n_views)
+{
+    PtParams p; pt_params_default(&p); p.passes = 1; p.first_pass = 0;
+    ptd::DevParams d;
+    if (n_views < 1) { pt_set_error("pt_views_floats: n_views=%d", n_views); return -1; }
+    if (fill_params(cam0, &p, d)) return -1;
+    return (int64_t)n_views * d.n_tiles_total * ptd::kTilePixels * 3;
+}
+
+int64_t pt_views_work_bytes(const PtCamera* cam0, const PtParams* prm, int32_t n_views)
+{
+    ptd::DevParams d;
+    if (fill_views_params(cam0, prm, n_views, prm ? prm->first_pass : 0, d)) return -1;
+    const int64_t means = (int64_t)d.n_tiles_local * ptd::kTilePixels * 3 * 4 * prm->passes;
+    const int64_t wave = (int64_t)ptk_wf_work_bytes((size_t)d.n_units, kTraceBlocks);
+    return means > wave ? means : wave;
+}
+
+// every host-side check of a batch (include/pt_api.h), before any HIP call
+static int views_args(const PtCamera* h_cams, int32_t n_views, const PtParams* prm, const int32_t* h_first_pass, ptd::DevParams& d)
+{
+    if (!h_cams || !prm) { pt_set_error("pt_render_views: NULL argument"); return PT_ERR_INVALID; }
+    if (n_views < 1) { pt_set_error("pt_render_views: n_views=%d", n_views); return PT_ERR_INVALID; }
+    int32_t maxFirst = prm->first_pass;
+    for (int32_t v = 0; v < n_views; v++) {
+        if (h_cams[v].W != h_cams[0].W || h_cams[v].H != h_cams[0].H) {
+            pt_set_error("pt_render_views: view %d is %dx%d, view 0 is %dx%d (all views of a batch share W and H)", v, h_cams[v].W, h_cams[v].H, h_cams[0].W, h_cams[0].H);
+            return PT_ERR_INVALID;
+        }
+        if (h_first_pass) {
+            if (h_first_pass[v] < 0) { pt_set_error("pt_render_views: first_pass of view %d is %d", v, h_first_pass[v]); return PT_ERR_INVALID; }
+            if (v == 0 || h_first_pass[v] > maxFirst) maxFirst = h_first_pass[v];
+        }
+    }
+    return fill_views_params(&h_cams[0], prm, n_views, maxFirst, d);
+}
+
+int pt_render_views(PtScene* s, const PtCamera* h_cams, int32_t n_views, const PtParams* prm, const int32_t* h_first_pass,
+                    float* d_tiles, void* d_work, void* hip_stream)
+{
+    if (!s || !d_tiles || !d_work) { pt_set_error("pt_render_views: NULL argument"); return PT_ERR_INVALID; }
+    ptd::DevParams d;
+    const int rc = views_args(h_cams, n_views, prm, h_first_pass, d);
+    if (rc) return rc;
+    if (s->n_lights < 1) {
+        pt_set_error("scene has no emissive triangle: the reference's `curand(s) %% Nl` is undefined (include/CudaUtil.cuh:235)");
+        return PT_ERR_NO_LIGHT;
+    }
+    hipStream_t stream = (hipStream_t)hip_stream;
+    HIPCHK(hipSetDevice(s->device));
+    if (s->view_cap < n_views) {
+        // the previous batch on this scene has drained (one render at a time per scene), so nothing reads the old buffer
+        if (s->d_views) { HIPCHK(hipFree(s->d_views)); s->d_views = nullptr; s->view_cap = 0; }
+        const int64_t cap = n_views < 64 ? 64 : n_views;
+        HIPCHK(hipMalloc(&s->d_views, (size_t)cap * (16 + sizeof(ptd::DevCamera) + 4)));
+        s->view_cap = cap;
+    }
+    // origins | cameras | first passes, each n_views long, packed for one copy (16-byte entries first: every part stays aligned)
+    const size_t offCam = (size_t)n_views * 16, offFirst = offCam + (size_t)n_views * sizeof(ptd::DevCamera), total = offFirst + (size_t)n_views * 4;
+    s->h_views.resize(total);
+    for (int32_t v = 0; v < n_views; v++) {
+        ptd::DevCamera c;
+        fill_camera(&h_cams[v], c);
+        const float org[4] = {c.pos[0], c.pos[1], c.pos[2], 0.f};
+        const int32_t first = h_first_pass ? h_first_pass[v] : prm->first_pass;
+        memcpy(s->h_views.data() + (size_t)v * 16, org, 16);
+        memcpy(s->h_views.data() + offCam + (size_t)v * sizeof(ptd::DevCamera), &c, sizeof(c));
+        memcpy(s->h_views.data() + offFirst + (size_t)v * 4, &first, 4);
+    }
+    // stream-ordered before wf_init_views; the render below returns only once it has drained, so the callers' arrays are not read after the call
+    HIPCHK(hipMemcpyAsync(s->d_views, s->h_views.data(), total, hipMemcpyHostToDevice, stream));
+    const char* dv = (const char*)s->d_views;
+    const int slot = s->ev_count % PtScene::kEvRing;
+    int iters = 0;
+    s->trace_ev_per = s->trace_ev.empty() ? 0 : (int)(s->trace_ev.size() / 3) / ptk_wf_cohorts((size_t)d.n_units);
+    for (int k = 0; k < 4; k++) s->trace_ev_used[k] = 0;
+    // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply)
+    HIPCHK(ptk_wf_render(s->device, &s->dev, nullptr, &d, d_work, kTraceBlocks, s->h_poll, stream, s->xstreams,
+                         s->ev[slot][0], s->ev[slot][1], s->ev_fork, s->ev_join, &iters,
+                         s->trace_ev.empty() ? nullptr : s->trace_ev.data(), (int)s->trace_ev.size() / 3, s->trace_ev_used,
+                         s->drain_below, s->shade_rounds, nullptr, s->early_below, nullptr,
+                         (const ptd::DevCamera*)(dv + offCam), (const int32_t*)(dv + offFirst), (const float4*)dv));
+    s->last_iters = iters;
+    s->ev_count++;
+    HIPCHK(ptk_sum_passes(ptk_wf_staging(d_work), d.passes, (long long)d.n_tiles_local * ptd::kTilePixels * 3, d_tiles, stream));
+    return PT_OK;
+}
+
+int pt_render_views_host(PtScene* s, const PtCamera* h_cams, int32_t n_views, const PtParams* prm, const int32_t* h_first_pass, float* h_rgb)
+{
+    if (!s || !h_rgb) { pt_set_error("pt_render_views_host: NULL argument"); return PT_ERR_INVALID; }
+    ptd::DevParams d;
+    int rc = views_args(h_cams, n_views, prm, h_first_pass, d);
+    if (rc) return rc;
+    const int64_t nt = pt_views_floats(&h_cams[0], n_views), wb = pt_views_work_bytes(&h_cams[0], prm, n_views);
+    if (nt < 0 || wb < 0) return PT_ERR_INVALID;
+    const size_t perView = (size_t)nt / (size_t)n_views, frame = (size_t)h_cams[0].W * h_cams[0].H * 3;
+    HIPCHK(hipSetDevice(s->device));
+    float *d_tiles = nullptr, *d_frames = nullptr; void* d_work = nullptr;
+    auto body = [&]() -> int {
+        HIPCHK(hipMalloc((void**)&d_tiles, (size_t)nt * 4));
+        HIPCHK(hipMalloc(&d_work, (size_t)wb));
+        HIPCHK(hipMalloc((void**)&d_frames, frame * 4 * (size_t)n_views));
+        int r = pt_render_views(s, h_cams, n_views, prm, h_first_pass, d_tiles, d_work, nullptr);
+        for (int32_t v = 0; v < n_views && !r; v++) r = pt_untile(d_tiles + (size_t)v * perView, &h_cams[v], 1, d_frames + (size_t)v * frame, nullptr);
+        if (!r) HIPCHK(hipMemcpy(h_rgb, d_frames, frame * 4 * (size_t)n_views, hipMemcpyDeviceToHost));
+        return r;
+    };
+    rc = body();
+    (void)hipFree(d_tiles); (void)hipFree(d_work); (void)hipFree(d_frames);
+    return rc;
 }
 
 int pt_untile(const float* d_gathered, const PtCamera* cam, int32_t world, float* d_frame_rgb, void* hip_stream)

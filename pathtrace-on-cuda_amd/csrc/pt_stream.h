@@ -167,6 +167,22 @@ struct WfBuf {
     uint8_t* res;        // per live-list position: what wf_shade's early phase did with the stream (R_* bits)
 };
 
+// A batch of views (pt_render_views): work unit u = pass * n_tiles_local + view * tilesPerView + tile, n_tiles_local = views x tilesPerView,
+// so the view of a stream follows from its slot alone.  The table is an argument of the views kernels only; DevParams, DevCamera,
+// DevScene and WfBuf are what they are for a single camera.
+struct ViewTable {
+    const float4* org;        // camera position of view v: org[v].xyz (n_views x 16 bytes: stays in cache)
+    uint32_t tilesPerView;    // 8x8 tiles of one view's frame
+};
+PT_DEV f3 camera_origin(const DevCamera& cam, const DevParams&, uint32_t) { return f3(cam.pos[0], cam.pos[1], cam.pos[2]); }
+PT_DEV f3 camera_origin(const ViewTable& views, const DevParams& prm, uint32_t sid)
+{
+    const uint32_t unit = (uint32_t)prm.unit_base + (sid >> 6);
+    const uint32_t view = (unit % (uint32_t)prm.n_tiles_local) / views.tilesPerView;
+    const float4 o = views.org[view];
+    return f3(o.x, o.y, o.z);
+}
+
 // StartRender prologue for one pixel & pass (srcs/pathtracer.cu:70-74): seeds the RNG, draws the
 // jittered camera direction and queues the camera ray, whose hit all samples of the pass share.
 PT_DEV void init_stream(const DevCamera& cam, const DevParams& prm, const WfBuf& b, uint32_t slot, int px, int py, int pass)
@@ -298,8 +314,11 @@ PT_DEV bool bounce(const DevScene& sc, const DevParams& prm, int prim, float t, 
 
 // Returns true when the stream has added its last sample to the pixel.  On return st.flags
 // describes the rays to trace next and the ray fields hold them.
-template <bool TWO>
-PT_DEV bool shade_step_t(const DevScene& sc, const DevCamera& cam, const DevParams& prm, const WfBuf& b, uint32_t sid, SState& st,
+// CAM: a DevCamera, or the ViewTable of a batch of views (pt_render_views).  The one thing a stream still needs of its camera after
+// wf_init is the origin of the cached camera ray, where a sample restarts at the cached camera hit (camera_origin): cam.pos, or the
+// view's entry of the batch's origin table, looked up inside that branch — once per sample, not once per step.
+template <bool TWO, class CAM>
+PT_DEV bool shade_step_t(const DevScene& sc, const CAM& cam, const DevParams& prm, const WfBuf& b, uint32_t sid, SState& st,
                          float2 hitP, float2 hitS, float2 hitA)
 {
     const float4* __restrict__ pixPtr = &b.pix[sid];
@@ -370,7 +389,7 @@ PT_DEV bool shade_step_t(const DevScene& sc, const DevCamera& cam, const DevPara
                 }
                 prim = __float_as_int(h0.y); t = h0.x;
                 const float4 d0 = ld_s(dir0Ptr);
-                rorg = f3(cam.pos[0], cam.pos[1], cam.pos[2]); rdir = f3(d0.x, d0.y, d0.z);
+                rorg = camera_origin(cam, prm, sid); rdir = f3(d0.x, d0.y, d0.z);
                 if (prim < 0) {
                     // the pixel looks past the scene: every remaining sample is the ambient term (no draws, no rays)
                     do { st.radiance = f3(0.f, 0.f, 0.f); st.radiance += f3(1.f, 1.f, 1.f) * f3(0.1f, 0.1f, 0.1f); add_to_pixel(st.radiance); } while (--st.toStart > 0);
@@ -429,7 +448,7 @@ PT_DEV bool shade_step_t(const DevScene& sc, const DevCamera& cam, const DevPara
             }
             prim = __float_as_int(h0.y); t = h0.x;
             const float4 d0 = ld_s(dir0Ptr);
-            rorg = f3(cam.pos[0], cam.pos[1], cam.pos[2]); rdir = f3(d0.x, d0.y, d0.z);
+            rorg = camera_origin(cam, prm, sid); rdir = f3(d0.x, d0.y, d0.z);
             if (prim < 0) {
                 // the pixel looks past the scene: every remaining sample is the ambient term (no draws, no rays)
                 do { st.radiance = f3(0.f, 0.f, 0.f); st.radiance += f3(1.f, 1.f, 1.f) * f3(0.1f, 0.1f, 0.1f); add_to_pixel(st.radiance); } while (--st.toStart > 0);
@@ -463,7 +482,8 @@ PT_DEV bool shade_step_t(const DevScene& sc, const DevCamera& cam, const DevPara
     return !cur && !shA && st.toStart == 0;
 }
 
-PT_DEV bool shade_step(const DevScene& sc, const DevCamera& cam, const DevParams& prm, const WfBuf& b, uint32_t sid, SState& st,
+template <class CAM>
+PT_DEV bool shade_step(const DevScene& sc, const CAM& cam, const DevParams& prm, const WfBuf& b, uint32_t sid, SState& st,
                        float2 hitP, float2 hitS, float2 hitA)
 {
     return shade_step_t<true>(sc, cam, prm, b, sid, st, hitP, hitS, hitA);

@@ -189,6 +189,47 @@ void wf_init_list(DevScene sc, DevCamera cam, DevParams prm, WfBuf b, uint32_t n
     block_append<kLists>(e, ids, c, l, top);
 }
 
+// wf_init_views: wf_init for a batch of cameras (pt_render_views).  Local tile lt -> (view = lt / tilesPerView, tile = lt % tilesPerView):
+// the camera comes from a device array, the pass is the view's own first pass + pass_rel.  prm is that of a world of one whose "frame"
+// has n_views x tilesPerView tiles (tiles_x / tiles_y / n_tiles_total are one view's), so the unit and staging arithmetic downstream is
+// what it is for one camera; like wf_init_list a kernel of its own, with wf_init left as it is.
+__global__ __launch_bounds__(256)
+void wf_init_views(DevScene sc, DevParams prm, WfBuf b, uint32_t nStreams, const DevCamera* __restrict__ cams, const int32_t* __restrict__ firstPass,
+                   uint32_t tilesPerView)
+{
+    const uint32_t sid = blockIdx.x * 256u + threadIdx.x;
+    bool live = false, camShort = false;
+    if (sid < nStreams) {
+        const uint32_t unit = (uint32_t)prm.unit_base + (sid >> 6), lane = sid & 63;
+        const int pass_rel = (int)(unit / (uint32_t)prm.n_tiles_local);
+        const uint32_t lt = unit % (uint32_t)prm.n_tiles_local;
+        const uint32_t view = lt / tilesPerView;
+        const int tile = (int)(lt % tilesPerView);
+        const int tx = tile % prm.tiles_x, ty = tile / prm.tiles_x;
+        const int px = tx * kTile + (int)(lane & 7), py = ty * kTile + (int)(lane >> 3);
+        const DevCamera cam = cams[view];
+        const int pass = firstPass[view] + pass_rel;
+        live = (px < cam.W) && (py < cam.H);
+        if (live) {
+            init_stream(cam, prm, b, sid, px, py, pass);
+            const float4 d0 = b.ray_d[0][sid];
+            camShort = ray_is_short(sc, f3(cam.pos[0], cam.pos[1], cam.pos[2]), f3(d0.x, d0.y, d0.z), 3.0e38f);
+        } else {
+            b.staging[3 * (size_t)sid + 0] = 0.f; b.staging[3 * (size_t)sid + 1] = 0.f; b.staging[3 * (size_t)sid + 2] = 0.f;
+        }
+    }
+    // the camera ray: queued by class like every other ray (a pixel that looks past the mesh has a short ray)
+    const bool shortRay = live && camShort;
+    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1: the last entry of a queue array
+    const bool e[kLists] = {live, live && !shortRay, false, false, shortRay, false, false};
+    uint32_t* const c[kLists] = {&b.cnt[0].nActive, &b.cnt[0].nRays[0][0], &b.cnt[0].nRays[1][0], &b.cnt[0].nRays[2][0],
+                                 &b.cnt[0].nRays[0][kShortWord], &b.cnt[0].nRays[1][kShortWord], &b.cnt[0].nRays[2][kShortWord]};
+    uint32_t* const l[kLists] = {b.active[0], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
+    const uint32_t ids[kLists] = {sid, sid, sid, sid, sid, sid, sid};
+    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
+    block_append<kLists>(e, ids, c, l, top);
+}
+
 // ---------------------------------------------------------------------------------------
 // wf_trace: persistent closest-hit kernel with lane refill.
 // Shadow rays (kinds 1 and 2, queue indices >= nPath): the ray only decides whether the closest hit is the sampled light point
@@ -631,82 +672,24 @@ PT_DEV float2 load_hit_coherent(const float2* p)
     return make_float2(__uint_as_float((uint32_t)v), __uint_as_float((uint32_t)(v >> 32)));
 }
 
+// The body of the step is one text (pt_shade_kernel.inc) compiled into two families of kernels: wf_shade for one camera, as it always
+// was, and wf_shade_views for a batch of them (pt_render_views), where `cam` is the batch's ViewTable instead of a DevCamera — all
+// that differs is where a restarted camera ray takes its origin from (pt_stream.h: camera_origin).  Shared as an include, not as a
+// device function both kernels call: with the step moved into a function the compiler allocated and scheduled the twelve existing
+// wf_shade instantiations and wf_drain differently (tools/kernel_isa_diff.sh), and their instruction streams are pinned.
 template <int WAVES, bool TWO, int PHASE = 0, bool MARK = false>
 __global__ __launch_bounds__(WAVES * 256, WAVES)
 void wf_shade(DevScene sc, DevCamera cam, DevParams prm, WfBuf b, int slotIn, int slotOut, int slotClear, int listIn)
 {
-    static_assert(PHASE == 0 || MARK, "the two-phase step needs the not-ready marks");
-    const uint32_t nIn = b.cnt[slotIn].nActive;
-    if (PHASE != 1 && blockIdx.x == 0) for (int k = threadIdx.x; k < kWfSlotBytes / 4; k += blockDim.x) ((uint32_t*)&b.cnt[slotClear])[k] = 0;
-    if ((uint32_t)blockIdx.x * blockDim.x >= nIn) return;
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool have = idx < nIn;
-    bool alive = false, emit[kRayKinds] = {false, false, false};
-    uint32_t sid = 0, resume = 0;      // resume: the queued rays are suspended traversals (wf_trace then reads their records)
-    uint32_t cls = 0;                  // bit k: the ray of kind k this step emitted is short (queued from the back of its queue)
-    bool step = have;
-    if (have) {
-        // While no stream has retired yet (more than half of a render's iterations) every stream is alive, so list position idx can
-        // simply take stream idx: one dependent fetch level less for the whole step (the list itself is in stream order only inside the
-        // blocks that appended to it; any one-to-one assignment of streams to lanes gives the same result).
-        sid = (nIn == (uint32_t)prm.n_units * 64u) ? idx : ld_s(&b.active[listIn][idx]);
-        if (PHASE == 2) {
-            const uint32_t r = b.res[idx];
-            if (r & R_DONE) {      // shaded by phase 1: only the appends are left
-                step = false;
-                alive = (r & R_ALIVE) != 0; emit[0] = (r & R_EMIT0) != 0; emit[1] = (r & R_EMIT1) != 0; emit[2] = (r & R_EMIT2) != 0;
-                cls = (r / R_SHORT0) & 7u;
-            }
-        }
-    }
-    if (step) {
-        SState st;
-        float2 hitP, hitS, hitA;
-        if (PHASE == 1) { hitP = load_hit_coherent(&b.hit[0][sid]); hitS = load_hit_coherent(&b.hit[1][sid]); hitA = load_hit_coherent(&b.hit[2][sid]); }
-        else { hitP = ld_s(&b.hit[0][sid]); hitS = ld_s(&b.hit[1][sid]); hitA = ld_s(&b.hit[2][sid]); }      // same fetch level as the state
-        load_state(b, sid, st);
-        // a ray of this stream is still being traversed (time-sliced): wait one iteration
-        const int pendP = (st.flags & F_PATH) ? __float_as_int(hitP.y) : -1, pendS = (st.flags & F_SHADOW) ? __float_as_int(hitS.y) : -1;
-        const int pendA = (st.flags & F_SHADOWA) ? __float_as_int(hitA.y) : -1;
-        if (PHASE == 1 && (pendP <= -2 || pendS <= -2 || pendA <= -2)) {
-            // phase 1: a ray is not back yet (kNotReady), or a traversal is suspended (its slot keeps the record number until wf_trace
-            // resumes it, so the slot cannot tell "back" from "not yet"): phase 2 takes the stream
-            step = false;
-        } else if (pendP <= -2 || pendS <= -2 || pendA <= -2) {
-            alive = true; emit[0] = pendP <= -2; emit[1] = pendS <= -2; emit[2] = pendA <= -2; resume = kResumeBit;
-        } else {
-            const bool done = shade_step_t<TWO>(sc, cam, prm, b, sid, st, hitP, hitS, hitA);
-            if (done) {
-                write_mean(b, prm, sid, st);
-            } else {
-                const uint32_t nf = st.flags;
-                store_state(b, sid, st);
-                alive = true;
-                emit[0] = (nf & F_PATH) != 0; emit[1] = (nf & F_SHADOW) != 0; emit[2] = (nf & F_SHADOWA) != 0;
-                cls = st.cls;
-            }
-        }
-    }
-    // MARK: the hit slot of every ray this step emitted says "not traced yet" until wf_trace publishes its hit (a suspended traversal
-    // that is re-queued keeps its slot: it holds the record number).  Written here, at the end, where nothing else is live.
-    if (MARK && step && !resume) {
-#pragma unroll
-        for (int k = 0; k < kRayKinds; k++) if (emit[k]) b.hit[k][sid] = make_float2(0.f, __int_as_float(kNotReady));
-    }
-    if (PHASE == 1) {
-        if (have) b.res[idx] = (uint8_t)(step ? (R_DONE | (alive ? R_ALIVE : 0u) | (emit[0] ? R_EMIT0 : 0u) | (emit[1] ? R_EMIT1 : 0u) | (emit[2] ? R_EMIT2 : 0u) | (cls & 7u) * R_SHORT0) : 0u);
-        return;
-    }
-    // a re-queued suspended traversal is long by definition: cls = 0 for it (it never went through the step)
-    const bool s0 = (cls & 1u) != 0, s1 = (cls & 2u) != 0, s2 = (cls & 4u) != 0;
-    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1
-    const bool e[kLists] = {alive, emit[0] && !s0, emit[1] && !s1, emit[2] && !s2, emit[0] && s0, emit[1] && s1, emit[2] && s2};
-    uint32_t* const c[kLists] = {&b.cnt[slotOut].nActive, &b.cnt[slotOut].nRays[0][0], &b.cnt[slotOut].nRays[1][0], &b.cnt[slotOut].nRays[2][0],
-                                 &b.cnt[slotOut].nRays[0][kShortWord], &b.cnt[slotOut].nRays[1][kShortWord], &b.cnt[slotOut].nRays[2][kShortWord]};
-    uint32_t* const l[kLists] = {b.active[listIn ^ 1], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
-    const uint32_t ids[kLists] = {sid, sid | resume, sid | resume, sid | resume, sid, sid, sid};
-    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
-    block_append<kLists>(e, ids, c, l, top);
+#include "pt_shade_kernel.inc"
+}
+
+// Built for 4 waves per SIMD only, the default shape of wf_shade (PTAMD_SW does not apply to a batch).
+template <bool TWO, int PHASE = 0, bool MARK = false>
+__global__ __launch_bounds__(4 * 256, 4)
+void wf_shade_views(DevScene sc, ViewTable cam, DevParams prm, WfBuf b, int slotIn, int slotOut, int slotClear, int listIn)
+{
+#include "pt_shade_kernel.inc"
 }
 
 // ---------------------------------------------------------------------------------------
@@ -787,64 +770,14 @@ template <bool QUAD>      // QUAD: walk the 4-wide tree (quad_step); the host pi
 __global__ __launch_bounds__(kBlockThreads, DRAIN_MINBLOCKS)
 void wf_drain(DevScene sc, DevCamera cam, DevParams prm, WfBuf b, int slotIn, int listIn, int spreadShift)
 {
-    __shared__ int lds_stack[kWavesPerBlock][(QUAD ? kDrainQuadStack : kStackDepth) * 64];
-    const uint32_t nIn = b.cnt[slotIn].nActive;
-    // spreadShift: only every 2^s-th lane carries a stream.  The kernel is bound by latency (a wave steps at the pace of its slowest
-    // lane, every bounce), and the chip is far from full at this point: thinner waves wait for the maximum of fewer paths
-    const uint32_t t = blockIdx.x * (uint32_t)kBlockThreads + threadIdx.x;
-    if (t & ((1u << spreadShift) - 1u)) return;
-    const uint32_t idx = t >> spreadShift;
-    if (idx >= nIn) return;
-    int* stack = &lds_stack[threadIdx.x >> 6][threadIdx.x & 63];
-    const uint32_t sid = b.active[listIn][idx];
-    SState st;
-    load_state(b, sid, st);
-    for (;;) {
-        float2 hitP = make_float2(0.f, __int_as_float(-1)), hitS = hitP, hitA = hitP;
-        TraceStats ts{0, 0, 0};
-        if (QUAD) {
-            // The rays of this bounce (second-to-last shadow ray, shadow ray, path ray: any subset) in ONE flat loop: a lane that has finished a ray
-            // sets up its next one inside the loop, so the wave waits for the lane with the most steps in all — not, as with one
-            // loop per ray kind, for the slowest lane of each kind in turn.
-            int todo = ((st.flags & F_SHADOWA) ? 1 : 0) | ((st.flags & F_SHADOW) ? 2 : 0) | ((st.flags & F_PATH) ? 4 : 0);
-            f3 org(0.f, 0.f, 0.f), dir(0.f, 0.f, 1.f), inv(0.f, 0.f, 0.f);
-            float cscale = 0.f, bestT = 0.f, stopBelow = 0.f;
-            bool degenerate = false;
-            int bestPrim = -1, cur = 0, sp = 0, kind = -1;
-            for (;;) {
-                if (kind < 0) {
-                    if (todo == 0) break;
-                    kind = __builtin_ctz((unsigned)todo); todo &= todo - 1;
-                    if (kind == 0) {
-                        const float4 ao = b.ray_o[2][sid], ad = b.ray_d[2][sid];
-                        org = f3(ao.x, ao.y, ao.z); dir = f3(ad.x, ad.y, ad.z); bestT = ao.w; stopBelow = ad.w;
-                    } else if (kind == 1) { org = st.shO; dir = st.shD; bestT = st.shTmax; stopBelow = shadow_stop_t(st.shO, st.shTmax); }
-                    else { org = st.pathO; dir = st.pathD; bestT = 999999.f; stopBelow = -__builtin_inff(); }
-                    ray_setup(dir, inv, cscale, degenerate);
-                    bestPrim = -1; cur = 0; sp = 0;
-                }
-                if (quad_step(sc, org, dir, inv, cscale, degenerate, stopBelow, stack, cur, sp, bestT, bestPrim)) {
-                    for (int s = 0; s < sc.n_spheres; s++) {      // spheres, in order, against the triangles' closest t (CudaUtil.cuh:137-145)
-                        const float4 c = sc.spheres[4 * s];
-                        float root;
-                        if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; }
-                    }
-                    const float2 h = make_float2(bestT, __int_as_float(bestPrim));
-                    if (kind == 0) hitA = h; else if (kind == 1) hitS = h; else hitP = h;
-                    kind = -1;
-                }
-            }
-        } else {
-        if (st.flags & F_SHADOWA) {
-            const float4 ao = b.ray_o[2][sid], ad = b.ray_d[2][sid];
-            float t; const int prim = trace_closest<false>(sc, f3(ao.x, ao.y, ao.z), f3(ad.x, ad.y, ad.z), ao.w, stack, t, ts); hitA = make_float2(t, __int_as_float(prim));
-        }
-        if (st.flags & F_SHADOW) { float t; const int prim = trace_closest<false>(sc, st.shO, st.shD, st.shTmax, stack, t, ts); hitS = make_float2(t, __int_as_float(prim)); }
-        if (st.flags & F_PATH) { float t; const int prim = trace_closest<false>(sc, st.pathO, st.pathD, 999999.f, stack, t, ts); hitP = make_float2(t, __int_as_float(prim)); }
-        }
-        if (shade_step(sc, cam, prm, b, sid, st, hitP, hitS, hitA)) break;
-    }
-    write_mean(b, prm, sid, st);
+#include "pt_drain_kernel.inc"
+}
+
+template <bool QUAD>      // a batch of views (pt_render_views): `cam` is its ViewTable, as in wf_shade_views
+__global__ __launch_bounds__(kBlockThreads, DRAIN_MINBLOCKS)
+void wf_drain_views(DevScene sc, ViewTable cam, DevParams prm, WfBuf b, int slotIn, int listIn, int spreadShift)
+{
+#include "pt_drain_kernel.inc"
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1031,7 +964,8 @@ static const WfTuning& wf_tuning()
 static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::DevCamera* cam, ptd::DevParams prm,
                              ptd::WfBuf b, int traceBlocks, uint32_t* h_cnt, hipStream_t stream,
                              hipEvent_t* trace_ev, int trace_ev_pairs, int* trace_ev_used, int drainBelow, int shadeRounds, int* iters_out, unsigned long long* traceStat,
-                             hipStream_t aux, hipEvent_t* evOvl, int earlyBelow, const int32_t* tileList)
+                             hipStream_t aux, hipEvent_t* evOvl, int earlyBelow, const int32_t* tileList,
+                             const ptd::DevCamera* viewCams, const int32_t* viewFirstPass, const float4* viewOrg)
 {
     using namespace ptd;
     hipError_t e;
@@ -1039,7 +973,11 @@ static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::Dev
     const size_t nStreams = (size_t)prm.n_units * 64;
     if ((e = hipMemsetAsync(b.cnt, 0, 3 * kWfSlotBytes, stream)) != hipSuccess) return e;
     const int nb = (int)((nStreams + 255) / 256);
-    if (tileList) hipLaunchKernelGGL(wf_init_list, dim3(nb), dim3(256), 0, stream, *sc, *cam, prm, b, (uint32_t)nStreams, tileList);
+    // a batch of views (viewCams != nullptr; cam is then nullptr): its own init kernel, and the views instantiations of wf_shade / wf_drain below
+    const bool batch = viewCams != nullptr;
+    const ViewTable views{viewOrg, (uint32_t)prm.n_tiles_total};
+    if (batch) hipLaunchKernelGGL(wf_init_views, dim3(nb), dim3(256), 0, stream, *sc, prm, b, (uint32_t)nStreams, viewCams, viewFirstPass, views.tilesPerView);
+    else if (tileList) hipLaunchKernelGGL(wf_init_list, dim3(nb), dim3(256), 0, stream, *sc, *cam, prm, b, (uint32_t)nStreams, tileList);
     else hipLaunchKernelGGL(wf_init, dim3(nb), dim3(256), 0, stream, *sc, *cam, prm, b, (uint32_t)nStreams);
     const int ovfStride = traceBlocks * 256;
     const int tb = traceBlocks < nb ? traceBlocks : nb;
@@ -1047,7 +985,7 @@ static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::Dev
     // (time-sliced rays add iterations; 64x is far beyond anything a finite tree can need)
     const long long hardCap = ((long long)prm.spp_per_pass * (prm.max_bounce + prm.max_refract + 3) + 8) * 64;
     const WfTuning& tn = wf_tuning();
-    const int guideShift = tn.guideShift, budgetShift = tn.budgetShift, budgetMin = tn.budgetMin, shadeWaves = tn.shadeWaves, shadeThreads = tn.shadeThreads;
+    const int guideShift = tn.guideShift, budgetShift = tn.budgetShift, budgetMin = tn.budgetMin, shadeWaves = viewCams ? 4 : tn.shadeWaves, shadeThreads = tn.shadeThreads;
     const int earlyPrio = tn.earlyPrio, earlyThreads = tn.earlyThreads, refillMin = tn.refillMin, triTrig = tn.triTrig, chunkShift = tn.chunkShift, topNodes = tn.topNodes;
     const bool pubOnly = tn.pubOnly, traceStatClk = tn.traceStat == 3, traceStatFull = tn.traceStat == 1;
     const uint32_t trStreams = tn.trStreams;
@@ -1089,7 +1027,9 @@ static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::Dev
             if (timed) (void)hipEventRecord(trace_ev[3 * it + 1], stream);
             const dim3 sg((liveBound + shadeThreads - 1) / shadeThreads), sb(shadeThreads);
             const bool twoRounds = shadeRounds >= 0 ? (shadeRounds != 0) : (liveBound < trStreams);
-#define PT_SHADE(W, T, P, M, S) hipLaunchKernelGGL((wf_shade<W, T, P, M>), sg, sb, 0, S, *sc, *cam, prm, b, sIn, sOut, sClr, it & 1)
+            // (a batch: W is not looked at — wf_shade_views exists for 4 waves per SIMD only, and the dispatch below passes 4 for it)
+#define PT_SHADE(W, T, P, M, S) do { if (batch) hipLaunchKernelGGL((wf_shade_views<T, P, M>), sg, sb, 0, S, *sc, views, prm, b, sIn, sOut, sClr, it & 1); \
+                                     else hipLaunchKernelGGL((wf_shade<W, T, P, M>), sg, sb, 0, S, *sc, *cam, prm, b, sIn, sOut, sClr, it & 1); } while (0)
             if (early) {
                 // phase 1 in small workgroups: a 256-thread workgroup needs one free wave slot per SIMD, i.e. two traversal workgroups of
                 // the CU gone, a 512-thread one four — it gets onto the chip earlier in the drain
@@ -1119,7 +1059,9 @@ static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::Dev
             int spread = 0;
             while (spread < tn.drainSpread && ((size_t)h_cnt[0] << (spread + 1)) <= drainLanes) spread++;
             const int db = (int)((((size_t)h_cnt[0] << spread) + kBlockThreads - 1) / kBlockThreads);
-            if (quadWalk) hipLaunchKernelGGL(wf_drain<true>, dim3(db), dim3(kBlockThreads), 0, stream, *sc, *cam, prm, b, it % 3, it & 1, spread);
+            if (batch && quadWalk) hipLaunchKernelGGL(wf_drain_views<true>, dim3(db), dim3(kBlockThreads), 0, stream, *sc, views, prm, b, it % 3, it & 1, spread);
+            else if (batch) hipLaunchKernelGGL(wf_drain_views<false>, dim3(db), dim3(kBlockThreads), 0, stream, *sc, views, prm, b, it % 3, it & 1, spread);
+            else if (quadWalk) hipLaunchKernelGGL(wf_drain<true>, dim3(db), dim3(kBlockThreads), 0, stream, *sc, *cam, prm, b, it % 3, it & 1, spread);
             else hipLaunchKernelGGL(wf_drain<false>, dim3(db), dim3(kBlockThreads), 0, stream, *sc, *cam, prm, b, it % 3, it & 1, spread);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
@@ -1140,12 +1082,15 @@ static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::Dev
 // optional event triples (before wf_trace, after it, after wf_shade), split evenly between cohorts; trace_ev_used[c] = triples used by cohort c.
 // tileList (device, prm->n_tiles_local global tile numbers; nullptr = the fixed share of prm->rank / world): every cohort's streams
 // are set up by wf_init_list from it; nothing else of the pipeline differs.
+// viewCams / viewFirstPass / viewOrg (device, one entry per view; nullptr = one camera): a batch of views (pt_render_views) — cam is
+// nullptr, prm is that of a world of one with n_tiles_local = views x prm->n_tiles_total, streams are set up by wf_init_views and
+// stepped by wf_shade_views / wf_drain_views.
 // Blocks the host until the render has drained.
 hipError_t ptk_wf_render(int device, const ptd::DevScene* sc, const ptd::DevCamera* cam, const ptd::DevParams* prm,
                          void* work, int traceBlocks, uint32_t* h_cnt, hipStream_t stream, hipStream_t* xstreams,
                          hipEvent_t ev_begin, hipEvent_t ev_end, hipEvent_t ev_fork, hipEvent_t* ev_join, int* iters_out,
                          hipEvent_t* trace_ev, int trace_ev_pairs, int* trace_ev_used, int drainBelow, int shadeRounds, void* traceStat, int earlyBelow,
-                         const int32_t* tileList)
+                         const int32_t* tileList, const ptd::DevCamera* viewCams, const int32_t* viewFirstPass, const float4* viewOrg)
 {
     using namespace ptd;
     const size_t nUnits = (size_t)prm->n_units;
@@ -1176,7 +1121,8 @@ hipError_t ptk_wf_render(int device, const ptd::DevScene* sc, const ptd::DevCame
         hipStream_t aux = (C == 1) ? xstreams[0] : nullptr;
         auto job = [=, &rc, &iters]() {
             hipEvent_t evOvl[4] = {ev_fork, ev_join[0], ev_join[1], ev_join[2]};
-            rc[(size_t)c] = run_cohort(device, sc, cam, cp, b, traceBlocks, h_cnt + 16 * c, cs, tev, evPer, used, drainBelow, shadeRounds, &iters[(size_t)c], (unsigned long long*)traceStat, aux, evOvl, earlyBelow, tileList);
+            rc[(size_t)c] = run_cohort(device, sc, cam, cp, b, traceBlocks, h_cnt + 16 * c, cs, tev, evPer, used, drainBelow, shadeRounds, &iters[(size_t)c], (unsigned long long*)traceStat, aux, evOvl, earlyBelow, tileList,
+                                         viewCams, viewFirstPass, viewOrg);
         };
         if (C == 1) job(); else th.emplace_back(job);
     }

@@ -85,6 +85,18 @@ static void write_raw(const std::string& path, const std::vector<float>& raw)
     if (!ok || rename(tmp.c_str(), path.c_str()) != 0) std::cout << "Export failed (" << path << ")" << std::endl;
 }
 
+static PtCamera to_pt_camera(Camera& camera, int W, int H, float aspect)
+{
+    PtCamera cam;
+    const vec3f f = camera.GetForward(), u = camera.GetUp(), r = camera.GetRight();
+    cam.pos[0] = camera.pos.x; cam.pos[1] = camera.pos.y; cam.pos[2] = camera.pos.z;
+    cam.forward[0] = f.x; cam.forward[1] = f.y; cam.forward[2] = f.z;
+    cam.up[0] = u.x; cam.up[1] = u.y; cam.up[2] = u.z;
+    cam.right[0] = r.x; cam.right[1] = r.y; cam.right[2] = r.z;
+    cam.fovy_deg = camera.fovy; cam.aspect = aspect; cam.W = W; cam.H = H;
+    return cam;
+}
+
 void PathTracer::Render(Camera& camera, BVH* bvh)
 {
     using clk = std::chrono::system_clock;
@@ -104,13 +116,29 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
                           CudaSpheres.empty() ? nullptr : CudaSpheres.data(), (int)CudaSpheres.size(), device, &scene), "pt_scene_create");
     for (int i = 0; i < pt_scene_num_lights(scene); i++) std::cout << "ADD light" << std::endl;
     std::cout << "Upload camera configuration on GPU" << std::endl << std::endl << std::endl;
-    PtCamera cam;
-    const vec3f f = camera.GetForward(), u = camera.GetUp(), r = camera.GetRight();
-    cam.pos[0] = camera.pos.x; cam.pos[1] = camera.pos.y; cam.pos[2] = camera.pos.z;
-    cam.forward[0] = f.x; cam.forward[1] = f.y; cam.forward[2] = f.z;
-    cam.up[0] = u.x; cam.up[1] = u.y; cam.up[2] = u.z;
-    cam.right[0] = r.x; cam.right[1] = r.y; cam.right[2] = r.z;
-    cam.fovy_deg = camera.fovy; cam.aspect = camera.aspect; cam.W = W; cam.H = H;
+    PtCamera cam = to_pt_camera(camera, W, H, camera.aspect);
+
+    if (!view_cameras.empty()) {
+        // a batch of views: one pipeline run for all of them, one frame file per view
+        using clk = std::chrono::system_clock;
+        const size_t nv = view_cameras.size(), frame = (size_t)W * H * 3;
+        std::vector<PtCamera> cams;
+        for (Camera& vc : view_cameras) cams.push_back(to_pt_camera(vc, W, H, camera.aspect));
+        std::vector<int32_t> first(view_first_pass.begin(), view_first_pass.end());
+        std::vector<float> frames(nv * frame);
+        const auto t0 = clk::now();
+        check(pt_render_views_host(scene, cams.data(), (int32_t)nv, &params, first.size() == nv ? first.data() : nullptr, frames.data()), "pt_render_views_host");
+        float ms = 0.f; pt_last_render_ms(scene, &ms); last_render_ms = ms;
+        passes_done = params.passes;
+        std::cout << "Delta time : " << std::chrono::duration_cast<std::chrono::milliseconds>(clk::now() - t0).count() << " (ms)" << std::endl;
+        for (size_t v = 0; v < nv; v++) {
+            char tag[16]; snprintf(tag, sizeof tag, "_%03d", (int)v);
+            exportImage(img, frames.data() + v * frame, (std::string("result") + tag + ".png").c_str(), H, W, params.passes);
+            if (!raw_path.empty()) write_raw(raw_path + tag, std::vector<float>(frames.begin() + v * frame, frames.begin() + (v + 1) * frame));
+        }
+        pt_scene_destroy(scene);
+        return;
+    }
 
     std::vector<float> raw((size_t)outW * outH * 3, 0.f), pass((size_t)outW * outH * 3);
     auto render = [&](const PtParams& p, float* out) {

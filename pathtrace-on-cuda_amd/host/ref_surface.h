@@ -117,4 +117,11 @@ public:
     // when window_x1 > window_x0 only the half-open pixel window is rendered (the 8x8 tiles that overlap it, not the frame) and
     // temp.png, result.png and raw_path hold the window — the pixels are those of the full frame's render, bit for bit.
     int window_x0 = 0, window_y0 = 0, window_x1 = 0, window_y1 = 0;
+    // A batch of views (new; include/pt_api.h: pt_render_views), single process only and without a window, a target, the denoiser or
+    // the AOVs: when non-empty, Render renders these cameras (pos, rotation and fovy of each; screen size and aspect are those of
+    // the camera Render is given) in ONE pipeline run and writes result_000.png, result_001.png, ... (and raw_path + "_000", ...)
+    // instead of result.png — each bit for bit what a Render of that camera alone writes.  view_first_pass: one first pass per
+    // view, or empty for params.first_pass.
+    std::vector<Camera> view_cameras;
+    std::vector<int> view_first_pass;
 };

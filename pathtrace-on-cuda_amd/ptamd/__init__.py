@@ -134,6 +134,10 @@ API = [
     ("pt_tiles_of_window", C.c_int32, [C.POINTER(PtCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     ("pt_untile_list", C.c_int, [_P, _P, C.c_int32, C.POINTER(PtCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     ("pt_render_window", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    ("pt_views_floats", C.c_int64, [C.POINTER(PtCamera), C.c_int32]),
+    ("pt_views_work_bytes", C.c_int64, [C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32]),
+    ("pt_render_views", C.c_int, [_P, C.POINTER(PtCamera), C.c_int32, C.POINTER(PtParams), _P, _P, _P, _P]),
+    ("pt_render_views_host", C.c_int, [_P, C.POINTER(PtCamera), C.c_int32, C.POINTER(PtParams), _P, _P]),
 ]
 
 
@@ -452,6 +456,25 @@ class Scene:
         _check(lib().pt_render_window(self._h, C.byref(cam), C.byref(prm), x0, y0, x1, y1, _ptr(out)), "pt_render_window")
         return out
 
+    def render_views_device(self, cams, prm, d_tiles_ptr, d_work_ptr, stream_ptr=0, first_pass=None):
+        """Device-resident render of a batch of cameras of one size in one pipeline run (raw device pointers: views_floats(cams[0],
+        n) floats, view-major, and views_work_bytes(cams[0], prm, n) bytes), enqueued on the given stream; blocks until the render
+        has drained.  first_pass: one first pass per view, or None for prm.first_pass (include/pt_api.h: pt_render_views)."""
+        arr = _camera_array(cams)
+        fp = _first_passes(first_pass, len(arr))
+        _check(lib().pt_render_views(self._h, arr, len(arr), C.byref(prm), _ptr(fp) if fp is not None else None, C.c_void_p(d_tiles_ptr),
+                                     C.c_void_p(d_work_ptr), C.c_void_p(stream_ptr)), "pt_render_views")
+
+    def render_views(self, cams, prm, first_pass=None):
+        """A batch of cameras of one size, synchronous: (V, H, W, 3) float32, [v] bit for bit render(cams[v], prm) (with
+        first_pass[v] as its first pass where given)."""
+        arr = _camera_array(cams)
+        fp = _first_passes(first_pass, len(arr))
+        out = np.zeros((len(arr), arr[0].H, arr[0].W, 3), np.float32)
+        _check(lib().pt_render_views_host(self._h, arr, len(arr), C.byref(prm), _ptr(fp) if fp is not None else None, _ptr(out)),
+               "pt_render_views_host")
+        return out
+
     def raycast(self, rays8):
         rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
         n = rays8.shape[0]
@@ -477,6 +500,36 @@ def work_bytes(cam, prm):
 
 def untile(d_gathered_ptr, cam, world, d_frame_ptr, stream_ptr=0):
     _check(lib().pt_untile(C.c_void_p(d_gathered_ptr), C.byref(cam), world, C.c_void_p(d_frame_ptr), C.c_void_p(stream_ptr)), "pt_untile")
+
+
+def _camera_array(cams):
+    cams = list(cams)
+    if not cams:
+        raise PtError("a batch of views holds at least one camera")
+    return (PtCamera * len(cams))(*cams)
+
+
+def _first_passes(first_pass, n):
+    if first_pass is None:
+        return None
+    fp = np.ascontiguousarray(first_pass, np.int32).reshape(-1)
+    if fp.size != n:
+        raise PtError(f"first_pass has {fp.size} entries for {n} views")
+    return fp
+
+
+def views_floats(cam, n_views):
+    n = lib().pt_views_floats(C.byref(cam), int(n_views))
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def views_work_bytes(cam, prm, n_views):
+    n = lib().pt_views_work_bytes(C.byref(cam), C.byref(prm), int(n_views))
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
 
 
 def _tile_list(tiles):

@@ -409,6 +409,47 @@ PT_API int  pt_render_views_host(PtScene* s, const PtCamera* h_cams, int32_t n_v
                                  float* h_rgb);
 
 /* ----------------------------------------------------------------------------------
+ * Dynamic geometry (new: the reference uploads a scene once).  Opt-in: every call above is as it was.
+ * The triangles of an uploaded scene move without a rebuild: the topology of both traversal trees is kept and every array a
+ * render reads that depends on a vertex is recomputed on the GPU from the new positions (csrc/pt_dynamic.hip).  A render is
+ * defined by the triangles and the reference leaf boxes only — the traversal trees steer the search — so the result is exact:
+ * after an update the scene is, for every entry point, the scene pt_scene_create(nodes', tris', ...) would give.
+ *
+ * pt_scene_update_vertices: d_pos is a DEVICE pointer to n_tris x 9 float32, V0 V1 V2 of every triangle in the order of the
+ *   `tris` array given to pt_scene_create.  d_frames is a DEVICE pointer to n_tris x 27 float32, N0 N1 N2 T0 T1 T2 B0 B1 B2
+ *   (floats 9..35 of the surface record), stored as given (the caller normalises), or NULL: the shading frames are kept.
+ *   tris' = tris with, in float32, every operation rounded once, in this order: V0 V1 V2 from d_pos; E1 = V1 - V0, E2 = V2 - V0;
+ *   c = (E1y E2z - E1z E2y, -(E1x E2z - E1z E2x), E1x E2y - E1y E2x); len = sqrt((cx cx + cy cy) + cz cz); normal = c / len;
+ *   area = len * 0.5f; the frames, if given.  nodes' = nodes with every leaf's box the min / max over its triangles in index
+ *   order, mn = min2(mn, min2(a, min2(b, c))), min2(a, b) = b < a ? b : a, starting from FLT_MAX / lowest, and every interior box
+ *   min2 / max2 of its children (childR first).  Positions must be finite; a zero-area triangle gets a NaN normal as on the host.
+ *   Materials, uv, the topology of both trees, the number of triangles and the set of emissive triangles stay as uploaded.
+ *   Every kernel is enqueued on `hip_stream` on the scene's device; no host synchronisation, nothing is read back, and nothing
+ *   is allocated after the first call (which allocates and uploads the maps of the build: pt_scene_device_bytes includes them
+ *   from then on).  A render enqueued on the same stream afterwards sees the new geometry; d_pos / d_frames must stay valid
+ *   until the stream has passed the update.  One update or render at a time per scene.
+ * pt_scene_update_vertices_host: h_pos / h_frames are HOST arrays; uploads them, updates on the NULL stream and waits.
+ * pt_scene_update_spheres: a HOST array of the scene's sphere count; centre and radius may change, the material bytes must be
+ *   those uploaded (else PT_ERR_INVALID).  A stream-ordered copy on the NULL stream.
+ * pt_scene_tree_inflation: *ratio = sum of the surface areas (float32 each, summed in float64 in a fixed order) of all boxes of
+ *   the binary traversal tree now / the same sum at upload: the caller's signal that refits have degraded the tree and a new
+ *   pt_scene_create is due.  Exactly 1.0 for a scene never updated.  Otherwise waits for the whole device (hipDeviceSynchronize: the
+ *   stream of the last update need not exist any more) and reduces on the NULL stream.
+ * pt_dbg_scene_array (parity hook, tests only): copies one device array of the scene to the host after a device synchronisation;
+ *   which = 0 nodes, 1 quad, 2 tri, 3 tripair, 4 leafbox, 5 surf, 6 lights, 7 spheres, 8 core (0 bytes if none; layouts:
+ *   csrc/pt_device.h).  Returns the array's size in bytes and writes at most cap_bytes (h_out may be NULL when cap_bytes is 0).
+ * NULL scene, NULL d_pos / h_pos / h_spheres / ratio, n_spheres different from the scene's and an unknown `which` return
+ * PT_ERR_INVALID before any HIP call.
+ * Out of scope: a change of the triangle count, the materials or the set of emissive triangles; a rebuild on the GPU or an
+ * automatic one; a tile-split update (every rank updates its own scene).
+ * -------------------------------------------------------------------------------- */
+PT_API int  pt_scene_update_vertices(PtScene* s, const float* d_pos, const float* d_frames, void* hip_stream);
+PT_API int  pt_scene_update_vertices_host(PtScene* s, const float* h_pos, const float* h_frames);
+PT_API int  pt_scene_update_spheres(PtScene* s, const PtSphere* h_spheres, int32_t n_spheres);
+PT_API int  pt_scene_tree_inflation(PtScene* s, double* ratio);
+PT_API int64_t pt_dbg_scene_array(PtScene* s, int32_t which, void* h_out, int64_t cap_bytes);
+
+/* ----------------------------------------------------------------------------------
  * (a12,a13) Output + camera helpers (host).
  * pt_tonemap_u8 = exportImage (srcs/pathtracer.cu:94-112): /SampleCnt, ACESFilm
  *   (include/CudaUtil.cuh:383-391), ConverToUint8 (include/image.h:5-8).

@@ -17,6 +17,7 @@
 #include "../../include/pt_api.h"
 #include "pt_device.h"
 #include "../host/accel_build.h"
+#include "pt_dynamic.h"
 
 extern "C" {
 hipError_t ptk_render_units(const ptd::DevScene*, const ptd::DevCamera*, const ptd::DevParams*, float*, unsigned int*, void*, int, int, hipStream_t);
@@ -96,6 +97,20 @@ struct PtScene {
     static constexpr int kEvRing = 64;
     hipEvent_t ev[kEvRing][2] = {};
     int ev_count = 0;        // launches recorded since the last pt_render_timings(reset)
+    // ---- dynamic geometry (pt_scene_update_vertices, csrc/pt_dynamic.hip) ----
+    size_t array_bytes[9] = {};          // nodes quad tri tripair leafbox surf lights spheres core, as uploaded (pt_dbg_scene_array)
+    std::vector<float> h_spheres;        // the uploaded sphere records: pt_scene_update_spheres checks the materials against them and copies from here
+    struct DynHost {                     // the maps of the build, kept on the host until the first update uploads them
+        std::vector<int32_t> bn, order, level_start, wide_bn, quad_bn, leaf_range, tmap, light_prim;
+        std::vector<uint8_t> small;
+        double area_sum = 0.0;
+    } dyn_host;
+    ptd::DynScene dyn{};                 // device side of the same, valid once dyn_ready
+    static constexpr int kDynAllocs = 12;    // 8 maps (bn order wide_bn quad_bn leaf_range tmap light_prim small) + 4 scratch (bbox maxabs core_partial area_partial)
+    void* d_dyn[kDynAllocs] = {};        // its allocations, in that order (dyn_prepare)
+    bool dyn_ready = false;
+    bool updated = false;
+    std::vector<double> h_area;          // host image of dyn.area_partial
 };
 
 static int upload(void** dptr, const void* h, size_t bytes, int64_t& total)
@@ -201,6 +216,7 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
 
     // ---- triangles: surface records (reference order), lights ----
     std::vector<float> surf((size_t)n_tris * 48), lights;
+    std::vector<int32_t> light_prim;          // reference-order triangle of every light (for a vertex update)
     int n_lights = 0;
     for (int i = 0; i < n_tris; i++) {
         const PtTriangle& t = tris[i];
@@ -216,6 +232,7 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
             const float rec[16] = {t.V0[0], t.V0[1], t.V0[2], t.V1[0], t.V1[1], t.V1[2], t.V2[0], t.V2[1], t.V2[2],
                                    t.normal[0], t.normal[1], t.normal[2], t.area, 0.f, 0.f, 0.f};
             lights.insert(lights.end(), rec, rec + 16);
+            light_prim.push_back(i);
             n_lights++;
         }
     }
@@ -232,6 +249,7 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
     // segment misses it can only meet the few big triangles, i.e. is short, and wf_shade queues such rays last (pt_stream.h:
     // ray_is_short) so that the traversal kernel's launch tail consists of short rays.  Scheduling only — any box gives the same frame.
     std::vector<float> core;
+    std::vector<uint8_t> small;               // per triangle: inside the core box's set (for a vertex update)
     {
         float smn[3] = {1e30f, 1e30f, 1e30f}, smx[3] = {-1e30f, -1e30f, -1e30f};
         auto tribox = [&](const PtTriangle& t, float* mn, float* mx) {
@@ -244,7 +262,7 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
         for (int i = 0; i < n_tris; i++) {
             float mn[3], mx[3]; tribox(tris[i], mn, mx);
             const float dd = std::sqrt((mx[0] - mn[0]) * (mx[0] - mn[0]) + (mx[1] - mn[1]) * (mx[1] - mn[1]) + (mx[2] - mn[2]) * (mx[2] - mn[2]));
-            if (dd * 8.f < sd) { nSmall++; for (int k = 0; k < 3; k++) { cmn[k] = std::fmin(cmn[k], mn[k]); cmx[k] = std::fmax(cmx[k], mx[k]); } }
+            if (dd * 8.f < sd) { if (small.empty()) small.assign((size_t)n_tris, 0); small[(size_t)i] = 1; nSmall++; for (int k = 0; k < 3; k++) { cmn[k] = std::fmin(cmn[k], mn[k]); cmx[k] = std::fmax(cmx[k], mx[k]); } }
         }
         const double sv = (double)(smx[0] - smn[0]) * (smx[1] - smn[1]) * (smx[2] - smn[2]);
         const double cv = nSmall ? (double)(cmx[0] - cmn[0]) * (cmx[1] - cmn[1]) * (cmx[2] - cmn[2]) : 0.0;
@@ -313,6 +331,18 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
     sc->dev.core = (const float*)sc->d_core;      // nullptr: no queue order by ray class
     sc->dev.nee_prune = (emitOk && !(getenv("PTAMD_PRUNE") && atoi(getenv("PTAMD_PRUNE")) == 0)) ? 1 : 0;      // PTAMD_PRUNE=0: A/B only
     sc->dev.n_nodes = n_wide; sc->dev.n_tris = n_tris; sc->dev.n_lights = n_lights; sc->dev.n_spheres = n_spheres;
+    // what a vertex update needs later: the sizes, the sphere records and the maps of the build (uploaded by the first update)
+    const size_t ab[9] = {accel.wide.size() * 4, accel.quad.size() * 4, accel.tri.size() * 4, accel.tripair.size() * 4, accel.leafbox.size() * 4,
+                          surf.size() * 4, lights.size() * 4, sph.size() * 4, core.size() * 4};
+    memcpy(sc->array_bytes, ab, sizeof(ab));
+    sc->h_spheres.swap(sph);
+    PtScene::DynHost& dh = sc->dyn_host;
+    dh.bn.swap(accel.bn); dh.order.swap(accel.order); dh.level_start.swap(accel.level_start); dh.wide_bn.swap(accel.wide_bn);
+    dh.quad_bn.swap(accel.quad_bn); dh.leaf_range.swap(accel.leaf_range); dh.tmap.swap(accel.tmap); dh.light_prim.swap(light_prim);
+    if (!core.empty()) dh.small.swap(small);
+    dh.area_sum = accel.area_sum;
+    sc->dyn.n_bn = (int32_t)(dh.bn.size() / 4); sc->dyn.n_wide = n_wide; sc->dyn.n_quad = accel.n_quad; sc->dyn.n_tris = n_tris;
+    sc->dyn.n_leaves = accel.n_leaves; sc->dyn.n_lights = n_lights;
     *out = sc;
     return PT_OK;
 }
@@ -323,6 +353,7 @@ void pt_scene_destroy(PtScene* s)
     (void)hipSetDevice(s->device);
     void* p[] = {s->d_nodes, s->d_quad, s->d_tri, s->d_tripair, s->d_leafbox, s->d_surf, s->d_lights, s->d_spheres, s->d_core, s->d_unit_counter, s->d_counters, s->d_tile_list, s->d_views};
     for (void* q : p) if (q) (void)hipFree(q);
+    for (void* q : s->d_dyn) if (q) (void)hipFree(q);
     for (int i = 0; i < PtScene::kEvRing; i++) for (int j = 0; j < 2; j++) if (s->ev[i][j]) (void)hipEventDestroy(s->ev[i][j]);
     if (s->h_poll) (void)hipHostFree(s->h_poll);
     for (int i = 0; i < 3; i++) { if (s->xstreams[i]) (void)hipStreamDestroy(s->xstreams[i]); if (s->ev_join[i]) (void)hipEventDestroy(s->ev_join[i]); }
@@ -1077,6 +1108,137 @@ int pt_render_converge(PtScene* s, const PtCamera* cam, const PtParams* prm, dou
     const int rc = body();
     (void)hipFree(d_tiles); (void)hipFree(d_sum); (void)hipFree(d_m2); (void)hipFree(d_work); (void)hipFree(d_scratch); (void)hipFree(d_frame);
     return rc;
+}
+
+// ---- dynamic geometry (csrc/pt_dynamic.hip) ----------------------------------------------------------------------------------
+// First update of a scene: the maps of the build go to the device and the scratch is allocated; the host copies are dropped.
+static int dyn_prepare(PtScene* s)
+{
+    if (s->dyn_ready) return PT_OK;
+    PtScene::DynHost& h = s->dyn_host;
+    ptd::DynScene& d = s->dyn;
+    int k = 0, rc;
+    const int64_t bytes_before = s->bytes;
+    auto up = [&](const void* src, size_t bytes, const void** dst) -> int {
+        if ((rc = upload(&s->d_dyn[k], src, bytes, s->bytes)) != PT_OK) return rc;
+        *dst = s->d_dyn[k++];
+        return PT_OK;
+    };
+    auto scratch = [&](size_t bytes, void** dst) -> int {
+        HIPCHK(hipMalloc(&s->d_dyn[k], bytes));
+        s->bytes += (int64_t)bytes;
+        *dst = s->d_dyn[k++];
+        return PT_OK;
+    };
+    const size_t area_blocks = ((size_t)d.n_bn + kAreaBlock - 1) / kAreaBlock;
+    if ((rc = up(h.bn.data(), h.bn.size() * 4, (const void**)&d.bn)) || (rc = up(h.order.data(), h.order.size() * 4, (const void**)&d.order)) ||
+        (rc = up(h.wide_bn.data(), h.wide_bn.size() * 4, (const void**)&d.wide_bn)) || (rc = up(h.quad_bn.data(), h.quad_bn.size() * 4, (const void**)&d.quad_bn)) ||
+        (rc = up(h.leaf_range.data(), h.leaf_range.size() * 4, (const void**)&d.leaf_range)) || (rc = up(h.tmap.data(), h.tmap.size() * 4, (const void**)&d.tmap)) ||
+        (rc = up(h.light_prim.data(), h.light_prim.size() * 4, (const void**)&d.light_prim)) ||
+        (!h.small.empty() && (rc = up(h.small.data(), h.small.size(), (const void**)&d.small))) ||
+        (rc = scratch((size_t)d.n_bn * 32, (void**)&d.bbox)) || (rc = scratch(16, (void**)&d.maxabs)) ||
+        (rc = scratch((size_t)ptd::kCoreBlocks * 32, (void**)&d.core_partial)) || (rc = scratch(area_blocks * 8, (void**)&d.area_partial)))
+    {
+        // leave the scene as it was before the call: a later update may try again
+        for (void*& q : s->d_dyn) if (q) { (void)hipFree(q); q = nullptr; }
+        s->bytes = bytes_before;
+        return rc;
+    }
+    d.nodes = (float4*)s->d_nodes; d.quad = (uint4*)s->d_quad; d.tri = (float4*)s->d_tri; d.tripair = (float4*)s->d_tripair;
+    d.leafbox = (float4*)s->d_leafbox; d.surf = (float4*)s->d_surf; d.lights = (float4*)s->d_lights; d.core = (float*)s->d_core;
+    s->h_area.assign(area_blocks, 0.0);
+    for (std::vector<int32_t>* v : {&h.bn, &h.order, &h.wide_bn, &h.quad_bn, &h.leaf_range, &h.tmap, &h.light_prim}) std::vector<int32_t>().swap(*v);
+    std::vector<uint8_t>().swap(h.small);      // level_start stays: the launch sequence reads it
+    s->dyn_ready = true;
+    return PT_OK;
+}
+
+int pt_scene_update_vertices(PtScene* s, const float* d_pos, const float* d_frames, void* hip_stream)
+{
+    if (!s || !d_pos) { pt_set_error("pt_scene_update_vertices: NULL %s", !s ? "scene" : "d_pos"); return PT_ERR_INVALID; }
+    HIPCHK(hipSetDevice(s->device));
+    int rc;
+    if ((rc = dyn_prepare(s)) != PT_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(ptk_dyn_update(&s->dyn, d_pos, d_frames, s->dyn_host.level_start.data(), (int)s->dyn_host.level_start.size() - 1, st));
+    s->updated = true;
+    return PT_OK;
+}
+
+int pt_scene_update_vertices_host(PtScene* s, const float* h_pos, const float* h_frames)
+{
+    if (!s || !h_pos) { pt_set_error("pt_scene_update_vertices_host: NULL %s", !s ? "scene" : "h_pos"); return PT_ERR_INVALID; }
+    HIPCHK(hipSetDevice(s->device));
+    const size_t n = (size_t)s->dev.n_tris;
+    float *d_pos = nullptr, *d_frames = nullptr;
+    auto body = [&]() -> int {
+        HIPCHK(hipMalloc((void**)&d_pos, n * 36));
+        HIPCHK(hipMemcpy(d_pos, h_pos, n * 36, hipMemcpyHostToDevice));
+        if (h_frames) {
+            HIPCHK(hipMalloc((void**)&d_frames, n * 108));
+            HIPCHK(hipMemcpy(d_frames, h_frames, n * 108, hipMemcpyHostToDevice));
+        }
+        const int rc = pt_scene_update_vertices(s, d_pos, d_frames, nullptr);
+        if (rc != PT_OK) return rc;
+        HIPCHK(hipStreamSynchronize(nullptr));
+        return PT_OK;
+    };
+    const int rc = body();
+    (void)hipFree(d_pos); (void)hipFree(d_frames);
+    return rc;
+}
+
+int pt_scene_update_spheres(PtScene* s, const PtSphere* h_spheres, int32_t n_spheres)
+{
+    if (!s || !h_spheres) { pt_set_error("pt_scene_update_spheres: NULL %s", !s ? "scene" : "h_spheres"); return PT_ERR_INVALID; }
+    if (n_spheres != s->dev.n_spheres || n_spheres < 1) {
+        pt_set_error("pt_scene_update_spheres: %d spheres given, the scene has %d", n_spheres, s->dev.n_spheres);
+        return PT_ERR_INVALID;
+    }
+    for (int i = 0; i < n_spheres; i++)
+        if (memcmp(&h_spheres[i].mat, &s->h_spheres[(size_t)i * 16 + 4], sizeof(PtMaterial)) != 0) {
+            pt_set_error("pt_scene_update_spheres: the material of sphere %d differs from the uploaded one (only centre and radius may change)", i);
+            return PT_ERR_INVALID;
+        }
+    HIPCHK(hipSetDevice(s->device));
+    for (int i = 0; i < n_spheres; i++) {
+        float* a = &s->h_spheres[(size_t)i * 16];
+        a[0] = h_spheres[i].center[0]; a[1] = h_spheres[i].center[1]; a[2] = h_spheres[i].center[2]; a[3] = h_spheres[i].rad;
+    }
+    HIPCHK(hipMemcpy(s->d_spheres, s->h_spheres.data(), (size_t)n_spheres * 64, hipMemcpyHostToDevice));      // ordered on the NULL stream
+    return PT_OK;
+}
+
+int pt_scene_tree_inflation(PtScene* s, double* ratio)
+{
+    if (!s || !ratio) { pt_set_error("pt_scene_tree_inflation: NULL %s", !s ? "scene" : "ratio"); return PT_ERR_INVALID; }
+    *ratio = 1.0;
+    if (!s->updated) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());      // the stream of the last update may be gone by now: wait for the device, reduce on the NULL stream
+    HIPCHK(ptk_dyn_area(&s->dyn, nullptr));
+    HIPCHK(hipMemcpy(s->h_area.data(), s->dyn.area_partial, s->h_area.size() * 8, hipMemcpyDeviceToHost));
+    double sum = 0.0;
+    for (double v : s->h_area) sum += v;      // block sums in index order (host/accel_build.cpp: pt_accel_area_sum)
+    *ratio = sum / s->dyn_host.area_sum;
+    return PT_OK;
+}
+
+int64_t pt_dbg_scene_array(PtScene* s, int32_t which, void* h_out, int64_t cap_bytes)
+{
+    if (!s || which < 0 || which > 8 || cap_bytes < 0 || (cap_bytes > 0 && !h_out)) {
+        pt_set_error("pt_dbg_scene_array: %s", !s ? "NULL scene" : (which < 0 || which > 8) ? "which must be 0..8" : "bad output buffer");
+        return PT_ERR_INVALID;
+    }
+    void* const src[9] = {s->d_nodes, s->d_quad, s->d_tri, s->d_tripair, s->d_leafbox, s->d_surf, s->d_lights, s->d_spheres, s->d_core};
+    const int64_t size = (int64_t)s->array_bytes[which];
+    const int64_t n = size < cap_bytes ? size : cap_bytes;
+    if (n > 0) {
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(h_out, src[which], (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return size;
 }
 
 // ---- parity hooks ------------------------------------------------------------------------

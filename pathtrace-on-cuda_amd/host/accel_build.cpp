@@ -340,6 +340,7 @@ void pt_build_accel(const PtBVHNode* rnodes, int n_rnodes, const PtTriangle* tri
     int quadDepth = 0;
     struct Emit {
         Builder& b; std::vector<Q4>& quad; float absPad; int& maxDepth;
+        std::vector<int32_t>& qch;                  // builder node of every child of every 4-wide node, -1 = none (for a refit)
         // with a depth cap (size-aware tree): a child whose subtree would end below kQuadDepthCap even if every level below it
         // were collapsed two binary levels at a time (height[] = binary levels under a node) is opened here first, the deepest
         // first; the rest of the four slots go by largest area.  Opening both children of a node that fits always fits, so the
@@ -373,6 +374,8 @@ void pt_build_accel(const PtBVHNode* rnodes, int n_rnodes, const PtTriangle* tri
             }
             const int me = (int)quad.size();
             quad.emplace_back();
+            qch.resize((size_t)(me + 1) * 4, -1);
+            for (int k = 0; k < nc; k++) qch[(size_t)me * 4 + k] = ch[k];
             float lo[4][3], hi[4][3];
             for (int k = 0; k < nc; k++) {
                 const BN& c = b.nodes[(size_t)ch[k]];
@@ -424,8 +427,10 @@ void pt_build_accel(const PtBVHNode* rnodes, int n_rnodes, const PtTriangle* tri
             return me;
         }
     };
+    std::vector<int32_t> qch;
     if (b.nodes[0].count > 0) {
         // a single leaf: one node whose first child is that leaf
+        qch = {0, -1, -1, -1};
         quad.emplace_back();
         Q4& q = quad[0];
         memset(&q, 0, sizeof(q));
@@ -448,7 +453,7 @@ void pt_build_accel(const PtBVHNode* rnodes, int n_rnodes, const PtTriangle* tri
         std::vector<int> height(b.nodes.size(), 0);      // a child's index is above its parent's
         for (size_t i = b.nodes.size(); i-- > 0;)
             if (b.nodes[i].count == 0) height[i] = 1 + std::max(height[(size_t)b.nodes[i].l], height[(size_t)b.nodes[i].r]);
-        Emit em{b, quad, absPad, quadDepth, sized ? &height : nullptr};
+        Emit em{b, quad, absPad, quadDepth, qch, sized ? &height : nullptr};
         em.run(0, 0);
     }
     // Renumber: the first kQuadTopBfs nodes in breadth-first order — every ray walks them, and wf_trace keeps a prefix of
@@ -477,9 +482,67 @@ void pt_build_accel(const PtBVHNode* rnodes, int n_rnodes, const PtTriangle* tri
             re[i] = q;
         }
         quad.swap(re);
+        out.quad_bn.resize(n * 4);
+        for (size_t i = 0; i < n; i++) memcpy(&out.quad_bn[i * 4], &qch[(size_t)order[i] * 4], 16);
     }
     out.quad.resize(quad.size() * 16);
     memcpy(out.quad.data(), quad.data(), quad.size() * sizeof(Q4));
     out.n_quad = (int)quad.size();
     out.quad_depth = quadDepth;
+
+    // ---- maps for a refit (accel_build.h) ----
+    const size_t n_bn = b.nodes.size();
+    out.bn.resize(n_bn * 4);
+    std::vector<int> hgt(n_bn, 0);
+    int top = 0;
+    for (size_t i = n_bn; i-- > 0;) {                 // a child's index is above its parent's
+        const BN& n = b.nodes[i];
+        const int32_t rec[4] = {n.l, n.r, n.count > 0 ? n.first : 0, n.count};
+        memcpy(&out.bn[i * 4], rec, 16);
+        if (n.count == 0) hgt[i] = 1 + std::max(hgt[(size_t)n.l], hgt[(size_t)n.r]);
+        top = std::max(top, hgt[i]);
+    }
+    out.level_start.assign((size_t)top + 2, 0);
+    for (size_t i = 0; i < n_bn; i++) out.level_start[(size_t)hgt[i] + 1]++;
+    for (int h = 0; h <= top; h++) out.level_start[(size_t)h + 1] += out.level_start[(size_t)h];
+    out.order.resize(n_bn);
+    {
+        std::vector<int32_t> at(out.level_start.begin(), out.level_start.end() - 1);
+        for (size_t i = 0; i < n_bn; i++) out.order[(size_t)at[(size_t)hgt[i]]++] = (int32_t)i;
+    }
+    out.wide_bn.assign((size_t)n_wide * 2, 0);          // a single leaf: both sides of the one record are node 0
+    for (size_t i = 0; i < n_bn; i++)
+        if (widx[i] >= 0) { out.wide_bn[(size_t)widx[i] * 2] = b.nodes[i].l; out.wide_bn[(size_t)widx[i] * 2 + 1] = b.nodes[i].r; }
+    out.leaf_range.clear();
+    for (int i = 0; i < n_rnodes; i++) {
+        const PtBVHNode& n = rnodes[i];
+        if (n.primStart == -1 || n.primEnd == -1) continue;
+        out.leaf_range.push_back(n.primStart); out.leaf_range.push_back(n.primEnd - n.primStart + 1);
+    }
+    out.tmap.resize((size_t)n_tris * 2);
+    for (int q = 0; q < n_tris; q++) { const int i = b.items[(size_t)q].tri; out.tmap[(size_t)q * 2] = i; out.tmap[(size_t)q * 2 + 1] = leafOf[(size_t)i]; }
+    {
+        std::vector<float> boxes(n_bn * 8, 0.f);
+        for (size_t i = 0; i < n_bn; i++) { memcpy(&boxes[i * 8], b.nodes[i].mn, 12); memcpy(&boxes[i * 8 + 4], b.nodes[i].mx, 12); }
+        out.area_sum = pt_accel_area_sum(boxes.data(), (int)n_bn);
+    }
+}
+
+double pt_accel_area_sum(const float* boxes8, int n)
+{
+    double total = 0.0;
+    for (int base = 0; base < n; base += kAreaBlock) {
+        double v[256];
+        for (int t = 0; t < 256; t++) {
+            double acc = 0.0;
+            for (int j = 0; j < 4; j++) {
+                const int i = base + t * 4 + j;
+                if (i < n) acc += (double)Builder::area(&boxes8[(size_t)i * 8], &boxes8[(size_t)i * 8 + 4]);
+            }
+            v[t] = acc;
+        }
+        for (int s = 128; s > 0; s >>= 1) for (int t = 0; t < s; t++) v[t] += v[t + s];
+        total += v[0];
+    }
+    return total;
 }

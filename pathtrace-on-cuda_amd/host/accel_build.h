@@ -17,6 +17,23 @@ struct PtAccel {
     std::vector<uint32_t> quad;          // n_quad x 16 dwords: the 4-wide quantised tree (layout: csrc/pt_device.h)
     int n_wide = 0, n_leaves = 0, depth = 0;
     int n_quad = 0, quad_depth = 0;
+    // ---- maps of the build, for a refit of the arrays above from new vertex positions (csrc/pt_dynamic.hip) ----
+    // The five arrays above do not depend on them.  A "builder node" is a node of the binary traversal tree in the builder's
+    // depth-first numbering (0 = root, a child's index is above its parent's).
+    std::vector<int32_t> bn;             // n_bn x 4: l, r, first, count — count > 0: a leaf over tri[first .. first + count), else its two children
+    std::vector<int32_t> order;          // n_bn builder nodes sorted by height (0 = leaf), ascending index within a height
+    std::vector<int32_t> level_start;    // heights + 2 offsets into `order`: height h is order[level_start[h] .. level_start[h + 1])
+    std::vector<int32_t> wide_bn;        // n_wide x 2: builder node whose box is the L / the R box of each `wide` record
+    std::vector<int32_t> quad_bn;        // n_quad x 4: builder node of each child of each `quad` record (after the renumbering), -1 = no child
+    std::vector<int32_t> leaf_range;     // n_leaves x 2: first triangle (reference order) and triangle count of each reference leaf
+    std::vector<int32_t> tmap;           // n_tris x 2, tree order: prim (index in the reference's order), reference leaf
+    double area_sum = 0.0;               // pt_accel_area_sum over the builder's own boxes: the denominator of pt_scene_tree_inflation
 };
+
+// Sum of Builder::area (float32) of n boxes (8 floats each: mn.xyz _ mx.xyz _), in float64, in the fixed order the device reduction
+// uses (csrc/pt_dynamic.hip: dyn_area): blocks of kAreaBlock boxes; in a block 256 partial sums of 4 consecutive boxes each, folded
+// by halving (v[t] += v[t + s], s = 128 .. 1); the block sums added in index order.
+constexpr int kAreaBlock = 1024;
+double pt_accel_area_sum(const float* boxes8, int n);
 
 void pt_build_accel(const PtBVHNode* ref_nodes, int n_ref_nodes, const PtTriangle* tris, int n_tris, PtAccel& out);

@@ -138,7 +138,16 @@ API = [
     ("pt_views_work_bytes", C.c_int64, [C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32]),
     ("pt_render_views", C.c_int, [_P, C.POINTER(PtCamera), C.c_int32, C.POINTER(PtParams), _P, _P, _P, _P]),
     ("pt_render_views_host", C.c_int, [_P, C.POINTER(PtCamera), C.c_int32, C.POINTER(PtParams), _P, _P]),
+    ("pt_scene_update_vertices", C.c_int, [_P, _P, _P, _P]),
+    ("pt_scene_update_vertices_host", C.c_int, [_P, _P, _P]),
+    ("pt_scene_update_spheres", C.c_int, [_P, _P, C.c_int32]),
+    ("pt_scene_tree_inflation", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("pt_dbg_scene_array", C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
 ]
+
+# pt_dbg_scene_array: name -> (which, dtype of the download)
+SCENE_ARRAYS = {"nodes": (0, np.float32), "quad": (1, np.uint32), "tri": (2, np.float32), "tripair": (3, np.float32), "leafbox": (4, np.float32),
+                "surf": (5, np.float32), "lights": (6, np.float32), "spheres": (7, np.float32), "core": (8, np.float32)}
 
 
 def lib():
@@ -261,6 +270,7 @@ class Scene:
             spheres = np.zeros((0, SPHERE_FLOATS), np.float32)
         spheres = np.ascontiguousarray(spheres, np.float32).reshape(-1, SPHERE_FLOATS)
         self.device = device
+        self.n_tris = tris.shape[0]
         self._h = C.c_void_p()
         _check(lib().pt_scene_create(_ptr(nodes), nodes.shape[0], _ptr(tris), tris.shape[0],
                                      _ptr(spheres) if spheres.shape[0] else None, spheres.shape[0], device, C.byref(self._h)),
@@ -473,6 +483,59 @@ class Scene:
         out = np.zeros((len(arr), arr[0].H, arr[0].W, 3), np.float32)
         _check(lib().pt_render_views_host(self._h, arr, len(arr), C.byref(prm), _ptr(fp) if fp is not None else None, _ptr(out)),
                "pt_render_views_host")
+        return out
+
+    def update_vertices(self, pos, frames=None, stream_ptr=0):
+        """Move the triangles (include/pt_api.h: pt_scene_update_vertices).  pos: n_tris x 9 (or n_tris x 3 x 3) float32, V0 V1 V2 in
+        the order of the `tris` given at upload; frames: None (keep the shading frames) or n_tris x 27 float32, N0 N1 N2 T0 T1 T2
+        B0 B1 B2.  torch tensors on the scene's device are used in place (data_ptr()), enqueued on stream_ptr, and must stay alive
+        until the stream has passed the update; numpy arrays go through pt_scene_update_vertices_host (synchronous)."""
+        n = self.n_tris
+        if isinstance(pos, np.ndarray):
+            if frames is not None and not isinstance(frames, np.ndarray):
+                raise PtError("update_vertices: pos and frames must both be numpy arrays or both be torch tensors")
+            p = np.ascontiguousarray(pos, np.float32)
+            if p.size != n * 9 or p.shape[0] != n:
+                raise PtError(f"update_vertices: pos has shape {p.shape}, the scene has {n} triangles")
+            f = None
+            if frames is not None:
+                f = np.ascontiguousarray(frames, np.float32)
+                if f.size != n * 27 or f.shape[0] != n:
+                    raise PtError(f"update_vertices: frames has shape {f.shape}, want ({n}, 27)")
+            _check(lib().pt_scene_update_vertices_host(self._h, _ptr(p), _ptr(f) if f is not None else None), "pt_scene_update_vertices_host")
+            return
+        for name, t, per in (("pos", pos, 9), ("frames", frames, 27)):
+            if t is None:
+                continue
+            if not (hasattr(t, "data_ptr") and hasattr(t, "is_contiguous")):
+                raise PtError(f"update_vertices: {name} must be a torch tensor or a numpy array")
+            if str(t.dtype) != "torch.float32" or not t.is_contiguous() or t.numel() != n * per or t.shape[0] != n:
+                raise PtError(f"update_vertices: {name} must be contiguous float32 with {n} x {per} elements, got {t.dtype} {tuple(t.shape)}")
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise PtError(f"update_vertices: {name} is on {t.device}, the scene is on device {self.device}")
+        _check(lib().pt_scene_update_vertices(self._h, C.c_void_p(pos.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None,
+                                              C.c_void_p(stream_ptr)), "pt_scene_update_vertices")
+
+    def update_spheres(self, spheres):
+        """Move the analytic spheres: (n, 16) float32 records of the uploaded count; centre and radius may change, materials may not."""
+        sph = np.ascontiguousarray(spheres, np.float32).reshape(-1, SPHERE_FLOATS)
+        _check(lib().pt_scene_update_spheres(self._h, _ptr(sph), sph.shape[0]), "pt_scene_update_spheres")
+
+    def tree_inflation(self):
+        """Summed box area of the binary traversal tree now / at upload (1.0 for a scene never updated); waits for the device."""
+        r = C.c_double(0.0)
+        _check(lib().pt_scene_tree_inflation(self._h, C.byref(r)), "pt_scene_tree_inflation")
+        return r.value
+
+    def dbg_array(self, name):
+        """pt_dbg_scene_array: one device array of the scene as a flat numpy array (SCENE_ARRAYS; layouts: csrc/pt_device.h)."""
+        which, dt = SCENE_ARRAYS[name]
+        size = lib().pt_dbg_scene_array(self._h, which, None, 0)
+        if size < 0:
+            _check(size, "pt_dbg_scene_array")
+        out = np.zeros(size // 4, dt)
+        if size and lib().pt_dbg_scene_array(self._h, which, _ptr(out), size) != size:
+            raise PtError("pt_dbg_scene_array: " + lib().pt_last_error().decode())
         return out
 
     def raycast(self, rays8):

@@ -14,51 +14,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pt_api.h"
-#include "pt_device.h"
+#include "pt_internal.h"
 #include "../host/accel_build.h"
-#include "pt_dynamic.h"
-
-extern "C" {
-hipError_t ptk_render_units(const ptd::DevScene*, const ptd::DevCamera*, const ptd::DevParams*, float*, unsigned int*, void*, int, int, hipStream_t);
-hipError_t ptk_sum_passes(const float*, int, long long, float*, hipStream_t);
-hipError_t ptk_untile(const float*, int, int, int, int, int, long long, float*, hipStream_t);
-hipError_t ptk_dbg_raycast(const ptd::DevScene*, const float*, int, float*, int*, hipStream_t);
-hipError_t ptk_dbg_bxdf(int, const float*, int, float*, hipStream_t);
-hipError_t ptk_dbg_rng(unsigned long long, int, uint32_t*, float*, hipStream_t);
-hipError_t ptk_dbg_math(const float*, int, float*, hipStream_t);
-hipError_t ptk_dbg_sincos(const float*, int, float*, hipStream_t);
-hipError_t ptk_dbg_ray_setup(const float*, int, float*, hipStream_t);
-hipError_t ptk_dbg_pixel_dir(const ptd::DevCamera*, const int*, int, float*, hipStream_t);
-hipError_t ptk_dbg_nee(const ptd::DevScene*, const float*, int, float*, hipStream_t);
-hipError_t ptk_aov(const ptd::DevScene*, const ptd::DevCamera*, int, int, float*, int*, hipStream_t);
-hipError_t ptk_denoise(const float*, const float*, int, int, int, int, float, float, float, int, float*, void*, hipStream_t);
-hipError_t ptk_stats_fold(const float*, int, long long, int, float*, float*, hipStream_t);
-hipError_t ptk_stats_variance(const float*, long long, int, float*, hipStream_t);
-int ptk_stats_blocks(long long);
-int ptk_stats_partial_bytes(void);
-hipError_t ptk_stats_estimate(const float*, const float*, long long, int, int, int, int, int, int, int, void*, hipStream_t);
-size_t ptk_wf_work_bytes(size_t nUnits, int traceBlocks);
-int ptk_wf_cohorts(size_t nUnits);
-const float* ptk_wf_staging(void* work);
-int ptk_wf_stack_capacity(void);
-hipError_t ptk_wf_render(int, const ptd::DevScene*, const ptd::DevCamera*, const ptd::DevParams*, void*, int, uint32_t*, hipStream_t, hipStream_t*,
-                         hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t*, int*, hipEvent_t*, int, int*, int, int, void*, int, const int32_t*,
-                         const ptd::DevCamera*, const int32_t*, const float4*);
-}
-
-void pt_set_error(const char* fmt, ...);   // pt_host.cpp
-
-#define HIPCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            pt_set_error("HIP error %d at %s:%d '%s': %s", (int)e_, __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-            return PT_ERR_DEVICE;                                                           \
-        }                                                                                   \
-    } while (0)
-
-static const size_t kCounterBytes = ptd::kStatBytes;   // 8 work counters + diagnostic launch timeline (3 x u64 per wf_trace launch) + wave-lifetime histogram + rays per launch
 
 struct PtScene {
     int device = 0;
@@ -302,8 +259,8 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
     // from here on every failure destroys the half-built scene (geometry already uploaded, events, streams)
     auto finish = [&]() -> int {
         HIPCHK(hipMalloc((void**)&sc->d_unit_counter, 64));
-        HIPCHK(hipMalloc(&sc->d_counters, kCounterBytes));      // 8 work counters (+ the diagnostic launch timeline of wf_trace)
-        HIPCHK(hipMemset(sc->d_counters, 0, kCounterBytes));
+        HIPCHK(hipMalloc(&sc->d_counters, ptd::kStatBytes));      // 8 work counters (+ the diagnostic launch timeline of wf_trace)
+        HIPCHK(hipMemset(sc->d_counters, 0, ptd::kStatBytes));
         for (int i = 0; i < PtScene::kEvRing; i++) { HIPCHK(hipEventCreate(&sc->ev[i][0])); HIPCHK(hipEventCreate(&sc->ev[i][1])); }
         HIPCHK(hipHostMalloc((void**)&sc->h_poll, 4 * 64, hipHostMallocDefault));
         for (int i = 0; i < 3; i++) { HIPCHK(hipStreamCreateWithFlags(&sc->xstreams[i], hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&sc->ev_join[i], hipEventDisableTiming)); }
@@ -416,23 +373,58 @@ int64_t pt_tiles_floats(const PtCamera* cam, const PtParams* prm)
     if (fill_params(cam, prm, d)) return -1;
     return (int64_t)d.n_tiles_local * ptd::kTilePixels * 3;
 }
+// d_work of a render of d: the per-pass means of the one-kernel mode or the pipeline's buffers, whichever is larger
+static int64_t work_bytes(const ptd::DevParams& d)
+{
+    const int64_t means = (int64_t)d.n_tiles_local * ptd::kTilePixels * 3 * 4 * d.passes;
+    const int64_t wave = (int64_t)ptk_wf_work_bytes((size_t)d.n_units, kTraceBlocks);
+    return means > wave ? means : wave;
+}
 int64_t pt_work_bytes(const PtCamera* cam, const PtParams* prm)
 {
     ptd::DevParams d;
     if (fill_params(cam, prm, d)) return -1;
-    const int64_t mega = (int64_t)d.n_tiles_local * ptd::kTilePixels * 3 * 4 * prm->passes;
-    const int64_t wave = (int64_t)ptk_wf_work_bytes((size_t)d.n_units, kTraceBlocks);
-    return mega > wave ? mega : wave;
+    return work_bytes(d);
+}
+
+static bool has_light(const PtScene* s)      // false: PT_ERR_NO_LIGHT, with the error text set
+{
+    if (s->n_lights < 1) pt_set_error("scene has no emissive triangle: the reference's `curand(s) %% Nl` is undefined (include/CudaUtil.cuh:235)");
+    return s->n_lights >= 1;
+}
+
+// The one way into the queue-driven pipeline (pt_wavefront.hip), for an entry point that has checked its arguments, set the device and filled in
+// what to render and from which pixels and cameras.  Lends the job the scene's resources and runs it — the pipeline polls the live-stream count,
+// so this returns once the render has drained — then sums the passes into d_tiles.  traceEvents: record the per-launch events of
+// pt_enable_trace_timing.  traceStat: the PTAMD_TSTAT diagnostics apply (wf_trace counts its trips and the lanes they serve; pt_last_counters).
+static int run_job(PtScene* s, ptd::WfJob& job, bool traceEvents, bool traceStat, float* d_tiles)
+{
+    const int slot = s->ev_count % PtScene::kEvRing;
+    job.device = s->device; job.scene = &s->dev; job.traceBlocks = kTraceBlocks;
+    job.h_poll = s->h_poll; job.xstreams = s->xstreams; job.ev_fork = s->ev_fork; job.ev_join = s->ev_join;
+    job.ev_begin = s->ev[slot][0]; job.ev_end = s->ev[slot][1];
+    job.drainBelow = s->drain_below; job.shadeRounds = s->shade_rounds; job.earlyBelow = s->early_below;
+    if (traceEvents && !s->trace_ev.empty()) { job.trace_ev = s->trace_ev.data(); job.trace_ev_triples = (int)s->trace_ev.size() / 3; }
+    s->trace_ev_per = job.trace_ev_triples / ptk_wf_cohorts((size_t)job.prm.n_units);
+    for (int k = 0; k < 4; k++) s->trace_ev_used[k] = 0;
+    job.trace_ev_used = s->trace_ev_used;
+    if (traceStat && ptk_wf_trace_stat() != 0) {
+        HIPCHK(hipMemsetAsync(s->d_counters, 0, ptd::kStatBytes, job.stream));
+        job.traceStat = (unsigned long long*)s->d_counters;
+    }
+    job.iters = &s->last_iters;
+    HIPCHK(ptk_wf_render(job));
+    s->ev_count++;
+    HIPCHK(ptk_sum_passes(ptk_wf_staging(job.work), job.prm.passes, (long long)job.prm.n_tiles_local * ptd::kTilePixels * 3, d_tiles, job.stream));
+    return PT_OK;
 }
 
 int pt_render_tiles(PtScene* s, const PtCamera* cam, const PtParams* prm, float* d_tiles, void* d_work, void* hip_stream)
 {
     if (!s || !d_tiles || !d_work) { pt_set_error("pt_render_tiles: NULL argument"); return PT_ERR_INVALID; }
-    if (s->n_lights < 1) {
-        pt_set_error("scene has no emissive triangle: the reference's `curand(s) %% Nl` is undefined (include/CudaUtil.cuh:235)");
-        return PT_ERR_NO_LIGHT;
-    }
-    ptd::DevParams d;
+    if (!has_light(s)) return PT_ERR_NO_LIGHT;
+    ptd::WfJob job{};
+    ptd::DevParams& d = job.prm;
     int rc = fill_params(cam, prm, d);
     if (rc) return rc;
     ptd::DevCamera c;
@@ -440,26 +432,12 @@ int pt_render_tiles(PtScene* s, const PtCamera* cam, const PtParams* prm, float*
 
     hipStream_t stream = (hipStream_t)hip_stream;
     HIPCHK(hipSetDevice(s->device));
-    const int slot = s->ev_count % PtScene::kEvRing;
-    const long long perPass = (long long)d.n_tiles_local * ptd::kTilePixels * 3;
     if (s->mode == 1 && !s->count_next) {
-        // queue-driven pipeline (pt_wavefront.hip); polls the live-stream count, so it returns once the render has drained
-        int iters = 0;
-        const int C = ptk_wf_cohorts((size_t)d.n_units);
-        s->trace_ev_per = s->trace_ev.empty() ? 0 : (int)(s->trace_ev.size() / 3) / C;
-        for (int k = 0; k < 4; k++) s->trace_ev_used[k] = 0;
-        // diagnostic (PTAMD_TSTAT=1): wf_trace counts its trips and the lanes they serve; read with pt_last_counters
-        static const bool kTraceStat = getenv("PTAMD_TSTAT") && atoi(getenv("PTAMD_TSTAT")) != 0;
-        if (kTraceStat) HIPCHK(hipMemsetAsync(s->d_counters, 0, kCounterBytes, stream));
-        HIPCHK(ptk_wf_render(s->device, &s->dev, &c, &d, d_work, kTraceBlocks, s->h_poll, stream, s->xstreams,
-                             s->ev[slot][0], s->ev[slot][1], s->ev_fork, s->ev_join, &iters,
-                             s->trace_ev.empty() ? nullptr : s->trace_ev.data(), (int)s->trace_ev.size() / 3, s->trace_ev_used, s->drain_below, s->shade_rounds,
-                             kTraceStat ? s->d_counters : nullptr, s->early_below, nullptr, nullptr, nullptr, nullptr));
-        s->last_iters = iters;
-        s->ev_count++;
-        HIPCHK(ptk_sum_passes(ptk_wf_staging(d_work), d.passes, perPass, d_tiles, stream));
-        return PT_OK;
+        // the only entry point that honours pt_set_mode(0), the counting build and the PTAMD_TSTAT diagnostics
+        job.work = d_work; job.stream = stream; job.cam = &c;
+        return run_job(s, job, /*traceEvents=*/true, /*traceStat=*/true, d_tiles);
     }
+    const int slot = s->ev_count % PtScene::kEvRing;
     HIPCHK(hipMemsetAsync(s->d_unit_counter, 0, 4, stream));
     if (s->count_next) HIPCHK(hipMemsetAsync(s->d_counters, 0, 64, stream));
     // persistent grid: 4 blocks of 4 waves per CU (16 waves/CU; register- and LDS-feasible), never more blocks than units need
@@ -472,7 +450,7 @@ int pt_render_tiles(PtScene* s, const PtCamera* cam, const PtParams* prm, float*
     HIPCHK(ptk_render_units(&s->dev, &c, &d, (float*)d_work, s->d_unit_counter, s->d_counters, blocks, s->count_next ? 1 : 0, stream));
     HIPCHK(hipEventRecord(s->ev[slot][1], stream));
     s->ev_count++;
-    HIPCHK(ptk_sum_passes((const float*)d_work, d.passes, perPass, d_tiles, stream));
+    HIPCHK(ptk_sum_passes((const float*)d_work, d.passes, (long long)d.n_tiles_local * ptd::kTilePixels * 3, d_tiles, stream));
     return PT_OK;
 }
 
@@ -499,16 +477,15 @@ int64_t pt_tile_list_work_bytes(const PtCamera* cam, const PtParams* prm, int32_
 {
     ptd::DevParams d;
     if (fill_list_params(cam, prm, n_tiles, d)) return -1;
-    const int64_t means = (int64_t)d.n_tiles_local * ptd::kTilePixels * 3 * 4 * prm->passes;
-    const int64_t wave = (int64_t)ptk_wf_work_bytes((size_t)d.n_units, kTraceBlocks);
-    return means > wave ? means : wave;
+    return work_bytes(d);
 }
 
 int pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, const int32_t* h_tiles, int32_t n_tiles,
                         float* d_tiles, void* d_work, void* hip_stream)
 {
     if (!s || !h_tiles || !d_tiles || !d_work) { pt_set_error("pt_render_tile_list: NULL argument"); return PT_ERR_INVALID; }
-    ptd::DevParams d;
+    ptd::WfJob job{};
+    ptd::DevParams& d = job.prm;
     int rc = fill_list_params(cam, prm, n_tiles, d);
     if (rc) return rc;
     {
@@ -520,14 +497,11 @@ int pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, co
             seen[(size_t)t] = true;
         }
     }
-    if (s->n_lights < 1) {
-        pt_set_error("scene has no emissive triangle: the reference's `curand(s) %% Nl` is undefined (include/CudaUtil.cuh:235)");
-        return PT_ERR_NO_LIGHT;
-    }
+    if (!has_light(s)) return PT_ERR_NO_LIGHT;
     ptd::DevCamera c;
     fill_camera(cam, c);
 
-    hipStream_t stream = (hipStream_t)hip_stream;
+    job.stream = (hipStream_t)hip_stream;
     HIPCHK(hipSetDevice(s->device));
     if (s->tile_list_cap < n_tiles) {
         // the previous list render on this scene has drained (one render at a time per scene), so nothing reads the old buffer
@@ -537,19 +511,10 @@ int pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, co
         s->tile_list_cap = cap;
     }
     // stream-ordered before wf_init_list; the render below returns only once it has drained, so h_tiles is not read after the call
-    HIPCHK(hipMemcpyAsync(s->d_tile_list, h_tiles, (size_t)n_tiles * 4, hipMemcpyHostToDevice, stream));
-    const int slot = s->ev_count % PtScene::kEvRing;
-    int iters = 0;
-    s->trace_ev_per = 0;
-    for (int k = 0; k < 4; k++) s->trace_ev_used[k] = 0;
-    // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply)
-    HIPCHK(ptk_wf_render(s->device, &s->dev, &c, &d, d_work, kTraceBlocks, s->h_poll, stream, s->xstreams,
-                         s->ev[slot][0], s->ev[slot][1], s->ev_fork, s->ev_join, &iters, nullptr, 0, s->trace_ev_used,
-                         s->drain_below, s->shade_rounds, nullptr, s->early_below, s->d_tile_list, nullptr, nullptr, nullptr));
-    s->last_iters = iters;
-    s->ev_count++;
-    HIPCHK(ptk_sum_passes(ptk_wf_staging(d_work), d.passes, (long long)d.n_tiles_local * ptd::kTilePixels * 3, d_tiles, stream));
-    return PT_OK;
+    HIPCHK(hipMemcpyAsync(s->d_tile_list, h_tiles, (size_t)n_tiles * 4, hipMemcpyHostToDevice, job.stream));
+    // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply); no per-launch trace events
+    job.work = d_work; job.cam = &c; job.tileList = s->d_tile_list;
+    return run_job(s, job, /*traceEvents=*/false, /*traceStat=*/false, d_tiles);
 }
 
 // ---- a batch of cameras in one pipeline run -----------------------------------------------------------------------------------------
@@ -589,9 +554,7 @@ int64_t pt_views_work_bytes(const PtCamera* cam0, const PtParams* prm, int32_t n
 {
     ptd::DevParams d;
     if (fill_views_params(cam0, prm, n_views, prm ? prm->first_pass : 0, d)) return -1;
-    const int64_t means = (int64_t)d.n_tiles_local * ptd::kTilePixels * 3 * 4 * prm->passes;
-    const int64_t wave = (int64_t)ptk_wf_work_bytes((size_t)d.n_units, kTraceBlocks);
-    return means > wave ? means : wave;
+    return work_bytes(d);
 }
 
 // every host-side check of a batch (include/pt_api.h), before any HIP call
@@ -617,14 +580,11 @@ int pt_render_views(PtScene* s, const PtCamera* h_cams, int32_t n_views, const P
                     float* d_tiles, void* d_work, void* hip_stream)
 {
     if (!s || !d_tiles || !d_work) { pt_set_error("pt_render_views: NULL argument"); return PT_ERR_INVALID; }
-    ptd::DevParams d;
-    const int rc = views_args(h_cams, n_views, prm, h_first_pass, d);
+    ptd::WfJob job{};
+    const int rc = views_args(h_cams, n_views, prm, h_first_pass, job.prm);
     if (rc) return rc;
-    if (s->n_lights < 1) {
-        pt_set_error("scene has no emissive triangle: the reference's `curand(s) %% Nl` is undefined (include/CudaUtil.cuh:235)");
-        return PT_ERR_NO_LIGHT;
-    }
-    hipStream_t stream = (hipStream_t)hip_stream;
+    if (!has_light(s)) return PT_ERR_NO_LIGHT;
+    job.stream = (hipStream_t)hip_stream;
     HIPCHK(hipSetDevice(s->device));
     if (s->view_cap < n_views) {
         // the previous batch on this scene has drained (one render at a time per scene), so nothing reads the old buffer
@@ -646,22 +606,12 @@ int pt_render_views(PtScene* s, const PtCamera* h_cams, int32_t n_views, const P
         memcpy(s->h_views.data() + offFirst + (size_t)v * 4, &first, 4);
     }
     // stream-ordered before wf_init_views; the render below returns only once it has drained, so the callers' arrays are not read after the call
-    HIPCHK(hipMemcpyAsync(s->d_views, s->h_views.data(), total, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(s->d_views, s->h_views.data(), total, hipMemcpyHostToDevice, job.stream));
     const char* dv = (const char*)s->d_views;
-    const int slot = s->ev_count % PtScene::kEvRing;
-    int iters = 0;
-    s->trace_ev_per = s->trace_ev.empty() ? 0 : (int)(s->trace_ev.size() / 3) / ptk_wf_cohorts((size_t)d.n_units);
-    for (int k = 0; k < 4; k++) s->trace_ev_used[k] = 0;
-    // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply)
-    HIPCHK(ptk_wf_render(s->device, &s->dev, nullptr, &d, d_work, kTraceBlocks, s->h_poll, stream, s->xstreams,
-                         s->ev[slot][0], s->ev[slot][1], s->ev_fork, s->ev_join, &iters,
-                         s->trace_ev.empty() ? nullptr : s->trace_ev.data(), (int)s->trace_ev.size() / 3, s->trace_ev_used,
-                         s->drain_below, s->shade_rounds, nullptr, s->early_below, nullptr,
-                         (const ptd::DevCamera*)(dv + offCam), (const int32_t*)(dv + offFirst), (const float4*)dv));
-    s->last_iters = iters;
-    s->ev_count++;
-    HIPCHK(ptk_sum_passes(ptk_wf_staging(d_work), d.passes, (long long)d.n_tiles_local * ptd::kTilePixels * 3, d_tiles, stream));
-    return PT_OK;
+    // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply); a batch passes no single camera
+    job.work = d_work;
+    job.viewOrg = (const float4*)dv; job.viewCams = (const ptd::DevCamera*)(dv + offCam); job.viewFirstPass = (const int32_t*)(dv + offFirst);
+    return run_job(s, job, /*traceEvents=*/true, /*traceStat=*/false, d_tiles);
 }
 
 int pt_render_views_host(PtScene* s, const PtCamera* h_cams, int32_t n_views, const PtParams* prm, const int32_t* h_first_pass, float* h_rgb)
@@ -809,61 +759,36 @@ PT_API int pt_set_shade_rounds(PtScene* s, int32_t mode)
 // Ask the next pt_render_tiles on this scene to run the counting build of the kernel.
 int pt_dbg_trace_timeline(PtScene* s, int64_t* out3n, int32_t n_launches)
 {
-    if (!s || !out3n || (n_launches < -2700 && (n_launches > -3000 || n_launches < -3005)) || n_launches > 2700) { pt_set_error("pt_dbg_trace_timeline: bad arguments"); return PT_ERR_INVALID; }
-    if (n_launches == -3005) {      // PTAMD_TSTAT=2: the raw timeline stripes, 2700 launches x kStatStripes x 3 int64 (maxima of ~start, ~dry, end per stripe of workgroups)
-        HIPCHK(hipSetDevice(s->device));
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(out3n, (const char*)s->d_counters + ptd::kStatStripeOff, (size_t)2700 * ptd::kStatStripes * 24, hipMemcpyDeviceToHost));
-        return PT_OK;
-    }
-    if (n_launches == -3003 || n_launches == -3004) {      // PTAMD_TSTAT=2 + PTAMD_TDUMP=launch: 8 x int64 per wave (kStatWaves) / the per-trip log (kStatLogWaves x kStatLogTrips uint32)
-        HIPCHK(hipSetDevice(s->device));
-        HIPCHK(hipDeviceSynchronize());
-        const size_t off = (size_t)ptd::kStatWords * 8, wb = (size_t)ptd::kStatWaves * 64;
-        if (n_launches == -3003) HIPCHK(hipMemcpy(out3n, (const char*)s->d_counters + off, wb, hipMemcpyDeviceToHost));
-        else HIPCHK(hipMemcpy(out3n, (const char*)s->d_counters + off + wb, (size_t)ptd::kStatLogWaves * ptd::kStatLogTrips * 4, hipMemcpyDeviceToHost));
-        return PT_OK;
-    }
-    if (n_launches == -3002) {      // shader clocks per section of wf_trace's loop, summed over waves (5 x int64: refill, vote, node step, triangle step, epilogue), PTAMD_TSTAT=1
-        HIPCHK(hipSetDevice(s->device));
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(out3n, (const char*)s->d_counters + 64 + 2700 * 24 + 32 * 8 + 2700 * 8 + 64 * 8 + 32 * 8, 5 * 8, hipMemcpyDeviceToHost));
-        return PT_OK;
-    }
-    if (n_launches == -3001) {      // histogram of the stack depth after each node step (32 x int64), PTAMD_TSTAT=1
-        HIPCHK(hipSetDevice(s->device));
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(out3n, (const char*)s->d_counters + 64 + 2700 * 24 + 32 * 8 + 2700 * 8 + 64 * 8, 32 * 8, hipMemcpyDeviceToHost));
-        return PT_OK;
-    }
-    if (n_launches == -3000) {      // the histogram of node steps per ray (64 x int64: bins of 4 steps), PTAMD_TSTAT=1
-        HIPCHK(hipSetDevice(s->device));
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(out3n, (const char*)s->d_counters + 64 + 2700 * 24 + 32 * 8 + 2700 * 8, 64 * 8, hipMemcpyDeviceToHost));
-        return PT_OK;
-    }
-    if (n_launches < 0) {      // -n: the ray count of each of the first n launches (n x int64)
-        HIPCHK(hipSetDevice(s->device));
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(out3n, (const char*)s->d_counters + 64 + 2700 * 24 + 32 * 8, (size_t)(-n_launches) * 8, hipMemcpyDeviceToHost));
-        return PT_OK;
-    }
+    using namespace ptd;
+    if (!s || !out3n || (n_launches < -kStatLaunches && (n_launches > -3000 || n_launches < -3005)) || n_launches > kStatLaunches) { pt_set_error("pt_dbg_trace_timeline: bad arguments"); return PT_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipDeviceSynchronize());
-    static const bool kStriped = getenv("PTAMD_TSTAT") && atoi(getenv("PTAMD_TSTAT")) == 2;
-    if (kStriped && n_launches > 0) {
+    auto read = [&](void* dst, size_t byteOff, size_t bytes) { return hipMemcpy(dst, (const char*)s->d_counters + byteOff, bytes, hipMemcpyDeviceToHost); };
+    const size_t waveOff = (size_t)kStatWords * 8, logOff = waveOff + (size_t)kStatWaves * 64;
+    const struct { int code; size_t byteOff, bytes; } section[] = {
+        {-3005, kStatStripeOff, (size_t)kStatLaunches * kStatStripes * 24},      // PTAMD_TSTAT=2: the raw timeline stripes, kStatLaunches launches x kStatStripes x 3 int64 (maxima of ~start, ~dry, end per stripe of workgroups)
+        {-3004, logOff, (size_t)kStatLogWaves * kStatLogTrips * 4},              // PTAMD_TSTAT=2 + PTAMD_TDUMP=launch: the per-trip log (kStatLogWaves x kStatLogTrips uint32)
+        {-3003, waveOff, logOff - waveOff},                                      // PTAMD_TSTAT=2 + PTAMD_TDUMP=launch: 8 x int64 per wave (kStatWaves)
+        {-3002, (size_t)kStatClocks * 8, 5 * 8},                                 // shader clocks per section of wf_trace's loop, summed over waves (5 x int64: refill, vote, node step, triangle step, epilogue), PTAMD_TSTAT=1
+        {-3001, (size_t)kStatDepthHist * 8, 32 * 8},                             // histogram of the stack depth after each node step (32 x int64), PTAMD_TSTAT=1
+        {-3000, (size_t)kStatStepHist * 8, 64 * 8},                              // the histogram of node steps per ray (64 x int64: bins of 4 steps), PTAMD_TSTAT=1
+        {0, (size_t)kStatLifeHist * 8, 32 * 8},                                  // the 32-bin histogram of wave lifetimes (32 us bins)
+    };
+    for (const auto& q : section)
+        if (q.code == n_launches) { HIPCHK(read(out3n, q.byteOff, q.bytes)); return PT_OK; }
+    if (n_launches < 0) { HIPCHK(read(out3n, (size_t)kStatLaunchRays * 8, (size_t)(-n_launches) * 8)); return PT_OK; }      // -n: the ray count of each of the first n launches (n x int64)
+    if (ptk_wf_trace_stat() == 2) {
         // the timestamp-only build keeps kStatStripes copies of every launch's three words (maxima of ~start, ~dry, end)
-        std::vector<unsigned long long> raw((size_t)n_launches * ptd::kStatStripes * 3);
-        HIPCHK(hipMemcpy(raw.data(), (const char*)s->d_counters + ptd::kStatStripeOff, raw.size() * 8, hipMemcpyDeviceToHost));
+        std::vector<unsigned long long> raw((size_t)n_launches * kStatStripes * 3);
+        HIPCHK(read(raw.data(), kStatStripeOff, raw.size() * 8));
         for (int l = 0; l < n_launches; l++)
             for (int k = 0; k < 3; k++) {
                 unsigned long long m = 0;
-                for (int st = 0; st < ptd::kStatStripes; st++) { const unsigned long long v = raw[((size_t)l * ptd::kStatStripes + st) * 3 + k]; if (v > m) m = v; }
+                for (int st = 0; st < kStatStripes; st++) { const unsigned long long v = raw[((size_t)l * kStatStripes + st) * 3 + k]; if (v > m) m = v; }
                 out3n[(size_t)l * 3 + k] = (int64_t)m;
             }
     } else
-    HIPCHK(hipMemcpy(out3n, (const char*)s->d_counters + 64, (size_t)n_launches * 24, hipMemcpyDeviceToHost));
-    if (n_launches == 0 && out3n) HIPCHK(hipMemcpy(out3n, (const char*)s->d_counters + 64 + 2700 * 24, 32 * 8, hipMemcpyDeviceToHost));   // n = 0: the 32-bin histogram of wave lifetimes (32 us bins)
+    HIPCHK(read(out3n, (size_t)kStatTimeline * 8, (size_t)n_launches * 24));
     return PT_OK;
 }
 

@@ -25,9 +25,7 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/pt_api.h"
-
-void pt_set_error(const char* fmt, ...);   // pt_host.cpp
+#include "pt_internal.h"
 
 static_assert(PT_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "PT_COMM_ID_BYTES must match ncclUniqueId");
 
@@ -84,17 +82,10 @@ struct PtComm {
     int32_t* d_status = nullptr;      // world > 1: one device word for the status all-reduce of pt_render_split
 };
 
-extern "C" int ptk_scene_device(const PtScene* s);      // pt_api.hip
-
 #define NCCLCHK(expr)                                                                                   \
     do {                                                                                                \
         ncclResult_t r_ = (expr);                                                                       \
         if (r_ != ncclSuccess) { pt_set_error("RCCL error at %s:%d '%s': %s", __FILE__, __LINE__, #expr, R->GetErrorString(r_)); return PT_ERR_DEVICE; } \
-    } while (0)
-#define HIPCHK(expr)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) { pt_set_error("HIP error %d at %s:%d '%s': %s", (int)e_, __FILE__, __LINE__, #expr, hipGetErrorString(e_)); return PT_ERR_DEVICE; } \
     } while (0)
 
 extern "C" {

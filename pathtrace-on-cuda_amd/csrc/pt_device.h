@@ -50,11 +50,21 @@ constexpr int kBlockThreads = 64 * kWavesPerBlock;
 
 // Diagnostic counter buffer (PtScene::d_counters, PTAMD_TSTAT): kStatWords 64-bit words of counters, launch timeline and histograms,
 // then — for one chosen launch of wf_trace (PTAMD_TDUMP) — 8 words per wave (kStatWaves) and a per-trip log of every kStatLogEvery-th wave
-constexpr int kStatWords = 8 + 2700 * 3 + 32 + 2700 + 64 + 32 + 8;
+constexpr int kStatLaunches = 2700;      // wf_trace launches the timeline has a slot for (later launches share the last one)
+// word offset of each section, after the 8 work counters of pt_last_counters (word 0)
+constexpr int kStatTimeline = 8;                                       // 3 words per launch: ~start, ~dry, end (100 MHz ticks)
+constexpr int kStatLifeHist = kStatTimeline + 3 * kStatLaunches;       // wave lifetimes, 32 bins of 32 us
+constexpr int kStatLaunchRays = kStatLifeHist + 32;                    // rays of each launch
+constexpr int kStatStepHist = kStatLaunchRays + kStatLaunches;         // node steps per ray, 64 bins of 4
+constexpr int kStatDepthHist = kStatStepHist + 64;                     // stack depth after a node step, 32 bins
+constexpr int kStatClocks = kStatDepthHist + 32;                       // 5 section clocks of wf_trace's loop (8 words kept)
+constexpr int kStatWords = kStatClocks + 8;
+static_assert(kStatTimeline == 8 && kStatLifeHist == 8108 && kStatLaunchRays == 8140 && kStatStepHist == 10840 && kStatDepthHist == 10904 &&
+              kStatClocks == 10936 && kStatWords == 10944, "tools/*.py and earlier profiles read these sections of the counter buffer by position");
 constexpr int kStatWaves = 8192, kStatLogEvery = 112, kStatLogWaves = 64, kStatLogTrips = 1024;
 constexpr int kStatStripes = 64;      // MODE 2: the launch timeline is kept in 64 copies (workgroup % 64), reduced on the host — one word per launch was 7,168 atomics on one address
 constexpr size_t kStatStripeOff = (size_t)kStatWords * 8 + (size_t)kStatWaves * 64 + (size_t)kStatLogWaves * kStatLogTrips * 4;      // bytes
-constexpr size_t kStatBytes = kStatStripeOff + (size_t)2700 * kStatStripes * 3 * 8;
+constexpr size_t kStatBytes = kStatStripeOff + (size_t)kStatLaunches * kStatStripes * 3 * 8;
 
 struct DevScene {
     const float4* nodes;      // traversal tree (SAH over triangles), 4 x float4 per record

@@ -16,7 +16,7 @@
 #include <cfloat>
 #include <cmath>
 
-#include "pt_dynamic.h"
+#include "pt_internal.h"
 #include "../host/accel_build.h"
 
 namespace {

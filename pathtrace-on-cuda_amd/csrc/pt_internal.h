@@ -1,0 +1,120 @@
+// pt_internal.h — what crosses translation units inside libptamd.so, on the host side: error reporting, the argument blocks of the wavefront
+// pipeline and of the vertex update, and the prototype of every ptk_* launcher.  Included by the files that define these functions and by
+// those that call them, so a signature that drifts is a compile error (with C linkage it would link and run).  Not part of the C-ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/pt_api.h"
+#include "pt_device.h"
+
+void pt_set_error(const char* fmt, ...);   // pt_host.cpp
+
+#define HIPCHK(expr)                                                                        \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess) {                                                             \
+            pt_set_error("HIP error %d at %s:%d '%s': %s", (int)e_, __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
+            return PT_ERR_DEVICE;                                                           \
+        }                                                                                   \
+    } while (0)
+
+namespace ptd {
+
+// One run of the wavefront pipeline (ptk_wf_render, pt_wavefront.hip).  pt_api.hip fills it in for a render call; the pipeline reads it
+// and writes through the two output pointers only.
+struct WfJob {
+    // ---- what to render
+    int device;
+    const DevScene* scene;
+    DevParams prm;                       // n_units (tile, pass) units; a list or a batch: a world of one whose frame has n_tiles_local tiles
+    void* work;                          // ptk_wf_work_bytes(prm.n_units, traceBlocks) bytes; the per-pass means end up at its start (ptk_wf_staging)
+    int traceBlocks;                     // persistent grid of wf_trace
+    hipStream_t stream;                  // the caller's
+    // ---- where a stream's pixel and camera come from, exactly one of:
+    //   cam                                  the fixed share of prm.rank / world (wf_init)
+    //   cam + tileList                       prm.n_tiles_local global tile numbers on the device (wf_init_list); nothing else of the pipeline differs
+    //   viewCams + viewFirstPass + viewOrg   a batch, one device entry per view and cam == nullptr: n_tiles_local = views x prm.n_tiles_total,
+    //                                        streams are set up by wf_init_views and stepped by wf_shade_views / wf_drain_views
+    const DevCamera* cam;
+    const int32_t* tileList;
+    const DevCamera* viewCams; const int32_t* viewFirstPass; const float4* viewOrg;
+    // ---- what the scene lends
+    uint32_t* h_poll;                    // pinned, one poll word per cohort, 64 B apart
+    hipStream_t* xstreams;               // 3 extra streams: cohorts 1..3, or early shade beside the traversal when there is one cohort
+    hipEvent_t ev_fork, *ev_join;        // [3]
+    hipEvent_t ev_begin, ev_end;         // bracket the whole render on `stream`
+    // ---- schedule (PtScene: drain_below, shade_rounds, early_below)
+    int drainBelow, shadeRounds, earlyBelow;
+    // ---- diagnostics, optional
+    hipEvent_t* trace_ev;                // triples (before wf_trace, after it, after wf_shade), split evenly between cohorts; nullptr = none
+    int trace_ev_triples;
+    unsigned long long* traceStat;       // the counter buffer (PTAMD_TSTAT), cleared by the caller; nullptr = the production wf_trace
+    // ---- out
+    int* trace_ev_used;                  // [4]: triples used by each cohort
+    int* iters;                          // bounce iterations of the longest cohort
+};
+
+// ---- argument block of the vertex update (pt_dynamic.hip) ----
+constexpr int kCoreBlocks = 256;         // partial boxes of the core-box reduction (one per workgroup)
+
+// Device pointers of one scene: the arrays a render reads (rewritten by an update), the maps of the build (host/accel_build.h,
+// read only) and the update's scratch.  "Builder node" = node of the binary traversal tree in the builder's numbering, 0 = root.
+struct DynScene {
+    // rewritten
+    float4* nodes; uint4* quad; float4* tri; float4* tripair; float4* leafbox; float4* surf; float4* lights; float* core;
+    // maps
+    const int4* bn;              // per builder node: l, r, first, count (count > 0: leaf over tree-order triangles first .. first + count)
+    const int32_t* order;        // builder nodes sorted by height
+    const int2* wide_bn;         // per `nodes` record: builder node of its L / R box
+    const int4* quad_bn;         // per `quad` record: builder node of each child, -1 = none
+    const int2* leaf_range;      // per reference leaf: first triangle (reference order), count
+    const int2* tmap;            // per tree-order triangle: prim (reference order), reference leaf
+    const int32_t* light_prim;   // per light: prim
+    const uint8_t* small;        // per prim: 1 = classified small at upload (core box), nullptr when the scene has no core box
+    // scratch
+    float4* bbox;                // per builder node: unpadded box, mn.xyz 0 | mx.xyz 0
+    float* maxabs;               // largest |coordinate| of the root box
+    float* core_partial;         // kCoreBlocks x 8 floats
+    double* area_partial;        // one block sum per kAreaBlock builder nodes
+    int32_t n_bn, n_wide, n_quad, n_tris, n_leaves, n_lights;
+};
+
+}  // namespace ptd
+
+extern "C" {
+int ptk_scene_device(const PtScene* s);      // pt_api.hip
+// pt_kernels.hip
+hipError_t ptk_render_units(const ptd::DevScene*, const ptd::DevCamera*, const ptd::DevParams*, float*, unsigned int*, void*, int, int, hipStream_t);
+hipError_t ptk_sum_passes(const float*, int, long long, float*, hipStream_t);
+hipError_t ptk_untile(const float*, int, int, int, int, int, long long, float*, hipStream_t);
+hipError_t ptk_dbg_raycast(const ptd::DevScene*, const float*, int, float*, int*, hipStream_t);
+hipError_t ptk_dbg_bxdf(int, const float*, int, float*, hipStream_t);
+hipError_t ptk_dbg_rng(unsigned long long, int, uint32_t*, float*, hipStream_t);
+hipError_t ptk_dbg_math(const float*, int, float*, hipStream_t);
+hipError_t ptk_dbg_sincos(const float*, int, float*, hipStream_t);
+// pt_denoise.hip
+hipError_t ptk_aov(const ptd::DevScene*, const ptd::DevCamera*, int, int, float*, int*, hipStream_t);
+hipError_t ptk_denoise(const float*, const float*, int, int, int, int, float, float, float, int, float*, void*, hipStream_t);
+// pt_stats.hip
+hipError_t ptk_stats_fold(const float*, int, long long, int, float*, float*, hipStream_t);
+hipError_t ptk_stats_variance(const float*, long long, int, float*, hipStream_t);
+int ptk_stats_blocks(long long);
+int ptk_stats_partial_bytes(void);
+hipError_t ptk_stats_estimate(const float*, const float*, long long, int, int, int, int, int, int, int, void*, hipStream_t);
+// pt_wavefront.hip
+hipError_t ptk_dbg_ray_setup(const float*, int, float*, hipStream_t);
+hipError_t ptk_dbg_pixel_dir(const ptd::DevCamera*, const int*, int, float*, hipStream_t);
+hipError_t ptk_dbg_nee(const ptd::DevScene*, const float*, int, float*, hipStream_t);
+size_t ptk_wf_work_bytes(size_t nUnits, int traceBlocks);
+int ptk_wf_cohorts(size_t nUnits);
+const float* ptk_wf_staging(void* work);
+int ptk_wf_stack_capacity(void);
+int ptk_wf_trace_stat(void);      // PTAMD_TSTAT as the pipeline read it (0 = off)
+hipError_t ptk_wf_render(const ptd::WfJob& job);
+// pt_dynamic.hip
+// Enqueues the whole update on `stream`.  level_start: host array of n_levels + 1 offsets into `order` (height h = one launch).
+hipError_t ptk_dyn_update(const ptd::DynScene* sc, const float* d_pos, const float* d_frames, const int32_t* level_start, int n_levels,
+                          hipStream_t stream);
+// Enqueues the area reduction over bbox into area_partial ((n_bn + 1023) / 1024 doubles).
+hipError_t ptk_dyn_area(const ptd::DynScene* sc, hipStream_t stream);
+}

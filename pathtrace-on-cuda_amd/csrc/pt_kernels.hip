@@ -23,6 +23,7 @@
 #include "pt_bxdf.h"
 #include "pt_trace.h"
 #include "pt_shade.h"
+#include "pt_internal.h"
 
 namespace ptd {
 

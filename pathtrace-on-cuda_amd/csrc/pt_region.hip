@@ -7,20 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/pt_api.h"
-#include "pt_device.h"
-
-void pt_set_error(const char* fmt, ...);   // pt_host.cpp
-extern "C" int ptk_scene_device(const PtScene* s);   // pt_api.hip
-
-#define HIPCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            pt_set_error("HIP error %d at %s:%d '%s': %s", (int)e_, __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-            return PT_ERR_DEVICE;                                                           \
-        }                                                                                   \
-    } while (0)
+#include "pt_internal.h"
 
 namespace ptd {
 

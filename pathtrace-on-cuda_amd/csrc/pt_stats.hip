@@ -23,6 +23,7 @@
 // buffers always are: pt_tiles_floats() is a multiple of 192), plain 16-byte loads and stores.
 #include <hip/hip_runtime.h>
 #include "pt_device.h"
+#include "pt_internal.h"
 
 namespace ptd {
 

@@ -37,6 +37,7 @@
 #include "pt_trace.h"
 #include "pt_shade.h"
 #include "pt_stream.h"
+#include "pt_internal.h"
 
 namespace ptd {
 
@@ -567,7 +568,7 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     cur = stack_at(sp);
                 }
 #endif
-                if (HIST) atomicAdd(&stat[8 + 3 * 2700 + 32 + 2700 + 64 + (sp > 31 ? 31 : sp)], 1ull);      // stack depth after this node step
+                if (HIST) atomicAdd(&stat[kStatDepthHist + (sp > 31 ? 31 : sp)], 1ull);      // stack depth after this node step
                 if (cur < 0 && cur != kDone && pend == 0) {
                     // park the leaf, carry on with the next stack entry
                     pend = cur;
@@ -602,7 +603,7 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                 else st_s(&b.hit[0][hs], make_float2(bestT, __int_as_float(bestPrim)));
                 hasRay = false;
                 if (STAT || MODE == 2) stRays++;
-                if (HIST) atomicAdd(&stat[8 + 3 * 2700 + 32 + 2700 + (steps >= 252 ? 63 : steps >> 2)], 1ull);      // node steps of this ray (this launch), bins of 4
+                if (HIST) atomicAdd(&stat[kStatStepHist + (steps >= 252 ? 63 : steps >> 2)], 1ull);      // node steps of this ray (this launch), bins of 4
             }
             PT_STCLK(4)
         }
@@ -627,24 +628,24 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
             // MODE 2 keeps it in kStatStripes copies and nothing else unless stat[5] asks for the pooled histograms (PTAMD_TPOOL=1): atomics from
             // every leaving wave on a handful of words stretched the very tail they were meant to measure (r03_b27.log: a launch of 100 us
             // became one of 287 us)
-            unsigned long long* tl = MODE == 2 ? stat + kStatStripeOff / 8 + 3 * ((size_t)statLaunch * kStatStripes + (blockIdx.x % kStatStripes)) : stat + 8 + 3 * (size_t)statLaunch;
+            unsigned long long* tl = MODE == 2 ? stat + kStatStripeOff / 8 + 3 * ((size_t)statLaunch * kStatStripes + (blockIdx.x % kStatStripes)) : stat + kStatTimeline + 3 * (size_t)statLaunch;
             const unsigned long long tEnd = __builtin_amdgcn_s_memrealtime();
             atomicMax(&tl[0], ~stT0); if (stTExh) atomicMax(&tl[1], ~stTExh); atomicMax(&tl[2], tEnd);
-            if (blockIdx.x == 0 && threadIdx.x == 0) stat[8 + 3 * 2700 + 32 + statLaunch] = n;      // rays of this launch
+            if (blockIdx.x == 0 && threadIdx.x == 0) stat[kStatLaunchRays + statLaunch] = n;      // rays of this launch
             if (MODE == 2 && stat[5] == 0ull) return;
             // distribution of wave exit times over the launch, all launches pooled (absolute: 32 us bins)
-            unsigned long long* hist = stat + 8 + 3 * 2700;
+            unsigned long long* hist = stat + kStatLifeHist;
             const unsigned long long dtk = (tEnd - stT0) / 3200ull;      // 32 us bins (100 MHz ticks)
             atomicAdd(&hist[dtk < 31 ? dtk : 31], 1ull);
             if (MODE == 2) {
                 // per-wave work, all launches pooled: trips per wave (64 bins of 4), trips after the wave found the queue dry (32 bins of 2: in the
                 // slots of MODE 1's per-ray histograms), and rays per wave summed into stat[7] / trips into stat[0] for averages
-                atomicAdd(&stat[8 + 3 * 2700 + 32 + 2700 + (stTrips >= 252 ? 63 : stTrips >> 2)], 1ull);
-                atomicAdd(&stat[8 + 3 * 2700 + 32 + 2700 + 64 + (stTripsDry >= 62 ? 31 : stTripsDry >> 1)], 1ull);
+                atomicAdd(&stat[kStatStepHist + (stTrips >= 252 ? 63 : stTrips >> 2)], 1ull);
+                atomicAdd(&stat[kStatDepthHist + (stTripsDry >= 62 ? 31 : stTripsDry >> 1)], 1ull);
                 atomicAdd(&stat[7], r); atomicAdd(&stat[0], (unsigned long long)stTrips); atomicAdd(&stat[2], (unsigned long long)stTripsDry);
             }
             if (STAT) { atomicAdd(&stat[4], stRefills); atomicAdd(&stat[5], stRefillLanes); atomicAdd(&stat[6], stNoRayLanes); atomicAdd(&stat[7], r); }
-            if (STAT) for (int k = 0; k < 5; k++) atomicAdd(&stat[8 + 3 * 2700 + 32 + 2700 + 64 + 32 + k], stClk[k]);
+            if (STAT) for (int k = 0; k < 5; k++) atomicAdd(&stat[kStatClocks + k], stClk[k]);
         }
     }
 }
@@ -958,45 +959,58 @@ static const WfTuning& wf_tuning()
     }();
     return t;
 }
+int ptk_wf_trace_stat(void) { return wf_tuning().traceStat; }
+
+// What ptk_wf_render carves out of a job for one cohort.
+struct WfCohort {
+    ptd::DevParams prm;           // the job's, with this cohort's unit_base / n_units
+    ptd::WfBuf b;
+    hipStream_t stream, aux;      // aux: a second stream for early shade, nullptr = none to spare
+    uint32_t* h_cnt;              // its pinned poll word
+    hipEvent_t* trace_ev;         // its slice of the job's event triples
+    int trace_ev_triples;
+    int* trace_ev_used;
+    int iters;                    // out
+};
 
 // One cohort's pipeline on its own stream.  Blocks the calling host thread until the cohort has
 // drained (it polls the live-stream count every 16..64 iterations).
-static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::DevCamera* cam, ptd::DevParams prm,
-                             ptd::WfBuf b, int traceBlocks, uint32_t* h_cnt, hipStream_t stream,
-                             hipEvent_t* trace_ev, int trace_ev_pairs, int* trace_ev_used, int drainBelow, int shadeRounds, int* iters_out, unsigned long long* traceStat,
-                             hipStream_t aux, hipEvent_t* evOvl, int earlyBelow, const int32_t* tileList,
-                             const ptd::DevCamera* viewCams, const int32_t* viewFirstPass, const float4* viewOrg)
+static hipError_t run_cohort(const ptd::WfJob& job, WfCohort& co)
 {
     using namespace ptd;
+    const DevParams& prm = co.prm;
+    const WfBuf& b = co.b;
+    const hipStream_t stream = co.stream, aux = co.aux;
+    hipEvent_t evOvl[4] = {job.ev_fork, job.ev_join[0], job.ev_join[1], job.ev_join[2]};
     hipError_t e;
-    if ((e = hipSetDevice(device)) != hipSuccess) return e;
+    if ((e = hipSetDevice(job.device)) != hipSuccess) return e;
     const size_t nStreams = (size_t)prm.n_units * 64;
     if ((e = hipMemsetAsync(b.cnt, 0, 3 * kWfSlotBytes, stream)) != hipSuccess) return e;
     const int nb = (int)((nStreams + 255) / 256);
     // a batch of views (viewCams != nullptr; cam is then nullptr): its own init kernel, and the views instantiations of wf_shade / wf_drain below
-    const bool batch = viewCams != nullptr;
-    const ViewTable views{viewOrg, (uint32_t)prm.n_tiles_total};
-    if (batch) hipLaunchKernelGGL(wf_init_views, dim3(nb), dim3(256), 0, stream, *sc, prm, b, (uint32_t)nStreams, viewCams, viewFirstPass, views.tilesPerView);
-    else if (tileList) hipLaunchKernelGGL(wf_init_list, dim3(nb), dim3(256), 0, stream, *sc, *cam, prm, b, (uint32_t)nStreams, tileList);
-    else hipLaunchKernelGGL(wf_init, dim3(nb), dim3(256), 0, stream, *sc, *cam, prm, b, (uint32_t)nStreams);
-    const int ovfStride = traceBlocks * 256;
-    const int tb = traceBlocks < nb ? traceBlocks : nb;
+    const bool batch = job.viewCams != nullptr;
+    const ViewTable views{job.viewOrg, (uint32_t)prm.n_tiles_total};
+    if (batch) hipLaunchKernelGGL(wf_init_views, dim3(nb), dim3(256), 0, stream, *job.scene, prm, b, (uint32_t)nStreams, job.viewCams, job.viewFirstPass, views.tilesPerView);
+    else if (job.tileList) hipLaunchKernelGGL(wf_init_list, dim3(nb), dim3(256), 0, stream, *job.scene, *job.cam, prm, b, (uint32_t)nStreams, job.tileList);
+    else hipLaunchKernelGGL(wf_init, dim3(nb), dim3(256), 0, stream, *job.scene, *job.cam, prm, b, (uint32_t)nStreams);
+    const int ovfStride = job.traceBlocks * 256;
+    const int tb = job.traceBlocks < nb ? job.traceBlocks : nb;
     // every sample needs at most max_bounce + (max_refract + 2) bounces, +1 iteration to retire
     // (time-sliced rays add iterations; 64x is far beyond anything a finite tree can need)
     const long long hardCap = ((long long)prm.spp_per_pass * (prm.max_bounce + prm.max_refract + 3) + 8) * 64;
     const WfTuning& tn = wf_tuning();
-    const int guideShift = tn.guideShift, budgetShift = tn.budgetShift, budgetMin = tn.budgetMin, shadeWaves = viewCams ? 4 : tn.shadeWaves, shadeThreads = tn.shadeThreads;
+    const int guideShift = tn.guideShift, budgetShift = tn.budgetShift, budgetMin = tn.budgetMin, shadeWaves = batch ? 4 : tn.shadeWaves, shadeThreads = tn.shadeThreads;
     const int earlyPrio = tn.earlyPrio, earlyThreads = tn.earlyThreads, refillMin = tn.refillMin, triTrig = tn.triTrig, chunkShift = tn.chunkShift, topNodes = tn.topNodes;
     const bool pubOnly = tn.pubOnly, traceStatClk = tn.traceStat == 3, traceStatFull = tn.traceStat == 1;
     const uint32_t trStreams = tn.trStreams;
-    if (traceStat && tn.traceStat == 2 && tn.tracePool) {
+    if (job.traceStat && tn.traceStat == 2 && tn.tracePool) {
         static const unsigned long long one = 1ull;
-        if ((e = hipMemcpyAsync(traceStat + 5, &one, 8, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(job.traceStat + 5, &one, 8, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
     }
-    if (traceStat && tn.traceStat == 2 && tn.traceDump >= 0) {
+    if (job.traceStat && tn.traceStat == 2 && tn.traceDump >= 0) {
         // diagnostic: wf_trace dumps a record per wave for this one launch (the word was cleared with the rest of the buffer by the caller)
         static unsigned long long dumpWord; dumpWord = (unsigned long long)tn.traceDump + 1ull;
-        if ((e = hipMemcpyAsync(traceStat + 6, &dumpWord, 8, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(job.traceStat + 6, &dumpWord, 8, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
     }
     int it = 0;
     int poll = 16;
@@ -1006,30 +1020,29 @@ static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::Dev
     for (;;) {
         for (int k = 0; k < poll; k++, it++) {
             const int sIn = it % 3, sOut = (it + 1) % 3, sClr = (it + 2) % 3;
-            const bool timed = trace_ev && it < trace_ev_pairs;
-            if (timed) (void)hipEventRecord(trace_ev[3 * it], stream);
+            const bool timed = co.trace_ev && it < co.trace_ev_triples;
+            if (timed) (void)hipEventRecord(co.trace_ev[3 * it], stream);
             // early shade (wf_shade PHASE 1 / 2): for a render of few enough streams that the traversal's launch tail is a large part of
             // every iteration (one rank of an 8-way tile split), the shade step starts on `aux` beside the draining wf_trace and the rest
             // follows both (result-neutral).  Decided once per render: a large render gains nothing from it in its last iterations.
             // (not below ~1/8 of the limit either: a render that small is bound by launch latency, and this adds a launch and two waits per iteration)
-            const bool early = aux != nullptr && earlyBelow > 0 && nStreams <= (size_t)earlyBelow && nStreams >= (size_t)earlyBelow / 8 && !traceStat && !pubOnly;
+            const bool early = aux != nullptr && job.earlyBelow > 0 && nStreams <= (size_t)job.earlyBelow && nStreams >= (size_t)job.earlyBelow / 8 && !job.traceStat && !pubOnly;
             const bool marks = early || pubOnly;
             if (early) {
                 // aux may start once the previous iteration's shade (everything on `stream` so far) is done
                 if ((e = hipEventRecord(evOvl[it & 1], stream)) != hipSuccess) return e;
                 if ((e = hipStreamWaitEvent(aux, evOvl[it & 1], 0)) != hipSuccess) return e;
             }
-            if (traceStat && traceStatClk) hipLaunchKernelGGL(wf_trace<3>, dim3(tb), dim3(256), 0, stream, *sc, b, sIn, ovfStride, it & 1, chunkShift, budgetShift, budgetMin, guideShift, triTrig, refillMin, topNodes, traceStat, it < 2700 ? it : 2699, tn.helpShards, tn.lateBudget);
-            else if (traceStat && traceStatFull) hipLaunchKernelGGL(wf_trace<1>, dim3(tb), dim3(256), 0, stream, *sc, b, sIn, ovfStride, it & 1, chunkShift, budgetShift, budgetMin, guideShift, triTrig, refillMin, topNodes, traceStat, it < 2700 ? it : 2699, tn.helpShards, tn.lateBudget);
-            else if (traceStat) hipLaunchKernelGGL(wf_trace<2>, dim3(tb), dim3(256), 0, stream, *sc, b, sIn, ovfStride, it & 1, chunkShift, budgetShift, budgetMin, guideShift, triTrig, refillMin, topNodes, traceStat, it < 2700 ? it : 2699, tn.helpShards, tn.lateBudget);
-            else if (early || pubOnly) hipLaunchKernelGGL((wf_trace<0, true>), dim3(tb), dim3(256), 0, stream, *sc, b, sIn, ovfStride, it & 1, chunkShift, budgetShift, budgetMin, guideShift, triTrig, refillMin, topNodes, (unsigned long long*)nullptr, earlyPrio, tn.helpShards, tn.lateBudget);
-            else hipLaunchKernelGGL(wf_trace<0>, dim3(tb), dim3(256), 0, stream, *sc, b, sIn, ovfStride, it & 1, chunkShift, budgetShift, budgetMin, guideShift, triTrig, refillMin, topNodes, (unsigned long long*)nullptr, 0, tn.helpShards, tn.lateBudget);
-            if (timed) (void)hipEventRecord(trace_ev[3 * it + 1], stream);
+            // one launch for every build of wf_trace; statLaunch is the timeline slot of a diagnostic build, the issue priority in production
+            const auto trace = job.traceStat ? (traceStatClk ? wf_trace<3> : traceStatFull ? wf_trace<1> : wf_trace<2>) : marks ? wf_trace<0, true> : wf_trace<0>;
+            const int statLaunch = job.traceStat ? (it < kStatLaunches ? it : kStatLaunches - 1) : marks ? earlyPrio : 0;
+            hipLaunchKernelGGL(trace, dim3(tb), dim3(256), 0, stream, *job.scene, b, sIn, ovfStride, it & 1, chunkShift, budgetShift, budgetMin, guideShift, triTrig, refillMin, topNodes, job.traceStat, statLaunch, tn.helpShards, tn.lateBudget);
+            if (timed) (void)hipEventRecord(co.trace_ev[3 * it + 1], stream);
             const dim3 sg((liveBound + shadeThreads - 1) / shadeThreads), sb(shadeThreads);
-            const bool twoRounds = shadeRounds >= 0 ? (shadeRounds != 0) : (liveBound < trStreams);
+            const bool twoRounds = job.shadeRounds >= 0 ? (job.shadeRounds != 0) : (liveBound < trStreams);
             // (a batch: W is not looked at — wf_shade_views exists for 4 waves per SIMD only, and the dispatch below passes 4 for it)
-#define PT_SHADE(W, T, P, M, S) do { if (batch) hipLaunchKernelGGL((wf_shade_views<T, P, M>), sg, sb, 0, S, *sc, views, prm, b, sIn, sOut, sClr, it & 1); \
-                                     else hipLaunchKernelGGL((wf_shade<W, T, P, M>), sg, sb, 0, S, *sc, *cam, prm, b, sIn, sOut, sClr, it & 1); } while (0)
+#define PT_SHADE(W, T, P, M, S) do { if (batch) hipLaunchKernelGGL((wf_shade_views<T, P, M>), sg, sb, 0, S, *job.scene, views, prm, b, sIn, sOut, sClr, it & 1); \
+                                     else hipLaunchKernelGGL((wf_shade<W, T, P, M>), sg, sb, 0, S, *job.scene, *job.cam, prm, b, sIn, sOut, sClr, it & 1); } while (0)
             if (early) {
                 // phase 1 in small workgroups: a 256-thread workgroup needs one free wave slot per SIMD, i.e. two traversal workgroups of
                 // the CU gone, a 512-thread one four — it gets onto the chip earlier in the drain
@@ -1043,99 +1056,86 @@ static hipError_t run_cohort(int device, const ptd::DevScene* sc, const ptd::Dev
             else if (twoRounds) { if (shadeWaves == 2) PT_SHADE(2, true, 0, false, stream); else if (shadeWaves == 3) PT_SHADE(3, true, 0, false, stream); else PT_SHADE(4, true, 0, false, stream); }
             else { if (shadeWaves == 2) PT_SHADE(2, false, 0, false, stream); else if (shadeWaves == 3) PT_SHADE(3, false, 0, false, stream); else PT_SHADE(4, false, 0, false, stream); }
 #undef PT_SHADE
-            if (timed) (void)hipEventRecord(trace_ev[3 * it + 2], stream);      // [3it+1, 3it+2] brackets this iteration's wf_shade
+            if (timed) (void)hipEventRecord(co.trace_ev[3 * it + 2], stream);      // [3it+1, 3it+2] brackets this iteration's wf_shade
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(h_cnt, &b.cnt[it % 3].nActive, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(co.h_cnt, &b.cnt[it % 3].nActive, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-        if (h_cnt[0] == 0) break;
-        liveBound = h_cnt[0];
-        if (h_cnt[0] <= (uint32_t)drainBelow) {
+        if (co.h_cnt[0] == 0) break;
+        liveBound = co.h_cnt[0];
+        if (co.h_cnt[0] <= (uint32_t)job.drainBelow) {
             // few streams left: finish them in one launch instead of hundreds of latency-bound iterations
             // the 4-wide tree if its walk fits the per-lane stack (any tree the builder makes for the config scenes does), else the binary one
-            const bool quadWalk = tn.drainQuad && 3 * sc->quad_depth + 2 <= kDrainQuadStack;
+            const bool quadWalk = tn.drainQuad && 3 * job.scene->quad_depth + 2 <= kDrainQuadStack;
             // 2 (4-wide walk: 189 VGPRs) or 3 (165) waves per SIMD of wf_drain fit: spread the streams over at most that many lanes
             const size_t drainLanes = (size_t)((quadWalk && DRAIN_MINBLOCKS < 3) ? 2 : 3) * 4 * 256 * 64;
             int spread = 0;
-            while (spread < tn.drainSpread && ((size_t)h_cnt[0] << (spread + 1)) <= drainLanes) spread++;
-            const int db = (int)((((size_t)h_cnt[0] << spread) + kBlockThreads - 1) / kBlockThreads);
-            if (batch && quadWalk) hipLaunchKernelGGL(wf_drain_views<true>, dim3(db), dim3(kBlockThreads), 0, stream, *sc, views, prm, b, it % 3, it & 1, spread);
-            else if (batch) hipLaunchKernelGGL(wf_drain_views<false>, dim3(db), dim3(kBlockThreads), 0, stream, *sc, views, prm, b, it % 3, it & 1, spread);
-            else if (quadWalk) hipLaunchKernelGGL(wf_drain<true>, dim3(db), dim3(kBlockThreads), 0, stream, *sc, *cam, prm, b, it % 3, it & 1, spread);
-            else hipLaunchKernelGGL(wf_drain<false>, dim3(db), dim3(kBlockThreads), 0, stream, *sc, *cam, prm, b, it % 3, it & 1, spread);
+            while (spread < tn.drainSpread && ((size_t)co.h_cnt[0] << (spread + 1)) <= drainLanes) spread++;
+            const int db = (int)((((size_t)co.h_cnt[0] << spread) + kBlockThreads - 1) / kBlockThreads);
+            if (batch && quadWalk) hipLaunchKernelGGL(wf_drain_views<true>, dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, views, prm, b, it % 3, it & 1, spread);
+            else if (batch) hipLaunchKernelGGL(wf_drain_views<false>, dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, views, prm, b, it % 3, it & 1, spread);
+            else if (quadWalk) hipLaunchKernelGGL(wf_drain<true>, dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, *job.cam, prm, b, it % 3, it & 1, spread);
+            else hipLaunchKernelGGL(wf_drain<false>, dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, *job.cam, prm, b, it % 3, it & 1, spread);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
             break;
         }
         if (it > hardCap) return hipErrorLaunchFailure;      // cannot happen for a well-formed scene; never spin forever
         if (poll < 64) poll *= 2;
-        if (drainBelow > 0 && (unsigned long long)h_cnt[0] <= (unsigned long long)drainBelow * 8ull) poll = 16;      // near the hand-over: look again soon
+        if (job.drainBelow > 0 && (unsigned long long)co.h_cnt[0] <= (unsigned long long)job.drainBelow * 8ull) poll = 16;      // near the hand-over: look again soon
     }
-    if (iters_out) *iters_out = it;
-    if (trace_ev_used) *trace_ev_used = trace_ev ? (it < trace_ev_pairs ? it : trace_ev_pairs) : 0;
+    co.iters = it;
+    *co.trace_ev_used = co.trace_ev ? (it < co.trace_ev_triples ? it : co.trace_ev_triples) : 0;
     return hipSuccess;
 }
 
-// Runs the whole pipeline for one pt_render_tiles / pt_render_tile_list call.  `stream` is the caller's stream;
-// `xstreams` are up to 3 extra streams owned by the scene; `h_cnt` holds one pinned poll word
-// (64 B apart) per cohort.  ev_begin/ev_end bracket the whole render on `stream`.  trace_ev:
-// optional event triples (before wf_trace, after it, after wf_shade), split evenly between cohorts; trace_ev_used[c] = triples used by cohort c.
-// tileList (device, prm->n_tiles_local global tile numbers; nullptr = the fixed share of prm->rank / world): every cohort's streams
-// are set up by wf_init_list from it; nothing else of the pipeline differs.
-// viewCams / viewFirstPass / viewOrg (device, one entry per view; nullptr = one camera): a batch of views (pt_render_views) — cam is
-// nullptr, prm is that of a world of one with n_tiles_local = views x prm->n_tiles_total, streams are set up by wf_init_views and
-// stepped by wf_shade_views / wf_drain_views.
-// Blocks the host until the render has drained.
-hipError_t ptk_wf_render(int device, const ptd::DevScene* sc, const ptd::DevCamera* cam, const ptd::DevParams* prm,
-                         void* work, int traceBlocks, uint32_t* h_cnt, hipStream_t stream, hipStream_t* xstreams,
-                         hipEvent_t ev_begin, hipEvent_t ev_end, hipEvent_t ev_fork, hipEvent_t* ev_join, int* iters_out,
-                         hipEvent_t* trace_ev, int trace_ev_pairs, int* trace_ev_used, int drainBelow, int shadeRounds, void* traceStat, int earlyBelow,
-                         const int32_t* tileList, const ptd::DevCamera* viewCams, const int32_t* viewFirstPass, const float4* viewOrg)
+// Runs the whole pipeline for one job (pt_internal.h: WfJob) and blocks the host until the render has drained.
+hipError_t ptk_wf_render(const ptd::WfJob& job)
 {
     using namespace ptd;
-    const size_t nUnits = (size_t)prm->n_units;
+    const hipStream_t stream = job.stream;
+    const size_t nUnits = (size_t)job.prm.n_units;
     const int C = ptk_wf_cohorts(nUnits);
     const size_t per = (nUnits + C - 1) / C;
-    char* base = (char*)work;
+    char* base = (char*)job.work;
     float* staging = (float*)base;
     char* p = base + staging_bytes(nUnits * 64);
     hipError_t e;
-    if (ev_begin) { if ((e = hipEventRecord(ev_begin, stream)) != hipSuccess) return e; }
-    if (C > 1) { if ((e = hipEventRecord(ev_fork, stream)) != hipSuccess) return e; }
+    if ((e = hipEventRecord(job.ev_begin, stream)) != hipSuccess) return e;
+    if (C > 1) { if ((e = hipEventRecord(job.ev_fork, stream)) != hipSuccess) return e; }
     std::vector<hipError_t> rc((size_t)C, hipSuccess);
-    std::vector<int> iters((size_t)C, 0);
+    std::vector<WfCohort> cohort((size_t)C);
     std::vector<std::thread> th;
-    const int evPer = trace_ev ? trace_ev_pairs / C : 0;
+    const int evPer = job.trace_ev ? job.trace_ev_triples / C : 0;
     for (int c = 0; c < C; c++) {
-        DevParams cp = *prm;
+        WfCohort& co = cohort[(size_t)c];
+        co.prm = job.prm;
         const size_t u0 = (size_t)c * per, u1 = (u0 + per < nUnits) ? u0 + per : nUnits;
-        cp.unit_base = (int)u0; cp.n_units = (int)(u1 > u0 ? u1 - u0 : 0);
-        WfBuf b; carve(p + (size_t)c * cohort_bytes(per * 64, traceBlocks), per * 64, traceBlocks, b);
-        b.staging = staging + u0 * 64 * 3;
-        hipStream_t cs = (c == 0) ? stream : xstreams[c - 1];
-        if (c > 0) { if ((e = hipStreamWaitEvent(cs, ev_fork, 0)) != hipSuccess) return e; }
-        hipEvent_t* tev = trace_ev ? trace_ev + (size_t)3 * evPer * c : nullptr;
-        int* used = trace_ev_used ? &trace_ev_used[c] : nullptr;
-        if (cp.n_units == 0) { if (used) *used = 0; continue; }
+        co.prm.unit_base = (int)u0; co.prm.n_units = (int)(u1 > u0 ? u1 - u0 : 0);
+        carve(p + (size_t)c * cohort_bytes(per * 64, job.traceBlocks), per * 64, job.traceBlocks, co.b);
+        co.b.staging = staging + u0 * 64 * 3;
+        co.stream = (c == 0) ? stream : job.xstreams[c - 1];
+        if (c > 0) { if ((e = hipStreamWaitEvent(co.stream, job.ev_fork, 0)) != hipSuccess) return e; }
+        co.trace_ev = job.trace_ev ? job.trace_ev + (size_t)3 * evPer * c : nullptr;
+        co.trace_ev_triples = evPer;
+        co.trace_ev_used = &job.trace_ev_used[c];
+        co.h_cnt = job.h_poll + 16 * c;
+        if (co.prm.n_units == 0) { *co.trace_ev_used = 0; continue; }
         // early shade needs a second stream and four events: with one cohort the scene's extra streams and fork / join events are free
-        hipStream_t aux = (C == 1) ? xstreams[0] : nullptr;
-        auto job = [=, &rc, &iters]() {
-            hipEvent_t evOvl[4] = {ev_fork, ev_join[0], ev_join[1], ev_join[2]};
-            rc[(size_t)c] = run_cohort(device, sc, cam, cp, b, traceBlocks, h_cnt + 16 * c, cs, tev, evPer, used, drainBelow, shadeRounds, &iters[(size_t)c], (unsigned long long*)traceStat, aux, evOvl, earlyBelow, tileList,
-                                         viewCams, viewFirstPass, viewOrg);
-        };
-        if (C == 1) job(); else th.emplace_back(job);
+        co.aux = (C == 1) ? job.xstreams[0] : nullptr;
+        auto run = [&job, &co, &rc, c]() { rc[(size_t)c] = run_cohort(job, co); };
+        if (C == 1) run(); else th.emplace_back(run);
     }
     for (auto& t : th) t.join();
     for (int c = 0; c < C; c++) if (rc[(size_t)c] != hipSuccess) return rc[(size_t)c];
     // every cohort stream has been synchronised by its poll loop; order the caller's stream after them anyway
     for (int c = 1; c < C; c++) {
-        if ((e = hipEventRecord(ev_join[c - 1], xstreams[c - 1])) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(stream, ev_join[c - 1], 0)) != hipSuccess) return e;
+        if ((e = hipEventRecord(job.ev_join[c - 1], job.xstreams[c - 1])) != hipSuccess) return e;
+        if ((e = hipStreamWaitEvent(stream, job.ev_join[c - 1], 0)) != hipSuccess) return e;
     }
-    if (ev_end) { if ((e = hipEventRecord(ev_end, stream)) != hipSuccess) return e; }
-    int mx = 0; for (int v : iters) mx = v > mx ? v : mx;
-    if (iters_out) *iters_out = mx;
+    if ((e = hipEventRecord(job.ev_end, stream)) != hipSuccess) return e;
+    int mx = 0; for (const WfCohort& co : cohort) mx = co.iters > mx ? co.iters : mx;
+    *job.iters = mx;
     return hipSuccess;
 }
 

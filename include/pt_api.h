@@ -450,6 +450,46 @@ PT_API int  pt_scene_tree_inflation(PtScene* s, double* ratio);
 PT_API int64_t pt_dbg_scene_array(PtScene* s, int32_t which, void* h_out, int64_t cap_bytes);
 
 /* ----------------------------------------------------------------------------------
+ * Ray queries (new: the reference casts rays only from inside its integrator).  Opt-in: every call above is as it was.
+ * The caller's own rays against an uploaded scene, on the device and in stream order (csrc/pt_query.hip): visibility between
+ * points, baking, picking, range simulation, collision probes against a mesh that pt_scene_update_vertices moves.
+ *
+ * Rays are RAY8 records (oracle/pt_oracle.h, pt_dbg_raycast): org.xyz | dir.xyz | reserved | tmax.  The reserved float is the
+ *   oracle's tmin: it must be 0 and the device does not read it.  The direction is used as given — not normalised —, t is the
+ *   parameter along it and the range is [0, tmax].  Semantics are the reference's RayCast (include/CudaUtil.cuh:93-148):
+ *   triangles are back-face culled, spheres are tested after the triangles, and among equal t the largest primitive index wins.
+ *   A triangle counts iff Triangle::hit accepts it and the ray enters its reference leaf box (the reference's slab arithmetic).  For
+ *   |(1/dx, 1/dy, 1/dz)| >= 1 — every direction with components in [-1, 1] — that IS the reference's result; for longer directions
+ *   the reference's box cull (a normalised entry distance against the un-scaled closest t) drops hits in an order-dependent way,
+ *   which the device, here as in pt_dbg_raycast, does not imitate: it returns the closest hit in [0, tmax].
+ * PT_QUERY_CLOSEST: d_hits[i] = (t, prim) of the closest hit, bit for bit what pt_dbg_raycast and the reference return; prim
+ *   counts triangles first (the order of `tris`) and spheres after them; a miss is prim = -1, t = 0.  d_surface29 is NULL or
+ *   receives, per ray, the 29-float HIT record exactly as pt_dbg_raycast writes it (zeros for a miss).
+ * PT_QUERY_ANY: prim >= 0 exactly when the closest-hit query of the same ray hits.  The hit returned is SOME hit the reference
+ *   would accept in [0, tmax] — t <= tmax, t >= the closest t —, not necessarily the closest; which one is unspecified and may
+ *   change between versions.  d_surface29 must be NULL.
+ * pt_trace_rays: d_rays8 (16-byte aligned), d_hits (8-byte aligned) and d_surface29 are DEVICE pointers on the scene's device
+ *   holding n records.  Everything is enqueued on `hip_stream`: no host wait, nothing is read back, nothing is allocated
+ *   (pt_scene_device_bytes stays what it was).  A query enqueued
+ *   after pt_scene_update_vertices on the same stream sees the moved geometry.  The buffers must stay valid until the stream has
+ *   passed the query.  A query leaves every render state alone: frames, pt_last_iterations, pt_last_counters, pt_last_render_ms.
+ *   Concurrency: ONE query, update or render at a time per scene (a query in flight on one stream while another query, an update
+ *   or a render of the same scene runs on another stream is not supported; different scenes are independent).
+ * pt_trace_rays_host: the same on HOST arrays: uploads, queries on the NULL stream, waits and downloads.
+ * NULL scene / rays / hits, n < 0, an unknown mode, misaligned d_rays8 / d_hits / d_surface29 and a surface buffer given with
+ *   PT_QUERY_ANY return PT_ERR_INVALID before any HIP call; n = 0 returns PT_OK without one.
+ * Rays with a non-finite component or a zero direction: the result for THAT ray is unspecified (prim stays in [-1, number of
+ *   primitives)), the other rays of the batch are unaffected, and the call ends: the walk is a depth-first search over a finite
+ *   tree, its stack bounded by the depth of the tree whatever the floats are (csrc/pt_trace.h: quad_step).
+ * Out of scope: tmin other than 0, sorting rays for coherence, hit callbacks, primitive masks, a tile-split or multi-GPU query.
+ * -------------------------------------------------------------------------------- */
+typedef struct PtRayHit { float t; int32_t prim; } PtRayHit;      /* 8 bytes */
+#define PT_QUERY_CLOSEST 0
+#define PT_QUERY_ANY     1
+PT_API int  pt_trace_rays(PtScene* s, const float* d_rays8, int64_t n, int32_t mode, PtRayHit* d_hits, float* d_surface29, void* hip_stream);
+PT_API int  pt_trace_rays_host(PtScene* s, const float* h_rays8, int64_t n, int32_t mode, PtRayHit* h_hits, float* h_surface29);
+
+/* ----------------------------------------------------------------------------------
  * (a12,a13) Output + camera helpers (host).
  * pt_tonemap_u8 = exportImage (srcs/pathtracer.cu:94-112): /SampleCnt, ACESFilm
  *   (include/CudaUtil.cuh:383-391), ConverToUint8 (include/image.h:5-8).

@@ -68,6 +68,8 @@ struct PtScene {
     bool dyn_ready = false;
     bool updated = false;
     std::vector<double> h_area;          // host image of dyn.area_partial
+    // ---- ray queries (pt_trace_rays, csrc/pt_query.hip) ----
+    bool query_quad = true;              // walk the 4-wide tree when it fits the kernel's stack (PTAMD_QUERY_QUAD=0: the binary tree, A/B)
 };
 
 static int upload(void** dptr, const void* h, size_t bytes, int64_t& total)
@@ -280,6 +282,7 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
     // millions of streams are alive; with the 69,564-triangle bunny it is neutral, and with few streams in flight it loses
     sc->shade_rounds = ((size_t)n_tris * 192 <= ((size_t)2 << 20)) ? -1 : 1;
     if (const char* m = getenv("PTAMD_TR")) { const int v = atoi(m); if (v >= -1 && v <= 1) sc->shade_rounds = v; }
+    if (const char* m = getenv("PTAMD_QUERY_QUAD")) sc->query_quad = atoi(m) != 0;
     sc->dev.nodes = (const float4*)sc->d_nodes; sc->dev.quad = (const uint4*)sc->d_quad; sc->dev.tri = (const float4*)sc->d_tri;
     sc->dev.tripair = (const float4*)sc->d_tripair;
     sc->dev.leafbox = (const float4*)sc->d_leafbox; sc->dev.surf = (const float4*)sc->d_surf;
@@ -1164,6 +1167,61 @@ int64_t pt_dbg_scene_array(PtScene* s, int32_t which, void* h_out, int64_t cap_b
         HIPCHK(hipMemcpy(h_out, src[which], (size_t)n, hipMemcpyDeviceToHost));
     }
     return size;
+}
+
+// ---- ray queries (csrc/pt_query.hip) -------------------------------------------------------------------------------------------
+static int query_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, int32_t mode, const PtRayHit* hits, const float* surface,
+                         bool device)
+{
+    const char* bad = !s ? "NULL scene" : !rays ? "NULL rays" : !hits ? "NULL hits" : n < 0 ? "n < 0" :
+                      (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_ANY) ? "mode must be PT_QUERY_CLOSEST or PT_QUERY_ANY" :
+                      (mode == PT_QUERY_ANY && surface) ? "an any-hit query has no surface record (d_surface29 must be NULL)" :
+                      (device && ((uintptr_t)rays & 15)) ? "rays must be 16-byte aligned" :
+                      (device && ((uintptr_t)hits & 7)) ? "hits must be 8-byte aligned" :
+                      (device && ((uintptr_t)surface & 3)) ? "surface must be 4-byte aligned" : nullptr;
+    if (bad) { pt_set_error("%s: %s", who, bad); return PT_ERR_INVALID; }
+    return PT_OK;
+}
+
+int pt_trace_rays(PtScene* s, const float* d_rays8, int64_t n, int32_t mode, PtRayHit* d_hits, float* d_surface29, void* hip_stream)
+{
+    int rc;
+    if ((rc = query_args_ok("pt_trace_rays", s, d_rays8, n, mode, d_hits, d_surface29, true)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = s->query_quad && ptk_query_quad_fits(s->dev.quad_depth);
+    const int64_t kBatch = (int64_t)1 << 30;      // rays per launch: ray numbers are 32-bit
+    for (int64_t off = 0; off < n; off += kBatch) {
+        const uint32_t m = (uint32_t)(n - off < kBatch ? n - off : kBatch);
+        HIPCHK(ptk_trace_rays(&s->dev, d_rays8 + off * 8, m, mode == PT_QUERY_ANY, quad, d_hits + off,
+                              d_surface29 ? d_surface29 + off * 29 : nullptr, (hipStream_t)hip_stream));
+    }
+    return PT_OK;
+}
+
+int pt_trace_rays_host(PtScene* s, const float* h_rays8, int64_t n, int32_t mode, PtRayHit* h_hits, float* h_surface29)
+{
+    int rc;
+    if ((rc = query_args_ok("pt_trace_rays_host", s, h_rays8, n, mode, h_hits, h_surface29, false)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    float *d_rays = nullptr, *d_surf = nullptr;
+    PtRayHit* d_hits = nullptr;
+    auto body = [&]() -> int {
+        HIPCHK(hipMalloc((void**)&d_rays, (size_t)n * 32));
+        HIPCHK(hipMalloc((void**)&d_hits, (size_t)n * 8));
+        if (h_surface29) HIPCHK(hipMalloc((void**)&d_surf, (size_t)n * 116));
+        HIPCHK(hipMemcpy(d_rays, h_rays8, (size_t)n * 32, hipMemcpyHostToDevice));
+        const int r = pt_trace_rays(s, d_rays, n, mode, d_hits, d_surf, nullptr);
+        if (r != PT_OK) return r;
+        HIPCHK(hipStreamSynchronize(nullptr));
+        HIPCHK(hipMemcpy(h_hits, d_hits, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (h_surface29) HIPCHK(hipMemcpy(h_surface29, d_surf, (size_t)n * 116, hipMemcpyDeviceToHost));
+        return PT_OK;
+    };
+    rc = body();
+    (void)hipFree(d_rays); (void)hipFree(d_hits); (void)hipFree(d_surf);
+    return rc;
 }
 
 // ---- parity hooks ------------------------------------------------------------------------

@@ -117,4 +117,10 @@ hipError_t ptk_dyn_update(const ptd::DynScene* sc, const float* d_pos, const flo
                           hipStream_t stream);
 // Enqueues the area reduction over bbox into area_partial ((n_bn + 1023) / 1024 doubles).
 hipError_t ptk_dyn_area(const ptd::DynScene* sc, hipStream_t stream);
+// pt_query.hip
+int ptk_query_quad_fits(int quad_depth);      // does the 4-wide walk of a tree this deep fit the query kernels' per-lane stack?
+// Enqueues one batch of n < 2^31 rays on `stream`: (t, prim) per ray, then the 29-float surface records if asked for.  quad: walk the
+// 4-wide tree (else the binary one).
+hipError_t ptk_trace_rays(const ptd::DevScene* sc, const float* d_rays8, uint32_t n, int any, int quad, PtRayHit* d_hits, float* d_surface29,
+                          hipStream_t stream);
 }

@@ -1,0 +1,127 @@
+// pt_query.hip — ray queries on an uploaded scene (include/pt_api.h: pt_trace_rays): the caller's rays, closest hit or any hit, on the
+// caller's stream, nothing but (t, prim) per ray written.  DESIGN.md section 14.
+//
+// One ray per lane.  The walk is wf_drain's: quad_step (pt_trace.h) over the 4-wide quantised tree with a per-lane stack in LDS, the
+// pair-record triangle test, the reference's acceptance and tie rule, then the spheres in order — so (t, prim) of a closest-hit query
+// are the bits trace_closest and the reference's RayCast give.  Workgroups are ONE wave (10 KB of stack each): a finished wave frees
+// its slot at once, where a 256-thread workgroup would hold four until its slowest wave is done.
+//
+// Lane i of the grid traces ray i; a wave lasts as long as its longest ray.  A persistent variant whose waves refilled
+// finished lanes from a global ray counter, as wf_trace does, was built and measured: 5-21 % faster on incoherent closest-hit sets,
+// 2.3-4 x slower on camera rays, slower over all six cases — not kept.
+// An any-hit query is the closest-hit walk with quad_step's early-out armed for every hit (stopBelow = +inf).
+// The 29-float surface record, when asked for, is a second kernel over the finished hits (query_surface): make_surf's registers
+// (12 float4 of surface record, three interpolated frames) never sit in the traversal loop.
+#include <hip/hip_runtime.h>
+#include "pt_device.h"
+#include "pt_math.h"
+#include "pt_bxdf.h"
+#include "pt_trace.h"
+#include "pt_shade.h"
+#include "pt_internal.h"
+
+namespace ptd {
+
+constexpr int kQueryStack = 40;       // per-lane stack entries of the 4-wide walk: trees up to 12 levels (host/accel_build.h: kQuadDepthCap)
+constexpr int kQueryWaves = 4;        // waves per SIMD the register allocation must allow: 16 one-wave workgroups x 10 KB = the CU's 160 KB of LDS
+
+// RAY8: org.xyz dir.xyz reserved tmax, as two 16-byte loads
+PT_DEV void load_ray(const float4* __restrict__ rays, size_t i, f3& org, f3& dir, float& tmax)
+{
+    const float4 a = rays[2 * i], b = rays[2 * i + 1];
+    org = f3(a.x, a.y, a.z); dir = f3(a.w, b.x, b.y); tmax = b.w;
+}
+
+// The spheres, in order, against the triangles' result (CudaUtil.cuh:137-145), and the 8-byte record.  An any-hit query that has its
+// triangle needs no sphere; one that has none tests them against tmax exactly as the closest-hit query does, and stops at the first.
+template <bool ANY>
+PT_DEV void finish_ray(const DevScene& sc, const f3& org, const f3& dir, float bestT, int bestPrim, float2* __restrict__ hit)
+{
+    if (!(ANY && bestPrim >= 0))
+        for (int s = 0; s < sc.n_spheres; s++) {
+            const float4 c = sc.spheres[4 * s];
+            float root;
+            if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; if (ANY) break; }
+        }
+    *hit = make_float2(bestPrim < 0 ? 0.f : bestT, __int_as_float(bestPrim));      // a miss is (0, -1)
+}
+
+// QUAD = false: the binary tree with trace_closest, for a scene whose 4-wide walk would not fit kQueryStack (or PTAMD_QUERY_QUAD=0).
+// Its closest hit is also a valid answer to an any-hit query.
+template <bool ANY, bool QUAD>
+__global__ __launch_bounds__(64, kQueryWaves)
+void query_rays(DevScene sc, const float4* __restrict__ rays, uint32_t n, float2* __restrict__ hits)
+{
+    __shared__ int lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    int* stack = &lds_stack[threadIdx.x];
+    f3 org, dir; float bestT;
+    load_ray(rays, i, org, dir, bestT);
+    if (QUAD) {
+        f3 inv; float cscale; bool degenerate;
+        ray_setup(dir, inv, cscale, degenerate);
+        const float stopBelow = ANY ? __builtin_inff() : -__builtin_inff();
+        int bestPrim = -1, cur = 0, sp = 0;
+        while (!quad_step(sc, org, dir, inv, cscale, degenerate, stopBelow, stack, cur, sp, bestT, bestPrim)) {}
+        finish_ray<ANY>(sc, org, dir, bestT, bestPrim, &hits[i]);
+    } else {
+        TraceStats ts{0, 0, 0};
+        float t;
+        const int prim = trace_closest<false>(sc, org, dir, bestT, stack, t, ts);
+        hits[i] = make_float2(prim < 0 ? 0.f : t, __int_as_float(prim));
+    }
+}
+
+// The HIT record of pt_dbg_raycast (29 floats) for every finished closest hit; zeros for a miss.
+__global__ __launch_bounds__(256)
+void query_surface(DevScene sc, const float4* __restrict__ rays, uint32_t n, const float2* __restrict__ hits, float* __restrict__ out29)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float2 h = hits[i];
+    const int prim = __float_as_int(h.y);
+    float* o = out29 + (size_t)i * 29;
+    if (prim < 0) { for (int k = 0; k < 29; k++) o[k] = 0.f; return; }
+    f3 org, dir; float tmax;
+    load_ray(rays, i, org, dir, tmax);
+    const float t = h.x;
+    Surf s;
+    make_surf(sc, prim, t, org, dir, s);
+    o[0] = 1.f; o[1] = t; o[2] = 0.f; o[3] = 0.f; o[4] = s.fr.front ? 1.f : 0.f;
+    o[5] = s.p.x; o[6] = s.p.y; o[7] = s.p.z;
+    o[8] = s.fr.n.x; o[9] = s.fr.n.y; o[10] = s.fr.n.z;
+    o[11] = s.fr.t.x; o[12] = s.fr.t.y; o[13] = s.fr.t.z;
+    o[14] = s.fr.b.x; o[15] = s.fr.b.y; o[16] = s.fr.b.z;
+    o[17] = s.m.emittance.x; o[18] = s.m.emittance.y; o[19] = s.m.emittance.z;
+    o[20] = s.m.albedo.x; o[21] = s.m.albedo.y; o[22] = s.m.albedo.z;
+    o[23] = s.m.specular.x; o[24] = s.m.specular.y; o[25] = s.m.specular.z;
+    o[26] = s.m.opacity; o[27] = s.m.roughness; o[28] = s.m.metallic;
+}
+
+}  // namespace ptd
+
+extern "C" {
+
+int ptk_query_quad_fits(int quad_depth) { return 3 * quad_depth + 2 <= ptd::kQueryStack; }
+
+// Enqueues one batch (n < 2^31) on `stream`.  quad: walk the 4-wide tree (the caller has checked ptk_query_quad_fits).
+hipError_t ptk_trace_rays(const ptd::DevScene* sc, const float* d_rays8, uint32_t n, int any, int quad, PtRayHit* d_hits, float* d_surface29,
+                          hipStream_t stream)
+{
+    using namespace ptd;
+    const float4* rays = (const float4*)d_rays8;
+    float2* hits = (float2*)d_hits;
+    const uint32_t blocks = (n + 63u) / 64u;
+    if (quad) {
+        if (any) hipLaunchKernelGGL((query_rays<true, true>), dim3(blocks), dim3(64), 0, stream, *sc, rays, n, hits);
+        else hipLaunchKernelGGL((query_rays<false, true>), dim3(blocks), dim3(64), 0, stream, *sc, rays, n, hits);
+    } else {
+        if (any) hipLaunchKernelGGL((query_rays<true, false>), dim3(blocks), dim3(64), 0, stream, *sc, rays, n, hits);
+        else hipLaunchKernelGGL((query_rays<false, false>), dim3(blocks), dim3(64), 0, stream, *sc, rays, n, hits);
+    }
+    if (d_surface29) hipLaunchKernelGGL(query_surface, dim3((n + 255u) / 256u), dim3(256), 0, stream, *sc, rays, n, (const float2*)hits, d_surface29);
+    return hipGetLastError();
+}
+
+}

@@ -285,4 +285,65 @@ PT_DEV int trace_closest(const DevScene& sc, const f3& org, const f3& dir, float
     return bestPrim;
 }
 
+// One step of one lane's walk through the 4-wide quantised tree, for wf_drain and the ray queries (pt_query.hip): wf_trace's node step (the box arithmetic is that kernel's,
+// statement by statement) or its pair-record leaf test, whichever `cur` asks for; returns true when the ray is finished.  The closest
+// hit does not depend on the order of tests (tie rule), and a shadow ray may stop at any hit below `stopBelow` (pt_stream.h:
+// shadow_stop_t) exactly as it does there.  The caller guarantees that its per-lane stack holds 3 * quad_depth + 2 entries.
+// Whatever the floats are (NaN, inf, a zero direction) the walk ends: a node pushes at most three of its children and descends into the
+// fourth, a leaf pushes nothing, so this is a depth-first walk over a finite tree whose stack never exceeds 3 entries per level.
+PT_DEV bool quad_step(const DevScene& sc, const f3& org, const f3& dir, const f3& inv, float cscale, bool degenerate, float stopBelow,
+                      int* stack, int& cur, int& sp, float& bestT, int& bestPrim)
+{
+    if (cur >= 0) {
+        const uint4* np = sc.quad + 4 * (size_t)cur;
+        const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
+        const float Ax = inv.x * __uint_as_float(n0.w), Ay = inv.y * __uint_as_float(n3.z), Az = inv.z * __uint_as_float(n3.w);
+        const float Bx = (__uint_as_float(n0.x) - org.x) * inv.x;
+        const float By = (__uint_as_float(n0.y) - org.y) * inv.y;
+        const float Bz = (__uint_as_float(n0.z) - org.z) * inv.z;
+        const float kSl = 9.5367431640625e-7f;                           // 2^-20
+        const float sx = (__builtin_fabsf(Bx) + 255.f * __builtin_fabsf(Ax)) * kSl;
+        const float sy = (__builtin_fabsf(By) + 255.f * __builtin_fabsf(Ay)) * kSl;
+        const float sz = (__builtin_fabsf(Bz) + 255.f * __builtin_fabsf(Az)) * kSl;
+        const float Bnx = Bx - sx, Bfx = Bx + sx, Bny = By - sy, Bfy = By + sy, Bnz = Bz - sz, Bfz = Bz + sz;
+        const uint32_t mx = (uint32_t)(__float_as_int(inv.x) >> 31), my = (uint32_t)(__float_as_int(inv.y) >> 31), mz = (uint32_t)(__float_as_int(inv.z) >> 31);
+        const uint32_t swx = (n2.x ^ n2.w) & mx, swy = (n2.y ^ n3.x) & my, swz = (n2.z ^ n3.y) & mz;
+        const uint32_t nqx = n2.x ^ swx, fqx = n2.w ^ swx, nqy = n2.y ^ swy, fqy = n3.x ^ swy, nqz = n2.z ^ swz, fqz = n3.y ^ swz;
+        const float cullT = bestT * cscale;
+        int key[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const float tnx = __builtin_fmaf((float)((nqx >> (8 * k)) & 0xffu), Ax, Bnx);
+            const float tny = __builtin_fmaf((float)((nqy >> (8 * k)) & 0xffu), Ay, Bny);
+            const float tnz = __builtin_fmaf((float)((nqz >> (8 * k)) & 0xffu), Az, Bnz);
+            const float tfx = __builtin_fmaf((float)((fqx >> (8 * k)) & 0xffu), Ax, Bfx);
+            const float tfy = __builtin_fmaf((float)((fqy >> (8 * k)) & 0xffu), Ay, Bfy);
+            const float tfz = __builtin_fmaf((float)((fqz >> (8 * k)) & 0xffu), Az, Bfz);
+            const float tn = __builtin_fmaxf(__builtin_fmaxf(tnx, tny), __builtin_fmaxf(tnz, 0.f));
+            const float tf = __builtin_fminf(__builtin_fminf(tfx, tfy), __builtin_fminf(tfz, cullT));
+            key[k] = (tn <= tf) ? __float_as_int(tn) : 0x7fffffff;
+        }
+        int k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3], r0 = (int)n1.x, r1 = (int)n1.y, r2 = (int)n1.z, r3 = (int)n1.w;
+#define PT_CE(ka, ra, kb, rb) { const bool sw = ka > kb; const int tk = sw ? kb : ka, tr = sw ? rb : ra; kb = sw ? ka : kb; rb = sw ? ra : rb; ka = tk; ra = tr; }
+        PT_CE(k0, r0, k1, r1) PT_CE(k2, r2, k3, r3) PT_CE(k0, r0, k2, r2) PT_CE(k1, r1, k3, r3) PT_CE(k1, r1, k2, r2)
+#undef PT_CE
+        if (k0 != 0x7fffffff) {
+            if (k3 != 0x7fffffff) { stack[sp * 64] = r3; sp++; }
+            if (k2 != 0x7fffffff) { stack[sp * 64] = r2; sp++; }
+            if (k1 != 0x7fffffff) { stack[sp * 64] = r1; sp++; }
+            cur = r0;
+            return false;
+        }
+    } else {
+        const int code = ~cur;
+        int first = code >> 3, cnt = code & 7;
+        while (cnt > 0) { tri_test_pairrec(sc, first, cnt > 1, org, dir, inv, degenerate, bestT, bestPrim); first += 2; cnt -= 2; }
+        if (bestPrim >= 0 && bestT < stopBelow) return true;
+    }
+    if (sp == 0) return true;
+    sp--;
+    cur = stack[sp * 64];
+    return false;
+}
+
 }  // namespace ptd

@@ -50,6 +50,12 @@ class PtErrorEstimate(C.Structure):
     _fields_ = [("rel_rms", C.c_double), ("mean_rel_se", C.c_double), ("pixels", C.c_int64), ("skipped", C.c_int64)]
 
 
+class PtRayHit(C.Structure):
+    _fields_ = [("t", C.c_float), ("prim", C.c_int32)]
+
+
+HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4")])      # PtRayHit as a numpy record
+QUERY_CLOSEST, QUERY_ANY = 0, 1
 AOV_FLOATS = 8        # floats per pixel of pt_render_aov: albedo.rgb | normal.xyz | depth | coverage
 
 _lib = None
@@ -143,6 +149,8 @@ API = [
     ("pt_scene_update_spheres", C.c_int, [_P, _P, C.c_int32]),
     ("pt_scene_tree_inflation", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("pt_dbg_scene_array", C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
+    ("pt_trace_rays", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    ("pt_trace_rays_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
 ]
 
 # pt_dbg_scene_array: name -> (which, dtype of the download)
@@ -526,6 +534,41 @@ class Scene:
         r = C.c_double(0.0)
         _check(lib().pt_scene_tree_inflation(self._h, C.byref(r)), "pt_scene_tree_inflation")
         return r.value
+
+    def trace_rays(self, rays, any_hit=False, surface=False, stream_ptr=0):
+        """Cast the caller's rays (include/pt_api.h: pt_trace_rays).  rays: (n, 8) float32 RAY8 records, org.xyz dir.xyz 0 tmax.
+        Returns (t, prim) — float32 and int32 of length n, a miss is (0, -1) — and, with surface=True (closest hit only), the (n, 29)
+        HIT records of raycast() as a third item.  any_hit=True: prim >= 0 iff the closest-hit query hits; which hit is unspecified.
+        A torch float32 tensor on the scene's device is used in place (data_ptr()): the query is enqueued on stream_ptr, the results
+        are torch tensors on that device, valid once the stream has passed the query, and `rays` must stay alive until then.
+        A numpy array goes through pt_trace_rays_host (synchronous) and returns numpy arrays."""
+        if any_hit and surface:
+            raise PtError("trace_rays: an any-hit query has no surface record")
+        mode = QUERY_ANY if any_hit else QUERY_CLOSEST
+        if isinstance(rays, np.ndarray):
+            r = np.ascontiguousarray(rays, np.float32)
+            if r.ndim != 2 or r.shape[1] != 8:
+                raise PtError(f"trace_rays: rays has shape {r.shape}, want (n, 8)")
+            n = r.shape[0]
+            hits = np.zeros(n, HIT_DTYPE)
+            surf = np.zeros((n, 29), np.float32) if surface else None
+            _check(lib().pt_trace_rays_host(self._h, _ptr(r), n, mode, _ptr(hits), _ptr(surf) if surface else None), "pt_trace_rays_host")
+            out = (np.ascontiguousarray(hits["t"]), np.ascontiguousarray(hits["prim"]))
+            return out + (surf,) if surface else out
+        if not (hasattr(rays, "data_ptr") and hasattr(rays, "is_contiguous")):
+            raise PtError("trace_rays: rays must be a torch tensor or a numpy array")
+        if str(rays.dtype) != "torch.float32" or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+            raise PtError(f"trace_rays: rays must be contiguous float32 of shape (n, 8), got {rays.dtype} {tuple(rays.shape)}")
+        if rays.device.type != "cuda" or rays.device.index != self.device:
+            raise PtError(f"trace_rays: rays is on {rays.device}, the scene is on device {self.device}")
+        import torch
+        n = rays.shape[0]
+        hits = torch.empty((n, 2), dtype=torch.int32, device=rays.device)      # PtRayHit: t's bits | prim
+        surf = torch.empty((n, 29), dtype=torch.float32, device=rays.device) if surface else None
+        _check(lib().pt_trace_rays(self._h, C.c_void_p(rays.data_ptr()), n, mode, C.c_void_p(hits.data_ptr()),
+                                   C.c_void_p(surf.data_ptr()) if surface else None, C.c_void_p(stream_ptr)), "pt_trace_rays")
+        out = (hits[:, 0].view(torch.float32), hits[:, 1])
+        return out + (surf,) if surface else out
 
     def dbg_array(self, name):
         """pt_dbg_scene_array: one device array of the scene as a flat numpy array (SCENE_ARRAYS; layouts: csrc/pt_device.h)."""

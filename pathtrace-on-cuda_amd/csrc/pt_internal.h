@@ -34,7 +34,7 @@ struct WfJob {
     //   cam                                  the fixed share of prm.rank / world (wf_init)
     //   cam + tileList                       prm.n_tiles_local global tile numbers on the device (wf_init_list); nothing else of the pipeline differs
     //   viewCams + viewFirstPass + viewOrg   a batch, one device entry per view and cam == nullptr: n_tiles_local = views x prm.n_tiles_total,
-    //                                        streams are set up by wf_init_views and stepped by wf_shade_views / wf_drain_views
+    //                                        streams are set up by wf_init_views and stepped by the ViewTable instantiations of wf_shade / wf_drain
     const DevCamera* cam;
     const int32_t* tileList;
     const DevCamera* viewCams; const int32_t* viewFirstPass; const float4* viewOrg;

@@ -63,20 +63,6 @@ constexpr uint32_t kShardBlock = SHARD_BLOCK;   // queue indices per block of th
 // launch resumes it.  hit.prim <= -2 encodes "pending, record = -2 - prim".
 constexpr int kWfBudget = 256;        // least node steps a ray may take per launch (measured: 96 cost 8 % on a 2M-stream render, >= 192 is flat)
 constexpr int kSuspInts = 4 + kWfLdsStack + kWfOvfLevels;
-// Top of the tree in LDS.  Every ray walks the first levels of the quad tree, and the kernel's vector-memory path is its
-// busiest unit (TA / TD ~70 % busy: each lane fetches its own 64-byte node, 4 x 16 B per lane per node step), so the
-// first kTopNodes nodes (breadth-first numbering, host/accel_build.cpp) are copied into LDS by every workgroup and
-// node steps on them read LDS instead.  80-byte stride: consecutive nodes start 20 banks apart, so the 16 lanes of
-// a ds_read_b128 group rarely collide.  Size: 16 KB of stacks + 6 KB of tree per workgroup, 7 workgroups per CU.
-// Node step: 1 = sort the four (entry distance, child) pairs (rounds 1-2), 0 = nearest child exactly, the others in slot order (round 3)
-#ifndef TRACE_SORT4
-#define TRACE_SORT4 1
-#endif
-#ifndef TRACE_TOP_NODES
-#define TRACE_TOP_NODES 0
-#endif
-constexpr int kTopNodes = TRACE_TOP_NODES > 0 ? TRACE_TOP_NODES : 1;
-[[maybe_unused]] constexpr int kTopStride = 5;         // uint4 per staged node
 
 // block-aggregated append to four lists at once (live streams + one ray queue per kind): one atomicAdd
 // per list per block.  (One atomic per wave was the shade kernel's bottleneck: ~100k returning atomics
@@ -116,119 +102,71 @@ PT_DEV void block_append(const bool (&e)[N], const uint32_t (&id)[N], uint32_t* 
 }
 
 // ---------------------------------------------------------------------------------------
-// wf_init: StartRender prologue for every stream (pathtracer.cu:70-74)
+// wf_init, wf_init_list, wf_init_views: StartRender prologue for every stream (pathtracer.cu:70-74).
+// This is the only place of the pipeline that turns a stream into a pixel: from here on a stream is its slot, so wf_trace, wf_shade
+// and wf_drain are the same for all three.  The kernels differ in `place` alone: it turns (local tile, pass relative to the job's
+// first) into the stream's camera, its tile of the frame and its pass.  TILE_TEST: a tile beyond the frame is a dead stream.
 // ---------------------------------------------------------------------------------------
+template <bool TILE_TEST, class Place>
+PT_DEV void init_streams(const DevScene& sc, const DevParams& prm, const WfBuf& b, uint32_t nStreams, Place place)
+{
+    const uint32_t sid = blockIdx.x * 256u + threadIdx.x;
+    bool live = false, camShort = false;
+    if (sid < nStreams) {
+        const uint32_t unit = (uint32_t)prm.unit_base + (sid >> 6), lane = sid & 63;
+        const int pass_rel = (int)(unit / (uint32_t)prm.n_tiles_local);
+        int tile, pass;
+        const DevCamera& cam = place(unit % (uint32_t)prm.n_tiles_local, pass_rel, tile, pass);
+        const int tx = tile % prm.tiles_x, ty = tile / prm.tiles_x;
+        const int px = tx * kTile + (int)(lane & 7), py = ty * kTile + (int)(lane >> 3);
+        live = (!TILE_TEST || tile < prm.n_tiles_total) && (px < cam.W) && (py < cam.H);
+        if (live) {
+            init_stream(cam, prm, b, sid, px, py, pass);
+            const float4 d0 = b.ray_d[0][sid];
+            camShort = ray_is_short(sc, f3(cam.pos[0], cam.pos[1], cam.pos[2]), f3(d0.x, d0.y, d0.z), 3.0e38f);
+        } else {
+            b.staging[3 * (size_t)sid + 0] = 0.f; b.staging[3 * (size_t)sid + 1] = 0.f; b.staging[3 * (size_t)sid + 2] = 0.f;
+        }
+    }
+    // the camera ray: queued by class like every other ray (a pixel that looks past the mesh has a short ray)
+    const bool shortRay = live && camShort;
+    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1: the last entry of a queue array
+    const bool e[kLists] = {live, live && !shortRay, false, false, shortRay, false, false};
+    uint32_t* const c[kLists] = {&b.cnt[0].nActive, &b.cnt[0].nRays[0][0], &b.cnt[0].nRays[1][0], &b.cnt[0].nRays[2][0],
+                                 &b.cnt[0].nRays[0][kShortWord], &b.cnt[0].nRays[1][kShortWord], &b.cnt[0].nRays[2][kShortWord]};
+    uint32_t* const l[kLists] = {b.active[0], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
+    const uint32_t ids[kLists] = {sid, sid, sid, sid, sid, sid, sid};
+    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
+    block_append<kLists>(e, ids, c, l, top);
+}
+
+// one camera, the fixed share of the frame: local tile lt is tile lt * world + rank
 __global__ __launch_bounds__(256)
 void wf_init(DevScene sc, DevCamera cam, DevParams prm, WfBuf b, uint32_t nStreams)
 {
-    const uint32_t sid = blockIdx.x * 256u + threadIdx.x;
-    bool live = false, camShort = false;
-    if (sid < nStreams) {
-        const uint32_t unit = (uint32_t)prm.unit_base + (sid >> 6), lane = sid & 63;
-        const int pass_rel = (int)(unit / (uint32_t)prm.n_tiles_local);
-        const int lt = (int)(unit % (uint32_t)prm.n_tiles_local);
-        const int tile = lt * prm.world + prm.rank;
-        const int tx = tile % prm.tiles_x, ty = tile / prm.tiles_x;
-        const int px = tx * kTile + (int)(lane & 7), py = ty * kTile + (int)(lane >> 3);
-        const int pass = prm.first_pass + pass_rel;
-        live = (tile < prm.n_tiles_total) && (px < cam.W) && (py < cam.H);
-        if (live) {
-            init_stream(cam, prm, b, sid, px, py, pass);
-            const float4 d0 = b.ray_d[0][sid];
-            camShort = ray_is_short(sc, f3(cam.pos[0], cam.pos[1], cam.pos[2]), f3(d0.x, d0.y, d0.z), 3.0e38f);
-        } else {
-            b.staging[3 * (size_t)sid + 0] = 0.f; b.staging[3 * (size_t)sid + 1] = 0.f; b.staging[3 * (size_t)sid + 2] = 0.f;
-        }
-    }
-    // the camera ray: queued by class like every other ray (a pixel that looks past the mesh has a short ray)
-    const bool shortRay = live && camShort;
-    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1: the last entry of a queue array
-    const bool e[kLists] = {live, live && !shortRay, false, false, shortRay, false, false};
-    uint32_t* const c[kLists] = {&b.cnt[0].nActive, &b.cnt[0].nRays[0][0], &b.cnt[0].nRays[1][0], &b.cnt[0].nRays[2][0],
-                                 &b.cnt[0].nRays[0][kShortWord], &b.cnt[0].nRays[1][kShortWord], &b.cnt[0].nRays[2][kShortWord]};
-    uint32_t* const l[kLists] = {b.active[0], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
-    const uint32_t ids[kLists] = {sid, sid, sid, sid, sid, sid, sid};
-    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
-    block_append<kLists>(e, ids, c, l, top);
+    init_streams<true>(sc, prm, b, nStreams, [&](uint32_t lt, int pass_rel, int& tile, int& pass) -> const DevCamera& {
+        tile = (int)lt * prm.world + prm.rank; pass = prm.first_pass + pass_rel; return cam; });
 }
 
-// wf_init_list: wf_init with the tile of local index lt taken from a list (pt_render_tile_list: any n_tiles_local tiles of the frame, in
-// any order) instead of the fixed share lt * world + rank — the one line that differs.  A kernel of its own, with the list as an extra
-// argument and wf_init left as it is: this is the only place of the pipeline that turns a stream into a pixel, from here on a stream is
-// its slot, so wf_trace, wf_shade and wf_drain (and the argument blocks they get by value) are the same for both.
+// one camera, local tile lt taken from a list (pt_render_tile_list: any n_tiles_local tiles of the frame, in any order)
 __global__ __launch_bounds__(256)
 void wf_init_list(DevScene sc, DevCamera cam, DevParams prm, WfBuf b, uint32_t nStreams, const int32_t* __restrict__ tileList)
 {
-    const uint32_t sid = blockIdx.x * 256u + threadIdx.x;
-    bool live = false, camShort = false;
-    if (sid < nStreams) {
-        const uint32_t unit = (uint32_t)prm.unit_base + (sid >> 6), lane = sid & 63;
-        const int pass_rel = (int)(unit / (uint32_t)prm.n_tiles_local);
-        const int lt = (int)(unit % (uint32_t)prm.n_tiles_local);
-        const int tile = tileList[lt];
-        const int tx = tile % prm.tiles_x, ty = tile / prm.tiles_x;
-        const int px = tx * kTile + (int)(lane & 7), py = ty * kTile + (int)(lane >> 3);
-        const int pass = prm.first_pass + pass_rel;
-        live = (tile < prm.n_tiles_total) && (px < cam.W) && (py < cam.H);
-        if (live) {
-            init_stream(cam, prm, b, sid, px, py, pass);
-            const float4 d0 = b.ray_d[0][sid];
-            camShort = ray_is_short(sc, f3(cam.pos[0], cam.pos[1], cam.pos[2]), f3(d0.x, d0.y, d0.z), 3.0e38f);
-        } else {
-            b.staging[3 * (size_t)sid + 0] = 0.f; b.staging[3 * (size_t)sid + 1] = 0.f; b.staging[3 * (size_t)sid + 2] = 0.f;
-        }
-    }
-    // the camera ray: queued by class like every other ray (a pixel that looks past the mesh has a short ray)
-    const bool shortRay = live && camShort;
-    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1: the last entry of a queue array
-    const bool e[kLists] = {live, live && !shortRay, false, false, shortRay, false, false};
-    uint32_t* const c[kLists] = {&b.cnt[0].nActive, &b.cnt[0].nRays[0][0], &b.cnt[0].nRays[1][0], &b.cnt[0].nRays[2][0],
-                                 &b.cnt[0].nRays[0][kShortWord], &b.cnt[0].nRays[1][kShortWord], &b.cnt[0].nRays[2][kShortWord]};
-    uint32_t* const l[kLists] = {b.active[0], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
-    const uint32_t ids[kLists] = {sid, sid, sid, sid, sid, sid, sid};
-    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
-    block_append<kLists>(e, ids, c, l, top);
+    init_streams<true>(sc, prm, b, nStreams, [&](uint32_t lt, int pass_rel, int& tile, int& pass) -> const DevCamera& {
+        tile = tileList[(int)lt]; pass = prm.first_pass + pass_rel; return cam; });
 }
 
-// wf_init_views: wf_init for a batch of cameras (pt_render_views).  Local tile lt -> (view = lt / tilesPerView, tile = lt % tilesPerView):
-// the camera comes from a device array, the pass is the view's own first pass + pass_rel.  prm is that of a world of one whose "frame"
-// has n_views x tilesPerView tiles (tiles_x / tiles_y / n_tiles_total are one view's), so the unit and staging arithmetic downstream is
-// what it is for one camera; like wf_init_list a kernel of its own, with wf_init left as it is.
+// a batch of cameras (pt_render_views).  Local tile lt -> (view = lt / tilesPerView, tile = lt % tilesPerView, inside the frame by
+// construction): the camera comes from a device array, the pass is the view's own first pass + pass_rel.  prm is that of a world of one
+// whose "frame" has n_views x tilesPerView tiles (tiles_x / tiles_y / n_tiles_total are one view's), so the unit and staging
+// arithmetic downstream is what it is for one camera.
 __global__ __launch_bounds__(256)
 void wf_init_views(DevScene sc, DevParams prm, WfBuf b, uint32_t nStreams, const DevCamera* __restrict__ cams, const int32_t* __restrict__ firstPass,
                    uint32_t tilesPerView)
 {
-    const uint32_t sid = blockIdx.x * 256u + threadIdx.x;
-    bool live = false, camShort = false;
-    if (sid < nStreams) {
-        const uint32_t unit = (uint32_t)prm.unit_base + (sid >> 6), lane = sid & 63;
-        const int pass_rel = (int)(unit / (uint32_t)prm.n_tiles_local);
-        const uint32_t lt = unit % (uint32_t)prm.n_tiles_local;
+    init_streams<false>(sc, prm, b, nStreams, [&](uint32_t lt, int pass_rel, int& tile, int& pass) -> DevCamera {
         const uint32_t view = lt / tilesPerView;
-        const int tile = (int)(lt % tilesPerView);
-        const int tx = tile % prm.tiles_x, ty = tile / prm.tiles_x;
-        const int px = tx * kTile + (int)(lane & 7), py = ty * kTile + (int)(lane >> 3);
-        const DevCamera cam = cams[view];
-        const int pass = firstPass[view] + pass_rel;
-        live = (px < cam.W) && (py < cam.H);
-        if (live) {
-            init_stream(cam, prm, b, sid, px, py, pass);
-            const float4 d0 = b.ray_d[0][sid];
-            camShort = ray_is_short(sc, f3(cam.pos[0], cam.pos[1], cam.pos[2]), f3(d0.x, d0.y, d0.z), 3.0e38f);
-        } else {
-            b.staging[3 * (size_t)sid + 0] = 0.f; b.staging[3 * (size_t)sid + 1] = 0.f; b.staging[3 * (size_t)sid + 2] = 0.f;
-        }
-    }
-    // the camera ray: queued by class like every other ray (a pixel that looks past the mesh has a short ray)
-    const bool shortRay = live && camShort;
-    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1: the last entry of a queue array
-    const bool e[kLists] = {live, live && !shortRay, false, false, shortRay, false, false};
-    uint32_t* const c[kLists] = {&b.cnt[0].nActive, &b.cnt[0].nRays[0][0], &b.cnt[0].nRays[1][0], &b.cnt[0].nRays[2][0],
-                                 &b.cnt[0].nRays[0][kShortWord], &b.cnt[0].nRays[1][kShortWord], &b.cnt[0].nRays[2][kShortWord]};
-    uint32_t* const l[kLists] = {b.active[0], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
-    const uint32_t ids[kLists] = {sid, sid, sid, sid, sid, sid, sid};
-    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
-    block_append<kLists>(e, ids, c, l, top);
+        tile = (int)(lt % tilesPerView); pass = firstPass[view] + pass_rel; return cams[view]; });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -244,7 +182,7 @@ void wf_init_views(DevScene sc, DevParams prm, WfBuf b, uint32_t nStreams, const
 template <int MODE, bool PUBLISH = false>      // PUBLISH: hits are stored device-coherently (wf_shade PHASE 1 reads them while this kernel drains);  MODE: 0 production, 1 trip counters + histograms + timeline (PTAMD_TSTAT=1), 2 timeline only (PTAMD_TSTAT=2), 3 trip counters + section clocks, no per-step atomics (PTAMD_TSTAT=3)
 __global__ __launch_bounds__(256, TRACE_WAVES)
 void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chunkShift, int budgetShift, int budgetMin, int guideShift, int triTrig, int refillMin,
-              int topWant, unsigned long long* stat, int statLaunch, int helpShards, int lateBudget)
+              unsigned long long* stat, int statLaunch, int helpShards, int lateBudget)
 {
     constexpr bool STAT = MODE == 1 || MODE == 3, HIST = MODE == 1, timeline = MODE != 0;
     // PUBLISH launches share the chip with wf_shade's early phase: the traversal is the critical path of the iteration (its last waves
@@ -270,12 +208,6 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
     const uint32_t p5 = p4 + b.cnt[slot].nRays[1][kShortWord];
     const uint32_t n = p5 + b.cnt[slot].nRays[2][kShortWord];
     if ((uint32_t)blockIdx.x * 256u >= n) return;      // surplus blocks leave before touching the queue (fewer rays per workgroup: no faster, r02_b21.log)
-#if TRACE_TOP_NODES > 0
-    __shared__ uint4 lds_top[kTopNodes * kTopStride];
-    const int topN = min(min(topWant, kTopNodes), sc.n_quad);
-    for (int i = threadIdx.x; i < topN * 4; i += 256) lds_top[(i >> 2) * kTopStride + (i & 3)] = sc.quad[i];
-    __syncthreads();
-#endif
 
     const int lane = threadIdx.x & 63;
     int* stack = &lds_stack[threadIdx.x >> 6][lane];
@@ -339,14 +271,9 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     // A shard owns every 16th block of kShardBlock queue indices (block b -> shard b % 16), so all shards walk the index
                     // space front to back together: path rays are started first and the (shorter, any-hit) shadow rays last, which
                     // is what is still in flight when the queue runs dry.  chunkPos / chunkEnd are shard-local positions.
-#ifdef PT_SHARD_CONTIG      // A/B build: a shard owns one contiguous sixteenth of the index space
-                    const uint32_t cLo = (uint32_t)(((unsigned long long)n * (unsigned)shard) / kWfShards);
-                    const uint32_t cnt = (uint32_t)(((unsigned long long)n * (unsigned)(shard + 1)) / kWfShards) - cLo;
-#else
                     const uint32_t rounds = n / (kShardBlock * kWfShards), rem = n % (kShardBlock * kWfShards);
                     const uint32_t part = rem > (uint32_t)shard * kShardBlock ? rem - (uint32_t)shard * kShardBlock : 0u;
                     const uint32_t cnt = rounds * kShardBlock + (part < kShardBlock ? part : kShardBlock);      // indices this shard owns
-#endif
                     // guided self-scheduling: the chunk shrinks with what this wave last saw left in the shard, so the
                     // last rays of a launch are spread over many waves instead of queuing behind one
                     uint32_t want = seenLeft >> guideShift;
@@ -371,11 +298,7 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     const uint32_t r = (uint32_t)__builtin_popcountll(idle & ((1ull << lane) - 1ull));
                     if (r < take) {
                         const uint32_t j = chunkPos + r;      // shard-local -> queue index
-#ifdef PT_SHARD_CONTIG
-                        const uint32_t q = (uint32_t)(((unsigned long long)n * (unsigned)shard) / kWfShards) + j;
-#else
                         const uint32_t q = ((j / kShardBlock) * kWfShards + (uint32_t)shard) * kShardBlock + (j % kShardBlock);
-#endif
                         // segment of q -> kind, position in the kind's queue array (front part upwards, short part downwards from n16 - 1)
                         const bool shortSeg = q >= p3;
                         const uint32_t b0 = shortSeg ? p3 : 0u, b1 = shortSeg ? p4 : p1, b2 = shortSeg ? p5 : p2;      // segment starts of kinds 0, 1, 2
@@ -384,7 +307,7 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                         const uint32_t local = q - (k0 ? b0 : (k1 ? b1 : b2));
                         const uint32_t qid = b.rq[0][kn + (shortSeg ? n16 - 1u - local : local)];
                         hs = kn + (qid & ~kResumeBit);
-                        const float4 o = ld_s(&b.ray_o[0][hs + kn]), d = ld_s(&b.ray_d[0][hs + kn]);
+                        const float4 o = b.ray_o[0][hs + kn], d = b.ray_d[0][hs + kn];
                         const int kind = k0 ? 0 : 1;      // all that is still asked of it: path ray or not
                         org = f3(o.x, o.y, o.z); dir = f3(d.x, d.y, d.z);
                         ray_setup(dir, inv, cscale, degenerate);      // pt_trace.h
@@ -479,20 +402,8 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                 // of a coordinate share a dword), and the far side is cut at the closest hit.  The boxes only
                 // steer the search — acceptance is Triangle::hit + the reference's leaf box — so all that
                 // matters is that no box containing a point the ray reaches is ever rejected.
-                uint4 n0, n1, n2, n3;
-#if TRACE_TOP_NODES > 0
-                if (cur < topN) {
-                    // explicit LDS reads: left to itself the compiler merges the two address spaces into flat_load instructions,
-                    // which cost the whole kernel 18 % (every node fetch then waits on both counters and the ray origin spills)
-                    const uint32_t la = (uint32_t)(uintptr_t)(lds_top + cur * kTopStride);
-                    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\tds_read_b128 %3, %4 offset:48\n\ts_waitcnt lgkmcnt(0)"
-                                 : "=&v"(n0), "=&v"(n1), "=&v"(n2), "=&v"(n3) : "v"(la) : "memory");
-                } else
-#endif
-                {
-                    const uint4* np = sc.quad + 4 * (size_t)cur;
-                    n0 = np[0]; n1 = np[1]; n2 = np[2]; n3 = np[3];
-                }
+                const uint4* np = sc.quad + 4 * (size_t)cur;
+                uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
                 if (MODE == 2 && stLogAt) {
                     asm volatile("s_waitcnt vmcnt(0)" : "+v"(n0.x), "+v"(n1.x), "+v"(n2.x), "+v"(n3.x) :: "memory");
                     stW3 = (uint32_t)((__builtin_amdgcn_s_memrealtime() - stT0) & 0xfffffull);
@@ -529,7 +440,6 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     const float tf = __builtin_fminf(__builtin_fminf(tfx, tfy), __builtin_fminf(tfz, cullT));
                     key[k] = (tn <= tf) ? __float_as_int(tn) : 0x7fffffff;   // tn >= 0: its bits order like ints
                 }
-#if TRACE_SORT4
                 // sort (entry distance, ref) pairs: 5 compare-exchanges, each one compare + four selects (equal distances: any order will do)
                 int k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3], r0 = (int)n1.x, r1 = (int)n1.y, r2 = (int)n1.z, r3 = (int)n1.w;
 #define PT_CE(ka, ra, kb, rb) { const bool sw = ka > kb; const int tk = sw ? kb : ka, tr = sw ? rb : ra; kb = sw ? ka : kb; rb = sw ? ra : rb; ka = tk; ra = tr; }
@@ -547,27 +457,6 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     sp--;
                     cur = stack_at(sp);
                 }
-#else
-                // The nearest hit child next, found exactly (a 4-way minimum of the entry distances and four equality tests: 9 slow-class
-                // instructions where sorting all four (distance, ref) pairs took 25); the other hit children go to the stack in slot order.
-                // Measured on the config scenes' ray mix (tools/quad_order_lab.cpp): +0 ... +1.2 % node steps against the full sort — what
-                // matters is which child is entered first, hardly in which order the others wait.  The closest hit does not depend on
-                // the order of tests (tie rule), so this is result-neutral.
-                const int kmin = min(min(key[0], key[1]), min(key[2], key[3]));
-                if (kmin != 0x7fffffff) {
-                    const bool m0 = key[0] == kmin, m1 = !m0 && key[1] == kmin, m2 = !m0 && !m1 && key[2] == kmin, m3 = !m0 && !m1 && !m2;
-                    if (key[3] != 0x7fffffff && !m3) { if (sp < kWfLdsStack) stack[sp * 64] = (int)n1.w; else ovf[(sp - kWfLdsStack) * ovfStride] = (int)n1.w; sp++; }
-                    if (key[2] != 0x7fffffff && !m2) { if (sp < kWfLdsStack) stack[sp * 64] = (int)n1.z; else ovf[(sp - kWfLdsStack) * ovfStride] = (int)n1.z; sp++; }
-                    if (key[1] != 0x7fffffff && !m1) { if (sp < kWfLdsStack) stack[sp * 64] = (int)n1.y; else ovf[(sp - kWfLdsStack) * ovfStride] = (int)n1.y; sp++; }
-                    if (key[0] != 0x7fffffff && !m0) { if (sp < kWfLdsStack) stack[sp * 64] = (int)n1.x; else ovf[(sp - kWfLdsStack) * ovfStride] = (int)n1.x; sp++; }
-                    cur = m0 ? (int)n1.x : (m1 ? (int)n1.y : (m2 ? (int)n1.z : (int)n1.w));
-                } else if (sp == 0) {
-                    cur = kDone;
-                } else {
-                    sp--;
-                    cur = stack_at(sp);
-                }
-#endif
                 if (HIST) atomicAdd(&stat[kStatDepthHist + (sp > 31 ? 31 : sp)], 1ull);      // stack depth after this node step
                 if (cur < 0 && cur != kDone && pend == 0) {
                     // park the leaf, carry on with the next stack entry
@@ -600,7 +489,7 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; }
                 }
                 if (PUBLISH) __hip_atomic_store((unsigned long long*)&b.hit[0][hs], (unsigned long long)__float_as_uint(bestT) | ((unsigned long long)(uint32_t)bestPrim << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else st_s(&b.hit[0][hs], make_float2(bestT, __int_as_float(bestPrim)));
+                else b.hit[0][hs] = make_float2(bestT, __int_as_float(bestPrim));
                 hasRay = false;
                 if (STAT || MODE == 2) stRays++;
                 if (HIST) atomicAdd(&stat[kStatStepHist + (steps >= 252 ? 63 : steps >> 2)], 1ull);      // node steps of this ray (this launch), bins of 4
@@ -667,30 +556,91 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
 // A stream goes through the same shade_step either way: result-neutral.
 enum : uint32_t { R_ALIVE = 1, R_EMIT0 = 2, R_EMIT1 = 4, R_EMIT2 = 8, R_SHORT0 = 16, R_SHORT1 = 32, R_SHORT2 = 64, R_DONE = 128 };      // res[]: what phase 1 did with a list position
 
-PT_DEV float2 load_hit_coherent(const float2* p)
+// A stream's hit slot, touched once per kernel.  COHERENT (PHASE 1): wf_trace is still publishing hits beside this kernel.
+template <bool COHERENT>
+PT_DEV float2 load_hit(const float2* p)
 {
+    if (!COHERENT) return *p;
     const unsigned long long v = __hip_atomic_load((const unsigned long long*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return make_float2(__uint_as_float((uint32_t)v), __uint_as_float((uint32_t)(v >> 32)));
 }
 
-// The body of the step is one text (pt_shade_kernel.inc) compiled into two families of kernels: wf_shade for one camera, as it always
-// was, and wf_shade_views for a batch of them (pt_render_views), where `cam` is the batch's ViewTable instead of a DevCamera — all
-// that differs is where a restarted camera ray takes its origin from (pt_stream.h: camera_origin).  Shared as an include, not as a
-// device function both kernels call: with the step moved into a function the compiler allocated and scheduled the twelve existing
-// wf_shade instantiations and wf_drain differently (tools/kernel_isa_diff.sh), and their instruction streams are pinned.
-template <int WAVES, bool TWO, int PHASE = 0, bool MARK = false>
+// Cam: a DevCamera, or the ViewTable of a batch of views (pt_render_views) — all that differs is where a restarted camera ray takes
+// its origin from (pt_stream.h: camera_origin).  A batch is built for 4 waves per SIMD only, the default shape (PTAMD_SW does not apply to it).
+template <int WAVES, bool TWO, int PHASE = 0, bool MARK = false, class Cam = DevCamera>
 __global__ __launch_bounds__(WAVES * 256, WAVES)
-void wf_shade(DevScene sc, DevCamera cam, DevParams prm, WfBuf b, int slotIn, int slotOut, int slotClear, int listIn)
+void wf_shade(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int slotOut, int slotClear, int listIn)
 {
-#include "pt_shade_kernel.inc"
-}
-
-// Built for 4 waves per SIMD only, the default shape of wf_shade (PTAMD_SW does not apply to a batch).
-template <bool TWO, int PHASE = 0, bool MARK = false>
-__global__ __launch_bounds__(4 * 256, 4)
-void wf_shade_views(DevScene sc, ViewTable cam, DevParams prm, WfBuf b, int slotIn, int slotOut, int slotClear, int listIn)
-{
-#include "pt_shade_kernel.inc"
+    static_assert(PHASE == 0 || MARK, "the two-phase step needs the not-ready marks");
+    const uint32_t nIn = b.cnt[slotIn].nActive;
+    if (PHASE != 1 && blockIdx.x == 0) for (int k = threadIdx.x; k < kWfSlotBytes / 4; k += blockDim.x) ((uint32_t*)&b.cnt[slotClear])[k] = 0;
+    if ((uint32_t)blockIdx.x * blockDim.x >= nIn) return;
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool have = idx < nIn;
+    bool alive = false, emit[kRayKinds] = {false, false, false};
+    uint32_t sid = 0, resume = 0;      // resume: the queued rays are suspended traversals (wf_trace then reads their records)
+    uint32_t cls = 0;                  // bit k: the ray of kind k this step emitted is short (queued from the back of its queue)
+    bool step = have;
+    if (have) {
+        // While no stream has retired yet (more than half of a render's iterations) every stream is alive, so list position idx can
+        // simply take stream idx: one dependent fetch level less for the whole step (the list itself is in stream order only inside the
+        // blocks that appended to it; any one-to-one assignment of streams to lanes gives the same result).
+        sid = (nIn == (uint32_t)prm.n_units * 64u) ? idx : b.active[listIn][idx];
+        if (PHASE == 2) {
+            const uint32_t r = b.res[idx];
+            if (r & R_DONE) {      // shaded by phase 1: only the appends are left
+                step = false;
+                alive = (r & R_ALIVE) != 0; emit[0] = (r & R_EMIT0) != 0; emit[1] = (r & R_EMIT1) != 0; emit[2] = (r & R_EMIT2) != 0;
+                cls = (r / R_SHORT0) & 7u;
+            }
+        }
+    }
+    if (step) {
+        SState st;
+        const float2 hitP = load_hit<PHASE == 1>(&b.hit[0][sid]), hitS = load_hit<PHASE == 1>(&b.hit[1][sid]), hitA = load_hit<PHASE == 1>(&b.hit[2][sid]);      // same fetch level as the state
+        load_state(b, sid, st);
+        // a ray of this stream is still being traversed (time-sliced): wait one iteration
+        const int pendP = (st.flags & F_PATH) ? __float_as_int(hitP.y) : -1, pendS = (st.flags & F_SHADOW) ? __float_as_int(hitS.y) : -1;
+        const int pendA = (st.flags & F_SHADOWA) ? __float_as_int(hitA.y) : -1;
+        if (PHASE == 1 && (pendP <= -2 || pendS <= -2 || pendA <= -2)) {
+            // phase 1: a ray is not back yet (kNotReady), or a traversal is suspended (its slot keeps the record number until wf_trace
+            // resumes it, so the slot cannot tell "back" from "not yet"): phase 2 takes the stream
+            step = false;
+        } else if (pendP <= -2 || pendS <= -2 || pendA <= -2) {
+            alive = true; emit[0] = pendP <= -2; emit[1] = pendS <= -2; emit[2] = pendA <= -2; resume = kResumeBit;
+        } else {
+            const bool done = shade_step_t<TWO>(sc, cam, prm, b, sid, st, hitP, hitS, hitA);
+            if (done) {
+                write_mean(b, prm, sid, st);
+            } else {
+                const uint32_t nf = st.flags;
+                store_state(b, sid, st);
+                alive = true;
+                emit[0] = (nf & F_PATH) != 0; emit[1] = (nf & F_SHADOW) != 0; emit[2] = (nf & F_SHADOWA) != 0;
+                cls = st.cls;
+            }
+        }
+    }
+    // MARK: the hit slot of every ray this step emitted says "not traced yet" until wf_trace publishes its hit (a suspended traversal
+    // that is re-queued keeps its slot: it holds the record number).  Written here, at the end, where nothing else is live.
+    if (MARK && step && !resume) {
+#pragma unroll
+        for (int k = 0; k < kRayKinds; k++) if (emit[k]) b.hit[k][sid] = make_float2(0.f, __int_as_float(kNotReady));
+    }
+    if (PHASE == 1) {
+        if (have) b.res[idx] = (uint8_t)(step ? (R_DONE | (alive ? R_ALIVE : 0u) | (emit[0] ? R_EMIT0 : 0u) | (emit[1] ? R_EMIT1 : 0u) | (emit[2] ? R_EMIT2 : 0u) | (cls & 7u) * R_SHORT0) : 0u);
+        return;
+    }
+    // a re-queued suspended traversal is long by definition: cls = 0 for it (it never went through the step)
+    const bool s0 = (cls & 1u) != 0, s1 = (cls & 2u) != 0, s2 = (cls & 4u) != 0;
+    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1
+    const bool e[kLists] = {alive, emit[0] && !s0, emit[1] && !s1, emit[2] && !s2, emit[0] && s0, emit[1] && s1, emit[2] && s2};
+    uint32_t* const c[kLists] = {&b.cnt[slotOut].nActive, &b.cnt[slotOut].nRays[0][0], &b.cnt[slotOut].nRays[1][0], &b.cnt[slotOut].nRays[2][0],
+                                 &b.cnt[slotOut].nRays[0][kShortWord], &b.cnt[slotOut].nRays[1][kShortWord], &b.cnt[slotOut].nRays[2][kShortWord]};
+    uint32_t* const l[kLists] = {b.active[listIn ^ 1], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
+    const uint32_t ids[kLists] = {sid, sid | resume, sid | resume, sid | resume, sid, sid, sid};
+    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
+    block_append<kLists>(e, ids, c, l, top);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -709,18 +659,83 @@ constexpr int kDrainQuadStack = 40;      // per-lane stack entries of wf_drain's
 #define DRAIN_MINBLOCKS 1      // workgroups per CU the register allocation of wf_drain must allow: 1 = free (189 VGPRs with the 4-wide walk: 2 waves/SIMD), 3 = 168 VGPRs (16 spilled)
 #endif
 // quad_step, one step of one lane's walk through the 4-wide tree, lives in pt_trace.h (pt_query.hip walks with it too).
-template <bool QUAD>      // QUAD: walk the 4-wide tree (quad_step); the host picks it when the walk fits the per-lane stack
+template <bool QUAD, class Cam = DevCamera>      // QUAD: walk the 4-wide tree (quad_step); the host picks it when the walk fits the per-lane stack.  Cam: as in wf_shade
 __global__ __launch_bounds__(kBlockThreads, DRAIN_MINBLOCKS)
-void wf_drain(DevScene sc, DevCamera cam, DevParams prm, WfBuf b, int slotIn, int listIn, int spreadShift)
+void wf_drain(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int listIn, int spreadShift)
 {
-#include "pt_drain_kernel.inc"
+    __shared__ int lds_stack[kWavesPerBlock][(QUAD ? kDrainQuadStack : kStackDepth) * 64];
+    const uint32_t nIn = b.cnt[slotIn].nActive;
+    // spreadShift: only every 2^s-th lane carries a stream.  The kernel is bound by latency (a wave steps at the pace of its slowest
+    // lane, every bounce), and the chip is far from full at this point: thinner waves wait for the maximum of fewer paths
+    const uint32_t t = blockIdx.x * (uint32_t)kBlockThreads + threadIdx.x;
+    if (t & ((1u << spreadShift) - 1u)) return;
+    const uint32_t idx = t >> spreadShift;
+    if (idx >= nIn) return;
+    int* stack = &lds_stack[threadIdx.x >> 6][threadIdx.x & 63];
+    const uint32_t sid = b.active[listIn][idx];
+    SState st;
+    load_state(b, sid, st);
+    for (;;) {
+        float2 hitP = make_float2(0.f, __int_as_float(-1)), hitS = hitP, hitA = hitP;
+        TraceStats ts{0, 0, 0};
+        if (QUAD) {
+            // The rays of this bounce (second-to-last shadow ray, shadow ray, path ray: any subset) in ONE flat loop: a lane that has finished a ray
+            // sets up its next one inside the loop, so the wave waits for the lane with the most steps in all — not, as with one
+            // loop per ray kind, for the slowest lane of each kind in turn.
+            int todo = ((st.flags & F_SHADOWA) ? 1 : 0) | ((st.flags & F_SHADOW) ? 2 : 0) | ((st.flags & F_PATH) ? 4 : 0);
+            f3 org(0.f, 0.f, 0.f), dir(0.f, 0.f, 1.f), inv(0.f, 0.f, 0.f);
+            float cscale = 0.f, bestT = 0.f, stopBelow = 0.f;
+            bool degenerate = false;
+            int bestPrim = -1, cur = 0, sp = 0, kind = -1;
+            for (;;) {
+                if (kind < 0) {
+                    if (todo == 0) break;
+                    kind = __builtin_ctz((unsigned)todo); todo &= todo - 1;
+                    if (kind == 0) {
+                        const float4 ao = b.ray_o[2][sid], ad = b.ray_d[2][sid];
+                        org = f3(ao.x, ao.y, ao.z); dir = f3(ad.x, ad.y, ad.z); bestT = ao.w; stopBelow = ad.w;
+                    } else if (kind == 1) { org = st.shO; dir = st.shD; bestT = st.shTmax; stopBelow = shadow_stop_t(st.shO, st.shTmax); }
+                    else { org = st.pathO; dir = st.pathD; bestT = 999999.f; stopBelow = -__builtin_inff(); }
+                    ray_setup(dir, inv, cscale, degenerate);
+                    bestPrim = -1; cur = 0; sp = 0;
+                }
+                if (quad_step(sc, org, dir, inv, cscale, degenerate, stopBelow, stack, cur, sp, bestT, bestPrim)) {
+                    for (int s = 0; s < sc.n_spheres; s++) {      // spheres, in order, against the triangles' closest t (CudaUtil.cuh:137-145)
+                        const float4 c = sc.spheres[4 * s];
+                        float root;
+                        if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; }
+                    }
+                    const float2 h = make_float2(bestT, __int_as_float(bestPrim));
+                    if (kind == 0) hitA = h; else if (kind == 1) hitS = h; else hitP = h;
+                    kind = -1;
+                }
+            }
+        } else {
+        if (st.flags & F_SHADOWA) {
+            const float4 ao = b.ray_o[2][sid], ad = b.ray_d[2][sid];
+            float t; const int prim = trace_closest<false>(sc, f3(ao.x, ao.y, ao.z), f3(ad.x, ad.y, ad.z), ao.w, stack, t, ts); hitA = make_float2(t, __int_as_float(prim));
+        }
+        if (st.flags & F_SHADOW) { float t; const int prim = trace_closest<false>(sc, st.shO, st.shD, st.shTmax, stack, t, ts); hitS = make_float2(t, __int_as_float(prim)); }
+        if (st.flags & F_PATH) { float t; const int prim = trace_closest<false>(sc, st.pathO, st.pathD, 999999.f, stack, t, ts); hitP = make_float2(t, __int_as_float(prim)); }
+        }
+        if (shade_step(sc, cam, prm, b, sid, st, hitP, hitS, hitA)) break;
+    }
+    write_mean(b, prm, sid, st);
 }
 
-template <bool QUAD>      // a batch of views (pt_render_views): `cam` is its ViewTable, as in wf_shade_views
-__global__ __launch_bounds__(kBlockThreads, DRAIN_MINBLOCKS)
-void wf_drain_views(DevScene sc, ViewTable cam, DevParams prm, WfBuf b, int slotIn, int listIn, int spreadShift)
+// The wf_shade instantiation for one step: every one the pipeline launches is named here, 12 for one camera and 8 for a batch of views
+// (4 waves per SIMD only).  The early phases and every launch with marks run the default shape.
+template <class Cam>
+static auto shade_kernel(int waves, bool two, int phase, bool mark) -> void (*)(DevScene, Cam, DevParams, WfBuf, int, int, int, int)
 {
-#include "pt_drain_kernel.inc"
+    if (phase == 1) return two ? wf_shade<4, true, 1, true, Cam> : wf_shade<4, false, 1, true, Cam>;
+    if (phase == 2) return two ? wf_shade<4, true, 2, true, Cam> : wf_shade<4, false, 2, true, Cam>;
+    if (mark) return two ? wf_shade<4, true, 0, true, Cam> : wf_shade<4, false, 0, true, Cam>;
+    if constexpr (std::is_same_v<Cam, DevCamera>) {
+        if (waves == 2) return two ? wf_shade<2, true> : wf_shade<2, false>;
+        if (waves == 3) return two ? wf_shade<3, true> : wf_shade<3, false>;
+    }
+    return two ? wf_shade<4, true, 0, false, Cam> : wf_shade<4, false, 0, false, Cam>;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -860,10 +875,9 @@ struct WfTuning {
                          // waves — one ray of several hundred steps, alone on its SIMD (tools/straggler_cost.py, r03_b41.log); cut there it goes on in
                          // the next launch among full waves, and no iteration is added: 4-way rank +3 %, 8-way +0.4 ... +2.5 %, configs[2] / [3] / [4]
                          // +0.3 / +0.5 / +1.2 % (32: -4 %, 48 / 96 / 128 within 1 % of 64; r03_b42.log, r03_b43.log)
-    int topNodes;        // PTAMD_TOP  quad nodes staged in LDS (TRACE_TOP_NODES builds only)
     // wf_shade: 4 waves/SIMD (126 VGPRs, nothing spilled since the library is built without the SLP vectoriser) in 512-thread workgroups =
     // two per CU; other shapes: 256 threads -4 %, 384 / 768 -13 %, 1024 -8 %, 3 waves/SIMD -9...-13 % (r02_t16_shade_shapes_after_noslp.log)
-    int shadeWaves;      // PTAMD_SW
+    int shadeWaves;      // PTAMD_SW   (one camera only: a batch of views runs the default shape)
     int shadeThreads;    // PTAMD_ST
     // wf_shade: may a stream whose path has just ended start its next sample in the same step (a second trip through the bounce code)?
     // It saves one iteration per sample but doubles the step's dependent chain: shadeRounds 0 / 1 forces it (pt_set_shade_rounds,
@@ -886,7 +900,7 @@ static const WfTuning& wf_tuning()
         WfTuning w;
         w.chunkShift = (int)num("PTAMD_CS", 12); w.guideShift = (int)num("PTAMD_GS", 9);
         w.budgetShift = (int)num("PTAMD_BS", 14); w.budgetMin = (int)num("PTAMD_BM", ptd::kWfBudget);
-        w.refillMin = (int)num("PTAMD_RF", ptd::kWfRefill); w.triTrig = (int)num("PTAMD_TT", 64); w.topNodes = (int)num("PTAMD_TOP", ptd::kTopNodes);
+        w.refillMin = (int)num("PTAMD_RF", ptd::kWfRefill); w.triTrig = (int)num("PTAMD_TT", 64);
         w.lateBudget = (int)num("PTAMD_LB", 64);
         w.helpShards = (int)num("PTAMD_HELP", 4); if (w.helpShards < 1) w.helpShards = 1; if (w.helpShards > ptd::kWfShards) w.helpShards = ptd::kWfShards;
         w.shadeWaves = (int)num("PTAMD_SW", 4); w.shadeThreads = threads("PTAMD_ST", 512);
@@ -917,7 +931,7 @@ struct WfCohort {
 
 // One cohort's pipeline on its own stream.  Blocks the calling host thread until the cohort has
 // drained (it polls the live-stream count every 16..64 iterations).
-static hipError_t run_cohort(const ptd::WfJob& job, WfCohort& co)
+static hipError_t cohort_pipeline(const ptd::WfJob& job, WfCohort& co)
 {
     using namespace ptd;
     const DevParams& prm = co.prm;
@@ -941,8 +955,8 @@ static hipError_t run_cohort(const ptd::WfJob& job, WfCohort& co)
     // (time-sliced rays add iterations; 64x is far beyond anything a finite tree can need)
     const long long hardCap = ((long long)prm.spp_per_pass * (prm.max_bounce + prm.max_refract + 3) + 8) * 64;
     const WfTuning& tn = wf_tuning();
-    const int guideShift = tn.guideShift, budgetShift = tn.budgetShift, budgetMin = tn.budgetMin, shadeWaves = batch ? 4 : tn.shadeWaves, shadeThreads = tn.shadeThreads;
-    const int earlyPrio = tn.earlyPrio, earlyThreads = tn.earlyThreads, refillMin = tn.refillMin, triTrig = tn.triTrig, chunkShift = tn.chunkShift, topNodes = tn.topNodes;
+    const int guideShift = tn.guideShift, budgetShift = tn.budgetShift, budgetMin = tn.budgetMin, shadeWaves = tn.shadeWaves, shadeThreads = tn.shadeThreads;
+    const int earlyPrio = tn.earlyPrio, earlyThreads = tn.earlyThreads, refillMin = tn.refillMin, triTrig = tn.triTrig, chunkShift = tn.chunkShift;
     const bool pubOnly = tn.pubOnly, traceStatClk = tn.traceStat == 3, traceStatFull = tn.traceStat == 1;
     const uint32_t trStreams = tn.trStreams;
     if (job.traceStat && tn.traceStat == 2 && tn.tracePool) {
@@ -978,26 +992,24 @@ static hipError_t run_cohort(const ptd::WfJob& job, WfCohort& co)
             // one launch for every build of wf_trace; statLaunch is the timeline slot of a diagnostic build, the issue priority in production
             const auto trace = job.traceStat ? (traceStatClk ? wf_trace<3> : traceStatFull ? wf_trace<1> : wf_trace<2>) : marks ? wf_trace<0, true> : wf_trace<0>;
             const int statLaunch = job.traceStat ? (it < kStatLaunches ? it : kStatLaunches - 1) : marks ? earlyPrio : 0;
-            hipLaunchKernelGGL(trace, dim3(tb), dim3(256), 0, stream, *job.scene, b, sIn, ovfStride, it & 1, chunkShift, budgetShift, budgetMin, guideShift, triTrig, refillMin, topNodes, job.traceStat, statLaunch, tn.helpShards, tn.lateBudget);
+            hipLaunchKernelGGL(trace, dim3(tb), dim3(256), 0, stream, *job.scene, b, sIn, ovfStride, it & 1, chunkShift, budgetShift, budgetMin, guideShift, triTrig, refillMin, job.traceStat, statLaunch, tn.helpShards, tn.lateBudget);
             if (timed) (void)hipEventRecord(co.trace_ev[3 * it + 1], stream);
             const dim3 sg((liveBound + shadeThreads - 1) / shadeThreads), sb(shadeThreads);
             const bool twoRounds = job.shadeRounds >= 0 ? (job.shadeRounds != 0) : (liveBound < trStreams);
-            // (a batch: W is not looked at — wf_shade_views exists for 4 waves per SIMD only, and the dispatch below passes 4 for it)
-#define PT_SHADE(W, T, P, M, S) do { if (batch) hipLaunchKernelGGL((wf_shade_views<T, P, M>), sg, sb, 0, S, *job.scene, views, prm, b, sIn, sOut, sClr, it & 1); \
-                                     else hipLaunchKernelGGL((wf_shade<W, T, P, M>), sg, sb, 0, S, *job.scene, *job.cam, prm, b, sIn, sOut, sClr, it & 1); } while (0)
+            // one launch for every instantiation of wf_shade (a batch: the views ones, 4 waves per SIMD whatever PTAMD_SW says)
+            auto shade = [&](int phase, hipStream_t s, dim3 g, dim3 blk) {
+                if (batch) hipLaunchKernelGGL(shade_kernel<ViewTable>(4, twoRounds, phase, marks), g, blk, 0, s, *job.scene, views, prm, b, sIn, sOut, sClr, it & 1);
+                else hipLaunchKernelGGL(shade_kernel<DevCamera>(shadeWaves, twoRounds, phase, marks), g, blk, 0, s, *job.scene, *job.cam, prm, b, sIn, sOut, sClr, it & 1);
+            };
             if (early) {
                 // phase 1 in small workgroups: a 256-thread workgroup needs one free wave slot per SIMD, i.e. two traversal workgroups of
                 // the CU gone, a 512-thread one four — it gets onto the chip earlier in the drain
-                { const dim3 sg((liveBound + earlyThreads - 1) / earlyThreads), sb(earlyThreads);
-                  if (twoRounds) PT_SHADE(4, true, 1, true, aux); else PT_SHADE(4, false, 1, true, aux); }
+                shade(1, aux, dim3((liveBound + earlyThreads - 1) / earlyThreads), dim3(earlyThreads));
                 if ((e = hipEventRecord(evOvl[2 + (it & 1)], aux)) != hipSuccess) return e;
                 if ((e = hipStreamWaitEvent(stream, evOvl[2 + (it & 1)], 0)) != hipSuccess) return e;
-                if (twoRounds) PT_SHADE(4, true, 2, true, stream); else PT_SHADE(4, false, 2, true, stream);
+                shade(2, stream, sg, sb);
             }
-            else if (marks) { if (twoRounds) PT_SHADE(4, true, 0, true, stream); else PT_SHADE(4, false, 0, true, stream); }
-            else if (twoRounds) { if (shadeWaves == 2) PT_SHADE(2, true, 0, false, stream); else if (shadeWaves == 3) PT_SHADE(3, true, 0, false, stream); else PT_SHADE(4, true, 0, false, stream); }
-            else { if (shadeWaves == 2) PT_SHADE(2, false, 0, false, stream); else if (shadeWaves == 3) PT_SHADE(3, false, 0, false, stream); else PT_SHADE(4, false, 0, false, stream); }
-#undef PT_SHADE
+            else shade(0, stream, sg, sb);
             if (timed) (void)hipEventRecord(co.trace_ev[3 * it + 2], stream);      // [3it+1, 3it+2] brackets this iteration's wf_shade
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -1014,10 +1026,8 @@ static hipError_t run_cohort(const ptd::WfJob& job, WfCohort& co)
             int spread = 0;
             while (spread < tn.drainSpread && ((size_t)co.h_cnt[0] << (spread + 1)) <= drainLanes) spread++;
             const int db = (int)((((size_t)co.h_cnt[0] << spread) + kBlockThreads - 1) / kBlockThreads);
-            if (batch && quadWalk) hipLaunchKernelGGL(wf_drain_views<true>, dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, views, prm, b, it % 3, it & 1, spread);
-            else if (batch) hipLaunchKernelGGL(wf_drain_views<false>, dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, views, prm, b, it % 3, it & 1, spread);
-            else if (quadWalk) hipLaunchKernelGGL(wf_drain<true>, dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, *job.cam, prm, b, it % 3, it & 1, spread);
-            else hipLaunchKernelGGL(wf_drain<false>, dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, *job.cam, prm, b, it % 3, it & 1, spread);
+            if (batch) hipLaunchKernelGGL((quadWalk ? wf_drain<true, ViewTable> : wf_drain<false, ViewTable>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, views, prm, b, it % 3, it & 1, spread);
+            else hipLaunchKernelGGL((quadWalk ? wf_drain<true> : wf_drain<false>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, *job.cam, prm, b, it % 3, it & 1, spread);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
             break;
@@ -1029,6 +1039,18 @@ static hipError_t run_cohort(const ptd::WfJob& job, WfCohort& co)
     co.iters = it;
     *co.trace_ev_used = co.trace_ev ? (it < co.trace_ev_triples ? it : co.trace_ev_triples) : 0;
     return hipSuccess;
+}
+
+// cohort_pipeline, and on any error nothing of it left running: callers free the work buffer on that path, and kernels already
+// launched — the early-shade ones on `aux` too — may still be using it.  The first error is what is returned.
+static hipError_t run_cohort(const ptd::WfJob& job, WfCohort& co)
+{
+    const hipError_t e = cohort_pipeline(job, co);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(co.stream);
+        if (co.aux) (void)hipStreamSynchronize(co.aux);
+    }
+    return e;
 }
 
 // Runs the whole pipeline for one job (pt_internal.h: WfJob) and blocks the host until the render has drained.
@@ -1047,8 +1069,8 @@ hipError_t ptk_wf_render(const ptd::WfJob& job)
     if (C > 1) { if ((e = hipEventRecord(job.ev_fork, stream)) != hipSuccess) return e; }
     std::vector<hipError_t> rc((size_t)C, hipSuccess);
     std::vector<WfCohort> cohort((size_t)C);
-    std::vector<std::thread> th;
     const int evPer = job.trace_ev ? job.trace_ev_triples / C : 0;
+    // every call of the set-up that can fail comes before the first thread starts: no path leaves this function with a joinable thread
     for (int c = 0; c < C; c++) {
         WfCohort& co = cohort[(size_t)c];
         co.prm = job.prm;
@@ -1062,9 +1084,14 @@ hipError_t ptk_wf_render(const ptd::WfJob& job)
         co.trace_ev_triples = evPer;
         co.trace_ev_used = &job.trace_ev_used[c];
         co.h_cnt = job.h_poll + 16 * c;
-        if (co.prm.n_units == 0) { *co.trace_ev_used = 0; continue; }
         // early shade needs a second stream and four events: with one cohort the scene's extra streams and fork / join events are free
         co.aux = (C == 1) ? job.xstreams[0] : nullptr;
+        if (co.prm.n_units == 0) *co.trace_ev_used = 0;
+    }
+    std::vector<std::thread> th;
+    for (int c = 0; c < C; c++) {
+        WfCohort& co = cohort[(size_t)c];
+        if (co.prm.n_units == 0) continue;
         auto run = [&job, &co, &rc, c]() { rc[(size_t)c] = run_cohort(job, co); };
         if (C == 1) run(); else th.emplace_back(run);
     }

@@ -308,12 +308,13 @@ def test_schedules_and_thresholds_are_result_neutral(_gpu, tmp_path):
         for f in files:
             if f.endswith(".csv"):
                 text += open(os.path.join(d, f)).read()
-    ran = set(re.findall(r"wf_shade_views<(?:true|false), [012], (?:true|false)>", text))
-    print("views shade kernels in the trace:", sorted(ran))
+    # wf_shade<WAVES, TWO, PHASE, MARK, Cam>: a batch runs the Cam = ptd::ViewTable instantiations (4 waves per SIMD), never a ptd::DevCamera one
+    shades = set(re.findall(r"wf_shade<[^>]*>", text))
+    print("shade kernels in the trace:", sorted(shades))
     for two in ("true", "false"):
         for phase in (1, 2):
-            assert f"wf_shade_views<{two}, {phase}, true>" in ran, (two, phase, sorted(ran))
-    assert "wf_init_views" in text and not re.search(r"wf_shade<", text)
+            assert f"wf_shade<4, {two}, {phase}, true, ptd::ViewTable>" in shades, (two, phase, sorted(shades))
+    assert "wf_init_views" in text and all(k.endswith(", ptd::ViewTable>") for k in shades), sorted(shades)
 
 
 class Device:

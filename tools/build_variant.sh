@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build an A/B variant of the library with extra device-compile flags: tools/build_variant.sh NAME "-DTRACE_TOP_NODES=0 ..."
+# Build an A/B variant of the library with extra device-compile flags: tools/build_variant.sh NAME "-DTRACE_WAVES=8 ..."
 # -> pathtrace-on-cuda_amd/build_NAME/libptamd_NAME.so  (use with PTAMD_LIB=...).  Only the .hip objects are rebuilt.
 set -e
 NAME=$1; EXTRA=$2

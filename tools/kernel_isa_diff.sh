@@ -1,10 +1,12 @@
 #!/bin/bash
 # Are the instruction streams of the kernels of two builds of one object file the same?  Compile only, no GPU needed:
-#   tools/kernel_isa_diff.sh OLD.o NEW.o [regex over demangled kernel names, default: every kernel]
+#   tools/kernel_isa_diff.sh OLD.o NEW.o [regex over demangled kernel names, default: every kernel] [sed -E script]
 # Takes the gfx950 code object out of each host object (.hip_fatbin section -> clang-offload-bundler), disassembles it and compares,
 # kernel by kernel, the instructions with addresses and comments stripped.  Prints one line per kernel and exits 1 if any differs.
+# The sed -E script, if given, renames kernels: it is applied to the demangled names of the OLD side (its whole disassembly: a name also
+# appears in branch targets) before matching, so a renamed kernel is compared with its parent instead of being reported as "only in".
 set -e
-old=$1; new=$2; pat=${3:-.}
+old=$1; new=$2; pat=${3:-.}; rename=${4:-}
 LLVM=${ROCM_PATH:-/opt/rocm}/llvm/bin
 tmp=$(mktemp -d); trap 'rm -rf "$tmp"' EXIT
 for side in old new; do
@@ -13,6 +15,7 @@ for side in old new; do
     $LLVM/clang-offload-bundler --type=o --unbundle --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$tmp/$side.fb --output=$tmp/$side.co
     $LLVM/llvm-objdump -d --no-show-raw-insn --no-leading-addr $tmp/$side.co | c++filt > $tmp/$side.s
 done
+[ -z "$rename" ] || sed -E -i "$rename" $tmp/old.s
 python3 - $tmp/old.s $tmp/new.s "$pat" <<'PY'
 import re, sys
 

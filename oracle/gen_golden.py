@@ -10,6 +10,8 @@ TEST INFRASTRUCTURE.  Two kinds of fixture are written:
  * oracle_*.npz images / ray tables produced by the CPU restatement under the pinned
                contract (o_set_libm(1)); they pin the oracle against regressions and let
                the GPU tests run where the oracle build is unavailable.
+ * ref_bxdf / ref_raycast / ref_nee / ref_image_*_b8.npz  inputs + outputs of oracle/_ref/ptref_int, the REAL reference's integrator
+               headers (include/CudaUtil.cuh, include/Bxdf.cuh) as host C++ behind oracle/curand_shim.h — gen_integrator() below.
  * anchors.json the three image means recorded in SURVEY.md Appendix A (measured by the
                survey on the reference's own source) — reproduced here with o_set_libm(0).
 """
@@ -25,7 +27,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "pathtrace-on-cuda_amd"))
 import oracle_lib as O  # noqa: E402
 import ptamd  # noqa: E402
-from scenes_util import jittered_grid, random_rays10, random_tris48, random_spheres16, scene_rays8, test_spheres  # noqa: E402
+from scenes_util import bxdf_inputs, jittered_grid, random_rays10, random_tris48, random_spheres16, scene_rays8, test_spheres  # noqa: E402
+import query_ref  # noqa: E402
 
 G = os.path.join(ROOT, "tests", "golden")
 
@@ -83,6 +86,148 @@ def gen_rocrand():
     np.savez_compressed(os.path.join(G, "ref_rocrand_xorwow.npz"), seeds=seeds, raw=np.stack(raw), uniform=np.stack(uni))
     print("ref_rocrand_xorwow.npz", np.stack(raw).shape)
 
+N_BXDF_RANDOM = 2048
+BXDF_SEED = 4100          # + lobe
+
+
+def _unit(v):
+    v = np.asarray(v, np.float64)
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def bxdf_edge_block(lobe):
+    """Hand-built rows (in28) at the places where eval / sample / pdf go wrong: n.wo from 1e-2 down to 1e-7 and exactly 0, on either side
+    of the surface, with front face 0 and 1 (total internal reflection for lobes 2 and 3); wo equal to n; wi equal to reflect(wo), to -wo,
+    exactly in the tangent plane; roughness 0, 0.0099, 0.01, 0.0101, 0.02 and 1 (the integrator's lobe threshold is 1e-2) times metallic
+    0 / 1, albedo 0 / 1, specular 0 (eta 1), 0.04 and 0.2.  Two frames: the axes (dot products exact) and a rotated one."""
+    rs = np.random.RandomState(BXDF_SEED + 50 + lobe)
+    frames = [(np.array([0., 0, 1]), np.array([1., 0, 0]), np.array([0., 1, 0]))]
+    n = _unit([0.36, -0.48, 0.8]); t = _unit(np.cross(n, [0.0, 0.0, 1.0])); frames.append((n, t, np.cross(n, t)))
+    base_rough = 0.0 if lobe in (1, 3) else 0.2
+    rows = []
+
+    def add(fr, front, albedo, spec, rough, metal, wo, wi):
+        n, t, b = fr
+        rows.append(np.concatenate([n, t, b, [front], np.full(3, albedo), np.full(3, spec), [rough, metal], wo, wi]))
+
+    def reflect(w, n):
+        return -w + 2 * np.dot(n, w) * n
+
+    for fr in frames:
+        n, t, b = fr
+        tang = _unit(0.6 * t + 0.8 * b)
+        up = _unit(0.5 * n + 0.3 * t - 0.4 * b)
+        # grazing wo, both sides, both faces
+        for c in (1e-2, 1e-3, 1e-4, 1e-5, 1e-6, 1e-7, 0.0):
+            for side in (1.0, -1.0):
+                wo = side * c * n + np.sqrt(1 - c * c) * tang
+                for front in (1.0, 0.0):
+                    for spec in (0.04, 0.2):
+                        for wi in (reflect(wo, n), -wo, _unit(-0.3 * t + 0.7 * b), up, -up):
+                            add(fr, front, 0.7, spec, base_rough, 0.0, wo, wi)
+        # wo equal to n (and to -n)
+        for wo in (n, -n):
+            for front in (1.0, 0.0):
+                for wi in (n, -n, tang, up, -up):
+                    add(fr, front, 0.7, 0.04, base_rough, 0.0, wo, wi)
+        # material sweep at a generic wo
+        wo = _unit(0.7 * n + 0.5 * t + 0.2 * b)
+        for rough in (0.0, 0.0099, 0.01, 0.0101, 0.02, 1.0):
+            for metal in (0.0, 1.0):
+                for albedo in (0.0, 1.0):
+                    for spec in (0.0, 0.04, 0.2):
+                        for front in (1.0, 0.0):
+                            for wi in (reflect(wo, n), up, -up, tang, -wo):
+                                add(fr, front, albedo, spec, rough, metal, wo, wi)
+    a = np.array(rows).astype(np.float32)
+    seeds = rs.randint(0, 2 ** 31, (a.shape[0], 2)).astype(np.uint32).view(np.float32)
+    return np.concatenate([a, seeds, np.zeros((a.shape[0], 2), np.float32)], 1)
+
+
+def bxdf_random_block(lobe):
+    a, seeds = bxdf_inputs(N_BXDF_RANDOM, np.random.RandomState(BXDF_SEED + lobe), lobe)
+    return np.concatenate([a, seeds, np.zeros((a.shape[0], 2), np.float32)], 1)
+
+
+def _sparse(full, base):
+    """Rows of `full` whose bits differ from `base` (NaN payloads included): indices and rows."""
+    d = np.nonzero((full.view(np.uint32) != base.view(np.uint32)).any(1))[0].astype(np.int32)
+    return d, full[d]
+
+
+def nee_rows(so):
+    """2,048 rows of o_nee's in5 on the lat_lon 24 scene with the test spheres: hit points of rays cast into the scene, the same points
+    pushed just under their surface, and points on and just under the light's plane."""
+    rs = np.random.RandomState(4200)
+    hits, prim, _ = so.raycast(scene_rays8(4000, rs))
+    h = hits[prim >= 0]
+    on = h[:1300, 5:8]
+    under = (h[1300:1748, 5:8] - np.float32(1e-3) * h[1300:1748, 8:11]).astype(np.float32)
+    lit = np.concatenate([np.stack([rs.uniform(-5, 5, 150), np.full(150, 39.98), rs.uniform(-5, 5, 150)], 1),
+                          np.stack([rs.uniform(-20, 20, 150), np.full(150, 39.999), rs.uniform(-20, 20, 150)], 1)])
+    pts = np.concatenate([on, under, lit]).astype(np.float32)
+    assert pts.shape[0] == 2048
+    seeds = rs.randint(0, 2 ** 32, (pts.shape[0], 2), dtype=np.uint64).astype(np.uint32)
+    return np.concatenate([pts, seeds.view(np.float32)], 1)
+
+
+INTEGRATOR_SCENES = (("cornell", 0, False), ("standin24", 1, False), ("standin24_spheres", 1, True))
+N_LONG = 1024
+LONG_SEED = 4300
+
+
+def gen_integrator():
+    """ref_bxdf / ref_raycast / ref_nee / ref_image_standin24_spheres_b8: what the REAL reference's integrator (oracle/_ref/ptref_int)
+    answers.  Own random streams, so every other fixture regenerates unchanged.  Data only: table rows in, table rows out.
+
+    ref_bxdf.npz      per lobe: the hand-built edge block (inputs stored), the sha256 of the 2,048 random rows (regenerated by
+                      scenes_util.bxdf_inputs from BXDF_SEED + lobe: 2,048 x 28 random floats x 4 lobes would be 0.9 MB), the reference's
+                      rows in contract mode for random + edge, and the rows that differ in glibc mode (indices + rows).
+    ref_raycast.npz   per scene: the reference's HIT records for the 4,096 scene_rays8 rays that oracle_<scene>.npz already stores, and for
+                      1,024 query_ref.set_c segments (stored once).  RayCast reaches no libm function besides sqrt: both modes, one answer.
+    ref_nee.npz       2,048 rows in, the reference's columns out."""
+    if not O.have_ref_int():
+        raise SystemExit("oracle/_ref/ptref_int missing: run `make -C oracle ref` first")
+    out = {}
+    for lobe in range(4):
+        rnd, edge = bxdf_random_block(lobe), bxdf_edge_block(lobe)
+        in28 = np.concatenate([rnd, edge])
+        con, gl = O.ref_int_bxdf(lobe, in28, 1), O.ref_int_bxdf(lobe, in28, 0)
+        idx, rows = _sparse(gl, con)
+        out.update({f"edge_in28_{lobe}": edge, f"random_sha256_{lobe}": np.array(sha(rnd)), f"contract_{lobe}": con,
+                    f"glibc_idx_{lobe}": idx, f"glibc_rows_{lobe}": rows})
+        print(f"ref_bxdf lobe {lobe}: {rnd.shape[0]} random + {edge.shape[0]} edge rows, {idx.size} differ between the libm modes")
+    np.savez_compressed(os.path.join(G, "ref_bxdf.npz"), n_random=N_BXDF_RANDOM, seed=BXDF_SEED, **out)
+
+    longs = query_ref.set_c(N_LONG, np.random.RandomState(LONG_SEED))
+    out = {"long_rays8": longs}
+    worlds = {}
+    for name, kind, with_sph in INTEGRATOR_SCENES:
+        nodes, tris, _ = O.bvh_build(ptamd.gen_scene(kind, 24))
+        sph = test_spheres() if with_sph else None
+        worlds[name] = (nodes, tris, sph)
+        rays8 = np.load(os.path.join(G, f"oracle_{name}.npz"))["rays8"]
+        for mode in (0, 1):
+            hits = O.ref_int_raycast(nodes, tris, sph, np.concatenate([rays8, longs]), mode)
+            assert mode == 0 or np.array_equal(hits.view(np.uint32), prev.view(np.uint32))
+            prev = hits
+        out[f"hits_{name}"], out[f"long_hits_{name}"] = hits[:len(rays8)], hits[len(rays8):]
+        print(f"ref_raycast {name}: {int(hits[:len(rays8), 0].sum())} of {len(rays8)} rays hit, {int(hits[len(rays8):, 0].sum())} of {N_LONG} segments")
+    np.savez_compressed(os.path.join(G, "ref_raycast.npz"), **out)
+
+    nodes, tris, sph = worlds["standin24_spheres"]
+    in5 = nee_rows(O.Scene(nodes, tris, sph))
+    nee = [O.ref_int_nee(nodes, tris, sph, in5, mode) for mode in (0, 1)]
+    assert np.array_equal(nee[0].view(np.uint32), nee[1].view(np.uint32))      # SamplePrimitive / GetLightColor: sqrt only
+    np.savez_compressed(os.path.join(G, "ref_nee.npz"), in5=in5, out12=nee[1], cols=np.array(O.NEE_REF_COLS))
+    print("ref_nee: lit rows", int((nee[1][:, 8:11].sum(1) > 0).sum()), "of", len(in5))
+
+    img = O.ref_int_render(nodes, tris, sph, O.make_camera(64, 64), 2, 8, 1)
+    np.savez_compressed(os.path.join(G, "ref_image_standin24_spheres_b8.npz"), image=img, passes=2, spp=8, max_bounce=8, spheres=sph)
+    print("ref_image_standin24_spheres_b8: mean", img.mean(dtype=np.float64))
+    for f in ("ref_bxdf", "ref_raycast", "ref_nee", "ref_image_standin24_spheres_b8"):
+        print(f, os.path.getsize(os.path.join(G, f + ".npz")), "bytes")
+
 
 def main():
     os.makedirs(G, exist_ok=True)
@@ -95,6 +240,9 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "png":
         gen_png()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "integrator":
+        gen_integrator()
         return
     if len(sys.argv) > 1 and sys.argv[1] == "camera_u8":
         gen_camera_u8()
@@ -154,6 +302,7 @@ def main():
                             image=img, image_counters=icnt, passes=2, spp=8, max_bounce=prm.max_bounce,
                             spheres=np.zeros((0, 16), np.float32) if sph is None else sph)
         print(name, "image mean", img.mean(dtype=np.float64), "hits", int((prim >= 0).sum()))
+    gen_integrator()      # after the oracle_*.npz files: it takes their rays
     print("golden fixtures written to", G)
 
 

@@ -91,6 +91,7 @@ int  o_render(void* scene, const OCamera* cam, const OParams* prm, float* accum_
 void o_tonemap(const float* raw_rgb, int n_pixels, int sample_cnt, unsigned char* rgb8);
 void o_u8(const float* v, int n, unsigned char* out);
 void o_pixel_dir(const OCamera* cam, const int* pxpypass, int n, float* out8);   /* StartRender prologue + GetPixelDirection, srcs/pathtracer.cu:33-40,70-74 */
+void o_pixel_dir_raw(const OCamera* cam, const int* pxpypass, int n, float* out3); /* GetPixelDirection's return value, before Ray's constructor */
 void o_nee(void* scene, const float* in5, int n, float* out12);                  /* NEE sample + GetLightColor, include/CudaUtil.cuh:38-48,150-166,235-245 */      /* ConverToUint8, include/image.h:5-8 */
 
 /* BxDF known-answer table.  lobe: 0 gltfpbr, 1 reflective, 2 refractive, 3 pure_refractive.

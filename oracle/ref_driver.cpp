@@ -11,10 +11,10 @@
 // and the headers include/CudaPrimitive.cuh, CudaVector.cuh, CudaRay.cuh
 // (Triangle::Copy/hit, Sphere::hit, HitResult::SetNormal, vec3, reflect, refract).
 // <cuda_runtime.h> is the REAL header bundled with this image's triton wheel; no CUDA
-// or cuRAND header is faked.  Everything that includes <curand_kernel.h>
-// (include/CudaUtil.cuh, include/Bxdf.cuh, srcs/pathtracer.cu) is NOT buildable in this
-// image and is therefore not part of this program: RayCast, the BxDFs and the
-// integrator are covered by the restatement in oracle/pt_oracle.cpp only.
+// or cuRAND header is faked for this program.  The integrator half (include/CudaUtil.cuh,
+// include/Bxdf.cuh: RayCast, the BxDFs, NEE, GetColor_iter) includes <curand_kernel.h> and
+// is therefore a program of its own, oracle/_ref/ptref_int (oracle/ref_int_driver.cpp behind
+// oracle/curand_shim.h); this one stays the host half, exactly as it was.
 //
 // The one thing the recipe adds is `lp64_min` below: srcs/bvh.cpp:204 (deprecated
 // K-means path, out of scope) calls min(unsigned long long, size_t), which only

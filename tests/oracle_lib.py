@@ -65,6 +65,7 @@ def lib():
         l.o_tonemap.argtypes = [P, C.c_int, C.c_int, P]
         l.o_u8.argtypes = [P, C.c_int, P]
         l.o_pixel_dir.argtypes = [C.POINTER(OCamera), P, C.c_int, P]
+        l.o_pixel_dir_raw.argtypes = [C.POINTER(OCamera), P, C.c_int, P]
         l.o_nee.argtypes = [P, P, C.c_int, P]
         l.o_bxdf.argtypes = [C.c_int, P, C.c_int, P]
         _lib = l
@@ -208,6 +209,24 @@ def pixel_dir(cam, pxpypass):
     return out
 
 
+def pixel_dir_raw(cam, pxpypass):
+    """GetPixelDirection's return value per (px, py, pass) row, before Ray's constructor normalises it again."""
+    a = np.ascontiguousarray(pxpypass, np.int32).reshape(-1, 3)
+    out = np.zeros((a.shape[0], 3), np.float32)
+    lib().o_pixel_dir_raw(C.byref(cam), _p(a), a.shape[0], _p(out))
+    return out
+
+
+def aces(rgb):
+    """The float stage of o_tonemap (ACESFilm) on (n, 3) values: o_tonemap with sample_cnt 1 ends in the uint8 cast, so the float
+    result is taken from the restatement's arithmetic in numpy float32, operation for operation (CudaUtil.cuh:383-391)."""
+    x = np.ascontiguousarray(rgb, np.float32)
+    f = np.float32
+    with np.errstate(all="ignore"):
+        r = (x * (f(2.51) * x + f(0.03))) / (x * (f(2.43) * x + f(0.59)) + f(0.14))
+        return np.where(r > 0, np.where(r < 1, r, f(1)), f(0)).astype(np.float32)      # saturate: NaN -> 0
+
+
 def u8(values):
     v = np.ascontiguousarray(values, np.float32)
     out = np.zeros(v.shape, np.uint8)
@@ -310,3 +329,97 @@ def rocrand_ref(seed, n):
     out = subprocess.run([ROCRAND_REF, str(int(seed)), str(int(n))], check=True, capture_output=True, text=True).stdout.split()
     a = np.array(out, dtype=np.uint64).astype(np.uint32).reshape(-1, 2)
     return a[:, 0].copy(), a[:, 1].copy().view(np.float32)
+
+
+# ---------------------------------------------------------------------------------------
+# oracle/_ref/ptref_int — the reference's integrator headers as host C++ (oracle/ref_int_driver.cpp)
+# ---------------------------------------------------------------------------------------
+PTREF_INT = os.path.join(ORACLE_DIR, "_ref", "ptref_int")
+LIBM_MODES = {0: "glibc", 1: "contract"}      # o_set_libm's modes and the driver's first argument
+NEE_REF_COLS = [0, 1, 2, 3, 4, 8, 9, 10, 11]  # the columns of o_nee the reference's own functions return
+
+
+def have_ref_int():
+    return os.path.exists(PTREF_INT) and os.access(PTREF_INT, os.X_OK)
+
+
+def _run_ref_int(mode, cmd, head, inputs, out_specs):
+    with tempfile.TemporaryDirectory() as d:
+        args = [PTREF_INT, LIBM_MODES[mode], cmd] + [str(h) for h in head]
+        for i, a in enumerate(inputs):
+            if isinstance(a, str):      # a file that is already there
+                args.append(a)
+                continue
+            p = os.path.join(d, f"in{i}.bin")
+            np.ascontiguousarray(a).tofile(p)
+            args.append(p)
+        outs = [os.path.join(d, f"out{i}.bin") for i in range(len(out_specs))]
+        subprocess.run(args + outs, check=True)
+        return [np.fromfile(p, dt) for p, dt in zip(outs, out_specs)]
+
+
+def _world(nodes, tris88, sph16):
+    sph = np.zeros((0, 16), np.float32) if sph16 is None else np.ascontiguousarray(sph16, np.float32)
+    return [np.frombuffer(np.ascontiguousarray(nodes).tobytes(), np.uint8), np.ascontiguousarray(tris88, np.float32), sph]
+
+
+def ref_int_rng(seed, n):
+    out = subprocess.run([PTREF_INT, "contract", "rng", str(int(seed)), str(int(n))], check=True, capture_output=True, text=True).stdout.split()
+    a = np.array(out, dtype=np.uint64).astype(np.uint32).reshape(-1, 2)
+    return a[:, 0].copy(), a[:, 1].copy().view(np.float32)
+
+
+def ref_int_bxdf(lobe, in28, mode):
+    (o,) = _run_ref_int(mode, "bxdf", [lobe], [np.ascontiguousarray(in28, np.float32)], [np.float32])
+    return o.reshape(-1, 12)
+
+
+def ref_int_raycast(nodes, tris88, sph16, rays8, mode=1):
+    (o,) = _run_ref_int(mode, "raycast", [], _world(nodes, tris88, sph16) + [np.ascontiguousarray(rays8, np.float32)], [np.float32])
+    return o.reshape(-1, HIT_FLOATS)
+
+
+def ref_int_nee(nodes, tris88, sph16, in5, mode=1):
+    (o,) = _run_ref_int(mode, "nee", [], _world(nodes, tris88, sph16) + [np.ascontiguousarray(in5, np.float32)], [np.float32])
+    return o.reshape(-1, 12)
+
+
+def ref_int_aces(rgb):
+    (o,) = _run_ref_int(1, "aces", [], [np.ascontiguousarray(rgb, np.float32)], [np.float32])
+    return o.reshape(-1, 3)
+
+
+def ref_int_render(nodes, tris88, sph16, cam, passes, spp, mode, nproc=8):
+    """A frame through `ptref_int paths`: one row per pixel and pass (camera position, GetPixelDirection's result from the oracle in the
+    same libm mode, seed = offset + pass * W * H, 2 draws to skip, spp), summed over the passes in pass order in float32 as
+    `image[offset] += pixelColor / NUM_SAMPLE` does (srcs/pathtracer.cu:81).  The rows are cut into nproc pieces run side by side."""
+    from concurrent.futures import ThreadPoolExecutor
+    W, H = cam.W, cam.H
+    py, px = np.mgrid[0:H, 0:W]
+    img = np.zeros((H * W, 3), np.float32)
+    old = set_libm(mode)
+    shared = tempfile.TemporaryDirectory()
+    try:
+        world = []
+        for i, a in enumerate(_world(nodes, tris88, sph16)):      # written once, read by every piece
+            world.append(os.path.join(shared.name, f"world{i}.bin"))
+            a.tofile(world[-1])
+        for ps in range(passes):
+            pix = np.stack([px.ravel(), py.ravel(), np.full(W * H, ps)], 1).astype(np.int32)
+            seed = (np.arange(W * H, dtype=np.int64) + ps * W * H).astype(np.uint64)
+            rows = np.zeros((W * H, 10), np.float32)
+            rows[:, 0:3] = np.array(list(cam.pos), np.float32)
+            rows[:, 3:6] = pixel_dir_raw(cam, pix)
+            u = rows.view(np.uint32)
+            u[:, 6] = (seed & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+            u[:, 7] = (seed >> np.uint64(32)).astype(np.uint32)
+            u[:, 8] = 2
+            u[:, 9] = spp
+            cuts = np.linspace(0, W * H, nproc + 1).astype(int)
+            with ThreadPoolExecutor(nproc) as ex:
+                parts = list(ex.map(lambda k: _run_ref_int(mode, "paths", [], world + [rows[cuts[k]:cuts[k + 1]]], [np.float32])[0], range(nproc)))
+            img = img + np.concatenate(parts).reshape(-1, 3)
+    finally:
+        set_libm(old)
+        shared.cleanup()
+    return img.reshape(H, W, 3)

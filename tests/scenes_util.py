@@ -123,6 +123,44 @@ def test_spheres():
     ], np.float32)
 
 
+def bxdf_inputs(n, rs, lobe):
+    """Random BxDF table rows (columns 0..23 of pt_dbg_bxdf / o_bxdf's in28) and their seed words (columns 24..25)."""
+    nrm = rs.standard_normal((n, 3)); nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    t = np.cross(nrm, rs.standard_normal((n, 3))); t /= np.linalg.norm(t, axis=1, keepdims=True)
+    b = np.cross(nrm, t)
+    front = (rs.uniform(0, 1, (n, 1)) < 0.5).astype(np.float64)
+    albedo = rs.uniform(0, 1, (n, 3)); spec = rs.uniform(0, 0.2, (n, 3))
+    spec[::5] = 0.04; spec[1::11] = 0.0
+    rough = rs.uniform(0.02, 1.0, (n, 1)); rough[::7] = 1.0
+    if lobe in (1, 3):
+        rough[:] = 0.0
+    metal = rs.uniform(0, 1, (n, 1)); metal[::3] = 0.0; metal[1::3] = 1.0
+    wo = rs.standard_normal((n, 3)); wo /= np.linalg.norm(wo, axis=1, keepdims=True)
+    wi = rs.standard_normal((n, 3)); wi /= np.linalg.norm(wi, axis=1, keepdims=True)
+    if lobe < 2:   # opaque lobes are evaluated with wo on the normal's side, as the integrator does
+        s = np.sign((wo * nrm).sum(1, keepdims=True)); wo *= np.where(s == 0, 1, s)
+    seeds = rs.randint(0, 2 ** 31, (n, 2)).astype(np.uint32).view(np.float32)
+    return np.concatenate([nrm, t, b, front, albedo, spec, rough, metal, wo, wi], 1).astype(np.float32), seeds
+
+
 def rel_rms(a, b):
     a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
     return float(np.sqrt(((a - b) ** 2).sum() / (b ** 2).sum()))
+
+
+def load_ref_bxdf(golden_dir, lobe):
+    """tests/golden/ref_bxdf.npz for one lobe -> (in28, rows in contract mode, rows in glibc mode, number of random rows).  The random
+    rows come first and are regenerated from the recorded seed (their sha256 is in the fixture); the hand-built edge block follows."""
+    import hashlib
+    import os
+    g = np.load(os.path.join(golden_dir, "ref_bxdf.npz"))
+    n = int(g["n_random"])
+    a, seeds = bxdf_inputs(n, np.random.RandomState(int(g["seed"]) + lobe), lobe)
+    rnd = np.concatenate([a, seeds, np.zeros((n, 2), np.float32)], 1)
+    assert hashlib.sha256(np.ascontiguousarray(rnd).tobytes()).hexdigest() == str(g[f"random_sha256_{lobe}"]), "random BxDF rows drifted"
+    in28 = np.concatenate([rnd, g[f"edge_in28_{lobe}"]])
+    contract = g[f"contract_{lobe}"]
+    glibc = contract.copy()
+    glibc[g[f"glibc_idx_{lobe}"]] = g[f"glibc_rows_{lobe}"]
+    assert in28.shape[0] == contract.shape[0]
+    return in28, contract, glibc, n

@@ -13,6 +13,7 @@ import pytest
 
 import oracle_lib as O
 import ptamd
+from scenes_util import bxdf_inputs as _bxdf_inputs
 from scenes_util import rel_rms, scene_rays8
 from scenes_util import test_spheres as make_test_spheres
 
@@ -133,25 +134,6 @@ def test_ray_setup_matches_ieee_arithmetic():
     assert np.array_equal(bits(out[ok, :3]), bits(ref[ok])), "normalised inverse direction differs from IEEE division"
     clamp = np.where(np.abs(inv[deg]) <= np.float32(1e30), inv[deg], np.copysign(np.float32(1e30), d[deg]))
     assert np.array_equal(bits(out[deg, :3]), bits(clamp.astype(np.float32)))
-
-
-def _bxdf_inputs(n, rs, lobe):
-    nrm = rs.standard_normal((n, 3)); nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
-    t = np.cross(nrm, rs.standard_normal((n, 3))); t /= np.linalg.norm(t, axis=1, keepdims=True)
-    b = np.cross(nrm, t)
-    front = (rs.uniform(0, 1, (n, 1)) < 0.5).astype(np.float64)
-    albedo = rs.uniform(0, 1, (n, 3)); spec = rs.uniform(0, 0.2, (n, 3))
-    spec[::5] = 0.04; spec[1::11] = 0.0
-    rough = rs.uniform(0.02, 1.0, (n, 1)); rough[::7] = 1.0
-    if lobe in (1, 3):
-        rough[:] = 0.0
-    metal = rs.uniform(0, 1, (n, 1)); metal[::3] = 0.0; metal[1::3] = 1.0
-    wo = rs.standard_normal((n, 3)); wo /= np.linalg.norm(wo, axis=1, keepdims=True)
-    wi = rs.standard_normal((n, 3)); wi /= np.linalg.norm(wi, axis=1, keepdims=True)
-    if lobe < 2:   # opaque lobes are evaluated with wo on the normal's side, as the integrator does
-        s = np.sign((wo * nrm).sum(1, keepdims=True)); wo *= np.where(s == 0, 1, s)
-    seeds = rs.randint(0, 2 ** 31, (n, 2)).astype(np.uint32).view(np.float32)
-    return np.concatenate([nrm, t, b, front, albedo, spec, rough, metal, wo, wi], 1).astype(np.float32), seeds
 
 
 @pytest.mark.parametrize("lobe", [0, 1, 2, 3])

@@ -1,7 +1,8 @@
-"""The oracle's integrator half has no reference fixture to pin it (the reference ships no
-tests and its integrator headers need cuRAND).  The outside anchors that exist are the
-image means SURVEY.md Appendix A recorded from the reference's own source; the oracle must
-reproduce them to all six printed digits under the same conditions (glibc float libm)."""
+"""The image means SURVEY.md Appendix A recorded from the reference's own source: the oracle must reproduce them to all six printed
+digits under the same conditions (glibc float libm), together with the reference algorithm's traversal counters.  They were the only
+outside evidence for the oracle's integrator half until the reference's integrator headers were built behind a cuRAND shim
+(oracle/_ref/ptref_int); tests/test_oracle_integrator.py now compares that half with the reference's own code row by row, and
+reproduces the same three means through it."""
 import json
 import os
 

@@ -25,7 +25,7 @@
 #include <cstring>
 #include <string>
 
-#include "pt_internal.h"
+#include "pt_scene.h"
 
 static_assert(PT_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "PT_COMM_ID_BYTES must match ncclUniqueId");
 
@@ -79,7 +79,7 @@ Rccl* rccl()
 struct PtComm {
     int rank = 0, world = 1, device = 0;
     ncclComm_t comm = nullptr;
-    int32_t* d_status = nullptr;      // world > 1: one device word for the status all-reduce of pt_render_split
+    DevBuf status;                    // world > 1: one device word (int32) for the status all-reduce of pt_render_split
 };
 
 #define NCCLCHK(expr)                                                                                   \
@@ -116,7 +116,7 @@ int pt_comm_create(const uint8_t id[PT_COMM_ID_BYTES], int32_t rank, int32_t wor
         memcpy(u.internal, id, PT_COMM_ID_BYTES);
         ncclResult_t r = R->CommInitRank(&c->comm, world, u, rank);
         if (r != ncclSuccess) { pt_set_error("ncclCommInitRank(rank %d of %d): %s", rank, world, R->GetErrorString(r)); delete c; return PT_ERR_DEVICE; }
-        if (hipMalloc((void**)&c->d_status, 4) != hipSuccess) { (void)R->CommDestroy(c->comm); delete c; pt_set_error("pt_comm_create: out of device memory"); return PT_ERR_DEVICE; }
+        if (c->status.alloc(4) != hipSuccess) { (void)R->CommDestroy(c->comm); delete c; pt_set_error("pt_comm_create: out of device memory"); return PT_ERR_DEVICE; }
     }
     *out = c;
     return PT_OK;
@@ -180,7 +180,7 @@ void pt_comm_destroy(PtComm* c)
 {
     if (!c) return;
     if (c->comm) { Rccl* R = rccl(); if (R) (void)R->CommDestroy(c->comm); }
-    if (c->d_status) { (void)hipSetDevice(c->device); (void)hipFree(c->d_status); }
+    if (c->status) (void)hipSetDevice(c->device);
     delete c;
 }
 
@@ -227,53 +227,49 @@ int pt_gather_frame(PtComm* c, const float* d_tiles, const PtCamera* cam, const 
 int pt_render_split(PtScene* s, const PtCamera* cam, const PtParams* prm, PtComm* c, float* h_accum_rgb)
 {
     if (!s || !cam || !prm || !c || (c->rank == 0 && !h_accum_rgb)) { pt_set_error("pt_render_split: NULL argument"); return PT_ERR_INVALID; }
-    if (ptk_scene_device(s) != c->device) {
-        pt_set_error("pt_render_split: the scene lives on device %d, the communicator on device %d", ptk_scene_device(s), c->device);
+    if (s->device != c->device) {
+        pt_set_error("pt_render_split: the scene lives on device %d, the communicator on device %d", s->device, c->device);
         return PT_ERR_INVALID;
     }
     PtParams p = *prm; p.rank = c->rank; p.world = c->world;
     const int64_t nt = pt_tiles_floats(cam, &p), wb = pt_work_bytes(cam, &p);
     if (nt < 0 || wb < 0) return PT_ERR_INVALID;      // the same on every rank (same camera and params): nobody enters a collective
     HIPCHK(hipSetDevice(c->device));
-    float *d_tiles = nullptr, *d_gathered = nullptr, *d_frame = nullptr; void* d_work = nullptr;
+    DevBuf d_tiles, d_work, d_gathered, d_frame;      // the last two stay null on the ranks above 0
     auto local = [&]() -> int {      // everything that can fail on this rank alone
-        HIPCHK(hipMalloc((void**)&d_tiles, (size_t)nt * 4));
-        HIPCHK(hipMalloc(&d_work, (size_t)wb));
+        HIPCHK(d_tiles.alloc((size_t)nt * 4));
+        HIPCHK(d_work.alloc((size_t)wb));
         if (c->rank == 0) {
-            HIPCHK(hipMalloc((void**)&d_gathered, (size_t)nt * 4 * (size_t)c->world));
-            HIPCHK(hipMalloc((void**)&d_frame, (size_t)cam->W * cam->H * 12));
+            HIPCHK(d_gathered.alloc((size_t)nt * 4 * (size_t)c->world));
+            HIPCHK(d_frame.alloc((size_t)cam->W * cam->H * 12));
         }
-        return pt_render_tiles(s, cam, &p, d_tiles, d_work, nullptr);
+        return pt_render_tiles(s, cam, &p, d_tiles.as<float>(), d_work.as<>(), nullptr);
     };
-    auto body = [&]() -> int {
-        int rc = local();
-        if (c->world > 1) {
-            // Every rank reports how its render went BEFORE the gather (a 4-byte max all-reduce): a rank that failed still takes
-            // part, so its peers learn of it and skip the gather instead of waiting in it for a buffer that will never come.
-            Rccl* R = rccl();
-            if (!R || !c->comm || !c->d_status) { pt_set_error("pt_render_split: communicator has no RCCL handle"); return PT_ERR_INVALID; }
-            const int32_t mine = rc ? 1 : 0;
-            int32_t any = 1;
-            if (hipMemcpy(c->d_status, &mine, 4, hipMemcpyHostToDevice) != hipSuccess ||
-                R->AllReduce(c->d_status, c->d_status, 1, ncclInt32, ncclMax, c->comm, nullptr) != ncclSuccess ||
-                hipMemcpy(&any, c->d_status, 4, hipMemcpyDeviceToHost) != hipSuccess) {
-                // the control collective itself failed: nothing sensible can follow on this communicator
-                (void)R->CommAbort(c->comm); c->comm = nullptr;
-                if (!rc) pt_set_error("pt_render_split: status exchange failed on rank %d; communicator aborted", c->rank);
-                return rc ? rc : PT_ERR_DEVICE;
-            }
-            if (rc) return rc;                                  // this rank's own error (message already set)
-            if (any) { pt_set_error("pt_render_split: another rank failed to render its tiles; gather skipped on rank %d", c->rank); return PT_ERR_DEVICE; }
-        } else if (rc) return rc;
-        rc = pt_gather_frame(c, d_tiles, cam, &p, d_gathered, d_frame, nullptr);
-        if (rc) return rc;
-        HIPCHK(hipDeviceSynchronize());
-        if (c->rank == 0) HIPCHK(hipMemcpy(h_accum_rgb, d_frame, (size_t)cam->W * cam->H * 12, hipMemcpyDeviceToHost));
-        return PT_OK;
-    };
-    const int rc = body();
-    (void)hipFree(d_tiles); (void)hipFree(d_work); (void)hipFree(d_gathered); (void)hipFree(d_frame);
-    return rc;
+    int rc = local();
+    if (c->world > 1) {
+        // Every rank reports how its render went BEFORE the gather (a 4-byte max all-reduce): a rank that failed still takes
+        // part, so its peers learn of it and skip the gather instead of waiting in it for a buffer that will never come.
+        Rccl* R = rccl();
+        if (!R || !c->comm || !c->status) { pt_set_error("pt_render_split: communicator has no RCCL handle"); return PT_ERR_INVALID; }
+        const int32_t mine = rc ? 1 : 0;
+        int32_t any = 1;
+        int32_t* d_status = c->status.as<int32_t>();
+        if (hipMemcpy(d_status, &mine, 4, hipMemcpyHostToDevice) != hipSuccess ||
+            R->AllReduce(d_status, d_status, 1, ncclInt32, ncclMax, c->comm, nullptr) != ncclSuccess ||
+            hipMemcpy(&any, d_status, 4, hipMemcpyDeviceToHost) != hipSuccess) {
+            // the control collective itself failed: nothing sensible can follow on this communicator
+            (void)R->CommAbort(c->comm); c->comm = nullptr;
+            if (!rc) pt_set_error("pt_render_split: status exchange failed on rank %d; communicator aborted", c->rank);
+            return rc ? rc : PT_ERR_DEVICE;
+        }
+        if (rc) return rc;                                  // this rank's own error (message already set)
+        if (any) { pt_set_error("pt_render_split: another rank failed to render its tiles; gather skipped on rank %d", c->rank); return PT_ERR_DEVICE; }
+    } else if (rc) return rc;
+    rc = pt_gather_frame(c, d_tiles.as<float>(), cam, &p, d_gathered.as<float>(), d_frame.as<float>(), nullptr);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if (c->rank == 0) HIPCHK(hipMemcpy(h_accum_rgb, d_frame.as<>(), (size_t)cam->W * cam->H * 12, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 }  // extern "C"

@@ -23,12 +23,13 @@
 // float4s in the work buffer), finish (remodulate, write RGB).  256-thread blocks, each wave an 8x8 pixel tile, plain 16-byte loads:
 // the 48 B/pixel working set (100 MB at 1080p) stays in the Infinity Cache, the 5x5 footprint of a wave in L2.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include "pt_device.h"
 #include "pt_math.h"
 #include "pt_bxdf.h"
 #include "pt_trace.h"
 #include "pt_shade.h"
-#include "pt_internal.h"
+#include "pt_scene.h"
 
 namespace ptd {
 
@@ -164,41 +165,143 @@ void dn_finish(const float4* __restrict__ color, const float4* __restrict__ aov,
 
 }  // namespace ptd
 
-// ---------------------------------------------------------------------------------------
-// Launchers (called from pt_api.hip)
-// ---------------------------------------------------------------------------------------
-extern "C" {
+// ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
+static const int64_t kMaxPixels = (int64_t)1 << 28;      // keeps every per-pixel float offset (x 8) inside int64 and the pixel index inside int
 
-hipError_t ptk_aov(const ptd::DevScene* sc, const ptd::DevCamera* cam, int first_pass, int passes, float* aov, int* prim, hipStream_t stream)
+static bool frame_ok(int32_t W, int32_t H) { return W >= 2 && H >= 2 && (int64_t)W * H <= kMaxPixels; }
+
+static int aov_args(const PtCamera* cam, const PtParams* prm)
 {
-    const int tiles_x = (cam->W + ptd::kTile - 1) / ptd::kTile, tiles_y = (cam->H + ptd::kTile - 1) / ptd::kTile;
-    const int n_tiles = tiles_x * tiles_y;
-    const int nb = (n_tiles + ptd::kWavesPerBlock - 1) / ptd::kWavesPerBlock;
-    if (nb > 0) hipLaunchKernelGGL(ptd::aov_kernel, dim3(nb), dim3(ptd::kBlockThreads), 0, stream, *sc, *cam, first_pass, passes, tiles_x, n_tiles,
-                                   (float4*)aov, prim);
-    return hipGetLastError();
+    if (!cam || !prm) { pt_set_error("NULL camera/params"); return PT_ERR_INVALID; }
+    if (!frame_ok(cam->W, cam->H)) { pt_set_error("frame %dx%d out of range", cam->W, cam->H); return PT_ERR_INVALID; }
+    if (prm->passes < 1 || prm->first_pass < 0) { pt_set_error("bad params: passes=%d first_pass=%d", prm->passes, prm->first_pass); return PT_ERR_INVALID; }
+    if (!ptd::seed_in_range(cam, prm->first_pass, prm->passes)) return PT_ERR_INVALID;
+    return PT_OK;
 }
 
-// work: 3 x W*H float4 (colour ping, colour pong, features); iterations >= 1
-hipError_t ptk_denoise(const float* rgb, const float* aov, int W, int H, int sample_cnt, int iterations, float sigma_color,
-                       float sigma_normal, float sigma_depth, int demodulate, float* out, void* work, hipStream_t stream)
+static bool overlaps(const void* a, size_t na, const void* b, size_t nb)
 {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+static int denoise_args(const void* rgb, const void* aov, int32_t W, int32_t H, int32_t sample_cnt, const PtDenoiseParams* p,
+                        const void* out, const void* work, bool device)
+{
+    if (!rgb || !aov || !p || !out || (device && !work)) { pt_set_error("pt_denoise: NULL argument"); return PT_ERR_INVALID; }
+    if (!frame_ok(W, H)) { pt_set_error("pt_denoise: frame %dx%d out of range", W, H); return PT_ERR_INVALID; }
+    if (sample_cnt <= 0) { pt_set_error("pt_denoise: sample_cnt %d <= 0", sample_cnt); return PT_ERR_INVALID; }
+    if (p->iterations < 0 || p->iterations > 12) { pt_set_error("pt_denoise: iterations %d outside 0..12", p->iterations); return PT_ERR_INVALID; }
+    if (!(p->sigma_color > 0.f) || !(p->sigma_normal > 0.f) || !(p->sigma_depth > 0.f) ||
+        !std::isfinite(p->sigma_color) || !std::isfinite(p->sigma_normal) || !std::isfinite(p->sigma_depth)) {
+        pt_set_error("pt_denoise: sigmas must be finite and > 0"); return PT_ERR_INVALID;
+    }
     const size_t n = (size_t)W * H;
-    float4* c0 = (float4*)work;
+    if (overlaps(out, n * 12, rgb, n * 12) || overlaps(out, n * 12, aov, n * 32) || (work && overlaps(out, n * 12, work, n * 48))) {
+        pt_set_error("pt_denoise: the output overlaps an input or the work buffer"); return PT_ERR_INVALID;
+    }
+    if (device && (((uintptr_t)aov % 16) || ((uintptr_t)work % 16) || overlaps(work, n * 48, rgb, n * 12) || overlaps(work, n * 48, aov, n * 32))) {
+        pt_set_error("pt_denoise: d_aov / d_work not 16-byte aligned, or d_work overlaps an input"); return PT_ERR_INVALID;
+    }
+    return PT_OK;
+}
+
+extern "C" {
+
+int64_t pt_aov_floats(const PtCamera* cam)
+{
+    if (!cam || !frame_ok(cam->W, cam->H)) { pt_set_error("pt_aov_floats: bad camera"); return -1; }
+    return (int64_t)cam->W * cam->H * 8;
+}
+
+int pt_render_aov(PtScene* s, const PtCamera* cam, const PtParams* prm, float* d_aov, int32_t* d_prim, void* hip_stream)
+{
+    if (!s || !d_aov) { pt_set_error("pt_render_aov: NULL argument"); return PT_ERR_INVALID; }
+    if ((uintptr_t)d_aov % 16) { pt_set_error("pt_render_aov: d_aov is not 16-byte aligned"); return PT_ERR_INVALID; }
+    int rc = aov_args(cam, prm);
+    if (rc) return rc;
+    ptd::DevCamera c;
+    pt_fill_camera(cam, c);
+    HIPCHK(hipSetDevice(s->device));
+    const ptd::TileGrid g = ptd::tile_grid(cam->W, cam->H);
+    const int nb = (g.total + ptd::kWavesPerBlock - 1) / ptd::kWavesPerBlock;
+    if (nb > 0) hipLaunchKernelGGL(ptd::aov_kernel, dim3(nb), dim3(ptd::kBlockThreads), 0, (hipStream_t)hip_stream, s->dev, c, prm->first_pass, prm->passes,
+                                   g.tiles_x, g.total, (float4*)d_aov, d_prim);
+    HIPCHK(hipGetLastError());
+    return PT_OK;
+}
+
+int pt_aov(PtScene* s, const PtCamera* cam, const PtParams* prm, float* h_aov, int32_t* h_prim)
+{
+    if (!s || !h_aov) { pt_set_error("pt_aov: NULL argument"); return PT_ERR_INVALID; }
+    int rc = aov_args(cam, prm);
+    if (rc) return rc;
+    const size_t n = (size_t)cam->W * cam->H;
+    HIPCHK(hipSetDevice(s->device));
+    DevBuf d_aov, d_prim;      // d_prim stays null when the caller asked for no primitive ids
+    HIPCHK(d_aov.alloc(n * 32));
+    if (h_prim) HIPCHK(d_prim.alloc(n * 4));
+    rc = pt_render_aov(s, cam, prm, d_aov.as<float>(), d_prim.as<int32_t>(), nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(h_aov, d_aov.as<>(), n * 32, hipMemcpyDeviceToHost));
+    if (h_prim) HIPCHK(hipMemcpy(h_prim, d_prim.as<>(), n * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int64_t pt_denoise_work_bytes(int32_t W, int32_t H)
+{
+    if (!frame_ok(W, H)) { pt_set_error("pt_denoise_work_bytes: frame %dx%d out of range", W, H); return -1; }
+    return (int64_t)W * H * 48;
+}
+
+int pt_denoise(const float* d_rgb, const float* d_aov, int32_t W, int32_t H, int32_t sample_cnt, const PtDenoiseParams* p,
+               float* d_out, void* d_work, void* hip_stream)
+{
+    const int rc = denoise_args(d_rgb, d_aov, W, H, sample_cnt, p, d_out, d_work, true);
+    if (rc) return rc;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    if (p->iterations == 0) { HIPCHK(hipMemcpyAsync(d_out, d_rgb, (size_t)W * H * 12, hipMemcpyDeviceToDevice, stream)); return PT_OK; }
+    // d_work: 3 x W*H float4 (colour ping, colour pong, features)
+    const size_t n = (size_t)W * H;
+    float4* c0 = (float4*)d_work;
     float4* c1 = c0 + n;
     float4* feat = c1 + n;
     const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16)), block(256);
     const float sc = (float)sample_cnt;
-    hipLaunchKernelGGL(ptd::dn_pack, grid, block, 0, stream, rgb, (const float4*)aov, W, H, sc, demodulate, c0, feat);
-    const float kn = 1.f / (sigma_normal * sigma_normal), kz = 1.f / sigma_depth;
-    float kc = 1.f / (sigma_color * sigma_color);
-    for (int it = 0; it < iterations; it++) {
+    const int demodulate = p->demodulate ? 1 : 0;
+    hipLaunchKernelGGL(ptd::dn_pack, grid, block, 0, stream, d_rgb, (const float4*)d_aov, W, H, sc, demodulate, c0, feat);
+    const float kn = 1.f / (p->sigma_normal * p->sigma_normal), kz = 1.f / p->sigma_depth;
+    float kc = 1.f / (p->sigma_color * p->sigma_color);
+    for (int it = 0; it < p->iterations; it++) {
         hipLaunchKernelGGL(ptd::dn_atrous, grid, block, 0, stream, (const float4*)c0, (const float4*)feat, W, H, 1 << it, kc, kn, kz, c1);
         float4* t = c0; c0 = c1; c1 = t;
         kc *= 4.f;
     }
-    hipLaunchKernelGGL(ptd::dn_finish, grid, block, 0, stream, (const float4*)c0, (const float4*)aov, W, H, sc, demodulate, out);
-    return hipGetLastError();
+    hipLaunchKernelGGL(ptd::dn_finish, grid, block, 0, stream, (const float4*)c0, (const float4*)d_aov, W, H, sc, demodulate, d_out);
+    HIPCHK(hipGetLastError());
+    return PT_OK;
+}
+
+int pt_denoise_host(int32_t device, const float* h_rgb, const float* h_aov, int32_t W, int32_t H, int32_t sample_cnt,
+                    const PtDenoiseParams* p, float* h_out)
+{
+    int rc = denoise_args(h_rgb, h_aov, W, H, sample_cnt, p, h_out, nullptr, false);
+    if (rc) return rc;
+    const size_t n = (size_t)W * H;
+    HIPCHK(hipSetDevice(device));
+    DevBuf buf;      // one allocation: rgb | aov | out | work
+    HIPCHK(buf.alloc(n * (12 + 32 + 12 + 48) + 64));
+    char* d = buf.as<char>();
+    float* d_rgb = (float*)d;
+    float* d_aov = (float*)(d + ((n * 12 + 15) & ~(size_t)15));
+    float* d_out = (float*)((char*)d_aov + n * 32);
+    void* d_work = (char*)d_aov + ((n * 44 + 15) & ~(size_t)15);
+    HIPCHK(hipMemcpy(d_rgb, h_rgb, n * 12, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_aov, h_aov, n * 32, hipMemcpyHostToDevice));
+    rc = pt_denoise(d_rgb, d_aov, W, H, sample_cnt, p, d_out, d_work, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(h_out, d_out, n * 12, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 }  // extern "C"

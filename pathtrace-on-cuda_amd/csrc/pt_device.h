@@ -1,5 +1,5 @@
 // pt_device.h — HBM data layout of an uploaded scene and the kernel argument blocks.
-// Shared by the host upload code (pt_api.hip) and the kernels (pt_kernels.hip).
+// Shared by the host upload code (pt_scene.hip) and the kernels (pt_kernels.hip).
 //
 // Everything is 16-byte records read with one global_load_dwordx4 per float4:
 //
@@ -48,7 +48,7 @@ constexpr int kStackDepth = 32;          // per-lane traversal stack entries (LD
 constexpr int kWavesPerBlock = 4;
 constexpr int kBlockThreads = 64 * kWavesPerBlock;
 
-// Diagnostic counter buffer (PtScene::d_counters, PTAMD_TSTAT): kStatWords 64-bit words of counters, launch timeline and histograms,
+// Diagnostic counter buffer (PtScene::counters, PTAMD_TSTAT): kStatWords 64-bit words of counters, launch timeline and histograms,
 // then — for one chosen launch of wf_trace (PTAMD_TDUMP) — 8 words per wave (kStatWaves) and a per-trip log of every kStatLogEvery-th wave
 constexpr int kStatLaunches = 2700;      // wf_trace launches the timeline has a slot for (later launches share the last one)
 // word offset of each section, after the 8 work counters of pt_last_counters (word 0)

@@ -15,8 +15,11 @@
 #include <hip/hip_runtime.h>
 #include <cfloat>
 #include <cmath>
+#include <cstring>
+#include <utility>
+#include <vector>
 
-#include "pt_internal.h"
+#include "pt_scene.h"
 #include "../host/accel_build.h"
 
 namespace {
@@ -269,7 +272,7 @@ __global__ __launch_bounds__(256) void dyn_core_final(DynScene s)
         const float dx = b1.x - b0.x, dy = b1.y - b0.y, dz = b1.z - b0.z;
         const float sd = sqrtf(dx * dx + dy * dy + dz * dz);
         for (int k = 0; k < 3; k++) {
-            const float pad = 0.01f * (lds[3 + k] - lds[k]) + 1e-4f * sd;      // pt_api.hip: pt_scene_create
+            const float pad = 0.01f * (lds[3 + k] - lds[k]) + 1e-4f * sd;      // pt_scene.hip: core_box
             s.core[k] = lds[k] - pad;
             s.core[3 + k] = lds[3 + k] + pad;
         }
@@ -306,12 +309,9 @@ inline unsigned blocks_of(int n, int per) { return (unsigned)((n + per - 1) / pe
 static_assert(ptd::kCoreBlocks == 256, "dyn_core_final reads one partial per thread of a 256-thread block");
 static_assert(kAreaBlock == 1024, "dyn_area folds 4 boxes per thread of a 256-thread block");
 
-extern "C" {
-
-hipError_t ptk_dyn_update(const ptd::DynScene* sc, const float* d_pos, const float* d_frames, const int32_t* level_start, int n_levels,
-                          hipStream_t stream)
+// Enqueues the whole update on `stream`.  level_start: host array of n_levels + 1 offsets into `order` (height h = one launch).
+static hipError_t launch_update(const DynScene& s, const float* d_pos, const float* d_frames, const int32_t* level_start, int n_levels, hipStream_t stream)
 {
-    const DynScene& s = *sc;
     // records: the leaf boxes first, the pair records carry them inline
     hipLaunchKernelGGL(dyn_leafbox, dim3(blocks_of(s.n_leaves, 256)), dim3(256), 0, stream, s, d_pos);
     hipLaunchKernelGGL(dyn_surf, dim3(blocks_of(s.n_tris, 256)), dim3(256), 0, stream, s, d_pos, d_frames);
@@ -331,10 +331,105 @@ hipError_t ptk_dyn_update(const ptd::DynScene* sc, const float* d_pos, const flo
     return hipGetLastError();
 }
 
-hipError_t ptk_dyn_area(const ptd::DynScene* sc, hipStream_t stream)
+// First update of a scene: the maps of the build go to the device and the scratch is allocated; the host copies are dropped.
+static int dyn_prepare(PtScene* s)
 {
-    hipLaunchKernelGGL(dyn_area, dim3(blocks_of(sc->n_bn, kAreaBlock)), dim3(256), 0, stream, *sc);
-    return hipGetLastError();
+    if (s->dyn_ready) return PT_OK;
+    PtScene::DynHost& h = s->dyn_host;
+    ptd::DynScene& d = s->dyn;
+    const size_t area_blocks = ((size_t)d.n_bn + kAreaBlock - 1) / kAreaBlock;
+    // in the order of enum DynAlloc: the maps with their host source, then the scratch (area_partial: (n_bn + 1023) / 1024 doubles)
+    const struct { const void* src; size_t bytes; } plan[kDynAllocs] = {
+        {h.bn.data(), h.bn.size() * 4}, {h.order.data(), h.order.size() * 4}, {h.wide_bn.data(), h.wide_bn.size() * 4}, {h.quad_bn.data(), h.quad_bn.size() * 4},
+        {h.leaf_range.data(), h.leaf_range.size() * 4}, {h.tmap.data(), h.tmap.size() * 4}, {h.light_prim.data(), h.light_prim.size() * 4}, {h.small.data(), h.small.size()},
+        {nullptr, (size_t)d.n_bn * 32}, {nullptr, 16}, {nullptr, (size_t)ptd::kCoreBlocks * 32}, {nullptr, area_blocks * 8}};
+    // built beside the scene and moved in only once all of them exist: a failure frees what it got and leaves the scene as it was,
+    // byte count included, and a later update may try again
+    DevBuf fresh[kDynAllocs];
+    int64_t bytes = 0;
+    for (int k = 0; k < kDynAllocs; k++) {
+        if (k == kDynSmall && h.small.empty()) continue;      // no core box: dyn.small stays null
+        HIPCHK(k < kDynBbox ? fresh[k].upload(plan[k].src, plan[k].bytes) : fresh[k].alloc(plan[k].bytes));
+        bytes += (int64_t)fresh[k].held();
+    }
+    DevBuf* b = s->dyn_buf;
+    for (int k = 0; k < kDynAllocs; k++) b[k] = std::move(fresh[k]);
+    s->bytes += bytes;
+    d.bn = b[kDynBn].as<const int4>(); d.order = b[kDynOrder].as<const int32_t>(); d.wide_bn = b[kDynWideBn].as<const int2>(); d.quad_bn = b[kDynQuadBn].as<const int4>();
+    d.leaf_range = b[kDynLeafRange].as<const int2>(); d.tmap = b[kDynTmap].as<const int2>(); d.light_prim = b[kDynLightPrim].as<const int32_t>();
+    d.small = b[kDynSmall].as<const uint8_t>();
+    d.bbox = b[kDynBbox].as<float4>(); d.maxabs = b[kDynMaxabs].as<float>(); d.core_partial = b[kDynCorePartial].as<float>(); d.area_partial = b[kDynAreaPartial].as<double>();
+    s->h_area.assign(area_blocks, 0.0);
+    for (std::vector<int32_t>* v : {&h.bn, &h.order, &h.wide_bn, &h.quad_bn, &h.leaf_range, &h.tmap, &h.light_prim}) std::vector<int32_t>().swap(*v);
+    std::vector<uint8_t>().swap(h.small);      // level_start stays: the launch sequence reads it
+    s->dyn_ready = true;
+    return PT_OK;
+}
+
+// ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
+extern "C" {
+
+int pt_scene_update_vertices(PtScene* s, const float* d_pos, const float* d_frames, void* hip_stream)
+{
+    if (!s || !d_pos) { pt_set_error("pt_scene_update_vertices: NULL %s", !s ? "scene" : "d_pos"); return PT_ERR_INVALID; }
+    HIPCHK(hipSetDevice(s->device));
+    int rc;
+    if ((rc = dyn_prepare(s)) != PT_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(launch_update(s->dyn, d_pos, d_frames, s->dyn_host.level_start.data(), (int)s->dyn_host.level_start.size() - 1, st));
+    s->updated = true;
+    return PT_OK;
+}
+
+int pt_scene_update_vertices_host(PtScene* s, const float* h_pos, const float* h_frames)
+{
+    if (!s || !h_pos) { pt_set_error("pt_scene_update_vertices_host: NULL %s", !s ? "scene" : "h_pos"); return PT_ERR_INVALID; }
+    HIPCHK(hipSetDevice(s->device));
+    const size_t n = (size_t)s->dev.n_tris;
+    DevBuf d_pos, d_frames;      // d_frames stays null when the caller passed no frames
+    HIPCHK(d_pos.upload(h_pos, n * 36));
+    if (h_frames) HIPCHK(d_frames.upload(h_frames, n * 108));
+    const int rc = pt_scene_update_vertices(s, d_pos.as<float>(), d_frames.as<float>(), nullptr);
+    if (rc != PT_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return PT_OK;
+}
+
+int pt_scene_update_spheres(PtScene* s, const PtSphere* h_spheres, int32_t n_spheres)
+{
+    if (!s || !h_spheres) { pt_set_error("pt_scene_update_spheres: NULL %s", !s ? "scene" : "h_spheres"); return PT_ERR_INVALID; }
+    if (n_spheres != s->dev.n_spheres || n_spheres < 1) {
+        pt_set_error("pt_scene_update_spheres: %d spheres given, the scene has %d", n_spheres, s->dev.n_spheres);
+        return PT_ERR_INVALID;
+    }
+    for (int i = 0; i < n_spheres; i++)
+        if (memcmp(&h_spheres[i].mat, &s->h_spheres[(size_t)i * 16 + 4], sizeof(PtMaterial)) != 0) {
+            pt_set_error("pt_scene_update_spheres: the material of sphere %d differs from the uploaded one (only centre and radius may change)", i);
+            return PT_ERR_INVALID;
+        }
+    HIPCHK(hipSetDevice(s->device));
+    for (int i = 0; i < n_spheres; i++) {
+        float* a = &s->h_spheres[(size_t)i * 16];
+        a[0] = h_spheres[i].center[0]; a[1] = h_spheres[i].center[1]; a[2] = h_spheres[i].center[2]; a[3] = h_spheres[i].rad;
+    }
+    HIPCHK(hipMemcpy(s->arr[kArrSpheres].as<>(), s->h_spheres.data(), (size_t)n_spheres * 64, hipMemcpyHostToDevice));      // ordered on the NULL stream
+    return PT_OK;
+}
+
+int pt_scene_tree_inflation(PtScene* s, double* ratio)
+{
+    if (!s || !ratio) { pt_set_error("pt_scene_tree_inflation: NULL %s", !s ? "scene" : "ratio"); return PT_ERR_INVALID; }
+    *ratio = 1.0;
+    if (!s->updated) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());      // the stream of the last update may be gone by now: wait for the device, reduce on the NULL stream
+    hipLaunchKernelGGL(dyn_area, dim3(blocks_of(s->dyn.n_bn, kAreaBlock)), dim3(256), 0, nullptr, s->dyn);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(s->h_area.data(), s->dyn.area_partial, s->h_area.size() * 8, hipMemcpyDeviceToHost));
+    double sum = 0.0;
+    for (double v : s->h_area) sum += v;      // block sums in index order (host/accel_build.cpp: pt_accel_area_sum)
+    *ratio = sum / s->dyn_host.area_sum;
+    return PT_OK;
 }
 
 }  // extern "C"

@@ -1,8 +1,11 @@
-// pt_internal.h — what crosses translation units inside libptamd.so, on the host side: error reporting, the argument blocks of the wavefront
-// pipeline and of the vertex update, and the prototype of every ptk_* launcher.  Included by the files that define these functions and by
-// those that call them, so a signature that drifts is a compile error (with C linkage it would link and run).  Not part of the C-ABI.
+// pt_internal.h — what crosses translation units inside libptamd.so, on the host side: error reporting, the owner of a device allocation,
+// the small facts every entry point states the same way (tile grid, seed range), the argument blocks of the wavefront pipeline and of the
+// vertex update, and the prototype of every ptk_* launcher that is called from another file.  Included by the files that define these
+// functions and by those that call them, so a signature that drifts is a compile error (with C linkage it would link and run).  Not part
+// of the C-ABI.  The scene itself (struct PtScene) is in pt_scene.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <utility>
 
 #include "../../include/pt_api.h"
 #include "pt_device.h"
@@ -18,7 +21,65 @@ void pt_set_error(const char* fmt, ...);   // pt_host.cpp
         }                                                                                   \
     } while (0)
 
+// Owner of one hipMalloc'ed block: whatever path leaves its scope, the block is freed.  Move-only (its move members delete the copies).  alloc(0) holds 16 bytes (a kernel
+// argument is never a null array) and remembers 0 as the size asked for.  A DevBuf that was never allocated is a null pointer.
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), bytes_(std::exchange(o.bytes_, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(bytes_, o.bytes_); return *this; }
+    ~DevBuf() { release(); }
+    void release() { if (p_) (void)hipFree(p_); p_ = nullptr; bytes_ = 0; }      // the device of the allocation is the current one
+    hipError_t alloc(size_t bytes)
+    {
+        release();
+        const hipError_t e = hipMalloc(&p_, bytes ? bytes : 16);
+        if (e == hipSuccess) bytes_ = bytes; else p_ = nullptr;
+        return e;
+    }
+    // alloc + one synchronous copy of `bytes` from the host
+    hipError_t upload(const void* h, size_t bytes)
+    {
+        const hipError_t e = alloc(bytes);
+        return (e != hipSuccess || !bytes) ? e : hipMemcpy(p_, h, bytes, hipMemcpyHostToDevice);
+    }
+    // grow-on-demand: room for `count` elements of `elem` bytes, at least `min` of them when it has to allocate.  The old block is
+    // freed first, so the caller must know that nothing on the device still reads it.
+    hipError_t reserve(int64_t count, int64_t min, size_t elem)
+    {
+        if (p_ && bytes_ >= (size_t)count * elem) return hipSuccess;
+        return alloc((size_t)(count < min ? min : count) * elem);
+    }
+    template <class T = void> T* as() const { return (T*)p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    size_t bytes() const { return bytes_; }                               // as asked for
+    size_t held() const { return p_ ? (bytes_ ? bytes_ : 16) : 0; }      // as allocated
+private:
+    void* p_ = nullptr;
+    size_t bytes_ = 0;
+};
+
 namespace ptd {
+
+// The 8x8 tile grid of a W x H frame, and a rank's share of it when `world` ranks split the frame.
+struct TileGrid { int tiles_x, tiles_y, total, per_rank; };
+inline TileGrid tile_grid(int W, int H, int world = 1)
+{
+    TileGrid g;
+    g.tiles_x = (W + kTile - 1) / kTile;
+    g.tiles_y = (H + kTile - 1) / kTile;
+    g.total = g.tiles_x * g.tiles_y;
+    g.per_rank = (g.total + world - 1) / world;
+    return g;
+}
+
+// The render seeds a pixel's stream with offset + SampleIDX * W * H as an int: false, with the error text set, when the last pass overflows it.
+inline bool seed_in_range(const PtCamera* cam, int first_pass, int passes)
+{
+    const bool ok = (long long)cam->W * cam->H * (long long)(first_pass + passes) <= 0x7fffffffLL;
+    if (!ok) pt_set_error("offset + SampleIDX*W*H overflows int (srcs/pathtracer.cu:71)");
+    return ok;
+}
 
 // One run of the wavefront pipeline (ptk_wf_render, pt_wavefront.hip).  pt_api.hip fills it in for a render call; the pipeline reads it
 // and writes through the two output pointers only.
@@ -81,8 +142,11 @@ struct DynScene {
 
 }  // namespace ptd
 
+// pt_api.hip: the checks and the geometry of a render call; the per-launch camera constants
+int pt_fill_params(const PtCamera* cam, const PtParams* prm, ptd::DevParams& d);
+void pt_fill_camera(const PtCamera* cam, ptd::DevCamera& c);
+
 extern "C" {
-int ptk_scene_device(const PtScene* s);      // pt_api.hip
 // pt_kernels.hip
 hipError_t ptk_render_units(const ptd::DevScene*, const ptd::DevCamera*, const ptd::DevParams*, float*, unsigned int*, void*, int, int, hipStream_t);
 hipError_t ptk_sum_passes(const float*, int, long long, float*, hipStream_t);
@@ -92,15 +156,6 @@ hipError_t ptk_dbg_bxdf(int, const float*, int, float*, hipStream_t);
 hipError_t ptk_dbg_rng(unsigned long long, int, uint32_t*, float*, hipStream_t);
 hipError_t ptk_dbg_math(const float*, int, float*, hipStream_t);
 hipError_t ptk_dbg_sincos(const float*, int, float*, hipStream_t);
-// pt_denoise.hip
-hipError_t ptk_aov(const ptd::DevScene*, const ptd::DevCamera*, int, int, float*, int*, hipStream_t);
-hipError_t ptk_denoise(const float*, const float*, int, int, int, int, float, float, float, int, float*, void*, hipStream_t);
-// pt_stats.hip
-hipError_t ptk_stats_fold(const float*, int, long long, int, float*, float*, hipStream_t);
-hipError_t ptk_stats_variance(const float*, long long, int, float*, hipStream_t);
-int ptk_stats_blocks(long long);
-int ptk_stats_partial_bytes(void);
-hipError_t ptk_stats_estimate(const float*, const float*, long long, int, int, int, int, int, int, int, void*, hipStream_t);
 // pt_wavefront.hip
 hipError_t ptk_dbg_ray_setup(const float*, int, float*, hipStream_t);
 hipError_t ptk_dbg_pixel_dir(const ptd::DevCamera*, const int*, int, float*, hipStream_t);
@@ -111,16 +166,4 @@ const float* ptk_wf_staging(void* work);
 int ptk_wf_stack_capacity(void);
 int ptk_wf_trace_stat(void);      // PTAMD_TSTAT as the pipeline read it (0 = off)
 hipError_t ptk_wf_render(const ptd::WfJob& job);
-// pt_dynamic.hip
-// Enqueues the whole update on `stream`.  level_start: host array of n_levels + 1 offsets into `order` (height h = one launch).
-hipError_t ptk_dyn_update(const ptd::DynScene* sc, const float* d_pos, const float* d_frames, const int32_t* level_start, int n_levels,
-                          hipStream_t stream);
-// Enqueues the area reduction over bbox into area_partial ((n_bn + 1023) / 1024 doubles).
-hipError_t ptk_dyn_area(const ptd::DynScene* sc, hipStream_t stream);
-// pt_query.hip
-int ptk_query_quad_fits(int quad_depth);      // does the 4-wide walk of a tree this deep fit the query kernels' per-lane stack?
-// Enqueues one batch of n < 2^31 rays on `stream`: (t, prim) per ray, then the 29-float surface records if asked for.  quad: walk the
-// 4-wide tree (else the binary one).
-hipError_t ptk_trace_rays(const ptd::DevScene* sc, const float* d_rays8, uint32_t n, int any, int quad, PtRayHit* d_hits, float* d_surface29,
-                          hipStream_t stream);
 }

@@ -1,16 +1,15 @@
-// pt_probe.hip — machine probes for the measurement side of the C-ABI (include/pt_api.h: pt_dbg_valu_rate).
+// pt_probe.hip — machine probes for the measurement side of the C-ABI (include/pt_api.h: pt_dbg_valu_rate, pt_dbg_triad).
 //
 // The traversal kernel is bound by vector-ALU issue, not by HBM, so its roofline needs the
 // chip's real VALU issue rate.  This probe measures it instead of assuming it: every wave runs a long
 // unrolled stream of INDEPENDENT vector instructions of one kind (no memory traffic, no dependent chains shorter
 // than 16 instructions), with a chosen number of waves per SIMD, and reports wave-instructions per second
 // chip-wide together with the shader clock it ran at (s_memtime ticks per s_memrealtime tick).
+// pt_dbg_triad is the matching memory probe: a STREAM triad (a = b + s * c) over three arrays, for the HBM side of the roofline.
 // Nothing of the render path depends on this file.
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "../../include/pt_api.h"
-
-void pt_set_error(const char* fmt, ...);   // pt_host.cpp
+#include "pt_internal.h"
 
 namespace {
 
@@ -356,10 +355,12 @@ PT_API int pt_dbg_valu_rate(int32_t device, int32_t op, int32_t waves_per_simd, 
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) { pt_set_error("pt_dbg_valu_rate: no device properties"); return PT_ERR_DEVICE; }
     const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     const int blocks = cus * waves_per_simd;
-    float* d_out = nullptr; unsigned long long* d_clk = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevBuf b_out, b_clk;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = PT_OK;
     do {
-        if (hipMalloc((void**)&d_out, 64) != hipSuccess || hipMalloc((void**)&d_clk, 64) != hipSuccess) { pt_set_error("pt_dbg_valu_rate: hipMalloc failed"); rc = PT_ERR_DEVICE; break; }
+        if (b_out.alloc(64) != hipSuccess || b_clk.alloc(64) != hipSuccess) { pt_set_error("pt_dbg_valu_rate: hipMalloc failed"); rc = PT_ERR_DEVICE; break; }
+        float* d_out = b_out.as<float>(); unsigned long long* d_clk = b_clk.as<unsigned long long>();
         (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
         hipError_t e;
         switch (op) {
@@ -443,8 +444,43 @@ PT_API int pt_dbg_valu_rate(int32_t device, int32_t op, int32_t waves_per_simd, 
     } while (0);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (d_out) (void)hipFree(d_out);
-    if (d_clk) (void)hipFree(d_clk);
+    return rc;
+}
+
+__global__ __launch_bounds__(256) void triad_kernel(float4* __restrict__ a, const float4* __restrict__ b, const float4* __restrict__ c, float s, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const float4 x = b[i], y = c[i];
+        a[i] = make_float4(x.x + s * y.x, x.y + s * y.y, x.z + s * y.z, x.w + s * y.w);
+    }
+}
+
+int pt_dbg_triad(int32_t device, int64_t bytes_per_array, int32_t iters, double* gb_per_s)
+{
+    if (!gb_per_s || bytes_per_array < 4096 || iters < 1) { pt_set_error("pt_dbg_triad: bad argument"); return PT_ERR_INVALID; }
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)bytes_per_array / 16;
+    DevBuf b_a, b_b, b_c;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = PT_OK;
+    do {
+        if (b_a.alloc(n * 16) != hipSuccess || b_b.alloc(n * 16) != hipSuccess || b_c.alloc(n * 16) != hipSuccess) { pt_set_error("pt_dbg_triad: out of device memory"); rc = PT_ERR_DEVICE; break; }
+        float4 *a = b_a.as<float4>(), *b = b_b.as<float4>(), *c = b_c.as<float4>();
+        (void)hipMemset(b, 0, n * 16); (void)hipMemset(c, 0, n * 16);
+        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+        const unsigned blocks = (unsigned)((n + 255) / 256);
+        hipLaunchKernelGGL(triad_kernel, dim3(blocks), dim3(256), 0, 0, a, b, c, 0.5f, n);       // warm-up
+        (void)hipEventRecord(e0, 0);
+        for (int k = 0; k < iters; k++) hipLaunchKernelGGL(triad_kernel, dim3(blocks), dim3(256), 0, 0, a, b, c, 0.5f, n);
+        (void)hipEventRecord(e1, 0);
+        if (hipEventSynchronize(e1) != hipSuccess) { pt_set_error("pt_dbg_triad: kernel failed"); rc = PT_ERR_DEVICE; break; }
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        *gb_per_s = 3.0 * (double)n * 16.0 * iters / ((double)ms * 1e-3) / 1e9;
+    } while (0);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
     return rc;
 }
 

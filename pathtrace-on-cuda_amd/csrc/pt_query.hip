@@ -18,7 +18,7 @@
 #include "pt_bxdf.h"
 #include "pt_trace.h"
 #include "pt_shade.h"
-#include "pt_internal.h"
+#include "pt_scene.h"
 
 namespace ptd {
 
@@ -101,27 +101,74 @@ void query_surface(DevScene sc, const float4* __restrict__ rays, uint32_t n, con
 
 }  // namespace ptd
 
-extern "C" {
-
-int ptk_query_quad_fits(int quad_depth) { return 3 * quad_depth + 2 <= ptd::kQueryStack; }
-
-// Enqueues one batch (n < 2^31) on `stream`.  quad: walk the 4-wide tree (the caller has checked ptk_query_quad_fits).
-hipError_t ptk_trace_rays(const ptd::DevScene* sc, const float* d_rays8, uint32_t n, int any, int quad, PtRayHit* d_hits, float* d_surface29,
-                          hipStream_t stream)
+// Enqueues one batch of n < 2^31 rays on `stream`: (t, prim) per ray, then the 29-float surface records if asked for.  quad: walk the
+// 4-wide tree (the caller has checked that it fits kQueryStack), else the binary one.
+static hipError_t launch_query(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, int any, int quad, PtRayHit* d_hits, float* d_surface29,
+                               hipStream_t stream)
 {
     using namespace ptd;
     const float4* rays = (const float4*)d_rays8;
     float2* hits = (float2*)d_hits;
     const uint32_t blocks = (n + 63u) / 64u;
     if (quad) {
-        if (any) hipLaunchKernelGGL((query_rays<true, true>), dim3(blocks), dim3(64), 0, stream, *sc, rays, n, hits);
-        else hipLaunchKernelGGL((query_rays<false, true>), dim3(blocks), dim3(64), 0, stream, *sc, rays, n, hits);
+        if (any) hipLaunchKernelGGL((query_rays<true, true>), dim3(blocks), dim3(64), 0, stream, sc, rays, n, hits);
+        else hipLaunchKernelGGL((query_rays<false, true>), dim3(blocks), dim3(64), 0, stream, sc, rays, n, hits);
     } else {
-        if (any) hipLaunchKernelGGL((query_rays<true, false>), dim3(blocks), dim3(64), 0, stream, *sc, rays, n, hits);
-        else hipLaunchKernelGGL((query_rays<false, false>), dim3(blocks), dim3(64), 0, stream, *sc, rays, n, hits);
+        if (any) hipLaunchKernelGGL((query_rays<true, false>), dim3(blocks), dim3(64), 0, stream, sc, rays, n, hits);
+        else hipLaunchKernelGGL((query_rays<false, false>), dim3(blocks), dim3(64), 0, stream, sc, rays, n, hits);
     }
-    if (d_surface29) hipLaunchKernelGGL(query_surface, dim3((n + 255u) / 256u), dim3(256), 0, stream, *sc, rays, n, (const float2*)hits, d_surface29);
+    if (d_surface29) hipLaunchKernelGGL(query_surface, dim3((n + 255u) / 256u), dim3(256), 0, stream, sc, rays, n, (const float2*)hits, d_surface29);
     return hipGetLastError();
 }
 
+// ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
+static int query_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, int32_t mode, const PtRayHit* hits, const float* surface,
+                         bool device)
+{
+    const char* bad = !s ? "NULL scene" : !rays ? "NULL rays" : !hits ? "NULL hits" : n < 0 ? "n < 0" :
+                      (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_ANY) ? "mode must be PT_QUERY_CLOSEST or PT_QUERY_ANY" :
+                      (mode == PT_QUERY_ANY && surface) ? "an any-hit query has no surface record (d_surface29 must be NULL)" :
+                      (device && ((uintptr_t)rays & 15)) ? "rays must be 16-byte aligned" :
+                      (device && ((uintptr_t)hits & 7)) ? "hits must be 8-byte aligned" :
+                      (device && ((uintptr_t)surface & 3)) ? "surface must be 4-byte aligned" : nullptr;
+    if (bad) { pt_set_error("%s: %s", who, bad); return PT_ERR_INVALID; }
+    return PT_OK;
 }
+
+extern "C" {
+
+int pt_trace_rays(PtScene* s, const float* d_rays8, int64_t n, int32_t mode, PtRayHit* d_hits, float* d_surface29, void* hip_stream)
+{
+    int rc;
+    if ((rc = query_args_ok("pt_trace_rays", s, d_rays8, n, mode, d_hits, d_surface29, true)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = s->query_quad && 3 * s->dev.quad_depth + 2 <= ptd::kQueryStack;      // does the 4-wide walk of a tree this deep fit the per-lane stack?
+    const int64_t kBatch = (int64_t)1 << 30;      // rays per launch: ray numbers are 32-bit
+    for (int64_t off = 0; off < n; off += kBatch) {
+        const uint32_t m = (uint32_t)(n - off < kBatch ? n - off : kBatch);
+        HIPCHK(launch_query(s->dev, d_rays8 + off * 8, m, mode == PT_QUERY_ANY, quad, d_hits + off,
+                              d_surface29 ? d_surface29 + off * 29 : nullptr, (hipStream_t)hip_stream));
+    }
+    return PT_OK;
+}
+
+int pt_trace_rays_host(PtScene* s, const float* h_rays8, int64_t n, int32_t mode, PtRayHit* h_hits, float* h_surface29)
+{
+    int rc;
+    if ((rc = query_args_ok("pt_trace_rays_host", s, h_rays8, n, mode, h_hits, h_surface29, false)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    DevBuf d_rays, d_hits, d_surf;      // d_surf stays null when the caller asked for no surface records
+    HIPCHK(d_rays.alloc((size_t)n * 32));
+    HIPCHK(d_hits.alloc((size_t)n * 8));
+    if (h_surface29) HIPCHK(d_surf.alloc((size_t)n * 116));
+    HIPCHK(hipMemcpy(d_rays.as<>(), h_rays8, (size_t)n * 32, hipMemcpyHostToDevice));
+    if ((rc = pt_trace_rays(s, d_rays.as<float>(), n, mode, d_hits.as<PtRayHit>(), d_surf.as<float>(), nullptr)) != PT_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(h_hits, d_hits.as<>(), (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (h_surface29) HIPCHK(hipMemcpy(h_surface29, d_surf.as<>(), (size_t)n * 116, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+}  // extern "C"

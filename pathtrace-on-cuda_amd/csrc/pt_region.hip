@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "pt_internal.h"
+#include "pt_scene.h"
 
 namespace ptd {
 
@@ -48,7 +48,7 @@ int32_t pt_tiles_of_window(const PtCamera* cam, int32_t x0, int32_t y0, int32_t 
     const int rc = window_args("pt_tiles_of_window", cam, x0, y0, x1, y1);
     if (rc) return rc;
     if (cap < 0 || (cap > 0 && !h_tiles)) { pt_set_error("pt_tiles_of_window: cap=%d with%s a buffer", cap, h_tiles ? "" : "out"); return PT_ERR_INVALID; }
-    const int tiles_x = (cam->W + ptd::kTile - 1) / ptd::kTile;
+    const int tiles_x = ptd::tile_grid(cam->W, cam->H).tiles_x;
     const int tx0 = x0 / ptd::kTile, tx1 = (x1 - 1) / ptd::kTile, ty0 = y0 / ptd::kTile, ty1 = (y1 - 1) / ptd::kTile;
     int32_t n = 0;
     for (int ty = ty0; ty <= ty1; ty++)
@@ -63,8 +63,8 @@ int pt_untile_list(const float* d_tiles, const int32_t* h_tiles, int32_t n_tiles
     if (!d_tiles || !h_tiles || !d_out) { pt_set_error("pt_untile_list: NULL argument"); return PT_ERR_INVALID; }
     const int rc = window_args("pt_untile_list", cam, x0, y0, x1, y1);
     if (rc) return rc;
-    const int tiles_x = (cam->W + ptd::kTile - 1) / ptd::kTile, tiles_y = (cam->H + ptd::kTile - 1) / ptd::kTile;
-    const int n_total = tiles_x * tiles_y;
+    const ptd::TileGrid g = ptd::tile_grid(cam->W, cam->H);
+    const int tiles_x = g.tiles_x, n_total = g.total;
     if (n_tiles < 1 || n_tiles > n_total) { pt_set_error("pt_untile_list: n_tiles=%d, the frame has %d tiles", n_tiles, n_total); return PT_ERR_INVALID; }
     for (int32_t i = 0; i < n_tiles; i++)      // an entry outside the frame would be a read or write out of bounds; a tile listed twice is only written twice
         if (h_tiles[i] < 0 || h_tiles[i] >= n_total) { pt_set_error("pt_untile_list: entry %d is tile %d, the frame has tiles 0 .. %d", i, h_tiles[i], n_total - 1); return PT_ERR_INVALID; }
@@ -99,19 +99,14 @@ int pt_render_window(PtScene* s, const PtCamera* cam, const PtParams* prm, int32
     const int64_t wb = pt_tile_list_work_bytes(cam, &p, n);
     if (wb < 0) return PT_ERR_INVALID;
     const size_t winBytes = (size_t)(x1 - x0) * (size_t)(y1 - y0) * 12;
-    HIPCHK(hipSetDevice(ptk_scene_device(s)));
-    float *d_tiles = nullptr, *d_win = nullptr; void* d_work = nullptr;
-    auto body = [&]() -> int {
-        HIPCHK(hipMalloc((void**)&d_tiles, (size_t)pt_tile_list_floats(n) * 4));
-        HIPCHK(hipMalloc(&d_work, (size_t)wb));
-        HIPCHK(hipMalloc((void**)&d_win, winBytes));
-        int r = pt_render_tile_list(s, cam, &p, list.data(), n, d_tiles, d_work, nullptr);
-        if (!r) r = pt_untile_list(d_tiles, list.data(), n, cam, x0, y0, x1, y1, d_win, nullptr);      // the list covers every pixel of the window
-        if (!r) HIPCHK(hipMemcpy(h_rgb, d_win, winBytes, hipMemcpyDeviceToHost));
-        return r;
-    };
-    const int rc = body();
-    (void)hipFree(d_tiles); (void)hipFree(d_work); (void)hipFree(d_win);
+    HIPCHK(hipSetDevice(s->device));
+    DevBuf d_tiles, d_work, d_win;
+    HIPCHK(d_tiles.alloc((size_t)pt_tile_list_floats(n) * 4));
+    HIPCHK(d_work.alloc((size_t)wb));
+    HIPCHK(d_win.alloc(winBytes));
+    int rc = pt_render_tile_list(s, cam, &p, list.data(), n, d_tiles.as<float>(), d_work.as<>(), nullptr);
+    if (!rc) rc = pt_untile_list(d_tiles.as<float>(), list.data(), n, cam, x0, y0, x1, y1, d_win.as<float>(), nullptr);      // the list covers every pixel of the window
+    if (!rc) HIPCHK(hipMemcpy(h_rgb, d_win.as<>(), winBytes, hipMemcpyDeviceToHost));
     return rc;
 }
 

@@ -1,0 +1,72 @@
+// pt_scene.h — the uploaded scene behind the C-ABI's opaque PtScene*: its device arrays, the resources it lends a render, its settings and
+// the state of the dynamic-geometry path.  Built by pt_scene.hip (pt_scene_create); included by every file whose entry points take a scene.
+// Everything the scene owns is released by its destructor, whichever path deletes it.
+#pragma once
+#include <vector>
+
+#include "pt_internal.h"
+
+// The device arrays a render reads (layouts: pt_device.h), in the order of pt_dbg_scene_array's `which` and of ptamd.SCENE_ARRAYS.
+enum SceneArray { kArrNodes, kArrQuad, kArrTri, kArrTripair, kArrLeafbox, kArrSurf, kArrLights, kArrSpheres, kArrCore, kSceneArrays };
+// The allocations of the first vertex update (pt_dynamic.hip: dyn_prepare): the 8 maps of the build, then 4 scratch arrays.
+enum DynAlloc { kDynBn, kDynOrder, kDynWideBn, kDynQuadBn, kDynLeafRange, kDynTmap, kDynLightPrim, kDynSmall,
+                kDynBbox, kDynMaxabs, kDynCorePartial, kDynAreaPartial, kDynAllocs };
+
+struct PtScene {
+    int device = 0;
+    ptd::DevScene dev{};
+    DevBuf arr[kSceneArrays];            // as uploaded; an empty array holds 16 bytes, kArrCore is null when the scene has no core box
+    DevBuf unit_counter;
+    DevBuf counters;
+    DevBuf tile_list;                    // the tile numbers (int32) of the pt_render_tile_list call in flight (grown on demand)
+    DevBuf views;                        // the cameras of the pt_render_views call in flight (grown on demand): origins (float4) | DevCamera | first pass (int32), one capacity each
+    std::vector<char> h_views;           // host image of `views` (the source of its stream-ordered copy)
+    int64_t bytes = 0;
+    int n_lights = 0;
+    int max_depth = 0;
+    int num_cus = 256;
+    bool count_next = false;
+    int mode = 1;            // 1 = wavefront pipeline (default), 0 = one-kernel state machine
+    uint32_t* h_poll = nullptr;   // pinned, for the pipeline's live-stream count
+    int last_iters = 0;
+    int shade_rounds = 1;        // wf_shade: 1 = a stream may start its next sample in the step its path ends, 0 = one bounce per step, -1 = by live-stream count (PTAMD_TRS)
+    int early_below = 2500000;   // renders of at most this many streams (pixels x passes of one call) run wf_shade's early phase beside the draining wf_trace (0 = never; pt_set_early_shade)
+    int drain_below = 80000;     // hand the last streams of a render to wf_drain once this few are live (0 = never; PTAMD_DRAIN, pt_set_drain_threshold):
+                                 // the last ~200 of ~1,100 bounce iterations serve < 5 % of the streams at the latency of the longest ray each
+                                 // (~200 us); wf_drain runs those streams to their end in one launch, spread over every SIMD.  40,000-120,000 is flat:
+                                 // +5...7 % for an 8-way rank, +3 % 4-way, +1 % on one GPU (r03_b31.log, r03_b32.log, r03_b33.log)
+    // optional per-launch timing of the traversal kernel (pt_enable_trace_timing)
+    std::vector<hipEvent_t> trace_ev;
+    int trace_ev_used[4] = {0, 0, 0, 0};     // per cohort
+    int trace_ev_per = 0;                    // event pairs per cohort in the last render
+    hipStream_t xstreams[3] = {nullptr, nullptr, nullptr};   // extra streams for concurrent cohorts
+    hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
+    // ring of HIP event pairs, one pair per render_units launch (pt_render_timings)
+    static constexpr int kEvRing = 64;
+    hipEvent_t ev[kEvRing][2] = {};
+    int ev_count = 0;        // launches recorded since the last pt_render_timings(reset)
+    // ---- dynamic geometry (pt_scene_update_vertices, csrc/pt_dynamic.hip) ----
+    std::vector<float> h_spheres;        // the uploaded sphere records: pt_scene_update_spheres checks the materials against them and copies from here
+    struct DynHost {                     // the maps of the build, kept on the host until the first update uploads them
+        std::vector<int32_t> bn, order, level_start, wide_bn, quad_bn, leaf_range, tmap, light_prim;
+        std::vector<uint8_t> small;
+        double area_sum = 0.0;
+    } dyn_host;
+    ptd::DynScene dyn{};                 // device side of the same: the rewritten arrays from upload on, the maps and scratch once dyn_ready
+    DevBuf dyn_buf[kDynAllocs];          // its allocations (dyn_prepare); kDynSmall stays null when the scene has no core box
+    bool dyn_ready = false;
+    bool updated = false;
+    std::vector<double> h_area;          // host image of dyn.area_partial
+    // ---- ray queries (pt_trace_rays, csrc/pt_query.hip) ----
+    bool query_quad = true;              // walk the 4-wide tree when it fits the kernel's stack (PTAMD_QUERY_QUAD=0: the binary tree, A/B)
+
+    // Events, streams and pinned memory; the DevBuf members free themselves after it.  The caller has made `device` current.
+    ~PtScene()
+    {
+        for (int i = 0; i < kEvRing; i++) for (int j = 0; j < 2; j++) if (ev[i][j]) (void)hipEventDestroy(ev[i][j]);
+        if (h_poll) (void)hipHostFree(h_poll);
+        for (int i = 0; i < 3; i++) { if (xstreams[i]) (void)hipStreamDestroy(xstreams[i]); if (ev_join[i]) (void)hipEventDestroy(ev_join[i]); }
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        for (hipEvent_t e : trace_ev) if (e) (void)hipEventDestroy(e);
+    }
+};

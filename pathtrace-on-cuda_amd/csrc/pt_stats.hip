@@ -22,8 +22,10 @@
 // Kernels: pure streams, 256-thread blocks, one float4 per thread where the buffers are 16-byte aligned (a render's tile
 // buffers always are: pt_tiles_floats() is a multiple of 192), plain 16-byte loads and stores.
 #include <hip/hip_runtime.h>
+#include <cmath>
+#include <vector>
 #include "pt_device.h"
-#include "pt_internal.h"
+#include "pt_scene.h"
 
 namespace ptd {
 
@@ -154,13 +156,9 @@ static inline bool st_aligned16(const void* a, const void* b, const void* c)
 }
 }  // namespace ptd
 
-// ---------------------------------------------------------------------------------------
-// Launchers (called from pt_api.hip)
-// ---------------------------------------------------------------------------------------
-extern "C" {
-
+// ---- launchers ----------------------------------------------------------------------------------------------------------------------
 // staging: passes x n floats (pass-major); sum, m2: n floats each
-hipError_t ptk_stats_fold(const float* staging, int passes, long long n, int n_before, float* sum, float* m2, hipStream_t stream)
+static hipError_t launch_fold(const float* staging, int passes, long long n, int n_before, float* sum, float* m2, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
     if (n % 4 == 0 && ptd::st_aligned16(staging, sum, m2)) {
@@ -174,7 +172,7 @@ hipError_t ptk_stats_fold(const float* staging, int passes, long long n, int n_b
     return hipGetLastError();
 }
 
-hipError_t ptk_stats_variance(const float* m2, long long n, int n_passes, float* var, hipStream_t stream)
+static hipError_t launch_variance(const float* m2, long long n, int n_passes, float* var, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
     const float nf = (float)n_passes, nf1 = (float)(n_passes - 1);
@@ -188,19 +186,18 @@ hipError_t ptk_stats_variance(const float* m2, long long n, int n_passes, float*
     return hipGetLastError();
 }
 
-// blocks of st_estimate for n floats (n a multiple of 192): one partial of ptk_stats_partial_bytes() bytes each
-int ptk_stats_blocks(long long n)
+// blocks of st_estimate for n floats (n a multiple of 192): one StPartial each
+static int estimate_blocks(long long n)
 {
     const long long nb = (n / 12 + 255) / 256;
     return nb < 1 ? 1 : nb > ptd::kStBlocks ? ptd::kStBlocks : (int)nb;
 }
-int ptk_stats_partial_bytes(void) { return (int)sizeof(ptd::StPartial); }
 
-hipError_t ptk_stats_estimate(const float* sum, const float* m2, long long n, int n_passes, int W, int H, int tiles_x, int n_tiles_total,
-                              int rank, int world, void* partial, hipStream_t stream)
+static hipError_t launch_estimate(const float* sum, const float* m2, long long n, int n_passes, int W, int H, int tiles_x, int n_tiles_total,
+                                  int rank, int world, void* partial, hipStream_t stream)
 {
     const float nf = (float)n_passes, nf1 = (float)(n_passes - 1);
-    const int nb = ptk_stats_blocks(n);
+    const int nb = estimate_blocks(n);
     if (ptd::st_aligned16(sum, m2, nullptr))
         hipLaunchKernelGGL(ptd::st_estimate<true>, dim3(nb), dim3(256), 0, stream, sum, m2, n / 12, nf, nf1, W, H, tiles_x, n_tiles_total,
                            rank, world, (ptd::StPartial*)partial);
@@ -208,6 +205,118 @@ hipError_t ptk_stats_estimate(const float* sum, const float* m2, long long n, in
         hipLaunchKernelGGL(ptd::st_estimate<false>, dim3(nb), dim3(256), 0, stream, sum, m2, n / 12, nf, nf1, W, H, tiles_x, n_tiles_total,
                            rank, world, (ptd::StPartial*)partial);
     return hipGetLastError();
+}
+
+
+// ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
+extern "C" {
+
+int pt_accumulate_passes(const void* d_work, const PtCamera* cam, const PtParams* prm, int32_t n_before, float* d_sum, float* d_m2,
+                         void* hip_stream)
+{
+    if (!d_work || !d_sum || !d_m2) { pt_set_error("pt_accumulate_passes: NULL argument"); return PT_ERR_INVALID; }
+    if (n_before < 0 || (prm && (long long)n_before + prm->passes > 0x7fffffffLL)) { pt_set_error("pt_accumulate_passes: bad n_before %d", n_before); return PT_ERR_INVALID; }
+    ptd::DevParams d;
+    const int rc = pt_fill_params(cam, prm, d);
+    if (rc) return rc;
+    const long long perPass = (long long)d.n_tiles_local * ptd::kTilePixels * 3;
+    // both render modes leave the per-pass means at the start of the work buffer (pt_render_tiles: what sum_passes reads)
+    HIPCHK(launch_fold(ptk_wf_staging(const_cast<void*>(d_work)), d.passes, perPass, n_before, d_sum, d_m2, (hipStream_t)hip_stream));
+    return PT_OK;
+}
+
+int pt_variance(const float* d_m2, int64_t n_floats, int32_t n_passes, float* d_var, void* hip_stream)
+{
+    if (!d_m2 || !d_var || n_floats < 1 || n_passes < 2) { pt_set_error("pt_variance: NULL buffer, n_floats < 1 or n_passes < 2"); return PT_ERR_INVALID; }
+    HIPCHK(launch_variance(d_m2, n_floats, n_passes, d_var, (hipStream_t)hip_stream));
+    return PT_OK;
+}
+
+int64_t pt_error_scratch_bytes(int64_t n_floats)
+{
+    if (n_floats < 1) { pt_set_error("pt_error_scratch_bytes: n_floats < 1"); return -1; }
+    const int64_t nb = (n_floats + 3071) / 3072;
+    return (nb > 1024 ? 1024 : nb) * (int64_t)sizeof(ptd::StPartial);
+}
+
+int pt_error_estimate(const float* d_sum, const float* d_m2, const PtCamera* cam, const PtParams* prm, int32_t n_passes,
+                      void* d_scratch, PtErrorEstimate* h_out, void* hip_stream)
+{
+    if (!d_sum || !d_m2 || !d_scratch || !h_out) { pt_set_error("pt_error_estimate: NULL argument"); return PT_ERR_INVALID; }
+    if (n_passes < 2) { pt_set_error("pt_error_estimate: n_passes %d < 2", n_passes); return PT_ERR_INVALID; }
+    if (!cam || !prm) { pt_set_error("NULL camera/params"); return PT_ERR_INVALID; }
+    PtParams p = *prm; p.passes = 1; p.first_pass = 0;      // only the geometry of the split is read
+    ptd::DevParams d;
+    const int rc = pt_fill_params(cam, &p, d);
+    if (rc) return rc;
+    const long long n = (long long)d.n_tiles_local * ptd::kTilePixels * 3;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    HIPCHK(launch_estimate(d_sum, d_m2, n, n_passes, cam->W, cam->H, d.tiles_x, d.n_tiles_total, d.rank, d.world, d_scratch, stream));
+    std::vector<ptd::StPartial> part((size_t)estimate_blocks(n));
+    HIPCHK(hipMemcpyAsync(part.data(), d_scratch, part.size() * sizeof(ptd::StPartial), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    double var = 0.0, s2 = 0.0, se = 0.0; long long pixels = 0, skipped = 0;
+    for (const ptd::StPartial& q : part) { var += q.var; s2 += q.s2; se += q.se; pixels += q.pixels; skipped += q.skipped; }      // block order
+    h_out->rel_rms = std::sqrt(var / s2);
+    h_out->mean_rel_se = se / (double)pixels;
+    h_out->pixels = pixels; h_out->skipped = skipped;
+    return PT_OK;
+}
+
+int pt_render_converge(PtScene* s, const PtCamera* cam, const PtParams* prm, double target_rel_rms, int32_t max_passes,
+                       float* h_accum_rgb, float* h_var_rgb, int32_t* passes_done, PtErrorEstimate* est)
+{
+    if (!s || !prm || !h_accum_rgb || !passes_done || !est) { pt_set_error("pt_render_converge: NULL argument"); return PT_ERR_INVALID; }
+    if (max_passes < 2 || !(target_rel_rms >= 0.0)) { pt_set_error("pt_render_converge: max_passes %d < 2 or target not >= 0", max_passes); return PT_ERR_INVALID; }
+    PtParams p = *prm; p.rank = 0; p.world = 1;
+    if (p.passes < 1) { pt_set_error("pt_render_converge: batch of %d passes", p.passes); return PT_ERR_INVALID; }
+    if (p.passes > max_passes) p.passes = max_passes;
+    const int batch = p.passes;
+    const int64_t nt = pt_tiles_floats(cam, &p);
+    int64_t wb = pt_work_bytes(cam, &p);
+    PtParams all = p; all.passes = max_passes;              // the seed limit for the last pass that may be rendered
+    if (nt < 0 || wb < 0 || pt_tiles_floats(cam, &all) < 0) return PT_ERR_INVALID;
+    if (max_passes % batch) {                               // the shortened last batch
+        PtParams q = p; q.passes = max_passes % batch;
+        const int64_t w2 = pt_work_bytes(cam, &q);
+        if (w2 < 0) return PT_ERR_INVALID;
+        if (w2 > wb) wb = w2;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    const size_t frameBytes = (size_t)cam->W * cam->H * 12;
+    DevBuf b_tiles, b_sum, b_m2, b_work, b_scratch, b_frame;
+    HIPCHK(b_tiles.alloc((size_t)nt * 4));
+    HIPCHK(b_sum.alloc((size_t)nt * 4));
+    HIPCHK(b_m2.alloc((size_t)nt * 4));
+    HIPCHK(b_work.alloc((size_t)wb));
+    HIPCHK(b_scratch.alloc((size_t)pt_error_scratch_bytes(nt)));
+    HIPCHK(b_frame.alloc(frameBytes));
+    float *d_tiles = b_tiles.as<float>(), *d_sum = b_sum.as<float>(), *d_m2 = b_m2.as<float>(), *d_frame = b_frame.as<float>();
+    void *d_work = b_work.as<>(), *d_scratch = b_scratch.as<>();
+    int done = 0;
+    while (done < max_passes) {
+        p.first_pass = prm->first_pass + done;
+        p.passes = max_passes - done < batch ? max_passes - done : batch;
+        int r = pt_render_tiles(s, cam, &p, d_tiles, d_work, nullptr);
+        if (!r) r = pt_accumulate_passes(d_work, cam, &p, done, d_sum, d_m2, nullptr);
+        if (r) return r;
+        done += p.passes;
+        if (done < 2) continue;
+        r = pt_error_estimate(d_sum, d_m2, cam, &p, done, d_scratch, est, nullptr);
+        if (r) return r;
+        if (est->rel_rms <= target_rel_rms) break;
+    }
+    *passes_done = done;
+    int r = pt_untile(d_sum, cam, 1, d_frame, nullptr);
+    if (r) return r;
+    HIPCHK(hipMemcpy(h_accum_rgb, d_frame, frameBytes, hipMemcpyDeviceToHost));
+    if (h_var_rgb) {
+        r = pt_variance(d_m2, nt, done, d_tiles, nullptr);      // d_tiles is free by now
+        if (!r) r = pt_untile(d_tiles, cam, 1, d_frame, nullptr);
+        if (r) return r;
+        HIPCHK(hipMemcpy(h_var_rgb, d_frame, frameBytes, hipMemcpyDeviceToHost));
+    }
+    return PT_OK;
 }
 
 }  // extern "C"

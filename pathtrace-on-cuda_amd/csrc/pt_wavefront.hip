@@ -652,7 +652,7 @@ void wf_shade(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int slot
 // one lane per stream (every 2^spreadShift-th lane: the kernel is bound by latency, so thinner waves are faster), state in
 // registers, rays traced in place (quad_step on the 4-wide tree, or trace_closest on the binary one when that walk would not fit
 // the per-lane stack), same shade_step.  Pending time-sliced traversals are simply redone (they are deterministic).
-// On by default for the last 80,000 live streams of a render (pt_api.hip: drain_below).
+// On by default for the last 80,000 live streams of a render (pt_scene.h: drain_below).
 // ---------------------------------------------------------------------------------------
 constexpr int kDrainQuadStack = 40;      // per-lane stack entries of wf_drain's 4-wide walk (40 KB of LDS per workgroup): trees up to 12 levels, the config scenes' depth
 #ifndef DRAIN_MINBLOCKS

@@ -204,7 +204,7 @@ def walk_quad(quad_arr, tri_arr, pos):
 def core_box(tris_uploaded, pos):
     """The `core` device array (6 floats, lo.xyz hi.xyz) after a move to pos (n, 3, 3): the box of the triangles pt_scene_create
     classified small on the uploaded geometry (box diagonal * 8 < the scene's), at their new positions, padded by
-    0.01 * extent + 1e-4 * (diagonal of the moved scene box) — csrc/pt_api.hip: pt_scene_create, all in float32."""
+    0.01 * extent + 1e-4 * (diagonal of the moved scene box) — csrc/pt_scene.hip: core_box, all in float32."""
     def diag(lo, hi):
         d = (hi - lo).astype(F)
         return np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])

@@ -28,7 +28,7 @@ def kernels(path):
             cur = out.setdefault(m.group(1), [])
             continue
         text = re.sub(r'//.*', '', line).strip()
-        if cur is not None and text:
+        if cur is not None and text and text != '...':      # '...': objdump's mark for the zero padding between two kernels
             cur.append(text)
     return out
 

@@ -490,6 +490,62 @@ PT_API int  pt_trace_rays(PtScene* s, const float* d_rays8, int64_t n, int32_t m
 PT_API int  pt_trace_rays_host(PtScene* s, const float* h_rays8, int64_t n, int32_t mode, PtRayHit* h_hits, float* h_surface29);
 
 /* ----------------------------------------------------------------------------------
+ * Radiance along the caller's own rays (new: the reference reaches its integrator through a pinhole camera only).
+ * Opt-in: every call above is as it was.  pt_trace_rays opened the geometry of an uploaded scene to the caller's rays; this opens
+ * the light transport: a panorama, fisheye, orthographic or thin-lens camera, a light probe at a point, a lightmap texel, the
+ * radiance arriving at a sensor in a scene that pt_scene_update_vertices moves — the caller makes the rays (csrc/pt_rays.hip).
+ *
+ * Rays are RAY8 records as in pt_trace_rays: org.xyz | dir.xyz | reserved (must be 0, not read) | tmax.  The direction must have
+ *   unit length and is used as given.  tmax bounds the PRIMARY ray only (it takes the place of the camera path's 999999); the rays
+ *   of later bounces are the integrator's own.
+ * Definition: ray i takes the place of a pixel.  For each pass k = prm->first_pass .. first_pass + passes - 1 one stream runs
+ *   exactly what StartRender runs for a pixel and a pass (srcs/pathtracer.cu:70-81):
+ *     1. the RNG is seeded with (uint64_t)(int64_t)(int32_t)(seed_i + k * seed_stride), the sum taken in wrapping uint32 arithmetic;
+ *        seed_i = d_seed[i], or i when d_seed is NULL;
+ *     2. two uniform draws are made and discarded — the jitter draws: with them a ray taken from a camera pixel (direction of
+ *        pt_dbg_pixel_dir, seed py * W + px, stride W * H) reproduces that pixel of pt_render bit for bit;
+ *     3. spp_per_pass paths all start down the ray; the primary ray is traced once and its hit shared;
+ *     4. the pass mean is pixelColor / spp_per_pass.
+ *   The same ray serves every pass of a call: a caller who wants a newly jittered ray per pass calls once per pass and folds with
+ *   the moments calls.  A primary ray with no hit in [0, tmax] gets what a pixel that looks past the scene gets: the ambient term
+ *   for every sample, no draws, no rays.
+ * pt_render_rays: d_rays8 (16-byte aligned, n_rays records), d_seed (NULL or n_rays int32), d_rgb (16-byte aligned) and d_work are
+ *   DEVICE pointers on the scene's device.  d_rgb[3 * i + c] = the sum over the call's passes, in pass order starting from 0, of
+ *   the per-pass means of ray i.  The buffer holds pt_rays_floats(n_rays) floats: rays are rendered in groups of 64, and the
+ *   padding rays of the last group are exactly +0.
+ *   Work buffer: d_work is scratch of pt_rays_work_bytes() bytes, and the contract of the moments section holds for it — after the
+ *   call its start holds the per-pass means, prm->passes x pt_rays_floats(n_rays) float32, pass-major, each pass in the layout of
+ *   d_rgb, valid until d_work is next written.  pt_accumulate_passes folds that slab when it is described to it by a camera of
+ *   W = 8 * ceil(n_rays / 64), H = 8 pixels (as many 8x8 tiles as there are groups of 64 rays; the moments come out in ray order
+ *   like d_rgb) and the prm of the call with first_pass = 0 — its seed limit then reads 64 * ceil(n / 64) * passes <= 2^31 - 1.
+ *   Checked on the host before any HIP call, else PT_ERR_INVALID: a NULL scene, rays, params, rgb or work; n_rays < 1;
+ *   seed_stride < 0; prm->rank != 0 || prm->world != 1; the parameter ranges of pt_render_tiles; d_rays8 or d_rgb not 16-byte
+ *   aligned; ceil(n_rays / 64) x passes work units beyond pt_render_tiles' own limit, or 64 x that not below 2^31.
+ *   Otherwise pt_render_tile_list's contract: BLOCKING as mode 1 is, one render, update or query at a time per scene, all GPU work
+ *   on `hip_stream`, always the queue-driven pipeline (pt_set_mode(0), pt_enable_counters, pt_enable_trace_timing and the PTAMD_TSTAT
+ *   diagnostics do not apply and are left as set for the next pt_render_tiles); pt_last_render_ms and pt_last_iterations report it.
+ *   pt_set_shade_rounds, pt_set_drain_threshold and pt_set_early_shade act on the stream count (64 * ceil(n / 64) * passes) as on
+ *   a frame's.  A ray render enqueued after pt_scene_update_vertices on the same stream sees the moved geometry.  The rays (and
+ *   seeds) are read where they are for as long as the call blocks — a sample that restarts at the shared first hit reads its origin
+ *   from d_rays8 —, so nothing is copied and nothing is allocated in the scene (pt_scene_device_bytes stays what it was).
+ * pt_rays_floats: 192 * ceil(n_rays / 64), or -1 (n_rays < 1 or beyond 2^31).
+ * pt_rays_work_bytes: pt_work_bytes of any frame that has ceil(n_rays / 64) tiles with the same prm, as pt_tile_list_work_bytes
+ *   is: the pipeline's need depends on the number of work units only.  -1 for arguments pt_render_rays would reject.
+ * pt_render_rays_host: the same on HOST arrays (h_seed may be NULL): uploads, renders on the NULL stream, waits and downloads
+ *   h_rgb[n_rays * 3] — no padding.
+ * Rays with a non-finite component or a zero direction: the result for THAT ray is unspecified, the other rays are unaffected, and
+ *   the call ends, by the argument of the ray-query section (a depth-first search over a finite tree) and the path-length limits.
+ * Out of scope: a tile-split or multi-GPU ray render, rays x views, a per-pass ray set inside one call, non-unit directions, tmin,
+ * AOVs or the denoiser on a ray batch, mode 0, a CLI option.
+ * -------------------------------------------------------------------------------- */
+PT_API int64_t pt_rays_floats(int64_t n_rays);                                    /* 192 * ceil(n / 64), or -1 */
+PT_API int64_t pt_rays_work_bytes(const PtParams* prm, int64_t n_rays);           /* or -1 */
+PT_API int  pt_render_rays(PtScene* s, const float* d_rays8, const int32_t* d_seed, int64_t n_rays, int32_t seed_stride,
+                           const PtParams* prm, float* d_rgb, void* d_work, void* hip_stream);
+PT_API int  pt_render_rays_host(PtScene* s, const float* h_rays8, const int32_t* h_seed, int64_t n_rays, int32_t seed_stride,
+                                const PtParams* prm, float* h_rgb /* n_rays * 3 */);
+
+/* ----------------------------------------------------------------------------------
  * (a12,a13) Output + camera helpers (host).
  * pt_tonemap_u8 = exportImage (srcs/pathtracer.cu:94-112): /SampleCnt, ACESFilm
  *   (include/CudaUtil.cuh:383-391), ConverToUint8 (include/image.h:5-8).

@@ -1,6 +1,6 @@
 // pt_api.hip — the render half of the C-ABI (include/pt_api.h): the checks and the geometry of a render call, the launch sequence of the
-// tile, tile-list and view-batch renders, tile gather helpers, timing and diagnostics, parity hooks.  The scene is built in pt_scene.hip;
-// every other feature's entry points sit beside its kernels (pt_denoise.hip, pt_stats.hip, pt_region.hip, pt_dynamic.hip, pt_query.hip).
+// tile, tile-list and view-batch renders (the ray render's is in pt_rays.hip), tile gather helpers, timing and diagnostics, parity hooks.  The scene is built in pt_scene.hip;
+// every other feature's entry points sit beside its kernels (pt_denoise.hip, pt_stats.hip, pt_region.hip, pt_dynamic.hip, pt_query.hip, pt_rays.hip).
 //
 // Replaces the render half of PathTracer::Render (srcs/pathtracer.cu:124-259): instead of NUM_MULTI_SAMPLE synchronous launches there is
 // one persistent launch over all (tile, pass) units on the caller's stream.  This file holds no device code.
@@ -32,10 +32,8 @@ static int with_buffers(int device, const void* in, size_t in_bytes, void* out, 
 static const int kTraceBlocks = (getenv("PTAMD_TB") && atoi(getenv("PTAMD_TB")) >= 1) ? (atoi(getenv("PTAMD_TB")) > 16384 ? 16384 : atoi(getenv("PTAMD_TB"))) : 1792;
 
 // ---- geometry of the tile split --------------------------------------------------------
-int pt_fill_params(const PtCamera* cam, const PtParams* prm, ptd::DevParams& d)
+int pt_check_params(const PtParams* prm)
 {
-    if (!cam || !prm) { pt_set_error("NULL camera/params"); return PT_ERR_INVALID; }
-    if (cam->W < 2 || cam->H < 2) { pt_set_error("frame %dx%d too small (W-1, H-1 divide, srcs/pathtracer.cu:35-36)", cam->W, cam->H); return PT_ERR_INVALID; }
     if (prm->spp_per_pass > 65535 || prm->max_bounce > 255 || prm->max_refract < 0 || prm->max_refract > 250) {
         pt_set_error("params out of range: spp_per_pass <= 65535, max_bounce <= 255, 0 <= max_refract <= 250");
         return PT_ERR_INVALID;
@@ -44,6 +42,14 @@ int pt_fill_params(const PtCamera* cam, const PtParams* prm, ptd::DevParams& d)
         pt_set_error("bad params: passes=%d spp=%d max_bounce=%d rank=%d world=%d", prm->passes, prm->spp_per_pass, prm->max_bounce, prm->rank, prm->world);
         return PT_ERR_INVALID;
     }
+    return PT_OK;
+}
+
+int pt_fill_params(const PtCamera* cam, const PtParams* prm, ptd::DevParams& d)
+{
+    if (!cam || !prm) { pt_set_error("NULL camera/params"); return PT_ERR_INVALID; }
+    if (cam->W < 2 || cam->H < 2) { pt_set_error("frame %dx%d too small (W-1, H-1 divide, srcs/pathtracer.cu:35-36)", cam->W, cam->H); return PT_ERR_INVALID; }
+    if (pt_check_params(prm)) return PT_ERR_INVALID;
     if (!ptd::seed_in_range(cam, prm->first_pass, prm->passes)) return PT_ERR_INVALID;
     d.passes = prm->passes; d.spp_per_pass = prm->spp_per_pass; d.max_bounce = prm->max_bounce; d.rr_bounce = prm->rr_bounce;
     d.rr_floor = prm->rr_floor; d.max_refract = prm->max_refract; d.first_pass = prm->first_pass;
@@ -77,7 +83,7 @@ int64_t pt_tiles_floats(const PtCamera* cam, const PtParams* prm)
     return (int64_t)d.n_tiles_local * ptd::kTilePixels * 3;
 }
 // d_work of a render of d: the per-pass means of the one-kernel mode or the pipeline's buffers, whichever is larger
-static int64_t work_bytes(const ptd::DevParams& d)
+int64_t pt_job_work_bytes(const ptd::DevParams& d)
 {
     const int64_t means = (int64_t)d.n_tiles_local * ptd::kTilePixels * 3 * 4 * d.passes;
     const int64_t wave = (int64_t)ptk_wf_work_bytes((size_t)d.n_units, kTraceBlocks);
@@ -87,10 +93,10 @@ int64_t pt_work_bytes(const PtCamera* cam, const PtParams* prm)
 {
     ptd::DevParams d;
     if (pt_fill_params(cam, prm, d)) return -1;
-    return work_bytes(d);
+    return pt_job_work_bytes(d);
 }
 
-static bool has_light(const PtScene* s)      // false: PT_ERR_NO_LIGHT, with the error text set
+bool pt_has_light(const PtScene* s)      // false: PT_ERR_NO_LIGHT, with the error text set
 {
     if (s->n_lights < 1) pt_set_error("scene has no emissive triangle: the reference's `curand(s) %% Nl` is undefined (include/CudaUtil.cuh:235)");
     return s->n_lights >= 1;
@@ -100,7 +106,7 @@ static bool has_light(const PtScene* s)      // false: PT_ERR_NO_LIGHT, with the
 // what to render and from which pixels and cameras.  Lends the job the scene's resources and runs it — the pipeline polls the live-stream count,
 // so this returns once the render has drained — then sums the passes into d_tiles.  traceEvents: record the per-launch events of
 // pt_enable_trace_timing.  traceStat: the PTAMD_TSTAT diagnostics apply (wf_trace counts its trips and the lanes they serve; pt_last_counters).
-static int run_job(PtScene* s, ptd::WfJob& job, bool traceEvents, bool traceStat, float* d_tiles)
+int pt_run_job(PtScene* s, ptd::WfJob& job, bool traceEvents, bool traceStat, float* d_tiles)
 {
     const int slot = s->ev_count % PtScene::kEvRing;
     job.device = s->device; job.scene = &s->dev; job.traceBlocks = kTraceBlocks;
@@ -125,7 +131,7 @@ static int run_job(PtScene* s, ptd::WfJob& job, bool traceEvents, bool traceStat
 int pt_render_tiles(PtScene* s, const PtCamera* cam, const PtParams* prm, float* d_tiles, void* d_work, void* hip_stream)
 {
     if (!s || !d_tiles || !d_work) { pt_set_error("pt_render_tiles: NULL argument"); return PT_ERR_INVALID; }
-    if (!has_light(s)) return PT_ERR_NO_LIGHT;
+    if (!pt_has_light(s)) return PT_ERR_NO_LIGHT;
     ptd::WfJob job{};
     ptd::DevParams& d = job.prm;
     int rc = pt_fill_params(cam, prm, d);
@@ -138,7 +144,7 @@ int pt_render_tiles(PtScene* s, const PtCamera* cam, const PtParams* prm, float*
     if (s->mode == 1 && !s->count_next) {
         // the only entry point that honours pt_set_mode(0), the counting build and the PTAMD_TSTAT diagnostics
         job.work = d_work; job.stream = stream; job.cam = &c;
-        return run_job(s, job, /*traceEvents=*/true, /*traceStat=*/true, d_tiles);
+        return pt_run_job(s, job, /*traceEvents=*/true, /*traceStat=*/true, d_tiles);
     }
     const int slot = s->ev_count % PtScene::kEvRing;
     HIPCHK(hipMemsetAsync(s->unit_counter.as<>(), 0, 4, stream));
@@ -180,7 +186,7 @@ int64_t pt_tile_list_work_bytes(const PtCamera* cam, const PtParams* prm, int32_
 {
     ptd::DevParams d;
     if (fill_list_params(cam, prm, n_tiles, d)) return -1;
-    return work_bytes(d);
+    return pt_job_work_bytes(d);
 }
 
 int pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, const int32_t* h_tiles, int32_t n_tiles,
@@ -200,7 +206,7 @@ int pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, co
             seen[(size_t)t] = true;
         }
     }
-    if (!has_light(s)) return PT_ERR_NO_LIGHT;
+    if (!pt_has_light(s)) return PT_ERR_NO_LIGHT;
     ptd::DevCamera c;
     pt_fill_camera(cam, c);
 
@@ -212,7 +218,7 @@ int pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, co
     HIPCHK(hipMemcpyAsync(s->tile_list.as<>(), h_tiles, (size_t)n_tiles * 4, hipMemcpyHostToDevice, job.stream));
     // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply); no per-launch trace events
     job.work = d_work; job.cam = &c; job.tileList = s->tile_list.as<int32_t>();
-    return run_job(s, job, /*traceEvents=*/false, /*traceStat=*/false, d_tiles);
+    return pt_run_job(s, job, /*traceEvents=*/false, /*traceStat=*/false, d_tiles);
 }
 
 // ---- a batch of cameras in one pipeline run -----------------------------------------------------------------------------------------
@@ -252,7 +258,7 @@ int64_t pt_views_work_bytes(const PtCamera* cam0, const PtParams* prm, int32_t n
 {
     ptd::DevParams d;
     if (fill_views_params(cam0, prm, n_views, prm ? prm->first_pass : 0, d)) return -1;
-    return work_bytes(d);
+    return pt_job_work_bytes(d);
 }
 
 // every host-side check of a batch (include/pt_api.h), before any HIP call
@@ -281,7 +287,7 @@ int pt_render_views(PtScene* s, const PtCamera* h_cams, int32_t n_views, const P
     ptd::WfJob job{};
     const int rc = views_args(h_cams, n_views, prm, h_first_pass, job.prm);
     if (rc) return rc;
-    if (!has_light(s)) return PT_ERR_NO_LIGHT;
+    if (!pt_has_light(s)) return PT_ERR_NO_LIGHT;
     job.stream = (hipStream_t)hip_stream;
     HIPCHK(hipSetDevice(s->device));
     // the previous batch on this scene has drained (one render at a time per scene), so nothing reads the old buffer
@@ -304,7 +310,7 @@ int pt_render_views(PtScene* s, const PtCamera* h_cams, int32_t n_views, const P
     // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply); a batch passes no single camera
     job.work = d_work;
     job.viewOrg = (const float4*)dv; job.viewCams = (const ptd::DevCamera*)(dv + offCam); job.viewFirstPass = (const int32_t*)(dv + offFirst);
-    return run_job(s, job, /*traceEvents=*/true, /*traceStat=*/false, d_tiles);
+    return pt_run_job(s, job, /*traceEvents=*/true, /*traceStat=*/false, d_tiles);
 }
 
 int pt_render_views_host(PtScene* s, const PtCamera* h_cams, int32_t n_views, const PtParams* prm, const int32_t* h_first_pass, float* h_rgb)

@@ -96,9 +96,13 @@ struct WfJob {
     //   cam + tileList                       prm.n_tiles_local global tile numbers on the device (wf_init_list); nothing else of the pipeline differs
     //   viewCams + viewFirstPass + viewOrg   a batch, one device entry per view and cam == nullptr: n_tiles_local = views x prm.n_tiles_total,
     //                                        streams are set up by wf_init_views and stepped by the ViewTable instantiations of wf_shade / wf_drain
+    //   rays8 + raySeed + seedStride + nRays the caller's own rays (pt_render_rays), cam == nullptr: n_tiles_local = ceil(nRays / 64) groups of 64 rays,
+    //                                        streams are set up by wf_init_rays and stepped by the RayTable instantiations; rays8 is the
+    //                                        caller's device buffer (also the origin table), raySeed may be nullptr (seed of ray i = i)
     const DevCamera* cam;
     const int32_t* tileList;
     const DevCamera* viewCams; const int32_t* viewFirstPass; const float4* viewOrg;
+    const float4* rays8; const int32_t* raySeed; int32_t seedStride; uint32_t nRays;
     // ---- what the scene lends
     uint32_t* h_poll;                    // pinned, one poll word per cohort, 64 B apart
     hipStream_t* xstreams;               // 3 extra streams: cohorts 1..3, or early shade beside the traversal when there is one cohort
@@ -143,10 +147,15 @@ struct DynScene {
 }  // namespace ptd
 
 // pt_api.hip: the checks and the geometry of a render call; the per-launch camera constants
+int pt_check_params(const PtParams* prm);                        // the parameter ranges alone (prm not NULL), the error text set
 int pt_fill_params(const PtCamera* cam, const PtParams* prm, ptd::DevParams& d);
 void pt_fill_camera(const PtCamera* cam, ptd::DevCamera& c);
 
 extern "C" {
+// pt_api.hip
+int64_t pt_job_work_bytes(const ptd::DevParams& d);      // d_work of a render of d
+bool pt_has_light(const PtScene* s);                     // false: PT_ERR_NO_LIGHT is due, the error text set
+int pt_run_job(PtScene* s, ptd::WfJob& job, bool traceEvents, bool traceStat, float* d_tiles);      // the one way into the queue-driven pipeline
 // pt_kernels.hip
 hipError_t ptk_render_units(const ptd::DevScene*, const ptd::DevCamera*, const ptd::DevParams*, float*, unsigned int*, void*, int, int, hipStream_t);
 hipError_t ptk_sum_passes(const float*, int, long long, float*, hipStream_t);

@@ -105,6 +105,25 @@ PT_DEV f3 camera_origin(const ViewTable& views, const DevParams& prm, uint32_t s
     return f3(o.x, o.y, o.z);
 }
 
+// The caller's own rays in place of a camera (pt_render_rays): ray i takes the place of a pixel, work unit u = pass * n_tiles_local + group,
+// group g = rays 64 g .. 64 g + 63, n_tiles_local = ceil(n / 64).  The origin table is the caller's RAY8 buffer itself (org.xyz | dir.x,
+// dir.yz | reserved | tmax: two float4 per ray), read where a sample restarts; like ViewTable it is an argument of its own kernels only.
+struct RayTable {
+    const float4* rays;
+};
+PT_DEV f3 camera_origin(const RayTable& t, const DevParams& prm, uint32_t sid)
+{
+    const uint32_t unit = (uint32_t)prm.unit_base + (sid >> 6);
+    const float4 o = t.rays[2 * (size_t)((unit % (uint32_t)prm.n_tiles_local) * 64u + (sid & 63u))];
+    return f3(o.x, o.y, o.z);
+}
+
+// t_max of a stream's primary ray where wf_drain traces it again (a time-sliced traversal still pending at the hand-over): the camera
+// paths' constant, or what the caller gave the ray (wf_init_rays left it in ray_o[0].w, and only a shaded bounce overwrites that)
+template <class CAM>
+PT_DEV float primary_tmax(const CAM&, const WfBuf&, uint32_t, uint32_t) { return 999999.f; }
+PT_DEV float primary_tmax(const RayTable&, const WfBuf& b, uint32_t sid, uint32_t flags) { return (flags & F_PRIMARY) ? b.ray_o[0][sid].w : 999999.f; }
+
 // StartRender prologue for one pixel & pass (srcs/pathtracer.cu:70-74): seeds the RNG, draws the
 // jittered camera direction and queues the camera ray, whose hit all samples of the pass share.
 PT_DEV void init_stream(const DevCamera& cam, const DevParams& prm, const WfBuf& b, uint32_t slot, int px, int py, int pass)
@@ -123,6 +142,25 @@ PT_DEV void init_stream(const DevCamera& cam, const DevParams& prm, const WfBuf&
     b.ray_o[0][slot] = make_float4(cam.pos[0], cam.pos[1], cam.pos[2], 999999.f);
     b.ray_d[0][slot] = make_float4(d0.x, d0.y, d0.z, -__builtin_inff());
     b.hit[0][slot] = make_float2(0.f, __int_as_float(kNotReady));      // the camera ray: emitted, not traced yet
+    for (int k = 1; k < kRayKinds; k++) b.hit[k][slot] = make_float2(0.f, __int_as_float(-1));
+}
+
+// The same prologue for a ray of the caller's: the seed is given, the two jitter draws are made and dropped (a ray taken from a camera
+// pixel then reproduces that pixel), and the primary ray is (org, dir) up to tmax.  Fills what init_stream fills.
+PT_DEV void init_ray_stream(const DevParams& prm, const WfBuf& b, uint32_t slot, const f3& org, const f3& dir, float tmax, uint32_t seed)
+{
+    Rng rng;
+    rng.init((uint64_t)(int64_t)(int32_t)seed);
+    (void)rng.uniform(); (void)rng.uniform();
+    b.rng0[slot] = make_uint4(rng.x0, rng.x1, rng.x2, rng.x3);
+    b.rng1[slot] = make_uint4(rng.x4, rng.d, ((uint32_t)prm.spp_per_pass << 16), F_PATH | F_PRIMARY);
+    b.weight[slot] = make_float4(1.f, 1.f, 1.f, 0.f);
+    b.rad[slot] = make_float4(0.f, 0.f, 0.f, 1.f);
+    b.pix[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
+    b.dir0[slot] = make_float4(dir.x, dir.y, dir.z, 0.f);
+    b.ray_o[0][slot] = make_float4(org.x, org.y, org.z, tmax);
+    b.ray_d[0][slot] = make_float4(dir.x, dir.y, dir.z, -__builtin_inff());
+    b.hit[0][slot] = make_float2(0.f, __int_as_float(kNotReady));      // the primary ray: emitted, not traced yet
     for (int k = 1; k < kRayKinds; k++) b.hit[k][slot] = make_float2(0.f, __int_as_float(-1));
 }
 

@@ -102,9 +102,9 @@ PT_DEV void block_append(const bool (&e)[N], const uint32_t (&id)[N], uint32_t* 
 }
 
 // ---------------------------------------------------------------------------------------
-// wf_init, wf_init_list, wf_init_views: StartRender prologue for every stream (pathtracer.cu:70-74).
+// wf_init, wf_init_list, wf_init_views, wf_init_rays: StartRender prologue for every stream (pathtracer.cu:70-74).
 // This is the only place of the pipeline that turns a stream into a pixel: from here on a stream is its slot, so wf_trace, wf_shade
-// and wf_drain are the same for all three.  The kernels differ in `place` alone: it turns (local tile, pass relative to the job's
+// and wf_drain are the same for all of them.  The three camera kernels differ in `place` alone: it turns (local tile, pass relative to the job's
 // first) into the stream's camera, its tile of the frame and its pass.  TILE_TEST: a tile beyond the frame is a dead stream.
 // ---------------------------------------------------------------------------------------
 template <bool TILE_TEST, class Place>
@@ -167,6 +167,39 @@ void wf_init_views(DevScene sc, DevParams prm, WfBuf b, uint32_t nStreams, const
     init_streams<false>(sc, prm, b, nStreams, [&](uint32_t lt, int pass_rel, int& tile, int& pass) -> DevCamera {
         const uint32_t view = lt / tilesPerView;
         tile = (int)(lt % tilesPerView); pass = firstPass[view] + pass_rel; return cams[view]; });
+}
+
+// the caller's rays (pt_render_rays): no camera and no pixel.  Stream -> unit -> (group g of 64 rays, pass relative to the job's first);
+// ray i = 64 g + lane is live iff i < nRays.  Seed: seed_i + pass * seedStride in wrapping 32-bit arithmetic, seed_i = raySeed[i], or i
+// when raySeed is null.  The ray is queued by class like a camera ray; the padding lanes of the last group are dead streams.
+__global__ __launch_bounds__(256)
+void wf_init_rays(DevScene sc, DevParams prm, WfBuf b, uint32_t nStreams, const float4* __restrict__ rays, const int32_t* __restrict__ raySeed,
+                  uint32_t seedStride, uint32_t nRays)
+{
+    const uint32_t sid = blockIdx.x * 256u + threadIdx.x;
+    bool live = false, shortRay = false;
+    if (sid < nStreams) {
+        const uint32_t unit = (uint32_t)prm.unit_base + (sid >> 6);
+        const uint32_t i = (unit % (uint32_t)prm.n_tiles_local) * 64u + (sid & 63u);
+        const uint32_t pass = (uint32_t)prm.first_pass + unit / (uint32_t)prm.n_tiles_local;
+        live = i < nRays;
+        if (live) {
+            const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];      // org.xyz dir.x | dir.yz reserved tmax
+            const f3 org(r0.x, r0.y, r0.z), dir(r0.w, r1.x, r1.y);
+            init_ray_stream(prm, b, sid, org, dir, r1.w, (raySeed ? (uint32_t)raySeed[i] : i) + pass * seedStride);
+            shortRay = ray_is_short(sc, org, dir, r1.w);
+        } else {
+            b.staging[3 * (size_t)sid + 0] = 0.f; b.staging[3 * (size_t)sid + 1] = 0.f; b.staging[3 * (size_t)sid + 2] = 0.f;
+        }
+    }
+    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1: the last entry of a queue array
+    const bool e[kLists] = {live, live && !shortRay, false, false, shortRay, false, false};
+    uint32_t* const c[kLists] = {&b.cnt[0].nActive, &b.cnt[0].nRays[0][0], &b.cnt[0].nRays[1][0], &b.cnt[0].nRays[2][0],
+                                 &b.cnt[0].nRays[0][kShortWord], &b.cnt[0].nRays[1][kShortWord], &b.cnt[0].nRays[2][kShortWord]};
+    uint32_t* const l[kLists] = {b.active[0], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
+    const uint32_t ids[kLists] = {sid, sid, sid, sid, sid, sid, sid};
+    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
+    block_append<kLists>(e, ids, c, l, top);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -565,8 +598,9 @@ PT_DEV float2 load_hit(const float2* p)
     return make_float2(__uint_as_float((uint32_t)v), __uint_as_float((uint32_t)(v >> 32)));
 }
 
-// Cam: a DevCamera, or the ViewTable of a batch of views (pt_render_views) — all that differs is where a restarted camera ray takes
-// its origin from (pt_stream.h: camera_origin).  A batch is built for 4 waves per SIMD only, the default shape (PTAMD_SW does not apply to it).
+// Cam: a DevCamera, the ViewTable of a batch of views (pt_render_views) or the RayTable of the caller's rays (pt_render_rays) — all that
+// differs is where a restarted camera ray takes its origin from (pt_stream.h: camera_origin).  A batch and a ray set are built for 4 waves
+// per SIMD only, the default shape (PTAMD_SW does not apply to them).
 template <int WAVES, bool TWO, int PHASE = 0, bool MARK = false, class Cam = DevCamera>
 __global__ __launch_bounds__(WAVES * 256, WAVES)
 void wf_shade(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int slotOut, int slotClear, int listIn)
@@ -695,7 +729,7 @@ void wf_drain(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int list
                         const float4 ao = b.ray_o[2][sid], ad = b.ray_d[2][sid];
                         org = f3(ao.x, ao.y, ao.z); dir = f3(ad.x, ad.y, ad.z); bestT = ao.w; stopBelow = ad.w;
                     } else if (kind == 1) { org = st.shO; dir = st.shD; bestT = st.shTmax; stopBelow = shadow_stop_t(st.shO, st.shTmax); }
-                    else { org = st.pathO; dir = st.pathD; bestT = 999999.f; stopBelow = -__builtin_inff(); }
+                    else { org = st.pathO; dir = st.pathD; bestT = primary_tmax(cam, b, sid, st.flags); stopBelow = -__builtin_inff(); }
                     ray_setup(dir, inv, cscale, degenerate);
                     bestPrim = -1; cur = 0; sp = 0;
                 }
@@ -716,15 +750,15 @@ void wf_drain(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int list
             float t; const int prim = trace_closest<false>(sc, f3(ao.x, ao.y, ao.z), f3(ad.x, ad.y, ad.z), ao.w, stack, t, ts); hitA = make_float2(t, __int_as_float(prim));
         }
         if (st.flags & F_SHADOW) { float t; const int prim = trace_closest<false>(sc, st.shO, st.shD, st.shTmax, stack, t, ts); hitS = make_float2(t, __int_as_float(prim)); }
-        if (st.flags & F_PATH) { float t; const int prim = trace_closest<false>(sc, st.pathO, st.pathD, 999999.f, stack, t, ts); hitP = make_float2(t, __int_as_float(prim)); }
+        if (st.flags & F_PATH) { float t; const int prim = trace_closest<false>(sc, st.pathO, st.pathD, primary_tmax(cam, b, sid, st.flags), stack, t, ts); hitP = make_float2(t, __int_as_float(prim)); }
         }
         if (shade_step(sc, cam, prm, b, sid, st, hitP, hitS, hitA)) break;
     }
     write_mean(b, prm, sid, st);
 }
 
-// The wf_shade instantiation for one step: every one the pipeline launches is named here, 12 for one camera and 8 for a batch of views
-// (4 waves per SIMD only).  The early phases and every launch with marks run the default shape.
+// The wf_shade instantiation for one step: every one the pipeline launches is named here, 12 for one camera and 8 each for a batch of
+// views and for a ray set (4 waves per SIMD only).  The early phases and every launch with marks run the default shape.
 template <class Cam>
 static auto shade_kernel(int waves, bool two, int phase, bool mark) -> void (*)(DevScene, Cam, DevParams, WfBuf, int, int, int, int)
 {
@@ -943,10 +977,13 @@ static hipError_t cohort_pipeline(const ptd::WfJob& job, WfCohort& co)
     const size_t nStreams = (size_t)prm.n_units * 64;
     if ((e = hipMemsetAsync(b.cnt, 0, 3 * kWfSlotBytes, stream)) != hipSuccess) return e;
     const int nb = (int)((nStreams + 255) / 256);
-    // a batch of views (viewCams != nullptr; cam is then nullptr): its own init kernel, and the views instantiations of wf_shade / wf_drain below
-    const bool batch = job.viewCams != nullptr;
+    // a batch of views (viewCams != nullptr; cam is then nullptr): its own init kernel, and the views instantiations of wf_shade / wf_drain below;
+    // the caller's rays (rays8 != nullptr; cam is nullptr too) likewise
+    const bool batch = job.viewCams != nullptr, ownRays = job.rays8 != nullptr;
     const ViewTable views{job.viewOrg, (uint32_t)prm.n_tiles_total};
-    if (batch) hipLaunchKernelGGL(wf_init_views, dim3(nb), dim3(256), 0, stream, *job.scene, prm, b, (uint32_t)nStreams, job.viewCams, job.viewFirstPass, views.tilesPerView);
+    const RayTable rayTab{job.rays8};
+    if (ownRays) hipLaunchKernelGGL(wf_init_rays, dim3(nb), dim3(256), 0, stream, *job.scene, prm, b, (uint32_t)nStreams, job.rays8, job.raySeed, (uint32_t)job.seedStride, job.nRays);
+    else if (batch) hipLaunchKernelGGL(wf_init_views, dim3(nb), dim3(256), 0, stream, *job.scene, prm, b, (uint32_t)nStreams, job.viewCams, job.viewFirstPass, views.tilesPerView);
     else if (job.tileList) hipLaunchKernelGGL(wf_init_list, dim3(nb), dim3(256), 0, stream, *job.scene, *job.cam, prm, b, (uint32_t)nStreams, job.tileList);
     else hipLaunchKernelGGL(wf_init, dim3(nb), dim3(256), 0, stream, *job.scene, *job.cam, prm, b, (uint32_t)nStreams);
     const int ovfStride = job.traceBlocks * 256;
@@ -996,9 +1033,10 @@ static hipError_t cohort_pipeline(const ptd::WfJob& job, WfCohort& co)
             if (timed) (void)hipEventRecord(co.trace_ev[3 * it + 1], stream);
             const dim3 sg((liveBound + shadeThreads - 1) / shadeThreads), sb(shadeThreads);
             const bool twoRounds = job.shadeRounds >= 0 ? (job.shadeRounds != 0) : (liveBound < trStreams);
-            // one launch for every instantiation of wf_shade (a batch: the views ones, 4 waves per SIMD whatever PTAMD_SW says)
+            // one launch for every instantiation of wf_shade (a batch or a ray set: their own, 4 waves per SIMD whatever PTAMD_SW says)
             auto shade = [&](int phase, hipStream_t s, dim3 g, dim3 blk) {
-                if (batch) hipLaunchKernelGGL(shade_kernel<ViewTable>(4, twoRounds, phase, marks), g, blk, 0, s, *job.scene, views, prm, b, sIn, sOut, sClr, it & 1);
+                if (ownRays) hipLaunchKernelGGL(shade_kernel<RayTable>(4, twoRounds, phase, marks), g, blk, 0, s, *job.scene, rayTab, prm, b, sIn, sOut, sClr, it & 1);
+                else if (batch) hipLaunchKernelGGL(shade_kernel<ViewTable>(4, twoRounds, phase, marks), g, blk, 0, s, *job.scene, views, prm, b, sIn, sOut, sClr, it & 1);
                 else hipLaunchKernelGGL(shade_kernel<DevCamera>(shadeWaves, twoRounds, phase, marks), g, blk, 0, s, *job.scene, *job.cam, prm, b, sIn, sOut, sClr, it & 1);
             };
             if (early) {
@@ -1026,7 +1064,8 @@ static hipError_t cohort_pipeline(const ptd::WfJob& job, WfCohort& co)
             int spread = 0;
             while (spread < tn.drainSpread && ((size_t)co.h_cnt[0] << (spread + 1)) <= drainLanes) spread++;
             const int db = (int)((((size_t)co.h_cnt[0] << spread) + kBlockThreads - 1) / kBlockThreads);
-            if (batch) hipLaunchKernelGGL((quadWalk ? wf_drain<true, ViewTable> : wf_drain<false, ViewTable>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, views, prm, b, it % 3, it & 1, spread);
+            if (ownRays) hipLaunchKernelGGL((quadWalk ? wf_drain<true, RayTable> : wf_drain<false, RayTable>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, rayTab, prm, b, it % 3, it & 1, spread);
+            else if (batch) hipLaunchKernelGGL((quadWalk ? wf_drain<true, ViewTable> : wf_drain<false, ViewTable>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, views, prm, b, it % 3, it & 1, spread);
             else hipLaunchKernelGGL((quadWalk ? wf_drain<true> : wf_drain<false>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, *job.cam, prm, b, it % 3, it & 1, spread);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;

@@ -151,6 +151,10 @@ API = [
     ("pt_dbg_scene_array", C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
     ("pt_trace_rays", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     ("pt_trace_rays_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
+    ("pt_rays_floats", C.c_int64, [C.c_int64]),
+    ("pt_rays_work_bytes", C.c_int64, [C.POINTER(PtParams), C.c_int64]),
+    ("pt_render_rays", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
+    ("pt_render_rays_host", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P]),
 ]
 
 # pt_dbg_scene_array: name -> (which, dtype of the download)
@@ -570,6 +574,52 @@ class Scene:
         out = (hits[:, 0].view(torch.float32), hits[:, 1])
         return out + (surf,) if surface else out
 
+    def render_rays_device(self, d_rays_ptr, n_rays, prm, d_rgb_ptr, d_work_ptr, d_seed_ptr=0, seed_stride=None, stream_ptr=0):
+        """Device-resident radiance along n_rays RAY8 records (raw device pointers: rays_floats(n) floats of output, rays_work_bytes(prm,
+        n) bytes of scratch, d_seed_ptr 0 = ray i is seeded with i), enqueued on the given stream; blocks until the render has drained.
+        seed_stride defaults to n_rays (include/pt_api.h: pt_render_rays)."""
+        n = int(n_rays)
+        _check(lib().pt_render_rays(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_seed_ptr or None), n, n if seed_stride is None else int(seed_stride),
+                                    C.byref(prm), C.c_void_p(d_rgb_ptr), C.c_void_p(d_work_ptr), C.c_void_p(stream_ptr)), "pt_render_rays")
+
+    def render_rays(self, rays, prm, seeds=None, seed_stride=None, stream_ptr=0):
+        """Radiance along the caller's own rays (include/pt_api.h: pt_render_rays): ray i takes the place of a pixel.  rays: (n, 8)
+        float32 RAY8 records, org.xyz dir.xyz 0 tmax, directions of unit length.  seeds: None (ray i is seeded with i) or n int32;
+        pass k adds k * seed_stride, which defaults to n.  Returns (n, 3) float32, the sum over prm.passes passes of the per-pass means.
+        A numpy array goes through pt_render_rays_host (synchronous) and returns a numpy array.  A torch float32 tensor on the scene's
+        device is used in place (data_ptr(); seeds then a torch int32 tensor there, or None): the render runs on stream_ptr and the
+        result is a torch tensor on that device, valid once the stream has passed the call."""
+        if isinstance(rays, np.ndarray):
+            r = np.ascontiguousarray(rays, np.float32)
+            if r.ndim != 2 or r.shape[1] != 8:
+                raise PtError(f"render_rays: rays has shape {r.shape}, want (n, 8)")
+            n = r.shape[0]
+            sd = None
+            if seeds is not None:
+                sd = np.ascontiguousarray(seeds, np.int32).reshape(-1)
+                if sd.size != n:
+                    raise PtError(f"render_rays: {sd.size} seeds for {n} rays")
+            out = np.zeros((n, 3), np.float32)
+            _check(lib().pt_render_rays_host(self._h, _ptr(r), _ptr(sd) if sd is not None else None, n, n if seed_stride is None else int(seed_stride),
+                                             C.byref(prm), _ptr(out)), "pt_render_rays_host")
+            return out
+        if not (hasattr(rays, "data_ptr") and hasattr(rays, "is_contiguous")):
+            raise PtError("render_rays: rays must be a torch tensor or a numpy array")
+        if str(rays.dtype) != "torch.float32" or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+            raise PtError(f"render_rays: rays must be contiguous float32 of shape (n, 8), got {rays.dtype} {tuple(rays.shape)}")
+        if rays.device.type != "cuda" or rays.device.index != self.device:
+            raise PtError(f"render_rays: rays is on {rays.device}, the scene is on device {self.device}")
+        n = rays.shape[0]
+        if seeds is not None:
+            if not hasattr(seeds, "data_ptr") or str(seeds.dtype) != "torch.int32" or not seeds.is_contiguous() or seeds.numel() != n or seeds.device != rays.device:
+                raise PtError(f"render_rays: seeds must be a contiguous int32 tensor of {n} elements on {rays.device}")
+        import torch
+        with torch.cuda.device(rays.device):
+            rgb = torch.empty(rays_floats(n), dtype=torch.float32, device=rays.device)
+            work = torch.empty(rays_work_bytes(prm, n), dtype=torch.uint8, device=rays.device)
+        self.render_rays_device(rays.data_ptr(), n, prm, rgb.data_ptr(), work.data_ptr(), seeds.data_ptr() if seeds is not None else 0, seed_stride, stream_ptr)
+        return rgb[:3 * n].view(n, 3)
+
     def dbg_array(self, name):
         """pt_dbg_scene_array: one device array of the scene as a flat numpy array (SCENE_ARRAYS; layouts: csrc/pt_device.h)."""
         which, dt = SCENE_ARRAYS[name]
@@ -636,6 +686,54 @@ def views_work_bytes(cam, prm, n_views):
     if n < 0:
         raise PtError(lib().pt_last_error().decode())
     return n
+
+
+def rays_floats(n_rays):
+    n = lib().pt_rays_floats(int(n_rays))
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def rays_work_bytes(prm, n_rays):
+    n = lib().pt_rays_work_bytes(C.byref(prm), int(n_rays))
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def camera_rays(cam, pass_index, device=0):
+    """The rays a camera's pass casts, for Scene.render_rays: (rays (H * W, 8) float32 in pixel order, row-major, seeds (H * W,) int32,
+    seed_stride).  Directions are the jittered ones of that pass (pt_dbg_pixel_dir, on the GPU), seeds are py * W + px and the stride is
+    W * H, so render_rays(rays, params(passes=1, first_pass=pass_index), seeds, seed_stride) is that pass of render(cam, ...) bit for bit."""
+    W, H = cam.W, cam.H
+    py, px = np.divmod(np.arange(W * H, dtype=np.int32), np.int32(W))
+    out8 = dbg_pixel_dir(cam, np.stack([px, py, np.full(W * H, int(pass_index), np.int32)], 1), device)
+    rays = np.zeros((W * H, 8), np.float32)
+    rays[:, 0:3] = np.array(cam.pos[:], np.float32)
+    rays[:, 3:6] = out8[:, 2:5]
+    rays[:, 7] = 999999.0
+    return rays, (py * np.int32(W) + px).astype(np.int32), W * H
+
+
+def equirect_rays(pos, W, H):
+    """A 360 x 180 degree panorama from `pos` as (H * W, 8) float32 RAY8 records, row-major.  Pixel (x, y) looks along azimuth
+    phi = 2 pi (x + 0.5 - W / 2) / W and polar angle theta = pi (y + 0.5) / H from +y: direction (sin theta sin phi, cos theta,
+    -sin theta cos phi), of unit length.  The middle of the image looks down -z (exactly the centre pixel when W and H are odd), x grows
+    to the right (+x), row 0 is nearest +y.  tmax = 999999, the camera path's."""
+    W, H = int(W), int(H)
+    if W < 1 or H < 1:
+        raise PtError(f"equirect_rays: {W}x{H}")
+    phi = 2.0 * np.pi * (np.arange(W, dtype=np.float64) + 0.5 - W / 2.0) / W
+    theta = np.pi * (np.arange(H, dtype=np.float64) + 0.5) / H
+    st, ct = np.sin(theta)[:, None], np.cos(theta)[:, None]
+    d = np.stack([st * np.sin(phi)[None, :], np.broadcast_to(ct, (H, W)), -st * np.cos(phi)[None, :]], -1)
+    d /= np.sqrt((d * d).sum(-1, keepdims=True))
+    rays = np.zeros((H * W, 8), np.float32)
+    rays[:, 0:3] = np.asarray(pos, np.float32).reshape(3)
+    rays[:, 3:6] = d.reshape(-1, 3)
+    rays[:, 7] = 999999.0
+    return rays
 
 
 def _tile_list(tiles):

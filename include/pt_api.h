@@ -576,6 +576,9 @@ PT_API int32_t pt_load_obj(const char* path, float scale, const float translate[
  * Parity hooks: run single device functions of the integrator on the GPU so tests can
  * compare them with the oracle record by record (host pointers in and out).
  * Record layouts are those of oracle/pt_oracle.h (RAY8, HIT(29 f), BXDF in 28 f / out 12 f).
+ * The HIT record's u and v (floats 2, 3) are HitResult::u / v of the reference: the triangle's vertex u, v (PtTriangle u0 .. v2)
+ * under the barycentric weights of the shading frame, 0 for a sphere.  (They were 0 for every hit before scenes kept the vertex u, v
+ * on the device; the same holds for the surface records of pt_trace_rays.)
  * -------------------------------------------------------------------------------- */
 PT_API int  pt_dbg_raycast(PtScene* s, const float* rays8, int32_t n, float* out_hits29, int32_t* out_prim);
 PT_API int  pt_dbg_bxdf(int32_t device, int32_t lobe, const float* in28, int32_t n, float* out12);

@@ -12,6 +12,8 @@ TEST INFRASTRUCTURE.  Two kinds of fixture are written:
                the GPU tests run where the oracle build is unavailable.
  * ref_bxdf / ref_raycast / ref_nee / ref_image_*_b8.npz  inputs + outputs of oracle/_ref/ptref_int, the REAL reference's integrator
                headers (include/CudaUtil.cuh, include/Bxdf.cuh) as host C++ behind oracle/curand_shim.h — gen_integrator() below.
+ * ref_attr.npz the same binary on scenes_util.attribute_scene (per-vertex frames and materials, glass triangles, eight lights, ties,
+               slivers) — gen_attr() below.
  * anchors.json the three image means recorded in SURVEY.md Appendix A (measured by the
                survey on the reference's own source) — reproduced here with o_set_libm(0).
 """
@@ -27,7 +29,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "pathtrace-on-cuda_amd"))
 import oracle_lib as O  # noqa: E402
 import ptamd  # noqa: E402
-from scenes_util import bxdf_inputs, jittered_grid, random_rays10, random_tris48, random_spheres16, scene_rays8, test_spheres  # noqa: E402
+from scenes_util import ATTR_RAY_SETS, attr_nee_rows, attribute_rays, attribute_scene, leaving_parents, leaving_rays, bxdf_inputs, jittered_grid, random_rays10, random_tris48, random_spheres16, scene_rays8, test_spheres  # noqa: E402
 import query_ref  # noqa: E402
 
 G = os.path.join(ROOT, "tests", "golden")
@@ -229,6 +231,41 @@ def gen_integrator():
         print(f, os.path.getsize(os.path.join(G, f + ".npz")), "bytes")
 
 
+ATTR_SEED = 7
+ATTR_N_RAYS = 2000
+
+
+def gen_attr(seed=ATTR_SEED):
+    """ref_attr.npz: what the REAL reference's integrator (oracle/_ref/ptref_int, contract mode) answers on scenes_util.attribute_scene
+    with the test spheres: HIT records of the four ray sets, one NEE table, one 64 x 64 frame of 2 passes x 8 spp.  Scene, rays and NEE
+    rows are regenerated from the seed by the tests (scenes_util.load_ref_attr); their sha256 is stored, results only otherwise."""
+    if not O.have_ref_int():
+        raise SystemExit("oracle/_ref/ptref_int missing: run `make -C oracle ref` first")
+    prims, groups = attribute_scene(seed)
+    nodes, tris, _ = O.bvh_build(prims)
+    sph = test_spheres()
+    rays = attribute_rays(prims, groups, seed + 1, ATTR_N_RAYS)
+    out = {"seed": seed, "lat_lon": 12, "n_rays": ATTR_N_RAYS, "prims_sha256": np.array(sha(prims)), "spheres": sph}
+    for name in ATTR_RAY_SETS:
+        if name == "leaving":
+            rays[name] = leaving_rays(*leaving_parents(rays, out["hits_scene"], out["hits_aimed"]), seed + 2)
+        for mode in (0, 1):      # RayCast reaches no libm function besides sqrt: both modes, one answer
+            hits = O.ref_int_raycast(nodes, tris, sph, rays[name], mode)
+            assert mode == 0 or np.array_equal(hits.view(np.uint32), prev.view(np.uint32))
+            prev = hits
+        out[f"hits_{name}"], out[f"rays_sha256_{name}"] = hits, np.array(sha(rays[name]))
+        print(f"ref_attr {name}: {int(hits[:, 0].sum())} of {len(hits)} rays hit")
+    in5 = attr_nee_rows(np.concatenate([out["hits_scene"], out["hits_aimed"]]), seed + 3)
+    nee = [O.ref_int_nee(nodes, tris, sph, in5, mode) for mode in (0, 1)]
+    assert np.array_equal(nee[0].view(np.uint32), nee[1].view(np.uint32))
+    out.update(nee_in5_sha256=np.array(sha(in5)), nee_out12=nee[1], nee_cols=np.array(O.NEE_REF_COLS))
+    print("ref_attr nee: lit rows", int((nee[1][:, 8:11].sum(1) > 0).sum()), "of", len(in5))
+    img = O.ref_int_render(nodes, tris, sph, O.make_camera(64, 64), 2, 8, 1)
+    out.update(image=img, passes=2, spp=8, max_bounce=8)
+    np.savez_compressed(os.path.join(G, "ref_attr.npz"), **out)
+    print("ref_attr: image mean", img.mean(dtype=np.float64), os.path.getsize(os.path.join(G, "ref_attr.npz")), "bytes")
+
+
 def main():
     os.makedirs(G, exist_ok=True)
     if not O.have_ref():
@@ -243,6 +280,9 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "integrator":
         gen_integrator()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "attr":
+        gen_attr()
         return
     if len(sys.argv) > 1 and sys.argv[1] == "camera_u8":
         gen_camera_u8()
@@ -303,6 +343,7 @@ def main():
                             spheres=np.zeros((0, 16), np.float32) if sph is None else sph)
         print(name, "image mean", img.mean(dtype=np.float64), "hits", int((prim >= 0).sum()))
     gen_integrator()      # after the oracle_*.npz files: it takes their rays
+    gen_attr()
     print("golden fixtures written to", G)
 
 

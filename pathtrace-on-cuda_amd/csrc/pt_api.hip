@@ -487,7 +487,7 @@ int pt_dbg_raycast(PtScene* s, const float* rays8, int32_t n, float* out_hits29,
 {
     if (!s || !rays8 || n < 0 || !out_hits29 || !out_prim) { pt_set_error("pt_dbg_raycast: bad argument"); return PT_ERR_INVALID; }
     return with_buffers(s->device, rays8, (size_t)n * 32, out_hits29, (size_t)n * 29 * 4, out_prim, (size_t)n * 4,
-                        [&](void* i, void* o, void* o2) { return ptk_dbg_raycast(&s->dev, (const float*)i, n, (float*)o, (int*)o2, nullptr); });
+                        [&](void* i, void* o, void* o2) { return ptk_dbg_raycast(&s->dev, s->uv.as<float>(), (const float*)i, n, (float*)o, (int*)o2, nullptr); });
 }
 int pt_dbg_bxdf(int32_t device, int32_t lobe, const float* in28, int32_t n, float* out12)
 {

@@ -160,7 +160,7 @@ int pt_run_job(PtScene* s, ptd::WfJob& job, bool traceEvents, bool traceStat, fl
 hipError_t ptk_render_units(const ptd::DevScene*, const ptd::DevCamera*, const ptd::DevParams*, float*, unsigned int*, void*, int, int, hipStream_t);
 hipError_t ptk_sum_passes(const float*, int, long long, float*, hipStream_t);
 hipError_t ptk_untile(const float*, int, int, int, int, int, long long, float*, hipStream_t);
-hipError_t ptk_dbg_raycast(const ptd::DevScene*, const float*, int, float*, int*, hipStream_t);
+hipError_t ptk_dbg_raycast(const ptd::DevScene*, const float* uv, const float*, int, float*, int*, hipStream_t);
 hipError_t ptk_dbg_bxdf(int, const float*, int, float*, hipStream_t);
 hipError_t ptk_dbg_rng(unsigned long long, int, uint32_t*, float*, hipStream_t);
 hipError_t ptk_dbg_math(const float*, int, float*, hipStream_t);

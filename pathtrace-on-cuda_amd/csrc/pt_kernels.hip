@@ -235,7 +235,7 @@ __global__ void untile(const float* __restrict__ gathered, int W, int H, int til
 // Parity hooks (pt_dbg_*): single device functions, one record per thread.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlockThreads)
-void dbg_raycast(DevScene sc, const float* __restrict__ rays8, int n, float* __restrict__ out29, int* __restrict__ out_prim)
+void dbg_raycast(DevScene sc, const float* __restrict__ uv, const float* __restrict__ rays8, int n, float* __restrict__ out29, int* __restrict__ out_prim)
 {
     __shared__ int lds_stack[kWavesPerBlock][kStackDepth * 64];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -250,7 +250,8 @@ void dbg_raycast(DevScene sc, const float* __restrict__ rays8, int n, float* __r
     if (prim < 0) { for (int k = 0; k < 29; k++) o[k] = 0.f; return; }
     Surf s;
     make_surf(sc, prim, t, org, dir, s);
-    o[0] = 1.f; o[1] = t; o[2] = 0.f; o[3] = 0.f; o[4] = s.fr.front ? 1.f : 0.f;
+    o[0] = 1.f; o[1] = t; o[4] = s.fr.front ? 1.f : 0.f;
+    hit_uv(sc, uv, prim, org, dir, o[2], o[3]);
     o[5] = s.p.x; o[6] = s.p.y; o[7] = s.p.z;
     o[8] = s.fr.n.x; o[9] = s.fr.n.y; o[10] = s.fr.n.z;
     o[11] = s.fr.t.x; o[12] = s.fr.t.y; o[13] = s.fr.t.z;
@@ -357,10 +358,10 @@ hipError_t ptk_untile(const float* gathered, int W, int H, int tiles_x, int n_ti
     return hipGetLastError();
 }
 
-hipError_t ptk_dbg_raycast(const ptd::DevScene* sc, const float* rays8, int n, float* out29, int* out_prim, hipStream_t stream)
+hipError_t ptk_dbg_raycast(const ptd::DevScene* sc, const float* uv, const float* rays8, int n, float* out29, int* out_prim, hipStream_t stream)
 {
     const int nb = (n + ptd::kBlockThreads - 1) / ptd::kBlockThreads;
-    if (nb > 0) hipLaunchKernelGGL(ptd::dbg_raycast, dim3(nb), dim3(ptd::kBlockThreads), 0, stream, *sc, rays8, n, out29, out_prim);
+    if (nb > 0) hipLaunchKernelGGL(ptd::dbg_raycast, dim3(nb), dim3(ptd::kBlockThreads), 0, stream, *sc, uv, rays8, n, out29, out_prim);
     return hipGetLastError();
 }
 hipError_t ptk_dbg_bxdf(int lobe, const float* in28, int n, float* out12, hipStream_t stream)

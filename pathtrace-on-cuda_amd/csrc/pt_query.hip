@@ -75,7 +75,7 @@ void query_rays(DevScene sc, const float4* __restrict__ rays, uint32_t n, float2
 
 // The HIT record of pt_dbg_raycast (29 floats) for every finished closest hit; zeros for a miss.
 __global__ __launch_bounds__(256)
-void query_surface(DevScene sc, const float4* __restrict__ rays, uint32_t n, const float2* __restrict__ hits, float* __restrict__ out29)
+void query_surface(DevScene sc, const float* __restrict__ uv, const float4* __restrict__ rays, uint32_t n, const float2* __restrict__ hits, float* __restrict__ out29)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
@@ -88,7 +88,8 @@ void query_surface(DevScene sc, const float4* __restrict__ rays, uint32_t n, con
     const float t = h.x;
     Surf s;
     make_surf(sc, prim, t, org, dir, s);
-    o[0] = 1.f; o[1] = t; o[2] = 0.f; o[3] = 0.f; o[4] = s.fr.front ? 1.f : 0.f;
+    o[0] = 1.f; o[1] = t; o[4] = s.fr.front ? 1.f : 0.f;
+    hit_uv(sc, uv, prim, org, dir, o[2], o[3]);
     o[5] = s.p.x; o[6] = s.p.y; o[7] = s.p.z;
     o[8] = s.fr.n.x; o[9] = s.fr.n.y; o[10] = s.fr.n.z;
     o[11] = s.fr.t.x; o[12] = s.fr.t.y; o[13] = s.fr.t.z;
@@ -103,7 +104,7 @@ void query_surface(DevScene sc, const float4* __restrict__ rays, uint32_t n, con
 
 // Enqueues one batch of n < 2^31 rays on `stream`: (t, prim) per ray, then the 29-float surface records if asked for.  quad: walk the
 // 4-wide tree (the caller has checked that it fits kQueryStack), else the binary one.
-static hipError_t launch_query(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, int any, int quad, PtRayHit* d_hits, float* d_surface29,
+static hipError_t launch_query(const ptd::DevScene& sc, const float* uv, const float* d_rays8, uint32_t n, int any, int quad, PtRayHit* d_hits, float* d_surface29,
                                hipStream_t stream)
 {
     using namespace ptd;
@@ -117,7 +118,7 @@ static hipError_t launch_query(const ptd::DevScene& sc, const float* d_rays8, ui
         if (any) hipLaunchKernelGGL((query_rays<true, false>), dim3(blocks), dim3(64), 0, stream, sc, rays, n, hits);
         else hipLaunchKernelGGL((query_rays<false, false>), dim3(blocks), dim3(64), 0, stream, sc, rays, n, hits);
     }
-    if (d_surface29) hipLaunchKernelGGL(query_surface, dim3((n + 255u) / 256u), dim3(256), 0, stream, sc, rays, n, (const float2*)hits, d_surface29);
+    if (d_surface29) hipLaunchKernelGGL(query_surface, dim3((n + 255u) / 256u), dim3(256), 0, stream, sc, uv, rays, n, (const float2*)hits, d_surface29);
     return hipGetLastError();
 }
 
@@ -147,7 +148,7 @@ int pt_trace_rays(PtScene* s, const float* d_rays8, int64_t n, int32_t mode, PtR
     const int64_t kBatch = (int64_t)1 << 30;      // rays per launch: ray numbers are 32-bit
     for (int64_t off = 0; off < n; off += kBatch) {
         const uint32_t m = (uint32_t)(n - off < kBatch ? n - off : kBatch);
-        HIPCHK(launch_query(s->dev, d_rays8 + off * 8, m, mode == PT_QUERY_ANY, quad, d_hits + off,
+        HIPCHK(launch_query(s->dev, s->uv.as<float>(), d_rays8 + off * 8, m, mode == PT_QUERY_ANY, quad, d_hits + off,
                               d_surface29 ? d_surface29 + off * 29 : nullptr, (hipStream_t)hip_stream));
     }
     return PT_OK;

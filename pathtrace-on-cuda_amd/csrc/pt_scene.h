@@ -16,6 +16,7 @@ struct PtScene {
     int device = 0;
     ptd::DevScene dev{};
     DevBuf arr[kSceneArrays];            // as uploaded; an empty array holds 16 bytes, kArrCore is null when the scene has no core box
+    DevBuf uv;                           // u0 v0 u1 v1 u2 v2 per triangle (reference order): HitResult::u / v of the HIT record (parity hook, surface pass of the queries)
     DevBuf unit_counter;
     DevBuf counters;
     DevBuf tile_list;                    // the tile numbers (int32) of the pt_render_tile_list call in flight (grown on demand)

@@ -234,6 +234,10 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
     src[kArrLeafbox] = host(accel.leafbox); src[kArrSurf] = host(surf); src[kArrLights] = host(lights); src[kArrSpheres] = host(sph);
     src[kArrCore] = host(core);
     if ((rc = upload_arrays(sc.get(), src)) != PT_OK) return rc;
+    std::vector<float> uv((size_t)n_tris * 6);
+    for (int i = 0; i < n_tris; i++) { const PtTriangle& t = tris[i]; const float c[6] = {t.u0, t.v0, t.u1, t.v1, t.u2, t.v2}; memcpy(&uv[(size_t)i * 6], c, sizeof(c)); }
+    HIPCHK(sc->uv.upload(uv.data(), uv.size() * sizeof(float)));
+    sc->bytes += (int64_t)sc->uv.held();
     if ((rc = create_resources(sc.get())) != PT_OK) return rc;
     apply_defaults(sc.get(), n_tris, emitOk);
     sc->dev.n_quad = accel.n_quad; sc->dev.quad_depth = accel.quad_depth;

@@ -97,6 +97,27 @@ PT_DEV void make_surf(const DevScene& sc, int prim, float t, const f3& org, cons
     }
 }
 
+// HitResult::u / v of the HIT record (Triangle::hit, CudaPrimitive.cuh:142-143: the vertices' u, v under the weights of the frame;
+// a sphere's are 0).  uv: u0 v0 u1 v1 u2 v2 per triangle, reference order.  Only the parity hook and the queries' surface pass read them.
+PT_DEV void hit_uv(const DevScene& sc, const float* __restrict__ uv, int prim, const f3& org, const f3& dir, float& hu, float& hv)
+{
+    hu = 0.f; hv = 0.f;
+    if (prim >= sc.n_tris) return;
+    const float4* __restrict__ q = sc.surf + 12 * (size_t)prim;
+    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+    const f3 V0(q0.x, q0.y, q0.z), E1(q0.w, q1.x, q1.y), E2(q1.z, q1.w, q2.x);
+    const f3 T = org - V0;
+    const f3 P = cross(dir, E2);
+    const f3 Q = cross(T, E1);
+    const float invDet = 1.f / dot(P, E1);
+    const float u = dot(P, T) * invDet;
+    const float v = dot(Q, dir) * invDet;
+    const float w = 1.f - v - u;
+    const float* __restrict__ c = uv + 6 * (size_t)prim;
+    hu = w * c[0] + v * c[2] + u * c[4];
+    hv = w * c[1] + v * c[3] + u * c[5];
+}
+
 // ---------------------------------------------------------------------------------------
 // Next-event estimation pieces and the pixel direction, shared by the render kernels and by the parity hooks
 // (pt_dbg_nee / pt_dbg_pixel_dir) that compare them with the oracle row by row.

@@ -123,6 +123,260 @@ def test_spheres():
     ], np.float32)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# attribute_scene: per-vertex frames and materials, glass and mirror triangles, eight lights, exact ties, slivers, zero areas
+# ---------------------------------------------------------------------------------------------------------------------------------
+ATTR_RAY_SETS = ("scene", "aimed", "leaving", "axis")
+MESH_CLASSES = ("delta_glass", "rough_glass", "v1_opacity", "mirror", "plain")
+
+
+def _unit64(v):
+    return v / np.sqrt((v * v).sum(-1, keepdims=True))
+
+
+def _cornell_walls():
+    """The five walls of pt_scene_gen(0) (host/scenes.cpp: cornell), without its light: 10 triangles."""
+    s = 20.0
+    quads = [((-s, 0, s), (s, 0, s), (s, 0, -s), (-s, 0, -s), (.73, .73, .73)),                    # floor
+             ((-s, 2 * s, -s), (s, 2 * s, -s), (s, 2 * s, s), (-s, 2 * s, s), (.73, .73, .73)),    # ceiling
+             ((-s, 0, -s), (s, 0, -s), (s, 2 * s, -s), (-s, 2 * s, -s), (.73, .73, .73)),          # back
+             ((-s, 0, s), (-s, 0, -s), (-s, 2 * s, -s), (-s, 2 * s, s), (.65, .05, .05)),          # left
+             ((s, 0, -s), (s, 0, s), (s, 2 * s, s), (s, 2 * s, -s), (.12, .45, .15))]              # right
+    out = []
+    for a, b, c, d, albedo in quads:
+        out.append(make_prims([a, a], [b, c], [c, d], albedo=albedo))
+    return np.concatenate(out)
+
+
+def _standin_positions(n, R=10.0, C=(0.0, 11.0, 0.0)):
+    """The triangles of pt_scene_gen(1, n)'s bumpy sphere (host/scenes.cpp: standin), in its order.  Evaluated in float64 and rounded
+    once, so that the bits do not depend on which float32 sine a numpy build has (they are within an ulp or two of pt_scene_gen's)."""
+    def P(i, j):
+        th = 3.14159265 * i / n
+        ph = 6.2831853 * j / n
+        r = R * (1.0 + 0.08 * np.sin(7.0 * th) * np.cos(5.0 * ph))
+        return (C[0] + r * np.sin(th) * np.cos(ph), C[1] + r * np.cos(th), C[2] + r * np.sin(th) * np.sin(ph))
+    A, B, Cc = [], [], []
+    for i in range(n):
+        for j in range(n):
+            a, b, c, d = P(i, j), P(i + 1, j), P(i + 1, j + 1), P(i, j + 1)
+            if i > 0:
+                A.append(a); B.append(d); Cc.append(c)
+            if i < n - 1:
+                A.append(a); B.append(c); Cc.append(b)
+    return tuple(np.array(x, np.float64).astype(np.float32) for x in (A, B, Cc))
+
+
+def _facing(a, b, c, want):
+    """The triangle (a, b, c), wound so that its geometric normal points along `want`."""
+    a, b, c = (np.asarray(x, np.float64) for x in (a, b, c))
+    return (a, b, c) if np.dot(np.cross(b - a, c - a), want) > 0 else (a, c, b)
+
+
+def attribute_scene(seed, lat_lon=12):
+    """A seeded scene with what the three scenes of pt_scene_gen lack.  Returns ((n, 84) float32 Primitive records, groups): groups maps
+    an ingredient to the indices of its primitives in the record array (input order), and "mesh_<class>" to those of a mesh class.
+
+    walls    the five walls of pt_scene_gen(0), flat frames, no light.
+    mesh     the stand-in of pt_scene_gen(1, lat_lon).  Per VERTEX, independently: a normal pointing roughly away from the centre
+             (noise 0.45, so that rays near grazing see a shading normal facing away), tangent and bitangent built on it, albedo,
+             specular, metallic, roughness, opacity, u, v.  On a fifth of the triangles the three normals are twice as long.  Vertex 0's
+             material is then set by the triangle's class (MESH_CLASSES; Triangle::hit copies mat0 alone): delta glass (opacity 0,
+             roughness 0), rough glass (opacity 0, roughness 0.05 .. 0.5), opaque with opacity 0 on vertex 1 only, mirror (opacity 1,
+             roughness < 1e-2), plain (opacity 1, roughness 0.02 .. 1); about a quarter each for the first three.
+    lights   eight, one after each eighth of the other primitives behind the walls: seven emissive triangles of areas 50 .. 0.005 and
+             seven colours (the floor light faces up, the smallest has 0.1 edges), and one whose SECOND vertex alone is emissive.
+    dups     40 exact copies of mesh triangles with another albedo: exact ties in t.
+    slivers  30 triangles 10 long and 1e-3 wide, nearly along an axis, above the mesh.
+    zero     two zero-area triangles (collinear vertices; two equal vertices), not emissive; their flat normal is NaN."""
+    rs = np.random.RandomState(seed)
+    walls = _cornell_walls()
+
+    # ---- mesh ----
+    a, b, c = _standin_positions(lat_lon)
+    m = a.shape[0]
+    mesh = make_prims(a, b, c).reshape(m, 3, 28)
+    centre = np.array([0.0, 11.0, 0.0])
+    for k, p in enumerate((a, b, c)):
+        nrm = _unit64(_unit64(p.astype(np.float64) - centre) + 0.45 * rs.standard_normal((m, 3)))
+        tan = _unit64(np.cross(nrm, rs.standard_normal((m, 3))))
+        mesh[:, k, V_NRM:V_NRM + 3] = nrm
+        mesh[:, k, V_TAN:V_TAN + 3] = tan
+        mesh[:, k, V_BIT:V_BIT + 3] = np.cross(nrm, tan)
+        mesh[:, k, V_UV:V_UV + 2] = rs.uniform(0, 1, (m, 2))
+        mesh[:, k, V_ALB:V_ALB + 3] = rs.uniform(0.05, 1.0, (m, 3))
+        mesh[:, k, V_SPEC:V_SPEC + 3] = rs.uniform(0.01, 0.2, (m, 3))
+        mesh[:, k, V_OPA] = rs.uniform(0, 1, m)
+        mesh[:, k, V_MET] = rs.uniform(0, 1, m)
+        mesh[:, k, V_ROU] = rs.uniform(0.02, 1.0, m)
+        mesh[:, k, V_U] = rs.uniform(0, 1, m)
+        mesh[:, k, V_V] = rs.uniform(0, 1, m)
+    mesh[::3, 0, V_MET] = 0.0
+    mesh[1::3, 0, V_MET] = 1.0
+    mesh[::5, 0, V_SPEC:V_SPEC + 3] = 0.04
+    long_normals = rs.uniform(0, 1, m) < 0.2
+    mesh[long_normals, :, V_NRM:V_NRM + 3] *= np.float32(2)
+    u = rs.uniform(0, 1, m)
+    cls = np.select([u < 0.25, u < 0.5, u < 0.75, u < 0.85], [0, 1, 2, 3], 4)
+    rough_glass = rs.uniform(0.05, 0.5, m).astype(np.float32)
+    mirror = rs.uniform(0.0, 0.009, m).astype(np.float32)
+    mesh[cls == 0, 0, V_OPA], mesh[cls == 0, 0, V_ROU] = 0.0, 0.0
+    mesh[cls == 1, 0, V_OPA], mesh[cls == 1, 0, V_ROU] = 0.0, rough_glass[cls == 1]
+    mesh[cls == 2, 0, V_OPA], mesh[cls == 2, 1, V_OPA], mesh[cls == 2, 2, V_OPA] = 1.0, 0.0, 1.0
+    mesh[(cls == 2) & (np.arange(m) % 2 == 0), 0, V_ROU] = 1.0
+    mesh[cls == 3, 0, V_OPA], mesh[cls == 3, 0, V_ROU] = 1.0, mirror[cls == 3]
+    mesh[cls == 4, 0, V_OPA] = 1.0
+    mesh = mesh.reshape(m, 84)
+
+    # ---- duplicates ----
+    pick = np.sort(rs.choice(m, 40, replace=False))
+    dups = mesh[pick].copy().reshape(40, 3, 28)
+    dups[:, :, V_ALB:V_ALB + 3] = rs.uniform(0.05, 1.0, (40, 1, 3)).astype(np.float32) * np.float32([0.2, 1.0, 0.2])
+    dups = dups.reshape(40, 84)
+
+    # ---- slivers ----
+    A, B, Cc = [], [], []
+    for i in range(30):
+        ax = i % 3
+        p0 = np.array([rs.uniform(-17, 7), rs.uniform(23, 35), rs.uniform(-17, 7)])
+        e_long = np.zeros(3); e_long[ax] = 10.0
+        e_long += rs.uniform(-1e-3, 1e-3, 3)
+        side = np.cross(e_long, rs.standard_normal(3))
+        side *= 1e-3 / np.sqrt((side * side).sum())
+        q = _facing(p0, p0 + e_long, p0 + 0.5 * e_long + side, np.array([0.0, 20.0, 60.0]) - p0)      # towards the reference camera
+        A.append(q[0]); B.append(q[1]); Cc.append(q[2])
+    slivers = make_prims(np.array(A), np.array(B), np.array(Cc), albedo=(0.9, 0.3, 0.7))
+
+    # ---- zero area ----
+    with np.errstate(invalid="ignore", divide="ignore"):
+        zero = make_prims(np.float32([[-6, 24, 5], [7, 25, -4]]), np.float32([[-4.5, 24, 5], [7, 25, -4]]), np.float32([[-3, 24, 5], [8, 26, -3]]),
+                          albedo=(0.5, 0.5, 0.5))
+
+    # ---- lights ----
+    down, up = np.array([0.0, -1.0, 0.0]), np.array([0.0, 1.0, 0.0])
+    spec = [   # vertices, facing, emittance
+        (((-5, 39.98, -5), (5, 39.98, -5), (5, 39.98, 5)), down, (15, 15, 15)),                        # area 50
+        (((8, 39.98, -15), (8.8, 39.98, -15), (8.8, 39.98, 5)), down, (20, 12, 4)),                    # 8
+        (((-19.98, 5, -10), (-19.98, 5, 10), (-19.98, 5.4, 10)), np.array([1.0, 0, 0]), (4, 10, 25)),  # 4, on the left wall
+        (((11, 0.02, 10), (14, 0.02, 10), (14, 0.02, 13)), up, (6, 30, 6)),                            # 4.5, on the floor, facing up
+        (((6, 26, 4), (6.1, 26, 4), (6, 26, 4.1)), down, (4000, 3000, 2000)),                          # 0.005
+        (((-5, 30, -19.98), (5, 30, -19.98), (5, 30.2, -19.98)), np.array([0.0, 0, 1]), (30, 5, 30)),  # 1, on the back wall
+        (((-13, 18, 6), (-12, 18.3, 6.8), (-13.2, 19, 6.4)), np.array([1.0, -1.0, 1.0]), (25, 25, 5)),  # about 0.5, tilted
+        (((-15, 34, -2), (-5, 34, -2), (-5, 34, -1.4)), down, (0, 0, 0)),                              # 3: only vertex 1 is emissive
+    ]
+    lights = []
+    for verts, want, emit in spec:
+        q = _facing(*verts, want)
+        lights.append(make_prims(*(np.float32([x]) for x in q), albedo=(0, 0, 0), emit=emit))
+    lights = np.concatenate(lights)
+    lights[7].reshape(3, 28)[1, V_EMIT:V_EMIT + 3] = (5.0, 5.0, 5.0)
+
+    # ---- input order: walls, then the rest in eight parts with a light behind each ----
+    body = np.concatenate([mesh, dups, slivers, zero])
+    tag = np.concatenate([np.full(m, 1), np.full(40, 2), np.full(30, 3), np.full(2, 4)])
+    parts, tags = [walls], [np.zeros(len(walls), int)]
+    for k, idx in enumerate(np.array_split(np.arange(len(body)), 8)):
+        parts += [body[idx], lights[k:k + 1]]
+        tags += [tag[idx], np.array([5])]
+    prims = np.ascontiguousarray(np.concatenate(parts), np.float32)
+    tags = np.concatenate(tags)
+    groups = {name: np.nonzero(tags == t)[0] for t, name in enumerate(("walls", "mesh", "dups", "slivers", "zero", "lights"))}
+    for k, name in enumerate(MESH_CLASSES):
+        groups["mesh_" + name] = groups["mesh"][cls == k]
+    groups["dup_of"] = groups["mesh"][pick]                  # the mesh triangle each duplicate copies
+    groups["dark_light"] = groups["lights"][7:8]             # mat0 emittance 0
+    return prims, groups
+
+
+def _prim_pos(prims, idx):
+    return prims[idx].reshape(-1, 3, 28)[:, :, V_POS:V_POS + 3]
+
+
+def _aim(org, tgt):
+    """RAY8 records from org to tgt: dir = (tgt - org) in float32 times a power of two that brings its components into [-1, 1], so the
+    ray passes through tgt as exactly as float32 subtraction allows."""
+    org, tgt = np.asarray(org, np.float32), np.asarray(tgt, np.float32)
+    d = (tgt - org).astype(np.float32)
+    e = np.frexp(np.abs(d).max(1))[1]                        # exact: |d|max * 2^-e is in [0.5, 1)
+    d = np.ldexp(d, -e[:, None]).astype(np.float32)
+    n = len(org)
+    return np.concatenate([org, d, np.zeros((n, 1), np.float32), np.full((n, 1), 999999.0, np.float32)], 1).astype(np.float32)
+
+
+def attribute_rays(prims, groups, seed, n=2000):
+    """The seeded ray sets of attribute_scene, n RAY8 records each, directions with components in [-1, 1]:
+    scene    scene_rays8.
+    aimed    from outside (off the front of the target triangle, inside the room), aimed in float32 at vertices, edge midpoints and
+             interior points of the duplicated triangles, the slivers, the mesh and the walls.
+    axis     axis-aligned; the origin shares one or two coordinates with a wall or with a vertex (every face of a leaf box is a vertex
+             coordinate).
+    `leaving_rays` makes the fourth set from the hit records of `scene` and `aimed` (leaving_parents)."""
+    rs = np.random.RandomState(seed)
+    out = {"scene": scene_rays8(n, rs)}
+
+    pool = np.concatenate([groups["dups"], groups["dup_of"], groups["slivers"], groups["slivers"], groups["mesh"], groups["walls"]])
+    idx = pool[np.arange(n) % len(pool)]
+    v = _prim_pos(prims, idx).astype(np.float64)
+    w = rs.dirichlet((1, 1, 1), n)
+    w[::8] = (1, 0, 0); w[1::8] = (0, 1, 0); w[2::8] = (0, 0, 1); w[3::8] = (0.5, 0.5, 0); w[4::8] = (0, 0.5, 0.5); w[5::8] = (0.5, 0, 0.5)
+    tgt = (v * w[:, :, None]).sum(1).astype(np.float32)
+    tgt[::8], tgt[1::8], tgt[2::8] = v[::8, 0], v[1::8, 1], v[2::8, 2]       # the vertices themselves, bit for bit
+    nrm = _unit64(np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]))
+    off = _unit64(nrm + 0.6 * rs.standard_normal((n, 3)))
+    off = np.where(((off * nrm).sum(1) < 0.2)[:, None], nrm, off)
+    org = tgt + off * rs.uniform(4, 14, (n, 1))
+    org = np.clip(org, [-19.5, 0.5, -19.5], [19.5, 39.5, 19.5]).astype(np.float32)
+    out["aimed"] = _aim(org, tgt)
+
+    verts = prims.reshape(-1, 3, 28)[:, :, V_POS:V_POS + 3].reshape(-1, 3)
+    verts = verts[np.isfinite(verts).all(1)]
+    pv = verts[rs.randint(0, len(verts), n)]
+    qv = verts[rs.randint(0, len(verts), n)]
+    ax = rs.randint(0, 3, n)
+    sign = np.where(rs.uniform(0, 1, n) < 0.5, -1.0, 1.0).astype(np.float32)
+    org = np.stack([rs.uniform(-19, 19, n), rs.uniform(1, 39, n), rs.uniform(-19, 19, n)], 1).astype(np.float32)
+    kind = np.arange(n) % 4
+    o1, o2 = (ax + 1) % 3, (ax + 2) % 3
+    r = np.arange(n)
+    org[r, o1] = np.where(kind != 3, pv[r, o1], org[r, o1])              # one coordinate of a vertex ...
+    org[r, o2] = np.where(kind == 1, qv[r, o2], org[r, o2])              # ... a second one of another vertex ...
+    org[r, o2] = np.where(kind == 2, pv[r, o2], org[r, o2])              # ... or the same vertex: the ray runs through it
+    wall = np.float32([[-20, 20], [0, 40], [-20, 20]])
+    wsel = kind == 3                                                      # on a wall's plane: along it, or starting on it
+    along = rs.uniform(0, 1, n) < 0.5
+    org[r, o1] = np.where(wsel & along, wall[o1, rs.randint(0, 2, n)], org[r, o1])
+    start_on = wsel & ~along
+    near = np.where(sign > 0, wall[ax, 0], wall[ax, 1])                  # the wall behind the ray: start on its plane, or half a unit off it
+    org[r, ax] = np.where(start_on, near, near + sign * np.float32(0.5))
+    d = np.zeros((n, 3), np.float32)
+    d[r, ax] = sign
+    out["axis"] = np.concatenate([org, d, np.zeros((n, 1), np.float32), np.full((n, 1), 999999.0, np.float32)], 1).astype(np.float32)
+    return out
+
+
+def leaving_parents(rays, hits_scene, hits_aimed):
+    """The rays `leaving_rays` starts from, and their HIT records: the first half of the `scene` set and the first half of `aimed`."""
+    h = len(rays["scene"]) // 2
+    return np.concatenate([rays["scene"][:h], rays["aimed"][:h]]), np.concatenate([hits_scene[:h], hits_aimed[:h]])
+
+
+def leaving_rays(rays, hits, seed):
+    """Rays leaving the hit points of `rays` (their HIT records: `hits`) along +-n * 1e-4, n the record's normal: even rows start just
+    under the surface and go in, odd rows start just above it and go out; where the parent ray missed, the row repeats the parent."""
+    rs = np.random.RandomState(seed)
+    n = len(rays)
+    out = np.ascontiguousarray(rays, np.float32).copy()
+    hit = hits[:, 0] > 0
+    side = np.where(np.arange(n) % 2 == 0, np.float32(-1), np.float32(1))[:, None]
+    nrm = hits[:, 8:11]
+    org = (hits[:, 5:8] + side * nrm * np.float32(1e-4)).astype(np.float32)
+    d = (side * nrm + np.float32(0.7) * rs.standard_normal((n, 3)).astype(np.float32)).astype(np.float32)
+    d = (d / np.sqrt((d * d).sum(1, keepdims=True))).astype(np.float32)
+    ok = hit & np.isfinite(org).all(1) & np.isfinite(d).all(1)
+    out[ok, 0:3], out[ok, 3:6], out[ok, 7] = org[ok], d[ok], 999999.0
+    return out
+
+
 def bxdf_inputs(n, rs, lobe):
     """Random BxDF table rows (columns 0..23 of pt_dbg_bxdf / o_bxdf's in28) and their seed words (columns 24..25)."""
     nrm = rs.standard_normal((n, 3)); nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
@@ -164,3 +418,46 @@ def load_ref_bxdf(golden_dir, lobe):
     glibc[g[f"glibc_idx_{lobe}"]] = g[f"glibc_rows_{lobe}"]
     assert in28.shape[0] == contract.shape[0]
     return in28, contract, glibc, n
+
+
+ATTR_NEE_ROWS = 2048
+
+
+def attr_tri_to_input(prims, tris88):
+    """For every TRI record of a BVH built from `prims`, the index of its primitive in the input order.  Keyed by the nine vertex floats
+    and vertex 0's albedo (a duplicate differs from its original in the albedo alone)."""
+    key = {}
+    for i, p in enumerate(np.ascontiguousarray(prims, np.float32)):
+        key[np.concatenate([p[0:3], p[28:31], p[56:59], p[V_ALB:V_ALB + 3]]).tobytes()] = i
+    assert len(key) == len(prims)
+    return np.array([key[np.concatenate([t[0:9], t[54:57]]).tobytes()] for t in np.ascontiguousarray(tris88, np.float32)])
+
+
+def attr_nee_rows(hits, seed, n=ATTR_NEE_ROWS):
+    """o_nee's in5 from HIT records: the hit points of the first 70 % of the rows that hit, then hit points pushed 1e-3 under their surface."""
+    rs = np.random.RandomState(seed)
+    h = hits[(hits[:, 0] > 0) & np.isfinite(hits[:, 5:11]).all(1)]
+    assert len(h) >= n
+    k = (7 * n) // 10
+    pts = np.concatenate([h[:k, 5:8], (h[k:n, 5:8] - np.float32(1e-3) * h[k:n, 8:11]).astype(np.float32)]).astype(np.float32)
+    seeds = rs.randint(0, 2 ** 32, (n, 2), dtype=np.uint64).astype(np.uint32)
+    return np.concatenate([pts, seeds.view(np.float32)], 1)
+
+
+def load_ref_attr(golden_dir):
+    """tests/golden/ref_attr.npz -> (fixture, prims, groups, {set: rays8}, NEE rows in5).  Scene and rays are regenerated from the recorded seed and
+    held against their recorded sha256; the `leaving` set and the NEE rows are derived from the fixture's own HIT records."""
+    import hashlib
+    import os
+    g = np.load(os.path.join(golden_dir, "ref_attr.npz"))
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()      # noqa: E731
+    seed, n = int(g["seed"]), int(g["n_rays"])
+    prims, groups = attribute_scene(seed, int(g["lat_lon"]))
+    assert sha(prims) == str(g["prims_sha256"]), "attribute_scene drifted"
+    rays = attribute_rays(prims, groups, seed + 1, n)
+    rays["leaving"] = leaving_rays(*leaving_parents(rays, g["hits_scene"], g["hits_aimed"]), seed + 2)
+    for name in ATTR_RAY_SETS:
+        assert sha(rays[name]) == str(g[f"rays_sha256_{name}"]), f"ray set {name} drifted"
+    in5 = attr_nee_rows(np.concatenate([g["hits_scene"], g["hits_aimed"]]), seed + 3)
+    assert sha(in5) == str(g["nee_in5_sha256"]), "NEE rows drifted"
+    return g, prims, groups, rays, in5

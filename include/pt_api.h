@@ -356,7 +356,7 @@ PT_API int  pt_render_converge(PtScene* s, const PtCamera* cam, const PtParams* 
  *   `hip_stream` once (until the list has been read from h_tiles); the copy itself is asynchronous on it.
  * pt_render_window: host convenience like pt_render, synchronous; h_rgb[(y1 - y0) * (x1 - x0) * 3] is the window, bit for bit
  *   pt_render(...)[y0:y1, x0:x1].  prm->rank / world are ignored as pt_render ignores them.
- * No list variants of pt_render_aov (full frame, 2.9 ms at 1080p), of the denoiser or of the moments calls.
+ * No list variants of pt_render_aov (full frame, 2.9 ms at 1080p) or of the denoiser; the moments of a list: the adaptive section below.
  * -------------------------------------------------------------------------------- */
 PT_API int64_t pt_tile_list_floats(int32_t n_tiles);                /* 192 * n_tiles, or -1 */
 PT_API int64_t pt_tile_list_work_bytes(const PtCamera* cam, const PtParams* prm, int32_t n_tiles);
@@ -544,6 +544,72 @@ PT_API int  pt_render_rays(PtScene* s, const float* d_rays8, const int32_t* d_se
                            const PtParams* prm, float* d_rgb, void* d_work, void* hip_stream);
 PT_API int  pt_render_rays_host(PtScene* s, const float* h_rays8, const int32_t* h_seed, int64_t n_rays, int32_t seed_stride,
                                 const PtParams* prm, float* h_rgb /* n_rays * 3 */);
+
+/* ----------------------------------------------------------------------------------
+ * Adaptive sampling: every tile rendered until ITS error estimate is met (new: the reference gives every pixel the same passes).
+ * Opt-in: every call above is as it was.  pt_render_converge stops the whole frame on one figure; here the moments calls meet
+ * pt_render_tile_list, so the passes go where the noise is (csrc/pt_stats.hip).
+ *
+ * "Frame tile layout" below = the layout of pt_render_tiles with rank 0 of world 1: tile t (row-major over the full frame) owns
+ *   floats 192 t .. 192 t + 191, pt_tiles_floats(cam, world 1) floats in all.  All buffers 16-byte aligned.
+ * pt_accumulate_tile_list: the list variant of pt_accumulate_passes.  d_work is the work buffer a pt_render_tile_list(cam, prm, list of
+ *   n_tiles) left behind (prm->passes x n_tiles x 192 means, pass-major, list order); entry i is folded into tile d_list[i] of d_sum /
+ *   d_m2 (frame tile layout), per float exactly the fold of pt_accumulate_passes with k = n_before + 1, ...: a tile's result is bit for
+ *   bit what pt_accumulate_passes gives it after a full-frame render of the same passes.  n_before = passes every LISTED tile holds so
+ *   far (0: the listed tiles are overwritten, not read); tiles not listed are not touched.  d_tile_passes (may be NULL): int32 per tile
+ *   of the frame, d_tile_passes[d_list[i]] = n_before + prm->passes.
+ * pt_tile_errors: one PtTileError per list entry (d_list NULL: tiles 0 .. n_tiles - 1 in order) from frame-layout moments of n_passes
+ *   passes.  A pixel is used if it lies inside W x H and its S and M2 are all finite; an in-frame pixel that is not used counts as
+ *   skipped.  Per used pixel, float32 as written: v_c = max(M2_c, 0) * n / (n - 1);
+ *     term = sqrt((v_r + v_g) + v_b) / (((|S_r| + |S_g|) + |S_b|) + 0.03f * n)      (the mean_rel_se term of pt_error_estimate)
+ *   The 64 terms of a tile (0.0 for a pixel not used), widened to float64, are summed in a fixed tree: for o = 32, 16, 8, 4, 2, 1,
+ *   pixel l < o adds pixel l + o (pixel = ty * 8 + tx).  mean_rel_se = sum / pixels in float64, 0 when pixels == 0.  No atomics: two
+ *   calls return the same bits.
+ * pt_finish_tiles: the frame of tiles with unequal pass counts.  Per float of the frame tile layout, n = d_tile_passes[tile], IEEE
+ *   float32, n converted to float once:  d_mean = S / n;  d_var = (max(M2, 0) * n) / (n - 1) (a NaN M2 stays NaN; n == 1 gives what
+ *   the formula gives).  A tile with n == 0 gets +0 in both.  Either output may be NULL, not both.
+ * The three calls take DEVICE pointers, are asynchronous on `hip_stream`, allocate nothing and read nothing back.  Checked before the
+ *   first HIP call, else PT_ERR_INVALID: NULL pointers, n_tiles < 1 or more than the frame has, n_before < 0, n_passes < 2,
+ *   prm->rank != 0 || prm->world != 1, a camera or params that pt_tiles_floats rejects, both outputs of pt_finish_tiles NULL.
+ *   The ENTRIES of d_list are the caller's responsibility, as the contents of any device buffer are: each must be a tile of the frame
+ *   and none may appear twice (an entry outside the frame is skipped by the fold and yields a zero record; a tile listed twice is
+ *   written by two threads).
+ *
+ * pt_render_adaptive: host convenience like pt_render_converge (whole frame, world = 1, synchronous).  The rule, in this order:
+ *   batch = prm->passes (>= 1, clamped to max_passes); min_passes is raised to 2; 2 <= min_passes <= max_passes, target >= 0 (not NaN)
+ *   and the seed limit of pt_render for prm->first_pass + max_passes are required.  The active list starts as all tiles, ascending;
+ *   done = 0.  Each round renders b = min(batch, max_passes - done) passes of the active list (pt_render_tile_list with first_pass =
+ *   prm->first_pass + done — every active tile holds exactly `done` passes), folds them (pt_accumulate_tile_list, n_before = done),
+ *   done += b; once done >= min_passes it takes pt_tile_errors of the active list for n_passes = done and drops every tile whose
+ *   mean_rel_se <= target (a NaN stays active), keeping the order.  It stops when the list is empty or done == max_passes.
+ *   h_accum_rgb[H*W*3] = S: every tile is bit for bit that tile of pt_render with passes = h_tile_passes[t] and the same first_pass.
+ *   h_mean_rgb (may be NULL) = the pt_finish_tiles mean, the frame to show: pt_tonemap_u8(mean, n, 1) and pt_denoise(..., sample_cnt = 1,
+ *   ...) take it as it is.  h_var_rgb (may be NULL) = the variance of S with each tile's own n.  h_tile_passes[tiles] (required) and
+ *   h_tile_err[tiles] (may be NULL; the error at the tile's last check) are row-major over the tile grid.
+ *   Deterministic: a tile's passes, seeds and fold do not depend on which other tiles are active, and the error of a tile is a fixed
+ *   tree over its own pixels, so the pass map is a function of the scene, the camera and the arguments alone.
+ *   A late round holds few tiles and is bound by launch latency (the pt_render_views section): the time saved trails the tile-passes
+ *   saved (the adaptive section, has the measurement).
+ * Out of scope: a tile-split or multi-GPU version, growing batches, dilating the active set to neighbours, adaptive views or rays,
+ * mode 0 (a list is always rendered by the queue-driven pipeline).
+ * -------------------------------------------------------------------------------- */
+typedef struct PtTileError { double mean_rel_se; int32_t pixels, skipped; } PtTileError;   /* 16 bytes */
+typedef struct PtAdaptiveReport {
+    int32_t rounds;                 /* list renders done */
+    int32_t tiles, tiles_converged; /* tiles of the frame; tiles that met the target (the rest stopped at max_passes) */
+    int64_t tile_passes;            /* sum over tiles of their passes: the work done, in tile-passes */
+    double  max_tile_err;           /* largest mean_rel_se over all tiles at their last check */
+} PtAdaptiveReport;
+
+PT_API int  pt_accumulate_tile_list(const void* d_work, const PtCamera* cam, const PtParams* prm, const int32_t* d_list, int32_t n_tiles,
+                                    int32_t n_before, float* d_sum, float* d_m2, int32_t* d_tile_passes /* may be NULL */, void* hip_stream);
+PT_API int  pt_tile_errors(const float* d_sum, const float* d_m2, const PtCamera* cam, const int32_t* d_list /* NULL: all */, int32_t n_tiles,
+                           int32_t n_passes, PtTileError* d_err, void* hip_stream);
+PT_API int  pt_finish_tiles(const float* d_sum, const float* d_m2, const int32_t* d_tile_passes, const PtCamera* cam,
+                            float* d_mean, float* d_var, void* hip_stream);
+PT_API int  pt_render_adaptive(PtScene* s, const PtCamera* cam, const PtParams* prm, double target, int32_t min_passes, int32_t max_passes,
+                               float* h_accum_rgb, float* h_mean_rgb, float* h_var_rgb, int32_t* h_tile_passes, double* h_tile_err,
+                               PtAdaptiveReport* report);
 
 /* ----------------------------------------------------------------------------------
  * (a12,a13) Output + camera helpers (host).

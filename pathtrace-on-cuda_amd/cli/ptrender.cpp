@@ -17,6 +17,7 @@ static void usage()
         "                [--glass-sphere] [--width W] [--height H] [--passes N] [--spp N] [--depth N]\n"
         "                [--lat-lon N] [--device D] [--no-progressive] [--raw FILE] [--denoise FILE.png] [--aov FILE]\n"
         "                [--target-error E [--max-passes N] [--variance FILE]] [--window X0,Y0,X1,Y1]\n"
+        "                [--adaptive E [--min-passes M] [--max-passes N] [--pass-map FILE] [--variance FILE]]\n"
         "                [--cam-pos X,Y,Z] [--cam-rot RX,RY,RZ] [--fov DEG] [--views FILE]\n"
         "                [--world N --rank R --id-file PATH [--job-tag T]]   (one process per GPU; rank 0 writes the frame;\n"
         "                 T = a number the ranks of this job share and other jobs do not, default: the parent process id)\n"
@@ -30,6 +31,11 @@ static void usage()
         "--window X0,Y0,X1,Y1: renders only the half-open pixel window [X0, X1) x [Y0, Y1) of the frame (the 8x8 tiles that overlap it);\n"
         "  temp.png, result.png and --raw are the window, pixel for pixel the crop of the full frame's.  Single process, and not with\n"
         "  --denoise, --aov or --target-error.\n"
+        "--adaptive E: renders every 8x8 tile in batches of --passes passes until the tile's own error estimate (the mean over its pixels of\n"
+        "  the relative standard error) is <= E, checked once --min-passes (default 2) are in, or --max-passes (default 8 batches) are in;\n"
+        "  prints the rounds and the tile-passes used.  result.png and --denoise show the mean frame (every tile divided by its own passes);\n"
+        "  --raw FILE: the sums, --variance FILE: their per-pixel variance (W*H*3 float32 each), --pass-map FILE: the passes of every tile\n"
+        "  (tiles_y x tiles_x int32).  Single process, and not with --target-error, --window or --views.\n"
         "--cam-pos X,Y,Z, --cam-rot RX,RY,RZ (degrees, as Camera::SetRotation), --fov DEG (vertical): the camera; defaults 0,20,60 /\n"
         "  0,90,0 / 45, the reference application's.\n"
         "--views FILE: renders a batch of cameras in one pipeline run.  Each line of FILE is `px py pz rx ry rz fov [first_pass]`\n"
@@ -70,6 +76,7 @@ int main(int argc, char** argv)
 {
     std::string scene = "cornell", obj, rawPath, denoisePath, aovPath, variancePath;
     double targetError = 0.0; int maxPasses = 0;
+    bool adaptive = false; double adaptiveTarget = 0.0; int minPasses = 0; std::string passMapPath;
     float objScale = 1.f; float objT[3] = {0, 0, 0};
     int W = 1920, H = 1080, passes = 8, spp = 64, depth = 8, latlon = 187, device = 0;
     bool glass = false, progressive = true;
@@ -97,6 +104,9 @@ int main(int argc, char** argv)
         else if (a == "--aov") aovPath = next();
         else if (a == "--target-error") targetError = atof(next());
         else if (a == "--max-passes") maxPasses = atoi(next());
+        else if (a == "--adaptive") { adaptive = true; adaptiveTarget = atof(next()); }
+        else if (a == "--min-passes") minPasses = atoi(next());
+        else if (a == "--pass-map") passMapPath = next();
         else if (a == "--variance") variancePath = next();
         else if (a == "--window") { if (sscanf(next(), "%d,%d,%d,%d", &win[0], &win[1], &win[2], &win[3]) != 4) { usage(); return 2; } windowed = true; }
         else if (a == "--cam-pos") { if (sscanf(next(), "%f,%f,%f", &camPos[0], &camPos[1], &camPos[2]) != 3) { usage(); return 2; } }
@@ -111,7 +121,10 @@ int main(int argc, char** argv)
         else { std::cerr << "unknown option " << a << "\n"; usage(); return 2; }
     }
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && idFile.empty())) { std::cerr << "--world N needs 0 <= --rank < N and --id-file PATH\n"; return 2; }
-    if ((maxPasses != 0 || !variancePath.empty()) && !(targetError > 0.0)) { std::cerr << "--max-passes and --variance need --target-error E > 0\n"; return 2; }
+    if (adaptive && (world > 1 || targetError > 0.0 || windowed || !viewsPath.empty())) { std::cerr << "--adaptive is single-process and does not go with --target-error, --window or --views\n"; return 2; }
+    if (adaptive && (!(adaptiveTarget >= 0.0) || minPasses < 0 || (maxPasses != 0 && (maxPasses < 2 || maxPasses < minPasses)))) { std::cerr << "--adaptive E needs E >= 0 and 2 <= --min-passes <= --max-passes\n"; return 2; }
+    if (!adaptive && (minPasses != 0 || !passMapPath.empty())) { std::cerr << "--min-passes and --pass-map need --adaptive E\n"; return 2; }
+    if (!adaptive && (maxPasses != 0 || !variancePath.empty()) && !(targetError > 0.0)) { std::cerr << "--max-passes and --variance need --target-error E > 0\n"; return 2; }
     if (targetError > 0.0 && (world > 1 || (maxPasses != 0 && maxPasses < 2))) { std::cerr << "--target-error is single-process and needs --max-passes >= 2\n"; return 2; }
     if (windowed && (world > 1 || !denoisePath.empty() || !aovPath.empty() || targetError > 0.0)) { std::cerr << "--window is single-process and does not go with --denoise, --aov or --target-error\n"; return 2; }
     if (windowed && (win[0] < 0 || win[1] < 0 || win[2] > W || win[3] > H || win[0] >= win[2] || win[1] >= win[3])) { std::cerr << "--window X0,Y0,X1,Y1 needs 0 <= X0 < X1 <= width and 0 <= Y0 < Y1 <= height\n"; return 2; }
@@ -148,10 +161,15 @@ int main(int argc, char** argv)
     tracer.device = device; tracer.progressive = progressive; tracer.raw_path = rawPath;
     tracer.denoise_path = denoisePath; tracer.aov_path = aovPath;
     tracer.target_error = targetError; tracer.max_passes = maxPasses; tracer.variance_path = variancePath;
+    tracer.adaptive = adaptive; tracer.adaptive_target = adaptiveTarget; tracer.min_passes = minPasses; tracer.pass_map_path = passMapPath;
     if (windowed) { tracer.window_x0 = win[0]; tracer.window_y0 = win[1]; tracer.window_x1 = win[2]; tracer.window_y1 = win[3]; }
     tracer.view_cameras = viewCams; tracer.view_first_pass = viewFirst;
     tracer.rank = rank; tracer.world = world; tracer.id_file = idFile; tracer.job_tag = jobTag;
     tracer.Render(camera, &bvh);
+    if (adaptive) {               // kernel_ms below would be the last round only
+        std::cout << "{\"tile_passes_done\": " << tracer.tile_passes_done << "}" << std::endl;
+        return 0;
+    }
     if (targetError > 0.0) {      // kernel_ms below would be the last batch only
         std::cout << "{\"passes_done\": " << tracer.passes_done << "}" << std::endl;
         return 0;

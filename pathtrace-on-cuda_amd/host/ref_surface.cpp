@@ -75,12 +75,13 @@ static void exportImage(Image& img, const float* raw, const char* path, int H, i
     std::cout << (img.WriteTo(path) ? "Export Success" : "Export failed") << std::endl;   // :114-121
 }
 
-static void write_raw(const std::string& path, const std::vector<float>& raw)
+template <class T>      // float or int32_t
+static void write_raw(const std::string& path, const std::vector<T>& raw)
 {
     if (path.empty()) return;
     const std::string tmp = path + ".tmp";
     FILE* f = fopen(tmp.c_str(), "wb");
-    const bool ok = f && fwrite(raw.data(), 4, raw.size(), f) == raw.size();
+    const bool ok = f && fwrite(raw.data(), sizeof(T), raw.size(), f) == raw.size();
     if (f) fclose(f);
     if (!ok || rename(tmp.c_str(), path.c_str()) != 0) std::cout << "Export failed (" << path << ")" << std::endl;
 }
@@ -146,6 +147,8 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
         else check(pt_render(scene, &cam, &p, out), "pt_render");
     };
     PtParams shown = params;      // the passes the frame holds: the export, the AOVs and the denoiser follow it
+    int shownDiv = 0;             // what the exported frame is divided by when that is not shown.passes (the adaptive mean frame: 1)
+    std::vector<float> mean;      // the adaptive mean frame
     const auto t0 = clk::now();
     last_render_ms = 0.0;
     if (world > 1) {
@@ -161,6 +164,26 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
         float ms = 0.f; pt_last_render_ms(scene, &ms); last_render_ms = ms;
         pt_comm_destroy(comm);
         if (rank != 0) { pt_scene_destroy(scene); return; }
+    } else if (adaptive) {
+        // every tile in batches of params.passes passes until its own error estimate reaches the target
+        const int cap = max_passes > 0 ? max_passes : 8 * params.passes;
+        const int tiles = ((W + 7) / 8) * ((H + 7) / 8);
+        std::vector<float> var(variance_path.empty() ? 0 : raw.size());
+        std::vector<int32_t> tilePasses((size_t)tiles);
+        mean.resize(raw.size());
+        PtAdaptiveReport rep;
+        check(pt_render_adaptive(scene, &cam, &params, adaptive_target, min_passes, cap, raw.data(), mean.data(), var.empty() ? nullptr : var.data(),
+                                 tilePasses.data(), nullptr, &rep), "pt_render_adaptive");
+        float ms = 0.f; pt_last_render_ms(scene, &ms); last_render_ms = ms;      // the last round
+        std::cout << "Adaptive : rounds " << rep.rounds << ", tile-passes " << rep.tile_passes << " of " << (long long)rep.tiles * cap << ", tiles converged "
+                  << rep.tiles_converged << " of " << rep.tiles << ", max tile error " << rep.max_tile_err << " (target " << adaptive_target << ")" << std::endl;
+        write_raw(variance_path, var);
+        write_raw(pass_map_path, tilePasses);
+        tile_passes_done = rep.tile_passes;
+        int most = 0;
+        for (int32_t n : tilePasses) most = n > most ? n : most;
+        shown.passes = most;      // the AOVs: the passes of the tiles rendered longest
+        shownDiv = 1;
     } else if (target_error > 0.0) {
         // batches of params.passes passes until the frame's own error estimate reaches the target
         const int cap = max_passes > 0 ? max_passes : 8 * params.passes;
@@ -192,7 +215,9 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
     }
     passes_done = shown.passes;
     std::cout << "Delta time : " << std::chrono::duration_cast<std::chrono::milliseconds>(clk::now() - t0).count() << " (ms)" << std::endl;
-    exportImage(img, raw.data(), "result.png", outH, outW, shown.passes);
+    const std::vector<float>& frame = shownDiv ? mean : raw;
+    const int div = shownDiv ? shownDiv : shown.passes;
+    exportImage(img, frame.data(), "result.png", outH, outW, div);
     write_raw(raw_path, raw);
     if (!denoise_path.empty() || !aov_path.empty()) {
         // the call's passes: first_pass .. first_pass + passes - 1, the same pixels the frame sums (whole frame, also in a split)
@@ -201,8 +226,8 @@ void PathTracer::Render(Camera& camera, BVH* bvh)
         write_raw(aov_path, aov);
         if (!denoise_path.empty()) {
             std::vector<float> den(raw.size());
-            check(pt_denoise_host(device, raw.data(), aov.data(), W, H, shown.passes, &denoise_params, den.data()), "pt_denoise_host");
-            exportImage(img, den.data(), denoise_path.c_str(), H, W, shown.passes);
+            check(pt_denoise_host(device, frame.data(), aov.data(), W, H, div, &denoise_params, den.data()), "pt_denoise_host");
+            exportImage(img, den.data(), denoise_path.c_str(), H, W, div);
         }
     }
     pt_scene_destroy(scene);

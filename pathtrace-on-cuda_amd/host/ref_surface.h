@@ -113,6 +113,16 @@ public:
     int max_passes = 0;
     std::string variance_path;
     int passes_done = 0;                    // passes in the frame of the last Render
+    // Adaptive sampling (new; include/pt_api.h: pt_render_adaptive), single process only and without a target_error, a window or views:
+    // when `adaptive` is set every 8x8 tile is rendered in batches of params.passes passes until ITS error estimate is <= adaptive_target
+    // (checked once min_passes are in) or max_passes (0 = 8 batches) are in.  result.png and the denoiser show the mean frame (each
+    // tile divided by its own passes); raw_path receives the sums, variance_path the per-pixel variance of them (W*H*3 float32 each) and
+    // pass_map_path the passes of every tile (tiles_y x tiles_x int32, row-major); one line reports the rounds and the work done.
+    bool adaptive = false;
+    double adaptive_target = 0.0;
+    int min_passes = 0;
+    std::string pass_map_path;
+    long long tile_passes_done = 0;         // tile-passes rendered by the last adaptive Render
     // Render region (new; include/pt_api.h: pt_render_window), single process only and without the denoiser, the AOVs or a target:
     // when window_x1 > window_x0 only the half-open pixel window is rendered (the 8x8 tiles that overlap it, not the frame) and
     // temp.png, result.png and raw_path hold the window — the pixels are those of the full frame's render, bit for bit.

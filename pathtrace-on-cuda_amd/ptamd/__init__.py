@@ -50,6 +50,18 @@ class PtErrorEstimate(C.Structure):
     _fields_ = [("rel_rms", C.c_double), ("mean_rel_se", C.c_double), ("pixels", C.c_int64), ("skipped", C.c_int64)]
 
 
+class PtTileError(C.Structure):
+    _fields_ = [("mean_rel_se", C.c_double), ("pixels", C.c_int32), ("skipped", C.c_int32)]
+
+
+class PtAdaptiveReport(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("tiles", C.c_int32), ("tiles_converged", C.c_int32), ("tile_passes", C.c_int64),
+                ("max_tile_err", C.c_double)]
+
+
+TILE_ERROR_DTYPE = np.dtype([("mean_rel_se", "<f8"), ("pixels", "<i4"), ("skipped", "<i4")])      # PtTileError as a numpy record
+
+
 class PtRayHit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_int32)]
 
@@ -134,6 +146,11 @@ API = [
     ("pt_error_estimate", C.c_int, [_P, _P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32, _P, C.POINTER(PtErrorEstimate), _P]),
     ("pt_render_converge", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_double, C.c_int32, _P, _P, C.POINTER(C.c_int32),
                                      C.POINTER(PtErrorEstimate)]),
+    ("pt_accumulate_tile_list", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    ("pt_tile_errors", C.c_int, [_P, _P, C.POINTER(PtCamera), _P, C.c_int32, C.c_int32, _P, _P]),
+    ("pt_finish_tiles", C.c_int, [_P, _P, _P, C.POINTER(PtCamera), _P, _P, _P]),
+    ("pt_render_adaptive", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_double, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                     C.POINTER(PtAdaptiveReport)]),
     ("pt_tile_list_floats", C.c_int64, [C.c_int32]),
     ("pt_tile_list_work_bytes", C.c_int64, [C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32]),
     ("pt_render_tile_list", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), _P, C.c_int32, _P, _P, _P]),
@@ -449,6 +466,22 @@ class Scene:
         _check(lib().pt_render_converge(self._h, C.byref(cam), C.byref(prm), float(target_rel_rms), int(max_passes), _ptr(rgb), _ptr(var),
                                         C.byref(done), C.byref(est)), "pt_render_converge")
         return rgb, var, done.value, _estimate_dict(est)
+
+    def render_adaptive(self, cam, prm, target, max_passes, min_passes=2):
+        """pt_render_adaptive: rounds of prm.passes passes over the tiles whose own error estimate (mean_rel_se over the tile's pixels)
+        is still above `target`, checked once min_passes are in, until no tile is left or max_passes are in.  Returns a dict:
+        rgb (H, W, 3) float32 = S, every tile the sum over ITS passes; mean (H, W, 3) = S / the tile's passes, the frame to show
+        (tonemap_u8(mean, 1)); var (H, W, 3) = the variance of S; tile_passes (tiles_y, tiles_x) int32; tile_err (tiles_y, tiles_x)
+        float64, the error at the tile's last check; report = dict(rounds, tiles, tiles_converged, tile_passes, max_tile_err)."""
+        ty, tx = (cam.H + TILE - 1) // TILE, (cam.W + TILE - 1) // TILE
+        rgb, mean, var = (np.zeros((cam.H, cam.W, 3), np.float32) for _ in range(3))
+        tile_passes, tile_err = np.zeros((ty, tx), np.int32), np.zeros((ty, tx), np.float64)
+        rep = PtAdaptiveReport()
+        _check(lib().pt_render_adaptive(self._h, C.byref(cam), C.byref(prm), float(target), int(min_passes), int(max_passes), _ptr(rgb), _ptr(mean),
+                                        _ptr(var), _ptr(tile_passes), _ptr(tile_err), C.byref(rep)), "pt_render_adaptive")
+        report = dict(rounds=rep.rounds, tiles=rep.tiles, tiles_converged=rep.tiles_converged, tile_passes=rep.tile_passes,
+                      max_tile_err=rep.max_tile_err)
+        return dict(rgb=rgb, mean=mean, var=var, tile_passes=tile_passes, tile_err=tile_err, report=report)
 
     def render_tile_list_device(self, cam, prm, tiles, d_tiles_ptr, d_work_ptr, stream_ptr=0):
         """Device-resident render of the listed tiles (global tile numbers, any order; raw device pointers: tile_list_floats(n)
@@ -851,6 +884,29 @@ def error_estimate(d_sum_ptr, d_m2_ptr, cam, prm, n_passes, d_scratch_ptr, strea
     _check(lib().pt_error_estimate(C.c_void_p(d_sum_ptr), C.c_void_p(d_m2_ptr), C.byref(cam), C.byref(prm), int(n_passes),
                                    C.c_void_p(d_scratch_ptr), C.byref(e), C.c_void_p(stream_ptr)), "pt_error_estimate")
     return _estimate_dict(e)
+
+
+def accumulate_tile_list(d_work_ptr, cam, prm, d_list_ptr, n_tiles, n_before, d_sum_ptr, d_m2_ptr, d_tile_passes_ptr=0, stream_ptr=0):
+    """pt_accumulate_tile_list on raw device pointers: folds the prm.passes per-pass means a render_tile_list_device of n_tiles tiles left
+    in d_work into the frame-layout moments S, M2 (tiles_floats(cam, world 1) floats each), list entry i into tile d_list[i] (int32 on the
+    device); n_before = passes the listed tiles hold so far; d_tile_passes (0 = none): int32 per tile, set to n_before + prm.passes."""
+    _check(lib().pt_accumulate_tile_list(C.c_void_p(d_work_ptr), C.byref(cam), C.byref(prm), C.c_void_p(d_list_ptr), int(n_tiles), int(n_before),
+                                         C.c_void_p(d_sum_ptr), C.c_void_p(d_m2_ptr), C.c_void_p(d_tile_passes_ptr or None), C.c_void_p(stream_ptr)),
+           "pt_accumulate_tile_list")
+
+
+def tile_errors(d_sum_ptr, d_m2_ptr, cam, d_list_ptr, n_tiles, n_passes, d_err_ptr, stream_ptr=0):
+    """pt_tile_errors on raw device pointers: one 16-byte PtTileError (TILE_ERROR_DTYPE) per list entry into d_err; d_list_ptr 0 = the
+    tiles 0 .. n_tiles - 1 in order."""
+    _check(lib().pt_tile_errors(C.c_void_p(d_sum_ptr), C.c_void_p(d_m2_ptr), C.byref(cam), C.c_void_p(d_list_ptr or None), int(n_tiles),
+                                int(n_passes), C.c_void_p(d_err_ptr), C.c_void_p(stream_ptr)), "pt_tile_errors")
+
+
+def finish_tiles(d_sum_ptr, d_m2_ptr, d_tile_passes_ptr, cam, d_mean_ptr=0, d_var_ptr=0, stream_ptr=0):
+    """pt_finish_tiles on raw device pointers: mean = S / n and variance of S per tile's own pass count n (frame tile layout; either
+    output may be 0, not both)."""
+    _check(lib().pt_finish_tiles(C.c_void_p(d_sum_ptr), C.c_void_p(d_m2_ptr), C.c_void_p(d_tile_passes_ptr), C.byref(cam),
+                                 C.c_void_p(d_mean_ptr or None), C.c_void_p(d_var_ptr or None), C.c_void_p(stream_ptr)), "pt_finish_tiles")
 
 
 class Comm:

@@ -51,8 +51,7 @@ int pt_fill_params(const PtCamera* cam, const PtParams* prm, ptd::DevParams& d)
     if (cam->W < 2 || cam->H < 2) { pt_set_error("frame %dx%d too small (W-1, H-1 divide, srcs/pathtracer.cu:35-36)", cam->W, cam->H); return PT_ERR_INVALID; }
     if (pt_check_params(prm)) return PT_ERR_INVALID;
     if (!ptd::seed_in_range(cam, prm->first_pass, prm->passes)) return PT_ERR_INVALID;
-    d.passes = prm->passes; d.spp_per_pass = prm->spp_per_pass; d.max_bounce = prm->max_bounce; d.rr_bounce = prm->rr_bounce;
-    d.rr_floor = prm->rr_floor; d.max_refract = prm->max_refract; d.first_pass = prm->first_pass;
+    ptd::path_params(prm, d);
     d.rank = prm->rank; d.world = prm->world;
     const ptd::TileGrid g = ptd::tile_grid(cam->W, cam->H, prm->world);
     d.tiles_x = g.tiles_x; d.tiles_y = g.tiles_y; d.n_tiles_total = g.total; d.n_tiles_local = g.per_rank;
@@ -102,21 +101,19 @@ bool pt_has_light(const PtScene* s)      // false: PT_ERR_NO_LIGHT, with the err
     return s->n_lights >= 1;
 }
 
-// The one way into the queue-driven pipeline (pt_wavefront.hip), for an entry point that has checked its arguments, set the device and filled in
-// what to render and from which pixels and cameras.  Lends the job the scene's resources and runs it — the pipeline polls the live-stream count,
+// The one way into the queue-driven pipeline (pt_wavefront.hip), for an entry point that has checked its arguments, made the scene's device current
+// and filled in what to render (prm, work, stream) and from which pixels and cameras (src).  Lends the job the scene's resources and runs it — the pipeline polls the live-stream count,
 // so this returns once the render has drained — then sums the passes into d_tiles.  traceEvents: record the per-launch events of
 // pt_enable_trace_timing.  traceStat: the PTAMD_TSTAT diagnostics apply (wf_trace counts its trips and the lanes they serve; pt_last_counters).
 int pt_run_job(PtScene* s, ptd::WfJob& job, bool traceEvents, bool traceStat, float* d_tiles)
 {
     const int slot = s->ev_count % PtScene::kEvRing;
-    job.device = s->device; job.scene = &s->dev; job.traceBlocks = kTraceBlocks;
-    job.h_poll = s->h_poll; job.xstreams = s->xstreams; job.ev_fork = s->ev_fork; job.ev_join = s->ev_join;
+    job.scene = &s->dev; job.traceBlocks = kTraceBlocks; job.lent = &s->wf;
     job.ev_begin = s->ev[slot][0]; job.ev_end = s->ev[slot][1];
     job.drainBelow = s->drain_below; job.shadeRounds = s->shade_rounds; job.earlyBelow = s->early_below;
     if (traceEvents && !s->trace_ev.empty()) { job.trace_ev = s->trace_ev.data(); job.trace_ev_triples = (int)s->trace_ev.size() / 3; }
-    s->trace_ev_per = job.trace_ev_triples / ptk_wf_cohorts((size_t)job.prm.n_units);
-    for (int k = 0; k < 4; k++) s->trace_ev_used[k] = 0;
-    job.trace_ev_used = s->trace_ev_used;
+    s->trace_ev_used = 0;
+    job.trace_ev_used = &s->trace_ev_used;
     if (traceStat && ptk_wf_trace_stat() != 0) {
         HIPCHK(hipMemsetAsync(s->counters.as<>(), 0, ptd::kStatBytes, job.stream));
         job.traceStat = s->counters.as<unsigned long long>();
@@ -136,14 +133,15 @@ int pt_render_tiles(PtScene* s, const PtCamera* cam, const PtParams* prm, float*
     ptd::DevParams& d = job.prm;
     int rc = pt_fill_params(cam, prm, d);
     if (rc) return rc;
-    ptd::DevCamera c;
+    job.src.kind = ptd::WfSource::kFrame;
+    ptd::DevCamera& c = job.src.frame.cam;
     pt_fill_camera(cam, c);
 
     hipStream_t stream = (hipStream_t)hip_stream;
     HIPCHK(hipSetDevice(s->device));
     if (s->mode == 1 && !s->count_next) {
         // the only entry point that honours pt_set_mode(0), the counting build and the PTAMD_TSTAT diagnostics
-        job.work = d_work; job.stream = stream; job.cam = &c;
+        job.work = d_work; job.stream = stream;
         return pt_run_job(s, job, /*traceEvents=*/true, /*traceStat=*/true, d_tiles);
     }
     const int slot = s->ev_count % PtScene::kEvRing;
@@ -207,8 +205,8 @@ int pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, co
         }
     }
     if (!pt_has_light(s)) return PT_ERR_NO_LIGHT;
-    ptd::DevCamera c;
-    pt_fill_camera(cam, c);
+    job.src.kind = ptd::WfSource::kTileList;
+    pt_fill_camera(cam, job.src.list.cam);
 
     job.stream = (hipStream_t)hip_stream;
     HIPCHK(hipSetDevice(s->device));
@@ -217,7 +215,7 @@ int pt_render_tile_list(PtScene* s, const PtCamera* cam, const PtParams* prm, co
     // stream-ordered before wf_init_list; the render below returns only once it has drained, so h_tiles is not read after the call
     HIPCHK(hipMemcpyAsync(s->tile_list.as<>(), h_tiles, (size_t)n_tiles * 4, hipMemcpyHostToDevice, job.stream));
     // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply); no per-launch trace events
-    job.work = d_work; job.cam = &c; job.tileList = s->tile_list.as<int32_t>();
+    job.work = d_work; job.src.list.tiles = s->tile_list.as<int32_t>();
     return pt_run_job(s, job, /*traceEvents=*/false, /*traceStat=*/false, d_tiles);
 }
 
@@ -307,9 +305,10 @@ int pt_render_views(PtScene* s, const PtCamera* h_cams, int32_t n_views, const P
     // stream-ordered before wf_init_views; the render below returns only once it has drained, so the callers' arrays are not read after the call
     HIPCHK(hipMemcpyAsync(s->views.as<>(), s->h_views.data(), total, hipMemcpyHostToDevice, job.stream));
     const char* dv = s->views.as<const char>();
-    // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply); a batch passes no single camera
+    // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply); per-launch trace events as for a frame
     job.work = d_work;
-    job.viewOrg = (const float4*)dv; job.viewCams = (const ptd::DevCamera*)(dv + offCam); job.viewFirstPass = (const int32_t*)(dv + offFirst);
+    job.src.kind = ptd::WfSource::kViews;
+    job.src.views = {(const ptd::DevCamera*)(dv + offCam), (const int32_t*)(dv + offFirst), (const float4*)dv};
     return pt_run_job(s, job, /*traceEvents=*/true, /*traceStat=*/false, d_tiles);
 }
 
@@ -401,7 +400,7 @@ PT_API int pt_enable_trace_timing(PtScene* s, int32_t max_launches)
     for (hipEvent_t e : s->trace_ev) (void)hipEventDestroy(e);
     s->trace_ev.assign((size_t)max_launches * 3, nullptr);
     for (auto& e : s->trace_ev) HIPCHK(hipEventCreate(&e));
-    for (int k = 0; k < 4; k++) s->trace_ev_used[k] = 0;
+    s->trace_ev_used = 0;
     return PT_OK;
 }
 static int kernel_timing(PtScene* s, int first, double* sum_ms, int32_t* launches, double* max_ms)
@@ -409,17 +408,14 @@ static int kernel_timing(PtScene* s, int first, double* sum_ms, int32_t* launche
     if (!s || !sum_ms || !launches) { pt_set_error("pt_trace_timing / pt_shade_timing: NULL"); return PT_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     double sum = 0, mx = 0;
-    int total = 0;
-    for (int c = 0; c < 4; c++)
-        for (int i = 0; i < s->trace_ev_used[c]; i++) {
-            const size_t k = ((size_t)c * s->trace_ev_per + i) * 3 + (size_t)first;
-            float ms = 0.f;
-            HIPCHK(hipEventSynchronize(s->trace_ev[k + 1]));
-            HIPCHK(hipEventElapsedTime(&ms, s->trace_ev[k], s->trace_ev[k + 1]));
-            sum += ms; if (ms > mx) mx = ms;
-            total++;
-        }
-    *sum_ms = sum; *launches = total; if (max_ms) *max_ms = mx;
+    for (int i = 0; i < s->trace_ev_used; i++) {
+        const size_t k = (size_t)i * 3 + (size_t)first;
+        float ms = 0.f;
+        HIPCHK(hipEventSynchronize(s->trace_ev[k + 1]));
+        HIPCHK(hipEventElapsedTime(&ms, s->trace_ev[k], s->trace_ev[k + 1]));
+        sum += ms; if (ms > mx) mx = ms;
+    }
+    *sum_ms = sum; *launches = s->trace_ev_used; if (max_ms) *max_ms = mx;
     return PT_OK;
 }
 PT_API int pt_trace_timing(PtScene* s, double* sum_ms, int32_t* launches, double* max_ms) { return kernel_timing(s, 0, sum_ms, launches, max_ms); }

@@ -95,8 +95,8 @@ struct DevParams {
     int32_t max_refract, first_pass;
     int32_t rank, world;
     int32_t tiles_x, tiles_y, n_tiles_total, n_tiles_local;
-    int32_t n_units;                     // n_tiles_local * passes (of this launch / cohort)
-    int32_t unit_base;                   // first global unit of this cohort (wavefront pipeline)
+    int32_t n_units;                     // n_tiles_local * passes (of this launch)
+    int32_t unit_base;                   // always 0 (every render starts at its first unit); kept because DevParams is a kernel argument block
 };
 
 }  // namespace ptd

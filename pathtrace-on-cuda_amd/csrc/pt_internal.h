@@ -81,42 +81,78 @@ inline bool seed_in_range(const PtCamera* cam, int first_pass, int passes)
     return ok;
 }
 
-// One run of the wavefront pipeline (ptk_wf_render, pt_wavefront.hip).  pt_api.hip fills it in for a render call; the pipeline reads it
-// and writes through the two output pointers only.
+// The seven path parameters every render copies from the caller's PtParams as they are (the geometry of the units is each entry point's own).
+inline void path_params(const PtParams* prm, DevParams& d)
+{
+    d.passes = prm->passes; d.spp_per_pass = prm->spp_per_pass; d.max_bounce = prm->max_bounce; d.rr_bounce = prm->rr_bounce;
+    d.rr_floor = prm->rr_floor; d.max_refract = prm->max_refract; d.first_pass = prm->first_pass;
+}
+
+// What a scene lends every run of the wavefront pipeline, for the scene's life: early shade's second stream with the events that order
+// it and the caller's stream, and the pinned word the host polls the live-stream count through.  One render at a time per scene.
+struct WfLent {
+    hipStream_t aux = nullptr;                                       // non-blocking: wf_shade PHASE 1 runs here beside the draining wf_trace
+    hipEvent_t toAux[2] = {nullptr, nullptr};                        // main -> aux: the previous iteration's shade is done, by iteration parity (no timing)
+    hipEvent_t toMain[2] = {nullptr, nullptr};                       // aux -> main: PHASE 1 is done, by iteration parity (no timing)
+    uint32_t* h_poll = nullptr;                                      // pinned
+    WfLent() = default;
+    WfLent(const WfLent&) = delete;
+    WfLent& operator=(const WfLent&) = delete;
+    hipError_t create()                                              // once; the device is the current one
+    {
+        hipError_t e = hipStreamCreateWithFlags(&aux, hipStreamNonBlocking);
+        for (int k = 0; k < 2 && e == hipSuccess; k++) {
+            e = hipEventCreateWithFlags(&toAux[k], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&toMain[k], hipEventDisableTiming);
+        }
+        return e != hipSuccess ? e : hipHostMalloc((void**)&h_poll, 64, hipHostMallocDefault);
+    }
+    ~WfLent()
+    {
+        if (h_poll) (void)hipHostFree(h_poll);
+        for (int k = 0; k < 2; k++) { if (toAux[k]) (void)hipEventDestroy(toAux[k]); if (toMain[k]) (void)hipEventDestroy(toMain[k]); }
+        if (aux) (void)hipStreamDestroy(aux);
+    }
+};
+
+// Where a stream's pixel and camera come from: the kind, and the fields of that kind alone.  Each render entry point fills in its own.
+struct WfSource {
+    enum Kind {
+        kFrame,      // pt_render_tiles: the fixed share of prm.rank / world (wf_init)
+        kTileList,   // pt_render_tile_list: prm.n_tiles_local global tile numbers (wf_init_list); nothing else of the pipeline differs from kFrame
+        kViews,      // pt_render_views: a batch, n_tiles_local = views x prm.n_tiles_total; wf_init_views, the ViewTable instantiations of wf_shade / wf_drain
+        kRays,       // pt_render_rays: n_tiles_local = ceil(nRays / 64) groups of 64 rays; wf_init_rays, the RayTable instantiations
+    } kind;
+    union {
+        struct { DevCamera cam; } frame;
+        struct { DevCamera cam; const int32_t* tiles; } list;                                        // tiles: on the device
+        struct { const DevCamera* cams; const int32_t* firstPass; const float4* org; } views;        // one device entry per view
+        struct { const float4* rays8; const int32_t* seed; int32_t seedStride; uint32_t nRays; } rays;      // rays8: the caller's device buffer (also the origin table); seed may be nullptr (seed of ray i = i)
+    };
+};
+
+// One run of the wavefront pipeline (ptk_wf_render, pt_wavefront.hip).  An entry point fills in what is its own (prm, work, stream, src)
+// and pt_run_job (pt_api.hip) the rest; the pipeline reads it and writes through the two output pointers only.
 struct WfJob {
     // ---- what to render
-    int device;
     const DevScene* scene;
-    DevParams prm;                       // n_units (tile, pass) units; a list or a batch: a world of one whose frame has n_tiles_local tiles
+    DevParams prm;                       // n_units (tile, pass) units; a list, a batch or a ray set: a world of one whose frame has n_tiles_local tiles
     void* work;                          // ptk_wf_work_bytes(prm.n_units, traceBlocks) bytes; the per-pass means end up at its start (ptk_wf_staging)
     int traceBlocks;                     // persistent grid of wf_trace
     hipStream_t stream;                  // the caller's
-    // ---- where a stream's pixel and camera come from, exactly one of:
-    //   cam                                  the fixed share of prm.rank / world (wf_init)
-    //   cam + tileList                       prm.n_tiles_local global tile numbers on the device (wf_init_list); nothing else of the pipeline differs
-    //   viewCams + viewFirstPass + viewOrg   a batch, one device entry per view and cam == nullptr: n_tiles_local = views x prm.n_tiles_total,
-    //                                        streams are set up by wf_init_views and stepped by the ViewTable instantiations of wf_shade / wf_drain
-    //   rays8 + raySeed + seedStride + nRays the caller's own rays (pt_render_rays), cam == nullptr: n_tiles_local = ceil(nRays / 64) groups of 64 rays,
-    //                                        streams are set up by wf_init_rays and stepped by the RayTable instantiations; rays8 is the
-    //                                        caller's device buffer (also the origin table), raySeed may be nullptr (seed of ray i = i)
-    const DevCamera* cam;
-    const int32_t* tileList;
-    const DevCamera* viewCams; const int32_t* viewFirstPass; const float4* viewOrg;
-    const float4* rays8; const int32_t* raySeed; int32_t seedStride; uint32_t nRays;
+    WfSource src;
     // ---- what the scene lends
-    uint32_t* h_poll;                    // pinned, one poll word per cohort, 64 B apart
-    hipStream_t* xstreams;               // 3 extra streams: cohorts 1..3, or early shade beside the traversal when there is one cohort
-    hipEvent_t ev_fork, *ev_join;        // [3]
+    const WfLent* lent;
     hipEvent_t ev_begin, ev_end;         // bracket the whole render on `stream`
     // ---- schedule (PtScene: drain_below, shade_rounds, early_below)
     int drainBelow, shadeRounds, earlyBelow;
     // ---- diagnostics, optional
-    hipEvent_t* trace_ev;                // triples (before wf_trace, after it, after wf_shade), split evenly between cohorts; nullptr = none
+    hipEvent_t* trace_ev;                // triples (before wf_trace, after it, after wf_shade), one per iteration; nullptr = none
     int trace_ev_triples;
     unsigned long long* traceStat;       // the counter buffer (PTAMD_TSTAT), cleared by the caller; nullptr = the production wf_trace
     // ---- out
-    int* trace_ev_used;                  // [4]: triples used by each cohort
-    int* iters;                          // bounce iterations of the longest cohort
+    int* trace_ev_used;                  // triples recorded
+    int* iters;                          // bounce iterations
 };
 
 // ---- argument block of the vertex update (pt_dynamic.hip) ----
@@ -170,7 +206,6 @@ hipError_t ptk_dbg_ray_setup(const float*, int, float*, hipStream_t);
 hipError_t ptk_dbg_pixel_dir(const ptd::DevCamera*, const int*, int, float*, hipStream_t);
 hipError_t ptk_dbg_nee(const ptd::DevScene*, const float*, int, float*, hipStream_t);
 size_t ptk_wf_work_bytes(size_t nUnits, int traceBlocks);
-int ptk_wf_cohorts(size_t nUnits);
 const float* ptk_wf_staging(void* work);
 int ptk_wf_stack_capacity(void);
 int ptk_wf_trace_stat(void);      // PTAMD_TSTAT as the pipeline read it (0 = off)

@@ -24,8 +24,7 @@ static int rays_params(const char* who, const PtParams* prm, int64_t n_rays, ptd
         pt_set_error("%s: %lld rays x %d passes: too many work units for one pipeline run (64 x ceil(n / 64) x passes must stay below 2^31)", who, (long long)n_rays, prm->passes);
         return PT_ERR_INVALID;
     }
-    d.passes = prm->passes; d.spp_per_pass = prm->spp_per_pass; d.max_bounce = prm->max_bounce; d.rr_bounce = prm->rr_bounce;
-    d.rr_floor = prm->rr_floor; d.max_refract = prm->max_refract; d.first_pass = prm->first_pass;
+    ptd::path_params(prm, d);
     d.rank = 0; d.world = 1;
     d.tiles_x = (int)groups; d.tiles_y = 1; d.n_tiles_total = (int)groups; d.n_tiles_local = (int)groups;
     d.n_units = (int)(groups * prm->passes);
@@ -71,7 +70,8 @@ int pt_render_rays(PtScene* s, const float* d_rays8, const int32_t* d_seed, int6
     // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply); the rays and seeds
     // are read where they are for as long as the call blocks: nothing is copied, nothing is allocated in the scene
     job.work = d_work;
-    job.rays8 = (const float4*)d_rays8; job.raySeed = d_seed; job.seedStride = seed_stride; job.nRays = (uint32_t)n_rays;
+    job.src.kind = ptd::WfSource::kRays;
+    job.src.rays = {(const float4*)d_rays8, d_seed, seed_stride, (uint32_t)n_rays};
     return pt_run_job(s, job, /*traceEvents=*/false, /*traceStat=*/false, d_rgb);
 }
 

@@ -28,7 +28,7 @@ struct PtScene {
     int num_cus = 256;
     bool count_next = false;
     int mode = 1;            // 1 = wavefront pipeline (default), 0 = one-kernel state machine
-    uint32_t* h_poll = nullptr;   // pinned, for the pipeline's live-stream count
+    ptd::WfLent wf;          // what every run of the wavefront pipeline borrows: early shade's stream and events, the pinned poll word (frees itself)
     int last_iters = 0;
     int shade_rounds = 1;        // wf_shade: 1 = a stream may start its next sample in the step its path ends, 0 = one bounce per step, -1 = by live-stream count (PTAMD_TRS)
     int early_below = 2500000;   // renders of at most this many streams (pixels x passes of one call) run wf_shade's early phase beside the draining wf_trace (0 = never; pt_set_early_shade)
@@ -38,10 +38,7 @@ struct PtScene {
                                  // +5...7 % for an 8-way rank, +3 % 4-way, +1 % on one GPU (r03_b31.log, r03_b32.log, r03_b33.log)
     // optional per-launch timing of the traversal kernel (pt_enable_trace_timing)
     std::vector<hipEvent_t> trace_ev;
-    int trace_ev_used[4] = {0, 0, 0, 0};     // per cohort
-    int trace_ev_per = 0;                    // event pairs per cohort in the last render
-    hipStream_t xstreams[3] = {nullptr, nullptr, nullptr};   // extra streams for concurrent cohorts
-    hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
+    int trace_ev_used = 0;                   // triples of trace_ev the last render recorded (one per iteration)
     // ring of HIP event pairs, one pair per render_units launch (pt_render_timings)
     static constexpr int kEvRing = 64;
     hipEvent_t ev[kEvRing][2] = {};
@@ -61,13 +58,10 @@ struct PtScene {
     // ---- ray queries (pt_trace_rays, csrc/pt_query.hip) ----
     bool query_quad = true;              // walk the 4-wide tree when it fits the kernel's stack (PTAMD_QUERY_QUAD=0: the binary tree, A/B)
 
-    // Events, streams and pinned memory; the DevBuf members free themselves after it.  The caller has made `device` current.
+    // The events; `wf` and the DevBuf members free themselves after it.  The caller has made `device` current.
     ~PtScene()
     {
         for (int i = 0; i < kEvRing; i++) for (int j = 0; j < 2; j++) if (ev[i][j]) (void)hipEventDestroy(ev[i][j]);
-        if (h_poll) (void)hipHostFree(h_poll);
-        for (int i = 0; i < 3; i++) { if (xstreams[i]) (void)hipStreamDestroy(xstreams[i]); if (ev_join[i]) (void)hipEventDestroy(ev_join[i]); }
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
         for (hipEvent_t e : trace_ev) if (e) (void)hipEventDestroy(e);
     }
 };

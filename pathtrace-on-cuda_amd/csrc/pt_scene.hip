@@ -157,16 +157,14 @@ static int upload_arrays(PtScene* sc, const HostArray (&src)[kSceneArrays])
     return PT_OK;
 }
 
-// ---- what the scene lends every render: counters, events, streams, the pinned poll words ----
+// ---- what the scene lends every render: counters, the event ring, and the pipeline's stream, events and pinned poll word (WfLent) ----
 static int create_resources(PtScene* sc)
 {
     HIPCHK(sc->unit_counter.alloc(64));
     HIPCHK(sc->counters.alloc(ptd::kStatBytes));      // 8 work counters (+ the diagnostic launch timeline of wf_trace)
     HIPCHK(hipMemset(sc->counters.as<>(), 0, ptd::kStatBytes));
     for (int i = 0; i < PtScene::kEvRing; i++) { HIPCHK(hipEventCreate(&sc->ev[i][0])); HIPCHK(hipEventCreate(&sc->ev[i][1])); }
-    HIPCHK(hipHostMalloc((void**)&sc->h_poll, 4 * 64, hipHostMallocDefault));
-    for (int i = 0; i < 3; i++) { HIPCHK(hipStreamCreateWithFlags(&sc->xstreams[i], hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&sc->ev_join[i], hipEventDisableTiming)); }
-    HIPCHK(hipEventCreateWithFlags(&sc->ev_fork, hipEventDisableTiming));
+    HIPCHK(sc->wf.create());
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, sc->device));
     sc->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;

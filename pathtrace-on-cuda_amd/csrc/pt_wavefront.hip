@@ -28,9 +28,7 @@
 // render_units / the reference's GetColor_iter, so images are bit-identical across modes.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include <thread>
 #include <type_traits>
-#include <vector>
 #include "pt_device.h"
 #include "pt_math.h"
 #include "pt_bxdf.h"
@@ -831,8 +829,8 @@ extern "C" {
 // entries a ray's traversal stack can hold (LDS + global overflow); a 4-wide walk needs at most 3 per level + 2
 int ptk_wf_stack_capacity(void) { return ptd::kWfLdsStack + ptd::kWfOvfLevels; }
 
-// ---- work buffer: [ staging (all streams) | cohort 0 | cohort 1 | ... ] ----------------------
-static size_t cohort_bytes(size_t nStreams, int traceBlocks)
+// ---- work buffer: [ staging (the per-pass means) | what carve() lays out | 256 spare ] ----------------------
+static size_t carved_bytes(size_t nStreams, int traceBlocks)
 {
     const size_t n16 = (nStreams + 3) & ~(size_t)3;
     size_t b = 0;
@@ -848,26 +846,9 @@ static size_t cohort_bytes(size_t nStreams, int traceBlocks)
 }
 static size_t staging_bytes(size_t nStreams) { return ((nStreams * 12 + 16) + 255) & ~(size_t)255; }
 
-// Streams can be split into cohorts that run the pipeline concurrently on separate HIP streams
-// (contiguous unit ranges, so each is a whole number of (tile, pass) units).  Measured on MI355X:
-// before the queue heads were sharded two cohorts gained 8 % on 16.6M streams (one cohort's
-// shade kernel overlapping the other's trace kernel); with sharded heads one cohort is as fast
-// (927 vs 920 Msamples/s) and small renders lose, so the default is one.  PTAMD_COHORTS=2..4
-// turns it on for experiments.
-int ptk_wf_cohorts(size_t nUnits)
-{
-    static const int forced = getenv("PTAMD_COHORTS") ? atoi(getenv("PTAMD_COHORTS")) : 0;
-    int c = forced > 0 ? forced : 1;
-    if (c > 4) c = 4;
-    if ((size_t)c > nUnits) c = (int)(nUnits ? nUnits : 1);
-    return c;
-}
-
 size_t ptk_wf_work_bytes(size_t nUnits, int traceBlocks)
 {
-    const int C = ptk_wf_cohorts(nUnits);
-    const size_t per = (nUnits + C - 1) / C;
-    return staging_bytes(nUnits * 64) + (size_t)C * cohort_bytes(per * 64, traceBlocks) + 256;
+    return staging_bytes(nUnits * 64) + carved_bytes(nUnits * 64, traceBlocks) + 256;
 }
 
 static void carve(char* p, size_t nStreams, int traceBlocks, ptd::WfBuf& b)
@@ -951,51 +932,30 @@ static const WfTuning& wf_tuning()
 }
 int ptk_wf_trace_stat(void) { return wf_tuning().traceStat; }
 
-// What ptk_wf_render carves out of a job for one cohort.
-struct WfCohort {
-    ptd::DevParams prm;           // the job's, with this cohort's unit_base / n_units
-    ptd::WfBuf b;
-    hipStream_t stream, aux;      // aux: a second stream for early shade, nullptr = none to spare
-    uint32_t* h_cnt;              // its pinned poll word
-    hipEvent_t* trace_ev;         // its slice of the job's event triples
-    int trace_ev_triples;
-    int* trace_ev_used;
-    int iters;                    // out
-};
+}  // extern "C"
 
-// One cohort's pipeline on its own stream.  Blocks the calling host thread until the cohort has
-// drained (it polls the live-stream count every 16..64 iterations).
-static hipError_t cohort_pipeline(const ptd::WfJob& job, WfCohort& co)
+// The pipeline for one job whose streams take their pixel and camera from `cam` (DevCamera: a frame share or a tile list; ViewTable; RayTable):
+// `init` launches the kind's init kernel, and every later launch names the Cam instantiation of its kernel.  shadeWaves: waves per SIMD of
+// wf_shade.  Blocks the host until the render has drained (it polls the live-stream count every 16..64 iterations).
+template <class Cam, class Init>
+static hipError_t pipeline(const ptd::WfJob& job, const ptd::WfBuf& b, const Cam& cam, int shadeWaves, Init init)
 {
     using namespace ptd;
-    const DevParams& prm = co.prm;
-    const WfBuf& b = co.b;
-    const hipStream_t stream = co.stream, aux = co.aux;
-    hipEvent_t evOvl[4] = {job.ev_fork, job.ev_join[0], job.ev_join[1], job.ev_join[2]};
+    const DevParams& prm = job.prm;
+    const hipStream_t stream = job.stream, aux = job.lent->aux;
+    const hipEvent_t *toAux = job.lent->toAux, *toMain = job.lent->toMain;
+    uint32_t* const h_cnt = job.lent->h_poll;
     hipError_t e;
-    if ((e = hipSetDevice(job.device)) != hipSuccess) return e;
     const size_t nStreams = (size_t)prm.n_units * 64;
     if ((e = hipMemsetAsync(b.cnt, 0, 3 * kWfSlotBytes, stream)) != hipSuccess) return e;
     const int nb = (int)((nStreams + 255) / 256);
-    // a batch of views (viewCams != nullptr; cam is then nullptr): its own init kernel, and the views instantiations of wf_shade / wf_drain below;
-    // the caller's rays (rays8 != nullptr; cam is nullptr too) likewise
-    const bool batch = job.viewCams != nullptr, ownRays = job.rays8 != nullptr;
-    const ViewTable views{job.viewOrg, (uint32_t)prm.n_tiles_total};
-    const RayTable rayTab{job.rays8};
-    if (ownRays) hipLaunchKernelGGL(wf_init_rays, dim3(nb), dim3(256), 0, stream, *job.scene, prm, b, (uint32_t)nStreams, job.rays8, job.raySeed, (uint32_t)job.seedStride, job.nRays);
-    else if (batch) hipLaunchKernelGGL(wf_init_views, dim3(nb), dim3(256), 0, stream, *job.scene, prm, b, (uint32_t)nStreams, job.viewCams, job.viewFirstPass, views.tilesPerView);
-    else if (job.tileList) hipLaunchKernelGGL(wf_init_list, dim3(nb), dim3(256), 0, stream, *job.scene, *job.cam, prm, b, (uint32_t)nStreams, job.tileList);
-    else hipLaunchKernelGGL(wf_init, dim3(nb), dim3(256), 0, stream, *job.scene, *job.cam, prm, b, (uint32_t)nStreams);
+    init(dim3(nb), (uint32_t)nStreams);
     const int ovfStride = job.traceBlocks * 256;
     const int tb = job.traceBlocks < nb ? job.traceBlocks : nb;
     // every sample needs at most max_bounce + (max_refract + 2) bounces, +1 iteration to retire
     // (time-sliced rays add iterations; 64x is far beyond anything a finite tree can need)
     const long long hardCap = ((long long)prm.spp_per_pass * (prm.max_bounce + prm.max_refract + 3) + 8) * 64;
     const WfTuning& tn = wf_tuning();
-    const int guideShift = tn.guideShift, budgetShift = tn.budgetShift, budgetMin = tn.budgetMin, shadeWaves = tn.shadeWaves, shadeThreads = tn.shadeThreads;
-    const int earlyPrio = tn.earlyPrio, earlyThreads = tn.earlyThreads, refillMin = tn.refillMin, triTrig = tn.triTrig, chunkShift = tn.chunkShift;
-    const bool pubOnly = tn.pubOnly, traceStatClk = tn.traceStat == 3, traceStatFull = tn.traceStat == 1;
-    const uint32_t trStreams = tn.trStreams;
     if (job.traceStat && tn.traceStat == 2 && tn.tracePool) {
         static const unsigned long long one = 1ull;
         if ((e = hipMemcpyAsync(job.traceStat + 5, &one, 8, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
@@ -1005,6 +965,14 @@ static hipError_t cohort_pipeline(const ptd::WfJob& job, WfCohort& co)
         static unsigned long long dumpWord; dumpWord = (unsigned long long)tn.traceDump + 1ull;
         if ((e = hipMemcpyAsync(job.traceStat + 6, &dumpWord, 8, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
     }
+    // early shade (wf_shade PHASE 1 / 2): for a render of few enough streams that the traversal's launch tail is a large part of
+    // every iteration (one rank of an 8-way tile split), the shade step starts on `aux` beside the draining wf_trace and the rest
+    // follows both (result-neutral).  Decided once per render: a large render gains nothing from it in its last iterations.
+    // (not below ~1/8 of the limit either: a render that small is bound by launch latency, and this adds a launch and two waits per iteration)
+    const bool early = job.earlyBelow > 0 && nStreams <= (size_t)job.earlyBelow && nStreams >= (size_t)job.earlyBelow / 8 && !job.traceStat && !tn.pubOnly;
+    const bool marks = early || tn.pubOnly;
+    // one launch for every build of wf_trace
+    const auto trace = job.traceStat ? (tn.traceStat == 3 ? wf_trace<3> : tn.traceStat == 1 ? wf_trace<1> : wf_trace<2>) : marks ? wf_trace<0, true> : wf_trace<0>;
     int it = 0;
     int poll = 16;
     // streams only ever retire, so the live count of the last poll bounds every later one: the shade grid
@@ -1013,138 +981,105 @@ static hipError_t cohort_pipeline(const ptd::WfJob& job, WfCohort& co)
     for (;;) {
         for (int k = 0; k < poll; k++, it++) {
             const int sIn = it % 3, sOut = (it + 1) % 3, sClr = (it + 2) % 3;
-            const bool timed = co.trace_ev && it < co.trace_ev_triples;
-            if (timed) (void)hipEventRecord(co.trace_ev[3 * it], stream);
-            // early shade (wf_shade PHASE 1 / 2): for a render of few enough streams that the traversal's launch tail is a large part of
-            // every iteration (one rank of an 8-way tile split), the shade step starts on `aux` beside the draining wf_trace and the rest
-            // follows both (result-neutral).  Decided once per render: a large render gains nothing from it in its last iterations.
-            // (not below ~1/8 of the limit either: a render that small is bound by launch latency, and this adds a launch and two waits per iteration)
-            const bool early = aux != nullptr && job.earlyBelow > 0 && nStreams <= (size_t)job.earlyBelow && nStreams >= (size_t)job.earlyBelow / 8 && !job.traceStat && !pubOnly;
-            const bool marks = early || pubOnly;
+            const bool timed = job.trace_ev && it < job.trace_ev_triples;
+            if (timed) (void)hipEventRecord(job.trace_ev[3 * it], stream);
             if (early) {
                 // aux may start once the previous iteration's shade (everything on `stream` so far) is done
-                if ((e = hipEventRecord(evOvl[it & 1], stream)) != hipSuccess) return e;
-                if ((e = hipStreamWaitEvent(aux, evOvl[it & 1], 0)) != hipSuccess) return e;
+                if ((e = hipEventRecord(toAux[it & 1], stream)) != hipSuccess) return e;
+                if ((e = hipStreamWaitEvent(aux, toAux[it & 1], 0)) != hipSuccess) return e;
             }
-            // one launch for every build of wf_trace; statLaunch is the timeline slot of a diagnostic build, the issue priority in production
-            const auto trace = job.traceStat ? (traceStatClk ? wf_trace<3> : traceStatFull ? wf_trace<1> : wf_trace<2>) : marks ? wf_trace<0, true> : wf_trace<0>;
-            const int statLaunch = job.traceStat ? (it < kStatLaunches ? it : kStatLaunches - 1) : marks ? earlyPrio : 0;
-            hipLaunchKernelGGL(trace, dim3(tb), dim3(256), 0, stream, *job.scene, b, sIn, ovfStride, it & 1, chunkShift, budgetShift, budgetMin, guideShift, triTrig, refillMin, job.traceStat, statLaunch, tn.helpShards, tn.lateBudget);
-            if (timed) (void)hipEventRecord(co.trace_ev[3 * it + 1], stream);
-            const dim3 sg((liveBound + shadeThreads - 1) / shadeThreads), sb(shadeThreads);
-            const bool twoRounds = job.shadeRounds >= 0 ? (job.shadeRounds != 0) : (liveBound < trStreams);
-            // one launch for every instantiation of wf_shade (a batch or a ray set: their own, 4 waves per SIMD whatever PTAMD_SW says)
+            // statLaunch is the timeline slot of a diagnostic build, the issue priority in production
+            const int statLaunch = job.traceStat ? (it < kStatLaunches ? it : kStatLaunches - 1) : marks ? tn.earlyPrio : 0;
+            hipLaunchKernelGGL(trace, dim3(tb), dim3(256), 0, stream, *job.scene, b, sIn, ovfStride, it & 1, tn.chunkShift, tn.budgetShift, tn.budgetMin, tn.guideShift, tn.triTrig, tn.refillMin, job.traceStat, statLaunch, tn.helpShards, tn.lateBudget);
+            if (timed) (void)hipEventRecord(job.trace_ev[3 * it + 1], stream);
+            const dim3 sg((liveBound + tn.shadeThreads - 1) / tn.shadeThreads), sb(tn.shadeThreads);
+            const bool twoRounds = job.shadeRounds >= 0 ? (job.shadeRounds != 0) : (liveBound < tn.trStreams);
+            // one launch for every instantiation of wf_shade
             auto shade = [&](int phase, hipStream_t s, dim3 g, dim3 blk) {
-                if (ownRays) hipLaunchKernelGGL(shade_kernel<RayTable>(4, twoRounds, phase, marks), g, blk, 0, s, *job.scene, rayTab, prm, b, sIn, sOut, sClr, it & 1);
-                else if (batch) hipLaunchKernelGGL(shade_kernel<ViewTable>(4, twoRounds, phase, marks), g, blk, 0, s, *job.scene, views, prm, b, sIn, sOut, sClr, it & 1);
-                else hipLaunchKernelGGL(shade_kernel<DevCamera>(shadeWaves, twoRounds, phase, marks), g, blk, 0, s, *job.scene, *job.cam, prm, b, sIn, sOut, sClr, it & 1);
+                hipLaunchKernelGGL(shade_kernel<Cam>(shadeWaves, twoRounds, phase, marks), g, blk, 0, s, *job.scene, cam, prm, b, sIn, sOut, sClr, it & 1);
             };
             if (early) {
                 // phase 1 in small workgroups: a 256-thread workgroup needs one free wave slot per SIMD, i.e. two traversal workgroups of
                 // the CU gone, a 512-thread one four — it gets onto the chip earlier in the drain
-                shade(1, aux, dim3((liveBound + earlyThreads - 1) / earlyThreads), dim3(earlyThreads));
-                if ((e = hipEventRecord(evOvl[2 + (it & 1)], aux)) != hipSuccess) return e;
-                if ((e = hipStreamWaitEvent(stream, evOvl[2 + (it & 1)], 0)) != hipSuccess) return e;
+                shade(1, aux, dim3((liveBound + tn.earlyThreads - 1) / tn.earlyThreads), dim3(tn.earlyThreads));
+                if ((e = hipEventRecord(toMain[it & 1], aux)) != hipSuccess) return e;
+                if ((e = hipStreamWaitEvent(stream, toMain[it & 1], 0)) != hipSuccess) return e;
                 shade(2, stream, sg, sb);
             }
             else shade(0, stream, sg, sb);
-            if (timed) (void)hipEventRecord(co.trace_ev[3 * it + 2], stream);      // [3it+1, 3it+2] brackets this iteration's wf_shade
+            if (timed) (void)hipEventRecord(job.trace_ev[3 * it + 2], stream);      // [3it+1, 3it+2] brackets this iteration's wf_shade
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(co.h_cnt, &b.cnt[it % 3].nActive, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(h_cnt, &b.cnt[it % 3].nActive, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-        if (co.h_cnt[0] == 0) break;
-        liveBound = co.h_cnt[0];
-        if (co.h_cnt[0] <= (uint32_t)job.drainBelow) {
+        const uint32_t live = *h_cnt;
+        if (live == 0) break;
+        liveBound = live;
+        if (live <= (uint32_t)job.drainBelow) {
             // few streams left: finish them in one launch instead of hundreds of latency-bound iterations
             // the 4-wide tree if its walk fits the per-lane stack (any tree the builder makes for the config scenes does), else the binary one
             const bool quadWalk = tn.drainQuad && 3 * job.scene->quad_depth + 2 <= kDrainQuadStack;
             // 2 (4-wide walk: 189 VGPRs) or 3 (165) waves per SIMD of wf_drain fit: spread the streams over at most that many lanes
             const size_t drainLanes = (size_t)((quadWalk && DRAIN_MINBLOCKS < 3) ? 2 : 3) * 4 * 256 * 64;
             int spread = 0;
-            while (spread < tn.drainSpread && ((size_t)co.h_cnt[0] << (spread + 1)) <= drainLanes) spread++;
-            const int db = (int)((((size_t)co.h_cnt[0] << spread) + kBlockThreads - 1) / kBlockThreads);
-            if (ownRays) hipLaunchKernelGGL((quadWalk ? wf_drain<true, RayTable> : wf_drain<false, RayTable>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, rayTab, prm, b, it % 3, it & 1, spread);
-            else if (batch) hipLaunchKernelGGL((quadWalk ? wf_drain<true, ViewTable> : wf_drain<false, ViewTable>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, views, prm, b, it % 3, it & 1, spread);
-            else hipLaunchKernelGGL((quadWalk ? wf_drain<true> : wf_drain<false>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, *job.cam, prm, b, it % 3, it & 1, spread);
+            while (spread < tn.drainSpread && ((size_t)live << (spread + 1)) <= drainLanes) spread++;
+            const int db = (int)((((size_t)live << spread) + kBlockThreads - 1) / kBlockThreads);
+            hipLaunchKernelGGL((quadWalk ? wf_drain<true, Cam> : wf_drain<false, Cam>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, cam, prm, b, it % 3, it & 1, spread);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
             break;
         }
         if (it > hardCap) return hipErrorLaunchFailure;      // cannot happen for a well-formed scene; never spin forever
         if (poll < 64) poll *= 2;
-        if (job.drainBelow > 0 && (unsigned long long)co.h_cnt[0] <= (unsigned long long)job.drainBelow * 8ull) poll = 16;      // near the hand-over: look again soon
+        if (job.drainBelow > 0 && (unsigned long long)live <= (unsigned long long)job.drainBelow * 8ull) poll = 16;      // near the hand-over: look again soon
     }
-    co.iters = it;
-    *co.trace_ev_used = co.trace_ev ? (it < co.trace_ev_triples ? it : co.trace_ev_triples) : 0;
+    *job.iters = it;
+    *job.trace_ev_used = job.trace_ev ? (it < job.trace_ev_triples ? it : job.trace_ev_triples) : 0;
     return hipSuccess;
 }
 
-// cohort_pipeline, and on any error nothing of it left running: callers free the work buffer on that path, and kernels already
-// launched — the early-shade ones on `aux` too — may still be using it.  The first error is what is returned.
-static hipError_t run_cohort(const ptd::WfJob& job, WfCohort& co)
-{
-    const hipError_t e = cohort_pipeline(job, co);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(co.stream);
-        if (co.aux) (void)hipStreamSynchronize(co.aux);
-    }
-    return e;
-}
+extern "C" {
 
-// Runs the whole pipeline for one job (pt_internal.h: WfJob) and blocks the host until the render has drained.
+// Runs the whole pipeline for one job (pt_internal.h: WfJob) on the caller's stream and blocks the host until the render has drained.
+// The pixel source is decided here, once: its init kernel and its camera type.  A batch of views and a ray set always run the
+// 4-waves-per-SIMD wf_shade (the only shape their instantiations are built for); one camera honours PTAMD_SW.
 hipError_t ptk_wf_render(const ptd::WfJob& job)
 {
     using namespace ptd;
     const hipStream_t stream = job.stream;
-    const size_t nUnits = (size_t)job.prm.n_units;
-    const int C = ptk_wf_cohorts(nUnits);
-    const size_t per = (nUnits + C - 1) / C;
-    char* base = (char*)job.work;
-    float* staging = (float*)base;
-    char* p = base + staging_bytes(nUnits * 64);
+    const DevParams& prm = job.prm;
+    const WfSource& src = job.src;
+    const size_t nStreams = (size_t)prm.n_units * 64;
+    WfBuf b{};
+    carve((char*)job.work + staging_bytes(nStreams), nStreams, job.traceBlocks, b);
+    b.staging = (float*)job.work;
     hipError_t e;
     if ((e = hipEventRecord(job.ev_begin, stream)) != hipSuccess) return e;
-    if (C > 1) { if ((e = hipEventRecord(job.ev_fork, stream)) != hipSuccess) return e; }
-    std::vector<hipError_t> rc((size_t)C, hipSuccess);
-    std::vector<WfCohort> cohort((size_t)C);
-    const int evPer = job.trace_ev ? job.trace_ev_triples / C : 0;
-    // every call of the set-up that can fail comes before the first thread starts: no path leaves this function with a joinable thread
-    for (int c = 0; c < C; c++) {
-        WfCohort& co = cohort[(size_t)c];
-        co.prm = job.prm;
-        const size_t u0 = (size_t)c * per, u1 = (u0 + per < nUnits) ? u0 + per : nUnits;
-        co.prm.unit_base = (int)u0; co.prm.n_units = (int)(u1 > u0 ? u1 - u0 : 0);
-        carve(p + (size_t)c * cohort_bytes(per * 64, job.traceBlocks), per * 64, job.traceBlocks, co.b);
-        co.b.staging = staging + u0 * 64 * 3;
-        co.stream = (c == 0) ? stream : job.xstreams[c - 1];
-        if (c > 0) { if ((e = hipStreamWaitEvent(co.stream, job.ev_fork, 0)) != hipSuccess) return e; }
-        co.trace_ev = job.trace_ev ? job.trace_ev + (size_t)3 * evPer * c : nullptr;
-        co.trace_ev_triples = evPer;
-        co.trace_ev_used = &job.trace_ev_used[c];
-        co.h_cnt = job.h_poll + 16 * c;
-        // early shade needs a second stream and four events: with one cohort the scene's extra streams and fork / join events are free
-        co.aux = (C == 1) ? job.xstreams[0] : nullptr;
-        if (co.prm.n_units == 0) *co.trace_ev_used = 0;
+    const int sw = wf_tuning().shadeWaves;
+    switch (src.kind) {
+    case WfSource::kFrame:
+        e = pipeline(job, b, src.frame.cam, sw, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init, g, dim3(256), 0, stream, *job.scene, src.frame.cam, prm, b, n); });
+        break;
+    case WfSource::kTileList:
+        e = pipeline(job, b, src.list.cam, sw, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init_list, g, dim3(256), 0, stream, *job.scene, src.list.cam, prm, b, n, src.list.tiles); });
+        break;
+    case WfSource::kViews: {
+        const ViewTable views{src.views.org, (uint32_t)prm.n_tiles_total};
+        e = pipeline(job, b, views, 4, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init_views, g, dim3(256), 0, stream, *job.scene, prm, b, n, src.views.cams, src.views.firstPass, views.tilesPerView); });
+        break;
     }
-    std::vector<std::thread> th;
-    for (int c = 0; c < C; c++) {
-        WfCohort& co = cohort[(size_t)c];
-        if (co.prm.n_units == 0) continue;
-        auto run = [&job, &co, &rc, c]() { rc[(size_t)c] = run_cohort(job, co); };
-        if (C == 1) run(); else th.emplace_back(run);
+    case WfSource::kRays:
+        e = pipeline(job, b, RayTable{src.rays.rays8}, 4, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init_rays, g, dim3(256), 0, stream, *job.scene, prm, b, n, src.rays.rays8, src.rays.seed, (uint32_t)src.rays.seedStride, src.rays.nRays); });
+        break;
     }
-    for (auto& t : th) t.join();
-    for (int c = 0; c < C; c++) if (rc[(size_t)c] != hipSuccess) return rc[(size_t)c];
-    // every cohort stream has been synchronised by its poll loop; order the caller's stream after them anyway
-    for (int c = 1; c < C; c++) {
-        if ((e = hipEventRecord(job.ev_join[c - 1], job.xstreams[c - 1])) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(stream, job.ev_join[c - 1], 0)) != hipSuccess) return e;
+    if (e != hipSuccess) {
+        // nothing of a failed run left running: callers free the work buffer on that path, and kernels already launched — the
+        // early-shade ones on the auxiliary stream too — may still be using it.  The first error is what is returned.
+        (void)hipStreamSynchronize(stream);
+        (void)hipStreamSynchronize(job.lent->aux);
+        return e;
     }
-    if ((e = hipEventRecord(job.ev_end, stream)) != hipSuccess) return e;
-    int mx = 0; for (const WfCohort& co : cohort) mx = co.iters > mx ? co.iters : mx;
-    *job.iters = mx;
-    return hipSuccess;
+    return hipEventRecord(job.ev_end, stream);
 }
 
 hipError_t ptk_dbg_ray_setup(const float* dir3, int n, float* out5, hipStream_t stream)

@@ -398,6 +398,51 @@ def test_early_shade_is_result_neutral():
     assert np.array_equal(bits(out[0]), bits(out[1]))
 
 
+def test_per_launch_timing_counts_each_render_on_its_own():
+    """pt_enable_trace_timing(N) records an event triple per bounce iteration of the following renders, at most N of them;
+    pt_trace_timing / pt_shade_timing report the launches of the LAST render: min(pt_last_iterations, N) of each, with N above and
+    below the iteration count, for two renders of different length on one scene (2 and 3 passes of a 32x32 frame), with early shade
+    forced on (the limit is the render's stream count) and off; and under one enable, for renders of different iteration counts.
+    Recording changes no bit of the frame."""
+    sc = ptamd.Scene.from_prims(ptamd.gen_scene(0))
+    cam = ptamd.make_camera(32, 32)
+    prms = [ptamd.default_params(passes=p, spp_per_pass=4) for p in (2, 3)]
+    for early in (True, False):
+        limit = [32 * 32 * prm.passes if early else 0 for prm in prms]
+        sc.enable_trace_timing(0)
+        base = []
+        for prm, below in zip(prms, limit):
+            sc.set_early_shade(below)
+            base.append(sc.render(cam, prm))
+            assert sc.trace_timing()[1] == 0 and sc.shade_timing()[1] == 0
+        assert np.isfinite(base[0]).all() and base[0].mean() > 0.05
+        for n in (2048, 4):
+            sc.enable_trace_timing(n)
+            for prm, below, want in zip(prms, limit, base):
+                sc.set_early_shade(below)
+                img = sc.render(cam, prm)
+                iters = sc.last_iterations()
+                tsum, tn, tmax = sc.trace_timing()
+                ssum, sn, smax = sc.shade_timing()
+                print(f"early={early} N={n} passes={prm.passes}: iterations {iters}, wf_trace {tn} launches {tsum:.3f} ms (max {tmax:.3f}), wf_shade {sn} launches {ssum:.3f} ms (max {smax:.3f})")
+                assert (n > iters) == (n == 2048) and iters > 4
+                assert tn == sn == min(iters, n), (early, n, prm.passes)
+                assert tsum > 0 and ssum > 0 and tmax <= tsum and smax <= ssum
+                assert np.array_equal(bits(img), bits(want)), (early, n, prm.passes)
+    # the two renders above poll at the same iterations, so they record equally many launches: under ONE enable, renders whose tail goes to
+    # wf_drain after the first poll (fewer iterations) and never (more) each report their own count, whichever came before
+    sc.enable_trace_timing(2048)
+    counts = []
+    for drain in (1 << 30, 0, 1 << 30):
+        sc.set_drain_threshold(drain)
+        img = sc.render(cam, prms[0])
+        counts.append(sc.last_iterations())
+        assert sc.trace_timing()[1] == sc.shade_timing()[1] == counts[-1], (drain, counts)
+        assert np.array_equal(bits(img), bits(base[0])), drain
+    print("iterations with the tail in wf_drain / the pipeline to the end / in wf_drain again:", counts)
+    assert counts[0] == counts[2] < counts[1]
+
+
 def test_very_bright_light_keeps_its_shadow_rays():
     """Dead-NEE pruning assumes (weight * brdfcos) * Le stays finite (pt_stream.h: bounce); the upload switches it off for a scene with
     an emittance above 1e8, where the product can overflow and the reference then adds inf * 0 = NaN (include/CudaUtil.cuh:271-272).

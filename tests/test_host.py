@@ -169,3 +169,19 @@ def test_bench_times_render_calls_of_the_configs_own_shape():
     assert bench.render_calls(8, 8, 1) == [(1, 8)] and bench.render_calls(3, 8) == [(0, 3)] and bench.render_calls(20, 20) == [(0, 20)]
     for c in bench.CONFIGS.values():
         assert c["passes"] == 8
+
+
+def test_work_buffer_sizes_are_those_of_the_build_before_the_host_driver_rework():
+    """The bytes every render door asks for (the default traversal grid of 1792 workgroups; no device is touched).  The literals were
+    recorded from the library of the commit before the pipeline's host driver lost its stream cohorts, loaded through
+    PTAMD_LIB: the layout of the work buffer — staging first, then the pipeline's arrays, 256 spare bytes — is unchanged by it.
+    Columns: pt_work_bytes, pt_tile_list_work_bytes (5 tiles), pt_views_work_bytes (3 views), pt_rays_work_bytes (1,000 rays)."""
+    recorded = {
+        (32, 32, 2): (89615280, 88949296, 91552688, 89615280),
+        (100, 52, 3): (96910832, 89100656, 113439344, 90099632),
+        (1920, 1080, 8): (7935148976, 89857456, 23628153776, 92521392),
+    }
+    for (W, H, passes), want in recorded.items():
+        cam, p = ptamd.make_camera(W, H), ptamd.default_params(passes=passes)
+        got = (ptamd.work_bytes(cam, p), ptamd.tile_list_work_bytes(cam, p, 5), ptamd.views_work_bytes(cam, p, 3), ptamd.rays_work_bytes(p, 1000))
+        assert got == want, (W, H, passes)

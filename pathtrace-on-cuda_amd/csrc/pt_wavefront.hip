@@ -40,7 +40,7 @@
 namespace ptd {
 
 constexpr int kWfLdsStack = 16;      // stack entries per lane kept in LDS (4 KB / wave)
-constexpr int kWfOvfLevels = 48;     // further levels spill to global memory (never needed on the config scenes: 4-wide depth 12 -> at most 38 entries)
+constexpr int kWfOvfLevels = 48;     // further levels spill to global memory (never needed on the config scenes: 4-wide depth 12 -> at most 38 entries; tests/test_needle_scene.py renders a scene whose rays do need them)
 constexpr int kWfChunk = 128;        // most ray ids a wave takes from a queue shard per atomic (measured optimum 116-229)
 constexpr int kWfRefill = 24;        // refill lanes once this many are idle (measured: 8..16 -2 %, 32 -0.4 %)
 constexpr int kDone = (int)0x80000000;
@@ -523,7 +523,9 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                 else b.hit[0][hs] = make_float2(bestT, __int_as_float(bestPrim));
                 hasRay = false;
                 if (STAT || MODE == 2) stRays++;
-                if (HIST) atomicAdd(&stat[kStatStepHist + (steps >= 252 ? 63 : steps >> 2)], 1ull);      // node steps of this ray (this launch), bins of 4
+                // node steps of this ray (this launch), bins of 4.  steps < 0: the ray spent its budget while the suspend pool was full and carried
+                // on (steps = -(1 << 28) above) — the last bin, never an index below the buffer
+                if (HIST) atomicAdd(&stat[kStatStepHist + ((steps < 0 || steps >= 252) ? 63 : steps >> 2)], 1ull);
             }
             PT_STCLK(4)
         }

@@ -408,6 +408,13 @@ class Scene:
         out[:, 1] = np.where(raw[:, 1] != 0, ~raw[:, 1], 0)
         return out
 
+    def trace_depth_hist(self):
+        """Diagnostic (PTAMD_TSTAT=1): over the wf_trace launches of the last render, how many node steps left the ray's traversal stack
+        with 0 .. 30 and with 31 or more entries (32 x int64).  Entries 16 and up lie in the stack's global-memory overflow."""
+        raw = np.zeros(32, np.int64)
+        _check(lib().pt_dbg_trace_timeline(self._h, _ptr(raw), -3001), "pt_dbg_trace_timeline")
+        return raw
+
     def nee(self, in5):
         """pt_dbg_nee: rows of (p.xyz, seed lo, seed hi as uint32 bits) -> (n, 12) float32 (see include/pt_api.h)."""
         a = np.ascontiguousarray(in5, np.float32).reshape(-1, 5)

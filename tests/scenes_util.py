@@ -288,6 +288,96 @@ def attribute_scene(seed, lat_lon=12):
     return prims, groups
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# needle_scene: long thin triangles whose boxes all overlap — a shallow tree whose traversal stack runs deep
+# ---------------------------------------------------------------------------------------------------------------------------------
+NEEDLE_CAMERA_POS = (0.0, 20.0, 40.0)      # make_camera(W, H, pos=NEEDLE_CAMERA_POS): the cube's front face covers the frame
+# 8192 needles already overflow the 16 LDS entries of wf_trace's stack for 0.76 of the camera rays, but only 0.013 of their node steps
+# are taken at a depth >= 16 (tools/stack_lab.cpp); at 16384 it is 0.029, three times the 0.01 tests/test_needle_scene.py asks of the device
+NEEDLE_N = 16384
+NEEDLE_SEED = 5
+
+
+def needle_positions(rs, n, side=30.0, centre=(0.0, 20.0, 0.0), centres=None):
+    """(n, 9) float32 vertex positions of n needles, and their (n, 3) float64 centres.  Needle i: centre c uniform in the cube (or
+    centres[i]), unit direction d from a normal draw, vertices c - 0.4 side d, c + 0.4 side d and c + 0.002 side t, t a unit vector
+    perpendicular to d."""
+    if centres is None:
+        centres = np.asarray(centre, np.float64) + rs.uniform(-0.5, 0.5, (n, 3)) * side
+    d = _unit64(rs.standard_normal((n, 3)))
+    t = _unit64(np.cross(d, rs.standard_normal((n, 3))))
+    pos = np.stack([centres - 0.4 * side * d, centres + 0.4 * side * d, centres + 0.002 * side * t], 1)
+    return pos.reshape(n, 9).astype(np.float32), centres
+
+
+def needle_scene(seed, n=NEEDLE_N, side=30.0, centre=(0.0, 20.0, 0.0)):
+    """n needles (needle_positions) in a cube of side `side` around `centre`, under a square light.  Returns ((n + 2, 84) float32
+    Primitive records, (n, 9) float32 needle positions, (n, 3) float64 needle centres); the needles come first, in order.
+
+    Every needle is 0.8 side long and 0.002 side wide, so its box overlaps most others': a ray hits three or four children at every
+    level of the 4-wide tree and its traversal stack fills at three entries per level, although the tree is shallow.
+    Albedo uniform in [0.2, 0.9] per needle; every eighth needle is a mirror (metallic 1, roughness 0).  The light: two emissive triangles,
+    a square of side `side` at y = centre_y + 0.75 side facing down, emittance 4 — shadow rays cross the whole stack of needles."""
+    rs = np.random.RandomState(seed)
+    pos, centres = needle_positions(rs, n, side, centre)
+    v = pos.reshape(n, 3, 3)
+    prims = make_prims(v[:, 0], v[:, 1], v[:, 2]).reshape(n, 3, 28)
+    prims[:, :, V_ALB:V_ALB + 3] = rs.uniform(0.2, 0.9, (n, 1, 3)).astype(np.float32)
+    prims[::8, :, V_MET] = 1.0
+    prims[::8, :, V_ROU] = 0.0
+    cx, cy, cz = (float(x) for x in centre)
+    y, h = cy + 0.75 * side, 0.5 * side
+    q = [(cx - h, y, cz - h), (cx + h, y, cz - h), (cx + h, y, cz + h), (cx - h, y, cz + h)]
+    down = np.array([0.0, -1.0, 0.0])
+    light = [make_prims(*(np.float32([x]) for x in _facing(q[i], q[j], q[k], down)), albedo=(0, 0, 0), emit=(4, 4, 4)) for i, j, k in ((0, 1, 2), (0, 2, 3))]
+    return np.ascontiguousarray(np.concatenate([prims.reshape(n, 84)] + light), np.float32), pos, centres
+
+
+def needle_inner_rays(rs, m, side=30.0, centre=(0.0, 20.0, 0.0)):
+    """2 m RAY8 records inside the needle cube: m rays from uniform points in unit normal directions with tmax 999999 (a path's bounce
+    rays), then m segments from one uniform point to another, tmax their length (a path's shadow rays)."""
+    c = np.asarray(centre, np.float64)
+    a, b, o = (c + rs.uniform(-0.5, 0.5, (m, 3)) * side for _ in range(3))
+    d = _unit64(rs.standard_normal((m, 3)))
+    seg = b - a
+    ln = np.sqrt((seg * seg).sum(1, keepdims=True))
+    rays = np.zeros((2 * m, 8), np.float32)
+    rays[:m, 0:3], rays[:m, 3:6], rays[:m, 7] = o, d, 999999.0
+    rays[m:, 0:3], rays[m:, 3:6], rays[m:, 7] = a, seg / ln, ln[:, 0]
+    return rays
+
+
+def pinhole_rays(cam):
+    """RAY8 records through the pixel centres of a camera (ptamd.make_camera or oracle_lib.make_camera), row-major, unit directions,
+    tmax 999999 — the camera path's rays without their jitter."""
+    W, H = cam.W, cam.H
+    f, u, r = (np.array(v[:], np.float64) for v in (cam.forward, cam.up, cam.right))
+    th = np.tan(0.5 * np.radians(float(cam.fovy_deg)))
+    py, px = np.mgrid[0:H, 0:W]
+    sx = (2.0 * (px.ravel() + 0.5) / W - 1.0) * th * float(cam.aspect)
+    sy = (1.0 - 2.0 * (py.ravel() + 0.5) / H) * th
+    d = _unit64(f[None, :] + sx[:, None] * r[None, :] + sy[:, None] * u[None, :])
+    rays = np.zeros((W * H, 8), np.float32)
+    rays[:, 0:3] = np.array(cam.pos[:], np.float32)
+    rays[:, 3:6] = d
+    rays[:, 7] = 999999.0
+    return rays
+
+
+REL_RMS_TOL = 1e-4          # north_star tolerance
+
+
+def check_image(img_g, img_o, what):
+    """The project's bar for a GPU frame against the oracle's (BASELINE.json north_star): every value finite, relative RMS within 1e-4
+    and at least 0.999 of the pixels bit-identical."""
+    rr = rel_rms(img_g, img_o)
+    same = (np.ascontiguousarray(img_g, np.float32).view(np.uint32) == np.ascontiguousarray(img_o, np.float32).view(np.uint32)).all(-1)
+    print(f"{what}: relRMS {rr:.3e}, bit-identical pixels {same.mean():.6f}")
+    assert np.isfinite(img_g).all()
+    assert rr <= REL_RMS_TOL, f"{what}: relative RMS {rr:.3e} > {REL_RMS_TOL}"
+    assert same.mean() >= 0.999, f"{what}: only {same.mean():.5f} of pixels bit-identical"
+
+
 def _prim_pos(prims, idx):
     return prims[idx].reshape(-1, 3, 28)[:, :, V_POS:V_POS + 3]
 

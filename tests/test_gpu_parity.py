@@ -14,12 +14,11 @@ import pytest
 import oracle_lib as O
 import ptamd
 from scenes_util import bxdf_inputs as _bxdf_inputs
-from scenes_util import rel_rms, scene_rays8
+from scenes_util import check_image as _check_image      # the bar: relative RMS <= 1e-4 and >= 0.999 of the pixels bit-identical
+from scenes_util import scene_rays8
 from scenes_util import test_spheres as make_test_spheres
 
 pytestmark = pytest.mark.gpu
-
-REL_RMS_TOL = 1e-4          # north_star tolerance
 
 
 def bits(a):
@@ -168,15 +167,6 @@ def test_closest_hit_big_scene_live():
     h_g, p_g = ptamd.Scene(nodes, tris, make_test_spheres()).raycast(rays)
     assert np.array_equal(p_g, p_o) and same_bits_or_nan(h_g, h_o).all()
     assert (p_o >= 0).mean() > 0.7
-
-
-def _check_image(img_g, img_o, what):
-    rr = rel_rms(img_g, img_o)
-    same = (bits(img_g) == bits(img_o)).all(-1)
-    print(f"{what}: relRMS {rr:.3e}, bit-identical pixels {same.mean():.6f}")
-    assert np.isfinite(img_g).all()
-    assert rr <= REL_RMS_TOL, f"{what}: relative RMS {rr:.3e} > {REL_RMS_TOL}"
-    assert same.mean() >= 0.999, f"{what}: only {same.mean():.5f} of pixels bit-identical"
 
 
 @pytest.mark.parametrize("name,kind", [("cornell", 0), ("standin24", 1), ("standin24_spheres", 1)])

@@ -113,11 +113,8 @@ void render_units(DevScene sc, DevCamera cam, DevParams prm, float* __restrict__
             bool pathDone = false;
             if (active && kind == KIND_SHADOW) {
                 // ---- NEE accumulate (GetLightColor tail + CudaUtil.cuh:271-272) ----
-                f3 Le(0.f, 0.f, 0.f);
-                if (prim >= 0) {
-                    const f3 hp = rorg + t * rdir;
-                    if (length(hp - lightP) < kEps) Le = prim_emittance(sc, prim);
-                }
+                const int seen = nee_verdict(rorg, rdir, lightP, t, prim);      // pt_shade.h: the one statement of the visibility test
+                const f3 Le = seen >= 0 ? prim_emittance(sc, seen) : f3(0.f, 0.f, 0.f);
                 if (neeOk) radiance += ((wb * Le) * cosA) / denom;
                 if (terminate) pathDone = true;
                 else { kind = KIND_PATH; rorg = nOrg; rdir = nDir; rtmax = 999999.f; }

@@ -147,16 +147,19 @@ PT_DEV NeeSample nee_sample(const DevScene& sc, Rng& rng, const f3& p)
     return n;
 }
 
-// GetLightColor's verdict (CudaUtil.cuh:157-165) from the shadow ray's closest hit (t, prim): the hit primitive's emittance (passed in:
-// the shade kernel fetches it ahead of time) if the hit point lies within EPS of the sampled light point, else black.
-PT_DEV f3 nee_light_color(const f3& shO, const f3& shD, const f3& lightP, float t, int prim, const f3& primEmittance)
+// GetLightColor's verdict (CudaUtil.cuh:157-165) on a shadow ray's closest hit (t, prim), formed where the ray ends — by whoever traced
+// it, with the ray still in registers: the primitive if the hit point lies within EPS of the sampled light point, else -1.  This is
+// what a shadow ray's hit record carries (t | verdict), so the step that applies the NEE term needs neither the ray nor the light point.
+PT_DEV int nee_verdict(const f3& shO, const f3& shD, const f3& lightP, float t, int prim)
 {
-    f3 Le(0.f, 0.f, 0.f);
-    if (prim >= 0) {
-        const f3 hp = shO + t * shD;
-        if (length(hp - lightP) < kEps) Le = primEmittance;
-    }
-    return Le;
+    if (prim < 0) return -1;
+    const f3 hp = shO + t * shD;
+    return (length(hp - lightP) < kEps) ? prim : -1;
+}
+// ... and its colour: the visible primitive's emittance (passed in: the shade kernel fetches it ahead of time), else black.
+PT_DEV f3 nee_light_color(int verdict, const f3& primEmittance)
+{
+    return verdict >= 0 ? primEmittance : f3(0.f, 0.f, 0.f);
 }
 
 // GetPixelDirection (srcs/pathtracer.cu:33-40) with the two jitter draws of StartRender (:72-73), then the Ray constructor's second

@@ -72,13 +72,13 @@ struct WfBuf {
     float4* dir0;        // camera ray direction of this pixel & pass (every sample of the pass shares it, Q2)
     float2* hit0;        // its closest hit, traced once: (t, primitive)
     float4* wb;          // weight*brdfcos of the pending NEE term
-    float4* lp;          // sampled light point of the pending NEE term
+    float4* lp;          // sampled light point of the pending NEE term (read by whoever traces the shadow ray; lpA = lp + n16: by kind, like the rays)
     float4* radA;        // older closed sample: radiance.xyz | denom
     float4* wbA;         //                      weight*brdfcos | cosA
     float4* lpA;         //                      light point
     float4* ray_o[kRayKinds];    // org.xyz | tmax
     float4* ray_d[kRayKinds];    // dir.xyz | shadow rays: the t below which any hit ends the traversal (shadow_stop_t); path rays: -inf
-    float2* hit[kRayKinds];      // t | primitive index (int bits); prim <= -2: traversal suspended, record -2-prim
+    float2* hit[kRayKinds];      // t | primitive index (int bits), of a shadow ray the verdict (nee_verdict: the primitive if it is the light point, else -1); prim <= -2: traversal suspended, record -2-prim
     uint32_t* active[2];         // live stream ids, ping-pong
     uint32_t* rq[kRayKinds];     // ray queues (stream ids)
     WfCounters* cnt;     // [3]
@@ -308,17 +308,15 @@ PT_DEV bool shade_step_t(const DevScene& sc, const CAM& cam, const DevParams& pr
     };
     // ---- a. the older closed sample: its last NEE term, then it joins the pixel ----
     if (flags & F_SHADOWA) {
-        const float4 ra = b.radA[sid], wa = b.wbA[sid], la = b.lpA[sid], ao = b.ray_o[2][sid], ad = b.ray_d[2][sid];
+        const float4 ra = b.radA[sid], wa = b.wbA[sid];
         f3 radA(ra.x, ra.y, ra.z);
-        const f3 Le = nee_light_color(f3(ao.x, ao.y, ao.z), f3(ad.x, ad.y, ad.z), f3(la.x, la.y, la.z), hitA.x, primA,
-                                      (primA < sc.n_tris) ? f3(emA.x, emA.y, emA.z) : prim_emittance(sc, primA < 0 ? 0 : primA));
+        const f3 Le = nee_light_color(primA, (primA < sc.n_tris) ? f3(emA.x, emA.y, emA.z) : prim_emittance(sc, primA < 0 ? 0 : primA));
         if (flags & F_NEEOKA) radA += ((f3(wa.x, wa.y, wa.z) * Le) * wa.w) / ra.w;      // GetLightColor tail + CudaUtil.cuh:271-272
         add_to_pixel(radA);
     }
     // ---- b. pending NEE term of the current sample ----
     if (flags & F_SHADOW) {
-        const f3 Le = nee_light_color(st.shO, st.shD, st.lightP, hitS.x, primS,
-                                      (primS < sc.n_tris) ? f3(emS.x, emS.y, emS.z) : prim_emittance(sc, primS < 0 ? 0 : primS));
+        const f3 Le = nee_light_color(primS, (primS < sc.n_tris) ? f3(emS.x, emS.y, emS.z) : prim_emittance(sc, primS < 0 ? 0 : primS));
         if (flags & F_NEEOK) st.radiance += ((st.wb * Le) * st.cosA) / st.denom;
     }
     bool cur = (flags & F_CUR) != 0;       // a current sample exists
@@ -469,9 +467,19 @@ PT_DEV void load_state(const WfBuf& b, uint32_t sid, SState& st)
     // never used): nearly every step has them, and waiting for the flags first only adds latency
     const float4 po = b.ray_o[0][sid], pd = b.ray_d[0][sid];
     st.pathO = f3(po.x, po.y, po.z); st.pathD = f3(pd.x, pd.y, pd.z);
-    const float4 so = b.ray_o[1][sid], sd = b.ray_d[1][sid], lpq = b.lp[sid], wbq = b.wb[sid];
+    const float4 wbq = b.wb[sid];
+    st.wb = f3(wbq.x, wbq.y, wbq.z);
+    // the shadow ray and the light point are not state a step reads: whoever traces the ray forms the verdict (pt_shade.h: nee_verdict),
+    // and the step only ever writes what bounce() produced
+    st.shO = f3(0.f, 0.f, 0.f); st.shD = f3(0.f, 0.f, 1.f); st.shTmax = 0.f; st.lightP = f3(0.f, 0.f, 0.f);
+}
+
+// The pending shadow ray of the current sample and its light point, for a kernel that traces the ray itself (wf_drain at the hand-over)
+PT_DEV void load_shadow_ray(const WfBuf& b, uint32_t sid, SState& st)
+{
+    const float4 so = b.ray_o[1][sid], sd = b.ray_d[1][sid], lpq = b.lp[sid];
     st.shO = f3(so.x, so.y, so.z); st.shD = f3(sd.x, sd.y, sd.z); st.shTmax = so.w;
-    st.lightP = f3(lpq.x, lpq.y, lpq.z); st.wb = f3(wbq.x, wbq.y, wbq.z);
+    st.lightP = f3(lpq.x, lpq.y, lpq.z);
 }
 
 PT_DEV void write_mean(const WfBuf& b, const DevParams& prm, uint32_t sid, const SState& st)

@@ -206,8 +206,9 @@ void wf_init_rays(DevScene sc, DevParams prm, WfBuf b, uint32_t nStreams, const 
 // (GetLightColor, CudaUtil.cuh:150-166: visible iff |hit.p - P| < EPS, with t_max = |P-p|+1).
 // Any hit at t < (t_max - 1) - 5e-4 proves the closest hit is at least ~4e-4 in front of P,
 // hence not within EPS = 1e-4 of it, so traversal may stop there; what is reported is then
-// some occluder, for which wf_shade's |hit.p - P| < EPS test fails exactly as it would for the
-// closest one.
+// some occluder, for which the |hit.p - P| < EPS test fails exactly as it would for the
+// closest one.  That test is made here, in the ray's epilogue (pt_shade.h: nee_verdict): the hit
+// record of a shadow ray carries the primitive only if it is the light point.
 // ---------------------------------------------------------------------------------------
 // STAT: a diagnostic build that also counts trips and the lanes they serve (pt_last_counters; PTAMD_TSTAT=1).
 template <int MODE, bool PUBLISH = false>      // PUBLISH: hits are stored device-coherently (wf_shade PHASE 1 reads them while this kernel drains);  MODE: 0 production, 1 trip counters + histograms + timeline (PTAMD_TSTAT=1), 2 timeline only (PTAMD_TSTAT=2), 3 trip counters + section clocks, no per-step atomics (PTAMD_TSTAT=3)
@@ -519,6 +520,17 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     float root;
                     if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; }
                 }
+                // A shadow ray (hs >= n16) that hit something: the verdict is formed here, where org, dir and t are still in registers — is the
+                // hit the sampled light point? — and the record carries the primitive only if it is (pt_shade.h: nee_verdict).  wf_shade then
+                // needs neither the ray nor the light point.  lp and lpA lie back to back like every per-kind array: lp[(kind - 1) n16 + sid].
+                // The light point is fetched here, not at the refill: it must not hold registers during the walk — and only for a hit that
+                // can be the light point at all: one below stopBelow is provably in front of it (pt_stream.h: shadow_stop_t, the argument
+                // the early stop rests on), so its verdict is known without it.
+                if (hs >= n16 && bestPrim >= 0 && bestT < stopBelow) bestPrim = -1;
+                if (hs >= n16 && bestPrim >= 0) {
+                    const float4 lq = b.lp[hs - n16];
+                    bestPrim = nee_verdict(org, dir, f3(lq.x, lq.y, lq.z), bestT, bestPrim);
+                }
                 if (PUBLISH) __hip_atomic_store((unsigned long long*)&b.hit[0][hs], (unsigned long long)__float_as_uint(bestT) | ((unsigned long long)(uint32_t)bestPrim << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 else b.hit[0][hs] = make_float2(bestT, __int_as_float(bestPrim));
                 hasRay = false;
@@ -709,6 +721,7 @@ void wf_drain(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int list
     const uint32_t sid = b.active[listIn][idx];
     SState st;
     load_state(b, sid, st);
+    load_shadow_ray(b, sid, st);      // this kernel traces the pending shadow ray itself (later ones come from bounce, in registers)
     for (;;) {
         float2 hitP = make_float2(0.f, __int_as_float(-1)), hitS = hitP, hitA = hitP;
         TraceStats ts{0, 0, 0};
@@ -717,7 +730,7 @@ void wf_drain(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int list
             // sets up its next one inside the loop, so the wave waits for the lane with the most steps in all — not, as with one
             // loop per ray kind, for the slowest lane of each kind in turn.
             int todo = ((st.flags & F_SHADOWA) ? 1 : 0) | ((st.flags & F_SHADOW) ? 2 : 0) | ((st.flags & F_PATH) ? 4 : 0);
-            f3 org(0.f, 0.f, 0.f), dir(0.f, 0.f, 1.f), inv(0.f, 0.f, 0.f);
+            f3 org(0.f, 0.f, 0.f), dir(0.f, 0.f, 1.f), inv(0.f, 0.f, 0.f), lightP(0.f, 0.f, 0.f);      // lightP: the light point a shadow ray aims at
             float cscale = 0.f, bestT = 0.f, stopBelow = 0.f;
             bool degenerate = false;
             int bestPrim = -1, cur = 0, sp = 0, kind = -1;
@@ -726,9 +739,9 @@ void wf_drain(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int list
                     if (todo == 0) break;
                     kind = __builtin_ctz((unsigned)todo); todo &= todo - 1;
                     if (kind == 0) {
-                        const float4 ao = b.ray_o[2][sid], ad = b.ray_d[2][sid];
-                        org = f3(ao.x, ao.y, ao.z); dir = f3(ad.x, ad.y, ad.z); bestT = ao.w; stopBelow = ad.w;
-                    } else if (kind == 1) { org = st.shO; dir = st.shD; bestT = st.shTmax; stopBelow = shadow_stop_t(st.shO, st.shTmax); }
+                        const float4 ao = b.ray_o[2][sid], ad = b.ray_d[2][sid], la = b.lpA[sid];
+                        org = f3(ao.x, ao.y, ao.z); dir = f3(ad.x, ad.y, ad.z); bestT = ao.w; stopBelow = ad.w; lightP = f3(la.x, la.y, la.z);
+                    } else if (kind == 1) { org = st.shO; dir = st.shD; bestT = st.shTmax; stopBelow = shadow_stop_t(st.shO, st.shTmax); lightP = st.lightP; }
                     else { org = st.pathO; dir = st.pathD; bestT = primary_tmax(cam, b, sid, st.flags); stopBelow = -__builtin_inff(); }
                     ray_setup(dir, inv, cscale, degenerate);
                     bestPrim = -1; cur = 0; sp = 0;
@@ -739,6 +752,7 @@ void wf_drain(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int list
                         float root;
                         if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; }
                     }
+                    if (kind != 2) bestPrim = nee_verdict(org, dir, lightP, bestT, bestPrim);      // a shadow ray's record carries the verdict
                     const float2 h = make_float2(bestT, __int_as_float(bestPrim));
                     if (kind == 0) hitA = h; else if (kind == 1) hitS = h; else hitP = h;
                     kind = -1;
@@ -746,10 +760,11 @@ void wf_drain(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int list
             }
         } else {
         if (st.flags & F_SHADOWA) {
-            const float4 ao = b.ray_o[2][sid], ad = b.ray_d[2][sid];
-            float t; const int prim = trace_closest<false>(sc, f3(ao.x, ao.y, ao.z), f3(ad.x, ad.y, ad.z), ao.w, stack, t, ts); hitA = make_float2(t, __int_as_float(prim));
+            const float4 ao = b.ray_o[2][sid], ad = b.ray_d[2][sid], la = b.lpA[sid];
+            const f3 o(ao.x, ao.y, ao.z), d(ad.x, ad.y, ad.z);
+            float t; const int prim = trace_closest<false>(sc, o, d, ao.w, stack, t, ts); hitA = make_float2(t, __int_as_float(nee_verdict(o, d, f3(la.x, la.y, la.z), t, prim)));
         }
-        if (st.flags & F_SHADOW) { float t; const int prim = trace_closest<false>(sc, st.shO, st.shD, st.shTmax, stack, t, ts); hitS = make_float2(t, __int_as_float(prim)); }
+        if (st.flags & F_SHADOW) { float t; const int prim = trace_closest<false>(sc, st.shO, st.shD, st.shTmax, stack, t, ts); hitS = make_float2(t, __int_as_float(nee_verdict(st.shO, st.shD, st.lightP, t, prim))); }
         if (st.flags & F_PATH) { float t; const int prim = trace_closest<false>(sc, st.pathO, st.pathD, primary_tmax(cam, b, sid, st.flags), stack, t, ts); hitP = make_float2(t, __int_as_float(prim)); }
         }
         if (shade_step(sc, cam, prm, b, sid, st, hitP, hitS, hitA)) break;
@@ -815,7 +830,7 @@ void dbg_nee(DevScene sc, const float* __restrict__ in5, int n, float* __restric
     const float tmax = length(ns.toL) + 1.0f;                               // GetLightColor, CudaUtil.cuh:152-157
     float t; TraceStats ts{0, 0, 0};
     const int prim = trace_closest<false>(sc, p, ns.wl, tmax, stack, t, ts);
-    const f3 Le = nee_light_color(p, ns.wl, ns.lightP, t, prim, prim_emittance(sc, prim < 0 ? 0 : prim));
+    const f3 Le = nee_light_color(nee_verdict(p, ns.wl, ns.lightP, t, prim), prim_emittance(sc, prim < 0 ? 0 : prim));
     float* o = out12 + (size_t)i * 12;
     o[0] = __int_as_float(ns.li); o[1] = ns.lightP.x; o[2] = ns.lightP.y; o[3] = ns.lightP.z; o[4] = ns.pdfLight; o[5] = ns.cosA;
     o[6] = tmax; o[7] = __int_as_float(prim); o[8] = Le.x; o[9] = Le.y; o[10] = Le.z; o[11] = rng.uniform();
@@ -859,8 +874,9 @@ static void carve(char* p, size_t nStreams, int traceBlocks, ptd::WfBuf& b)
     auto take = [&](size_t bytes) { char* q = p; p += (bytes + 15) & ~(size_t)15; return q; };
     b.rng0 = (uint4*)take(n16 * 16); b.rng1 = (uint4*)take(n16 * 16);
     b.weight = (float4*)take(n16 * 16); b.rad = (float4*)take(n16 * 16); b.pix = (float4*)take(n16 * 16);
-    b.dir0 = (float4*)take(n16 * 16); b.wb = (float4*)take(n16 * 16); b.lp = (float4*)take(n16 * 16);
-    b.radA = (float4*)take(n16 * 16); b.wbA = (float4*)take(n16 * 16); b.lpA = (float4*)take(n16 * 16);
+    b.dir0 = (float4*)take(n16 * 16); b.wb = (float4*)take(n16 * 16);
+    b.radA = (float4*)take(n16 * 16); b.wbA = (float4*)take(n16 * 16);
+    b.lp = (float4*)take(n16 * 16); b.lpA = (float4*)take(n16 * 16);      // back to back: wf_trace reads lp[(kind - 1) n16 + stream]
     for (int k = 0; k < ptd::kRayKinds; k++) { b.ray_o[k] = (float4*)take(n16 * 16); b.ray_d[k] = (float4*)take(n16 * 16); }
     for (int k = 0; k < ptd::kRayKinds; k++) b.hit[k] = (float2*)take(n16 * 8);
     b.hit0 = (float2*)take(n16 * 8);

@@ -423,14 +423,15 @@ PT_API int  pt_render_views_host(PtScene* s, const PtCamera* h_cams, int32_t n_v
  *   area = len * 0.5f; the frames, if given.  nodes' = nodes with every leaf's box the min / max over its triangles in index
  *   order, mn = min2(mn, min2(a, min2(b, c))), min2(a, b) = b < a ? b : a, starting from FLT_MAX / lowest, and every interior box
  *   min2 / max2 of its children (childR first).  Positions must be finite; a zero-area triangle gets a NaN normal as on the host.
- *   Materials, uv, the topology of both trees, the number of triangles and the set of emissive triangles stay as uploaded.
+ *   Materials, uv, the topology of both trees, the number of triangles and the set of emissive triangles stay as they are
+ *   (as uploaded, or as the last pt_scene_update_materials left them).
  *   Every kernel is enqueued on `hip_stream` on the scene's device; no host synchronisation, nothing is read back, and nothing
  *   is allocated after the first call (which allocates and uploads the maps of the build: pt_scene_device_bytes includes them
  *   from then on).  A render enqueued on the same stream afterwards sees the new geometry; d_pos / d_frames must stay valid
  *   until the stream has passed the update.  One update or render at a time per scene.
  * pt_scene_update_vertices_host: h_pos / h_frames are HOST arrays; uploads them, updates on the NULL stream and waits.
  * pt_scene_update_spheres: a HOST array of the scene's sphere count; centre and radius may change, the material bytes must be
- *   those uploaded (else PT_ERR_INVALID).  A stream-ordered copy on the NULL stream.
+ *   those uploaded, or those of the last pt_scene_update_sphere_materials (else PT_ERR_INVALID).  A stream-ordered copy on the NULL stream.
  * pt_scene_tree_inflation: *ratio = sum of the surface areas (float32 each, summed in float64 in a fixed order) of all boxes of
  *   the binary traversal tree now / the same sum at upload: the caller's signal that refits have degraded the tree and a new
  *   pt_scene_create is due.  Exactly 1.0 for a scene never updated.  Otherwise waits for the whole device (hipDeviceSynchronize: the
@@ -440,14 +441,57 @@ PT_API int  pt_render_views_host(PtScene* s, const PtCamera* h_cams, int32_t n_v
  *   csrc/pt_device.h).  Returns the array's size in bytes and writes at most cap_bytes (h_out may be NULL when cap_bytes is 0).
  * NULL scene, NULL d_pos / h_pos / h_spheres / ratio, n_spheres different from the scene's and an unknown `which` return
  * PT_ERR_INVALID before any HIP call.
- * Out of scope: a change of the triangle count, the materials or the set of emissive triangles; a rebuild on the GPU or an
- * automatic one; a tile-split update (every rank updates its own scene).
+ * Out of scope: a change of the triangle count; a rebuild on the GPU or an automatic one; a tile-split update (every rank updates
+ * its own scene).  The materials and the set of emissive triangles change through the calls of the next section.
  * -------------------------------------------------------------------------------- */
 PT_API int  pt_scene_update_vertices(PtScene* s, const float* d_pos, const float* d_frames, void* hip_stream);
 PT_API int  pt_scene_update_vertices_host(PtScene* s, const float* h_pos, const float* h_frames);
 PT_API int  pt_scene_update_spheres(PtScene* s, const PtSphere* h_spheres, int32_t n_spheres);
 PT_API int  pt_scene_tree_inflation(PtScene* s, double* ratio);
 PT_API int64_t pt_dbg_scene_array(PtScene* s, int32_t which, void* h_out, int64_t cap_bytes);
+
+/* ----------------------------------------------------------------------------------
+ * Materials and lights of an uploaded scene (new: the reference uploads a scene once).  Opt-in: every call above is as it was.
+ * A lamp switched on, a light dimmed, a wall recoloured, without pt_scene_create and its tree build: a render reads a material
+ * only in floats 36..47 of the surface record and in the `lights` array with its count and the pruning flag, and no traversal
+ * array depends on one (csrc/pt_material.hip).
+ *
+ * pt_scene_update_materials: d_mat12 is a DEVICE pointer to n_tris x 12 float32, one PtMaterial per triangle in the order of the
+ *   `tris` given to pt_scene_create: emittance albedo specular opacity roughness metallic.  All three vertex materials of
+ *   triangle i become that material m_i.  After the call the scene is, for every entry point (pt_render*, pt_render_aov,
+ *   pt_render_views, pt_render_rays, pt_render_tile_list, pt_render_adaptive, pt_trace_rays with surface records, pt_dbg_raycast,
+ *   pt_dbg_nee, both render modes), the scene pt_scene_create(nodes_cur, tris', spheres_cur) would give.  tris' = the scene's
+ *   current triangles — as uploaded, or as the last pt_scene_update_vertices left them, normal and area restated from the current
+ *   positions by that call's expressions — with mat0 = mat1 = mat2 = m_i.  So: surface-record floats 36..47 become m_i; triangle
+ *   i is a light iff sqrtf((ex*ex + ey*ey) + ez*ez) > 0.0001f for its new emittance, in float32, every operation rounded once (a
+ *   NaN makes no light); `lights` holds the records V0 V1 V2 normal area 0 0 0 of the lights in ascending triangle index, made
+ *   from the scene's own copy of the current positions; pt_scene_num_lights and the lights a later vertex update moves follow
+ *   the new set; the pruning flag (pt_scene_nee_prune) is 1 iff every triangle's new emittance and every sphere's emittance is
+ *   finite, >= 0 and <= 1e8 and PTAMD_PRUNE is not 0.  The traversal arrays, uv, the shading schedule and the core box are
+ *   untouched.  A scene may end up with no light: it then behaves like a scene created so (renders and pt_dbg_nee return
+ *   PT_ERR_NO_LIGHT, queries and AOVs work), and a later update may bring lights back.
+ *   Every kernel is enqueued on `hip_stream` on the scene's device.  The call waits for that stream ONCE: the number of lights
+ *   and the flag are kernel arguments of every later render, so 8 bytes are read back, and the same number sizes `lights`.
+ *   d_mat12 is free when the call returns; the light records are written in stream order after it, so a render enqueued on the
+ *   same stream sees them.  `lights` grows on demand and never shrinks (pt_scene_device_bytes follows); an update with no more
+ *   lights than any earlier one allocates nothing, except that the first update of either kind uploads the maps of the build and
+ *   the positions, as pt_scene_update_vertices states.  One update, query or render at a time per scene.  After PT_ERR_DEVICE
+ *   the materials of the scene are unspecified: update again or destroy it.
+ * pt_scene_update_materials_host: h_mat12 is a HOST array; uploads it, updates on the NULL stream and waits.
+ * pt_scene_update_sphere_materials: a HOST array of the scene's sphere count; centre, radius and material may all change.  A
+ *   stream-ordered copy on the NULL stream; the pruning flag is formed again from these spheres and the triangles' current
+ *   materials.  pt_scene_update_spheres compares against these materials from then on.
+ * pt_scene_nee_prune (parity hook): the pruning flag as the next render will see it; 0 for NULL.
+ * NULL scene, NULL d_mat12 / h_mat12 / h_spheres and n_spheres different from the scene's return PT_ERR_INVALID before any HIP
+ * call; the pointers are not dereferenced on that path.
+ * Out of scope: per-vertex materials that differ within a triangle (the device shades with mat0 alone); a change of the
+ * triangle or sphere count; a tile-split update (every rank updates its own scene); a ptrender option; asynchronous operation
+ * without the one wait.
+ * -------------------------------------------------------------------------------- */
+PT_API int  pt_scene_update_materials(PtScene* s, const float* d_mat12, void* hip_stream);
+PT_API int  pt_scene_update_materials_host(PtScene* s, const float* h_mat12);
+PT_API int  pt_scene_update_sphere_materials(PtScene* s, const PtSphere* h_spheres, int32_t n_spheres);
+PT_API int32_t pt_scene_nee_prune(const PtScene* s);
 
 /* ----------------------------------------------------------------------------------
  * Ray queries (new: the reference casts rays only from inside its integrator).  Opt-in: every call above is as it was.

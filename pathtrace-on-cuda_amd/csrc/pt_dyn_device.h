@@ -1,0 +1,41 @@
+// pt_dyn_device.h — the device expressions that the vertex update (pt_dynamic.hip) and the material update (pt_material.hip) share:
+// a triangle's nine position floats, its edges and its light record.  They are the host's own expressions (host/bvh_build.cpp:
+// flatten_tri) and are stated once, so that a light record comes out with the same bits whichever update writes it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace ptd {
+
+struct Tri9 { float v0[3], v1[3], v2[3]; };
+struct Edges { float e1[3], e2[3]; };
+
+__device__ __forceinline__ Tri9 load_tri(const float* __restrict__ pos, int prim)
+{
+    const float* p = pos + (size_t)prim * 9;
+    Tri9 t;
+    for (int k = 0; k < 3; k++) { t.v0[k] = p[k]; t.v1[k] = p[3 + k]; t.v2[k] = p[6 + k]; }
+    return t;
+}
+__device__ __forceinline__ Edges edges_of(const Tri9& t)
+{
+    Edges e;
+    for (int k = 0; k < 3; k++) { e.e1[k] = t.v1[k] - t.v0[k]; e.e2[k] = t.v2[k] - t.v0[k]; }
+    return e;
+}
+
+// the 64-byte light record of triangle t: V0 V1 V2 normal area 0 0 0
+__device__ __forceinline__ void write_light(float4* r, const Tri9& t)
+{
+    const Edges e = edges_of(t);
+    // bvh_build.cpp: flatten_tri (the reference's component forms, CudaVector.cuh:109-113)
+    const float cx = e.e1[1] * e.e2[2] - e.e1[2] * e.e2[1];
+    const float cy = -(e.e1[0] * e.e2[2] - e.e1[2] * e.e2[0]);
+    const float cz = e.e1[0] * e.e2[1] - e.e1[1] * e.e2[0];
+    const float len = sqrtf(cx * cx + cy * cy + cz * cz);
+    r[0] = make_float4(t.v0[0], t.v0[1], t.v0[2], t.v1[0]);
+    r[1] = make_float4(t.v1[1], t.v1[2], t.v2[0], t.v2[1]);
+    r[2] = make_float4(t.v2[2], cx / len, cy / len, cz / len);
+    r[3] = make_float4(len * 0.5f, 0.f, 0.f, 0.f);
+}
+
+}  // namespace ptd

@@ -20,33 +20,22 @@
 #include <vector>
 
 #include "pt_scene.h"
+#include "pt_dyn_device.h"
 #include "../host/accel_build.h"
 
 namespace {
 
 using ptd::DynScene;
+using ptd::Tri9;
+using ptd::Edges;
+using ptd::load_tri;
+using ptd::edges_of;
 
 __device__ __forceinline__ float min2(float x, float y) { return (y < x) ? y : x; }      // glm::min / std::min
 __device__ __forceinline__ float max2(float x, float y) { return (x < y) ? y : x; }      // glm::max / std::max
 __device__ __forceinline__ float pad_lo(float v) { return v - (fabsf(v) * 1.52587890625e-5f + 1e-30f); }      // accel_build.cpp
 __device__ __forceinline__ float pad_hi(float v) { return v + (fabsf(v) * 1.52587890625e-5f + 1e-30f); }
 
-struct Tri9 { float v0[3], v1[3], v2[3]; };
-struct Edges { float e1[3], e2[3]; };
-
-__device__ __forceinline__ Tri9 load_tri(const float* __restrict__ pos, int prim)
-{
-    const float* p = pos + (size_t)prim * 9;
-    Tri9 t;
-    for (int k = 0; k < 3; k++) { t.v0[k] = p[k]; t.v1[k] = p[3 + k]; t.v2[k] = p[6 + k]; }
-    return t;
-}
-__device__ __forceinline__ Edges edges_of(const Tri9& t)
-{
-    Edges e;
-    for (int k = 0; k < 3; k++) { e.e1[k] = t.v1[k] - t.v0[k]; e.e2[k] = t.v2[k] - t.v0[k]; }
-    return e;
-}
 __device__ __forceinline__ void grow(float* mn, float* mx, const Tri9& t)
 {
     for (int d = 0; d < 3; d++) {
@@ -67,11 +56,14 @@ __global__ __launch_bounds__(256) void dyn_leafbox(DynScene s, const float* __re
     s.leafbox[(size_t)i * 2 + 1] = make_float4(mx[1], mx[2], 0.f, 0.f);
 }
 
-__global__ __launch_bounds__(256) void dyn_surf(DynScene s, const float* __restrict__ pos, const float* __restrict__ frames)
+// ... and the scene's own copy of the positions (`keep`): a material update makes light records from it (pt_material.hip)
+__global__ __launch_bounds__(256) void dyn_surf(DynScene s, const float* __restrict__ pos, const float* __restrict__ frames, float* __restrict__ keep)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= s.n_tris) return;
     const Tri9 t = load_tri(pos, i);
+    float* k9 = keep + (size_t)i * 9;
+    for (int k = 0; k < 3; k++) { k9[k] = t.v0[k]; k9[3 + k] = t.v1[k]; k9[6 + k] = t.v2[k]; }
     const Edges e = edges_of(t);
     float4* rec = s.surf + (size_t)i * 12;
     rec[0] = make_float4(t.v0[0], t.v0[1], t.v0[2], e.e1[0]);
@@ -117,18 +109,7 @@ __global__ __launch_bounds__(64) void dyn_lights(DynScene s, const float* __rest
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= s.n_lights) return;
-    const Tri9 t = load_tri(pos, s.light_prim[i]);
-    const Edges e = edges_of(t);
-    // bvh_build.cpp: flatten_tri (the reference's component forms, CudaVector.cuh:109-113)
-    const float cx = e.e1[1] * e.e2[2] - e.e1[2] * e.e2[1];
-    const float cy = -(e.e1[0] * e.e2[2] - e.e1[2] * e.e2[0]);
-    const float cz = e.e1[0] * e.e2[1] - e.e1[1] * e.e2[0];
-    const float len = sqrtf(cx * cx + cy * cy + cz * cz);
-    float4* r = s.lights + (size_t)i * 4;
-    r[0] = make_float4(t.v0[0], t.v0[1], t.v0[2], t.v1[0]);
-    r[1] = make_float4(t.v1[1], t.v1[2], t.v2[0], t.v2[1]);
-    r[2] = make_float4(t.v2[2], cx / len, cy / len, cz / len);
-    r[3] = make_float4(len * 0.5f, 0.f, 0.f, 0.f);
+    ptd::write_light(s.lights + (size_t)i * 4, load_tri(pos, s.light_prim[i]));
 }
 
 // ---- binary traversal tree: unpadded boxes, one launch per height -------------------------------------------------------------
@@ -310,11 +291,11 @@ static_assert(ptd::kCoreBlocks == 256, "dyn_core_final reads one partial per thr
 static_assert(kAreaBlock == 1024, "dyn_area folds 4 boxes per thread of a 256-thread block");
 
 // Enqueues the whole update on `stream`.  level_start: host array of n_levels + 1 offsets into `order` (height h = one launch).
-static hipError_t launch_update(const DynScene& s, const float* d_pos, const float* d_frames, const int32_t* level_start, int n_levels, hipStream_t stream)
+static hipError_t launch_update(const DynScene& s, const float* d_pos, const float* d_frames, float* d_keep, const int32_t* level_start, int n_levels, hipStream_t stream)
 {
     // records: the leaf boxes first, the pair records carry them inline
     hipLaunchKernelGGL(dyn_leafbox, dim3(blocks_of(s.n_leaves, 256)), dim3(256), 0, stream, s, d_pos);
-    hipLaunchKernelGGL(dyn_surf, dim3(blocks_of(s.n_tris, 256)), dim3(256), 0, stream, s, d_pos, d_frames);
+    hipLaunchKernelGGL(dyn_surf, dim3(blocks_of(s.n_tris, 256)), dim3(256), 0, stream, s, d_pos, d_frames, d_keep);
     hipLaunchKernelGGL(dyn_tri, dim3(blocks_of(s.n_tris, 256)), dim3(256), 0, stream, s, d_pos);
     if (s.n_lights > 0) hipLaunchKernelGGL(dyn_lights, dim3(blocks_of(s.n_lights, 64)), dim3(64), 0, stream, s, d_pos);
     // binary tree, bottom up
@@ -331,18 +312,22 @@ static hipError_t launch_update(const DynScene& s, const float* d_pos, const flo
     return hipGetLastError();
 }
 
-// First update of a scene: the maps of the build go to the device and the scratch is allocated; the host copies are dropped.
-static int dyn_prepare(PtScene* s)
+// First update of a scene, of its vertices or of its materials: the maps of the build and the positions go to the device and the
+// scratch is allocated; the host copies are dropped.
+int pt_dyn_prepare(PtScene* s)
 {
     if (s->dyn_ready) return PT_OK;
     PtScene::DynHost& h = s->dyn_host;
     ptd::DynScene& d = s->dyn;
     const size_t area_blocks = ((size_t)d.n_bn + kAreaBlock - 1) / kAreaBlock;
-    // in the order of enum DynAlloc: the maps with their host source, then the scratch (area_partial: (n_bn + 1023) / 1024 doubles)
+    const size_t mat_blocks = ((size_t)d.n_tris + kMatBlock - 1) / kMatBlock;
+    // in the order of enum DynAlloc: the maps and the positions with their host source, then the scratch (area_partial: (n_bn + 1023) / 1024
+    // doubles; the material update's partials: one int2 per kMatBlock triangles and one for the total)
     const struct { const void* src; size_t bytes; } plan[kDynAllocs] = {
         {h.bn.data(), h.bn.size() * 4}, {h.order.data(), h.order.size() * 4}, {h.wide_bn.data(), h.wide_bn.size() * 4}, {h.quad_bn.data(), h.quad_bn.size() * 4},
         {h.leaf_range.data(), h.leaf_range.size() * 4}, {h.tmap.data(), h.tmap.size() * 4}, {h.light_prim.data(), h.light_prim.size() * 4}, {h.small.data(), h.small.size()},
-        {nullptr, (size_t)d.n_bn * 32}, {nullptr, 16}, {nullptr, (size_t)ptd::kCoreBlocks * 32}, {nullptr, area_blocks * 8}};
+        {h.pos.data(), h.pos.size() * 4},
+        {nullptr, (size_t)d.n_bn * 32}, {nullptr, 16}, {nullptr, (size_t)ptd::kCoreBlocks * 32}, {nullptr, area_blocks * 8}, {nullptr, (mat_blocks + 1) * 8}};
     // built beside the scene and moved in only once all of them exist: a failure frees what it got and leaves the scene as it was,
     // byte count included, and a later update may try again
     DevBuf fresh[kDynAllocs];
@@ -352,6 +337,7 @@ static int dyn_prepare(PtScene* s)
         HIPCHK(k < kDynBbox ? fresh[k].upload(plan[k].src, plan[k].bytes) : fresh[k].alloc(plan[k].bytes));
         bytes += (int64_t)fresh[k].held();
     }
+    if (!s->h_mat) HIPCHK(hipHostMalloc((void**)&s->h_mat, 8, hipHostMallocDefault));
     DevBuf* b = s->dyn_buf;
     for (int k = 0; k < kDynAllocs; k++) b[k] = std::move(fresh[k]);
     s->bytes += bytes;
@@ -362,6 +348,7 @@ static int dyn_prepare(PtScene* s)
     s->h_area.assign(area_blocks, 0.0);
     for (std::vector<int32_t>* v : {&h.bn, &h.order, &h.wide_bn, &h.quad_bn, &h.leaf_range, &h.tmap, &h.light_prim}) std::vector<int32_t>().swap(*v);
     std::vector<uint8_t>().swap(h.small);      // level_start stays: the launch sequence reads it
+    std::vector<float>().swap(h.pos);
     s->dyn_ready = true;
     return PT_OK;
 }
@@ -374,9 +361,9 @@ int pt_scene_update_vertices(PtScene* s, const float* d_pos, const float* d_fram
     if (!s || !d_pos) { pt_set_error("pt_scene_update_vertices: NULL %s", !s ? "scene" : "d_pos"); return PT_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     int rc;
-    if ((rc = dyn_prepare(s)) != PT_OK) return rc;
+    if ((rc = pt_dyn_prepare(s)) != PT_OK) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(launch_update(s->dyn, d_pos, d_frames, s->dyn_host.level_start.data(), (int)s->dyn_host.level_start.size() - 1, st));
+    HIPCHK(launch_update(s->dyn, d_pos, d_frames, s->dyn_buf[kDynPos].as<float>(), s->dyn_host.level_start.data(), (int)s->dyn_host.level_start.size() - 1, st));
     s->updated = true;
     return PT_OK;
 }
@@ -402,7 +389,7 @@ int pt_scene_update_spheres(PtScene* s, const PtSphere* h_spheres, int32_t n_sph
         pt_set_error("pt_scene_update_spheres: %d spheres given, the scene has %d", n_spheres, s->dev.n_spheres);
         return PT_ERR_INVALID;
     }
-    for (int i = 0; i < n_spheres; i++)
+    for (int i = 0; i < n_spheres; i++)      // h_spheres: as uploaded, or as the last pt_scene_update_sphere_materials left them
         if (memcmp(&h_spheres[i].mat, &s->h_spheres[(size_t)i * 16 + 4], sizeof(PtMaterial)) != 0) {
             pt_set_error("pt_scene_update_spheres: the material of sphere %d differs from the uploaded one (only centre and radius may change)", i);
             return PT_ERR_INVALID;

@@ -2,15 +2,18 @@
 // the state of the dynamic-geometry path.  Built by pt_scene.hip (pt_scene_create); included by every file whose entry points take a scene.
 // Everything the scene owns is released by its destructor, whichever path deletes it.
 #pragma once
+#include <cstdlib>
 #include <vector>
 
 #include "pt_internal.h"
 
 // The device arrays a render reads (layouts: pt_device.h), in the order of pt_dbg_scene_array's `which` and of ptamd.SCENE_ARRAYS.
 enum SceneArray { kArrNodes, kArrQuad, kArrTri, kArrTripair, kArrLeafbox, kArrSurf, kArrLights, kArrSpheres, kArrCore, kSceneArrays };
-// The allocations of the first vertex update (pt_dynamic.hip: dyn_prepare): the 8 maps of the build, then 4 scratch arrays.
-enum DynAlloc { kDynBn, kDynOrder, kDynWideBn, kDynQuadBn, kDynLeafRange, kDynTmap, kDynLightPrim, kDynSmall,
-                kDynBbox, kDynMaxabs, kDynCorePartial, kDynAreaPartial, kDynAllocs };
+// The allocations of the first update (pt_dynamic.hip: pt_dyn_prepare): the 8 maps of the build and the position mirror, which come
+// from the host, then 5 scratch arrays.  kDynLightPrim grows with the set of lights (pt_material.hip).
+constexpr int kMatBlock = 256;      // triangles per block of the material update: kDynMatPartial holds one int2 per block and one more
+enum DynAlloc { kDynBn, kDynOrder, kDynWideBn, kDynQuadBn, kDynLeafRange, kDynTmap, kDynLightPrim, kDynSmall, kDynPos,
+                kDynBbox, kDynMaxabs, kDynCorePartial, kDynAreaPartial, kDynMatPartial, kDynAllocs };
 
 struct PtScene {
     int device = 0;
@@ -45,9 +48,10 @@ struct PtScene {
     int ev_count = 0;        // launches recorded since the last pt_render_timings(reset)
     // ---- dynamic geometry (pt_scene_update_vertices, csrc/pt_dynamic.hip) ----
     std::vector<float> h_spheres;        // the uploaded sphere records: pt_scene_update_spheres checks the materials against them and copies from here
-    struct DynHost {                     // the maps of the build, kept on the host until the first update uploads them
+    struct DynHost {                     // the maps of the build and the positions, kept on the host until the first update uploads them
         std::vector<int32_t> bn, order, level_start, wide_bn, quad_bn, leaf_range, tmap, light_prim;
         std::vector<uint8_t> small;
+        std::vector<float> pos;          // V0 V1 V2 per triangle (reference order): becomes the device mirror kDynPos, which every vertex update refreshes
         double area_sum = 0.0;
     } dyn_host;
     ptd::DynScene dyn{};                 // device side of the same: the rewritten arrays from upload on, the maps and scratch once dyn_ready
@@ -55,6 +59,9 @@ struct PtScene {
     bool dyn_ready = false;
     bool updated = false;
     std::vector<double> h_area;          // host image of dyn.area_partial
+    // ---- materials and lights (pt_scene_update_materials, csrc/pt_material.hip) ----
+    bool tri_emit_ok = true;             // emittance_ok's test over the triangles alone, from pt_scene_create or the last material update (the spheres' part: h_spheres)
+    int32_t* h_mat = nullptr;            // pinned, 2 words: the light count and the flag a material update reads back (pt_dyn_prepare)
     // ---- ray queries (pt_trace_rays, csrc/pt_query.hip) ----
     bool query_quad = true;              // walk the 4-wide tree when it fits the kernel's stack (PTAMD_QUERY_QUAD=0: the binary tree, A/B)
 
@@ -63,5 +70,11 @@ struct PtScene {
     {
         for (int i = 0; i < kEvRing; i++) for (int j = 0; j < 2; j++) if (ev[i][j]) (void)hipEventDestroy(ev[i][j]);
         for (hipEvent_t e : trace_ev) if (e) (void)hipEventDestroy(e);
+        if (h_mat) (void)hipHostFree(h_mat);
     }
 };
+
+// DevScene::nee_prune may be 1 unless PTAMD_PRUNE=0 (A/B only); read whenever the flag is formed
+inline bool pt_prune_allowed() { const char* m = getenv("PTAMD_PRUNE"); return !(m && atoi(m) == 0); }
+// pt_dynamic.hip: the first update of either kind brings the maps and the position mirror to the device (no-op afterwards)
+int pt_dyn_prepare(PtScene* s);

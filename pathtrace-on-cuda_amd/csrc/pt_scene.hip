@@ -98,12 +98,14 @@ static std::vector<float> pack_spheres(const PtSphere* spheres, int32_t n_sphere
 // enough that (weight * brdfcos) * Le cannot overflow where the pruned case assumes it is finite: |wb| < 1e30 and Le <= 1e8 give
 // |wb * Le| < 1e38 < FLT_MAX.  (With a brighter light wb * Le can be inf, inf * 0 is NaN, and the reference adds that NaN to the
 // radiance, include/CudaUtil.cuh:271-272; such scenes keep all their shadow rays.)
-static bool emittance_ok(const PtTriangle* tris, int32_t n_tris, const PtSphere* spheres, int32_t n_spheres)
+// triOk: the triangles' part alone, which a material update of the spheres combines with the new spheres (pt_material.hip).
+static bool emittance_ok(const PtTriangle* tris, int32_t n_tris, const PtSphere* spheres, int32_t n_spheres, bool& triOk)
 {
     bool emitOk = true;
     auto okE = [](const float* e) { return std::isfinite(e[0]) && std::isfinite(e[1]) && std::isfinite(e[2]) && e[0] >= 0.f && e[1] >= 0.f && e[2] >= 0.f &&
                                            e[0] <= 1e8f && e[1] <= 1e8f && e[2] <= 1e8f; };
     for (int i = 0; i < n_tris; i++) emitOk = emitOk && okE(tris[i].mat0.emittance);
+    triOk = emitOk;
     for (int i = 0; i < n_spheres; i++) emitOk = emitOk && okE(spheres[i].mat.emittance);
     return emitOk;
 }
@@ -183,7 +185,7 @@ static void apply_defaults(PtScene* sc, int32_t n_tris, bool emitOk)
     sc->shade_rounds = ((size_t)n_tris * 192 <= ((size_t)2 << 20)) ? -1 : 1;
     if (const char* m = getenv("PTAMD_TR")) { const int v = atoi(m); if (v >= -1 && v <= 1) sc->shade_rounds = v; }
     if (const char* m = getenv("PTAMD_QUERY_QUAD")) sc->query_quad = atoi(m) != 0;
-    sc->dev.nee_prune = (emitOk && !(getenv("PTAMD_PRUNE") && atoi(getenv("PTAMD_PRUNE")) == 0)) ? 1 : 0;      // PTAMD_PRUNE=0: A/B only
+    sc->dev.nee_prune = (emitOk && pt_prune_allowed()) ? 1 : 0;
 }
 
 extern "C" {
@@ -216,7 +218,8 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
     std::vector<uint8_t> small;
     pack_surfaces(tris, n_tris, surf, lights, light_prim);
     const int n_lights = (int)light_prim.size();
-    const bool emitOk = emittance_ok(tris, n_tris, spheres, n_spheres);
+    bool triOk;
+    const bool emitOk = emittance_ok(tris, n_tris, spheres, n_spheres, triOk);
     core_box(tris, n_tris, core, small);
     std::vector<float> sph = pack_spheres(spheres, n_spheres);
 
@@ -238,6 +241,7 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
     sc->bytes += (int64_t)sc->uv.held();
     if ((rc = create_resources(sc.get())) != PT_OK) return rc;
     apply_defaults(sc.get(), n_tris, emitOk);
+    sc->tri_emit_ok = triOk;
     sc->dev.n_quad = accel.n_quad; sc->dev.quad_depth = accel.quad_depth;
     sc->dev.n_nodes = accel.n_wide; sc->dev.n_tris = n_tris; sc->dev.n_lights = n_lights; sc->dev.n_spheres = n_spheres;
     // what a vertex update needs later: the sphere records and the maps of the build (uploaded by the first update)
@@ -246,6 +250,8 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
     dh.bn.swap(accel.bn); dh.order.swap(accel.order); dh.level_start.swap(accel.level_start); dh.wide_bn.swap(accel.wide_bn);
     dh.quad_bn.swap(accel.quad_bn); dh.leaf_range.swap(accel.leaf_range); dh.tmap.swap(accel.tmap); dh.light_prim.swap(light_prim);
     if (!core.empty()) dh.small.swap(small);
+    dh.pos.resize((size_t)n_tris * 9);      // a triangle that becomes a light needs V1 and V2 themselves: V0 + E1 is not V1
+    for (int i = 0; i < n_tris; i++) memcpy(&dh.pos[(size_t)i * 9], &tris[i], 36);      // V0 V1 V2 are the first nine floats of a PtTriangle
     dh.area_sum = accel.area_sum;
     sc->dyn.n_bn = (int32_t)(dh.bn.size() / 4); sc->dyn.n_wide = accel.n_wide; sc->dyn.n_quad = accel.n_quad; sc->dyn.n_tris = n_tris;
     sc->dyn.n_leaves = accel.n_leaves; sc->dyn.n_lights = n_lights;
@@ -269,7 +275,8 @@ int64_t pt_dbg_scene_array(PtScene* s, int32_t which, void* h_out, int64_t cap_b
         pt_set_error("pt_dbg_scene_array: %s", !s ? "NULL scene" : (which < 0 || which > 8) ? "which must be 0..8" : "bad output buffer");
         return PT_ERR_INVALID;
     }
-    const int64_t size = (int64_t)s->arr[which].bytes();
+    // `lights` keeps its largest size through the material updates: what a render reads is the current n_lights records
+    const int64_t size = which == kArrLights ? (int64_t)s->n_lights * 64 : (int64_t)s->arr[which].bytes();
     const int64_t n = size < cap_bytes ? size : cap_bytes;
     if (n > 0) {
         HIPCHK(hipSetDevice(s->device));

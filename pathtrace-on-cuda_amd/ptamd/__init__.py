@@ -166,6 +166,10 @@ API = [
     ("pt_scene_update_spheres", C.c_int, [_P, _P, C.c_int32]),
     ("pt_scene_tree_inflation", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("pt_dbg_scene_array", C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
+    ("pt_scene_update_materials", C.c_int, [_P, _P, _P]),
+    ("pt_scene_update_materials_host", C.c_int, [_P, _P]),
+    ("pt_scene_update_sphere_materials", C.c_int, [_P, _P, C.c_int32]),
+    ("pt_scene_nee_prune", C.c_int32, [_P]),
     ("pt_trace_rays", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     ("pt_trace_rays_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     ("pt_rays_floats", C.c_int64, [C.c_int64]),
@@ -572,6 +576,36 @@ class Scene:
         """Move the analytic spheres: (n, 16) float32 records of the uploaded count; centre and radius may change, materials may not."""
         sph = np.ascontiguousarray(spheres, np.float32).reshape(-1, SPHERE_FLOATS)
         _check(lib().pt_scene_update_spheres(self._h, _ptr(sph), sph.shape[0]), "pt_scene_update_spheres")
+
+    def update_materials(self, mat, stream_ptr=0):
+        """Give every triangle a new material (include/pt_api.h: pt_scene_update_materials).  mat: (n_tris, 12) float32, emittance
+        albedo specular opacity roughness metallic in the order of the `tris` given at upload; the set of lights follows the new
+        emittances.  A torch tensor on the scene's device is used in place (data_ptr()), enqueued on stream_ptr; the call waits for
+        that stream once, and the tensor is free when it returns.  A numpy array goes through pt_scene_update_materials_host."""
+        n = self.n_tris
+        if isinstance(mat, np.ndarray):
+            m = np.ascontiguousarray(mat, np.float32)
+            if m.size != n * 12 or m.shape[0] != n:
+                raise PtError(f"update_materials: mat has shape {m.shape}, the scene has {n} triangles")
+            _check(lib().pt_scene_update_materials_host(self._h, _ptr(m)), "pt_scene_update_materials_host")
+            return
+        if not (hasattr(mat, "data_ptr") and hasattr(mat, "is_contiguous")):
+            raise PtError("update_materials: mat must be a torch tensor or a numpy array")
+        if str(mat.dtype) != "torch.float32" or not mat.is_contiguous() or mat.numel() != n * 12 or mat.shape[0] != n:
+            raise PtError(f"update_materials: mat must be contiguous float32 with {n} x 12 elements, got {mat.dtype} {tuple(mat.shape)}")
+        if mat.device.type != "cuda" or mat.device.index != self.device:
+            raise PtError(f"update_materials: mat is on {mat.device}, the scene is on device {self.device}")
+        _check(lib().pt_scene_update_materials(self._h, C.c_void_p(mat.data_ptr()), C.c_void_p(stream_ptr)), "pt_scene_update_materials")
+
+    def update_sphere_materials(self, spheres):
+        """New records for the analytic spheres: (n, 16) float32 of the uploaded count; centre, radius and material may all change."""
+        sph = np.ascontiguousarray(spheres, np.float32).reshape(-1, SPHERE_FLOATS)
+        _check(lib().pt_scene_update_sphere_materials(self._h, _ptr(sph), sph.shape[0]), "pt_scene_update_sphere_materials")
+
+    @property
+    def nee_prune(self):
+        """DevScene::nee_prune as the next render will see it (parity hook)."""
+        return lib().pt_scene_nee_prune(self._h)
 
     def tree_inflation(self):
         """Summed box area of the binary traversal tree now / at upload (1.0 for a scene never updated); waits for the device."""

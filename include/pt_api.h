@@ -760,7 +760,7 @@ PT_API int  pt_set_drain_threshold(PtScene* s, int32_t live_streams);
 PT_API int  pt_set_early_shade(PtScene* s, int32_t max_streams);
 /* Mode 1, shading schedule: 1 = a stream whose path ends starts its next sample in the same step (bounces - 1 steps per sample,
  * two bounce evaluations per step), 0 = one bounce evaluation per step (bounces steps per sample, a shorter step), -1 = 0 while
- * more than PTAMD_TRS (4 M) streams are alive, 1 below.  Default: -1 for scenes whose surface table fits in L2 (<= 2 MB: +10 % on
+ * more than 4 M streams are alive, 1 below.  Default: -1 for scenes whose surface table fits in L2 (<= 2 MB: +10 % on
  * the Cornell room), 1 otherwise (with the bunny one bounce per step is neutral on a full frame and costs 6 % for one rank of an
  * 8-way split).  Result-neutral: a stream goes through the same operations in the same order either way
  * (pathtrace-on-cuda_amd/csrc/pt_stream.h: shade_step_t). */

@@ -32,17 +32,12 @@ PT_DEV void load_ray(const float4* __restrict__ rays, size_t i, f3& org, f3& dir
     org = f3(a.x, a.y, a.z); dir = f3(a.w, b.x, b.y); tmax = b.w;
 }
 
-// The spheres, in order, against the triangles' result (CudaUtil.cuh:137-145), and the 8-byte record.  An any-hit query that has its
+// The spheres, in order, against the triangles' result (pt_trace.h: spheres_closest), and the 8-byte record.  An any-hit query that has its
 // triangle needs no sphere; one that has none tests them against tmax exactly as the closest-hit query does, and stops at the first.
 template <bool ANY>
 PT_DEV void finish_ray(const DevScene& sc, const f3& org, const f3& dir, float bestT, int bestPrim, float2* __restrict__ hit)
 {
-    if (!(ANY && bestPrim >= 0))
-        for (int s = 0; s < sc.n_spheres; s++) {
-            const float4 c = sc.spheres[4 * s];
-            float root;
-            if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; if (ANY) break; }
-        }
+    if (!(ANY && bestPrim >= 0)) spheres_closest<ANY>(sc, org, dir, bestT, bestPrim);
     *hit = make_float2(bestPrim < 0 ? 0.f : bestT, __int_as_float(bestPrim));      // a miss is (0, -1)
 }
 

@@ -33,7 +33,7 @@ struct PtScene {
     int mode = 1;            // 1 = wavefront pipeline (default), 0 = one-kernel state machine
     ptd::WfLent wf;          // what every run of the wavefront pipeline borrows: early shade's stream and events, the pinned poll word (frees itself)
     int last_iters = 0;
-    int shade_rounds = 1;        // wf_shade: 1 = a stream may start its next sample in the step its path ends, 0 = one bounce per step, -1 = by live-stream count (PTAMD_TRS)
+    int shade_rounds = 1;        // wf_shade: 1 = a stream may start its next sample in the step its path ends, 0 = one bounce per step, -1 = by live-stream count (pt_wavefront.hip: kTwoRoundsBelow)
     int early_below = 2500000;   // renders of at most this many streams (pixels x passes of one call) run wf_shade's early phase beside the draining wf_trace (0 = never; pt_set_early_shade)
     int drain_below = 80000;     // hand the last streams of a render to wf_drain once this few are live (0 = never; PTAMD_DRAIN, pt_set_drain_threshold):
                                  // the last ~200 of ~1,100 bounce iterations serve < 5 % of the streams at the latency of the longest ray each

@@ -208,6 +208,19 @@ PT_DEV bool sphere_root(const f3& center, float rad, const f3& org, const f3& di
     return true;
 }
 
+// The spheres, in order, against the triangles' closest t (CudaUtil.cuh:137-145): a sphere hit no farther than the closest so far
+// replaces it.  FIRST_ONLY (an any-hit query, pt_query.hip): stop at the first sphere hit —
+// a compile-time choice, the closest-hit loop has no such branch.
+template <bool FIRST_ONLY = false>
+PT_DEV void spheres_closest(const DevScene& sc, const f3& org, const f3& dir, float& bestT, int& bestPrim)
+{
+    for (int s = 0; s < sc.n_spheres; s++) {
+        const float4 c = sc.spheres[4 * s];
+        float root;
+        if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; if (FIRST_ONLY) break; }
+    }
+}
+
 // Closest hit of (org, dir) in [0, tmax].  `stack` points at this lane's column of the
 // wave's LDS stack: entry k lives at stack[k * 64].
 // Returns primitive index (triangle i, n_tris + sphere j) or -1; bestT = its t.
@@ -275,18 +288,75 @@ PT_DEV int trace_closest(const DevScene& sc, const f3& org, const f3& dir, float
         }
     }
 
-    // spheres, in order, against the triangles' closest t (CudaUtil.cuh:137-145)
-    for (int s = 0; s < sc.n_spheres; s++) {
-        const float4 c = sc.spheres[4 * s];
-        float root;
-        if (COUNT) st.spheres++;
-        if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; }
-    }
+    if (COUNT) st.spheres += sc.n_spheres;      // every sphere is tested
+    spheres_closest(sc, org, dir, bestT, bestPrim);
     return bestPrim;
 }
 
-// One step of one lane's walk through the 4-wide quantised tree, for wf_drain and the ray queries (pt_query.hip): wf_trace's node step (the box arithmetic is that kernel's,
-// statement by statement) or its pair-record leaf test, whichever `cur` asks for; returns true when the ray is finished.  The closest
+// One node of the 4-wide quantised tree (pt_device.h: quad node; n0..n3 are its four loaded words): the conservative slab test of its four
+// child boxes, and the (entry key, child ref) pairs sorted by entry distance — k0 <= k1 <= k2 <= k3, a child the ray misses has key
+// kQuadMiss and sorts last.  wf_trace's node step and quad_step both walk with this.
+// Child box = origin + 2^e * q.  Along each axis t(q) = q*A + B with A = 2^e * inv and B = (origin - org) * inv; both are widened by
+// `sl` (2^-20 of their magnitudes, ~16 ulps), the near/far bytes are picked by the sign of the direction once per node (all four
+// children of a coordinate share a dword), and the far side is cut at the closest hit (cullT, in the walk's units).  The boxes only
+// steer the search — acceptance is Triangle::hit + the reference's leaf box — so all that matters is that no box containing a point
+// the ray reaches is ever rejected.
+constexpr int kQuadMiss = 0x7fffffff;
+PT_DEV void quad_order(const uint4& n0, const uint4& n1, const uint4& n2, const uint4& n3, const f3& org, const f3& inv, float cullT,
+                       int& k0, int& k1, int& k2, int& k3, int& r0, int& r1, int& r2, int& r3)
+{
+    const float Ax = inv.x * __uint_as_float(n0.w), Ay = inv.y * __uint_as_float(n3.z), Az = inv.z * __uint_as_float(n3.w);      // scales are powers of two
+    const float Bx = (__uint_as_float(n0.x) - org.x) * inv.x;
+    const float By = (__uint_as_float(n0.y) - org.y) * inv.y;
+    const float Bz = (__uint_as_float(n0.z) - org.z) * inv.z;
+    const float kSl = 9.5367431640625e-7f;                           // 2^-20
+    const float sx = (__builtin_fabsf(Bx) + 255.f * __builtin_fabsf(Ax)) * kSl;
+    const float sy = (__builtin_fabsf(By) + 255.f * __builtin_fabsf(Ay)) * kSl;
+    const float sz = (__builtin_fabsf(Bz) + 255.f * __builtin_fabsf(Az)) * kSl;
+    const float Bnx = Bx - sx, Bfx = Bx + sx, Bny = By - sy, Bfy = By + sy, Bnz = Bz - sz, Bfz = Bz + sz;
+    // near / far bytes by the sign of the direction, as a masked swap: on this chip a second v_cndmask on the same vcc costs
+    // ~23 clocks (tools/valu_probe.py), xor / and / arithmetic shift ~2.3 each.  (A zero component of either sign gives
+    // A = B = +-0 on that axis: both planes at t = 0, so either assignment is the same test.)
+    const uint32_t mx = (uint32_t)(__float_as_int(inv.x) >> 31), my = (uint32_t)(__float_as_int(inv.y) >> 31), mz = (uint32_t)(__float_as_int(inv.z) >> 31);
+    const uint32_t swx = (n2.x ^ n2.w) & mx, swy = (n2.y ^ n3.x) & my, swz = (n2.z ^ n3.y) & mz;
+    const uint32_t nqx = n2.x ^ swx, fqx = n2.w ^ swx;   // lo.x = n2.x, hi.x = n2.w
+    const uint32_t nqy = n2.y ^ swy, fqy = n3.x ^ swy;   // lo.y = n2.y, hi.y = n3.x
+    const uint32_t nqz = n2.z ^ swz, fqz = n3.y ^ swz;   // lo.z = n2.z, hi.z = n3.y
+    int key[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float tnx = __builtin_fmaf((float)((nqx >> (8 * k)) & 0xffu), Ax, Bnx);
+        const float tny = __builtin_fmaf((float)((nqy >> (8 * k)) & 0xffu), Ay, Bny);
+        const float tnz = __builtin_fmaf((float)((nqz >> (8 * k)) & 0xffu), Az, Bnz);
+        const float tfx = __builtin_fmaf((float)((fqx >> (8 * k)) & 0xffu), Ax, Bfx);
+        const float tfy = __builtin_fmaf((float)((fqy >> (8 * k)) & 0xffu), Ay, Bfy);
+        const float tfz = __builtin_fmaf((float)((fqz >> (8 * k)) & 0xffu), Az, Bfz);
+        const float tn = __builtin_fmaxf(__builtin_fmaxf(tnx, tny), __builtin_fmaxf(tnz, 0.f));
+        const float tf = __builtin_fminf(__builtin_fminf(tfx, tfy), __builtin_fminf(tfz, cullT));
+        key[k] = (tn <= tf) ? __float_as_int(tn) : kQuadMiss;   // tn >= 0: its bits order like ints
+    }
+    // sort (entry distance, ref) pairs: 5 compare-exchanges, each one compare + four selects (equal distances: any order will do)
+    k0 = key[0]; k1 = key[1]; k2 = key[2]; k3 = key[3]; r0 = (int)n1.x; r1 = (int)n1.y; r2 = (int)n1.z; r3 = (int)n1.w;
+#define PT_CE(ka, ra, kb, rb) { const bool sw = ka > kb; const int tk = sw ? kb : ka, tr = sw ? rb : ra; kb = sw ? ka : kb; rb = sw ? ra : rb; ka = tk; ra = tr; }
+    PT_CE(k0, r0, k1, r1) PT_CE(k2, r2, k3, r3) PT_CE(k0, r0, k2, r2) PT_CE(k1, r1, k3, r3) PT_CE(k1, r1, k2, r2)
+#undef PT_CE
+}
+
+// What a walk does with a node's sorted children: the nearest hit child is next, the other hit children go to the stack, farthest first
+// (push(ref) is the walk's own stack).  False: the ray misses all four, and the walk takes its next entry from the stack.
+template <class Push>
+PT_DEV bool quad_descend(int k0, int k1, int k2, int k3, int r0, int r1, int r2, int r3, int& cur, Push push)
+{
+    if (k0 == kQuadMiss) return false;
+    if (k3 != kQuadMiss) push(r3);
+    if (k2 != kQuadMiss) push(r2);
+    if (k1 != kQuadMiss) push(r1);
+    cur = r0;
+    return true;
+}
+
+// One step of one lane's walk through the 4-wide quantised tree, for wf_drain and the ray queries (pt_query.hip): wf_trace's node step
+// (quad_order, quad_descend) or its pair-record leaf test, whichever `cur` asks for; returns true when the ray is finished.  The closest
 // hit does not depend on the order of tests (tie rule), and a shadow ray may stop at any hit below `stopBelow` (pt_stream.h:
 // shadow_stop_t) exactly as it does there.  The caller guarantees that its per-lane stack holds 3 * quad_depth + 2 entries.
 // Whatever the floats are (NaN, inf, a zero direction) the walk ends: a node pushes at most three of its children and descends into the
@@ -297,43 +367,9 @@ PT_DEV bool quad_step(const DevScene& sc, const f3& org, const f3& dir, const f3
     if (cur >= 0) {
         const uint4* np = sc.quad + 4 * (size_t)cur;
         const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
-        const float Ax = inv.x * __uint_as_float(n0.w), Ay = inv.y * __uint_as_float(n3.z), Az = inv.z * __uint_as_float(n3.w);
-        const float Bx = (__uint_as_float(n0.x) - org.x) * inv.x;
-        const float By = (__uint_as_float(n0.y) - org.y) * inv.y;
-        const float Bz = (__uint_as_float(n0.z) - org.z) * inv.z;
-        const float kSl = 9.5367431640625e-7f;                           // 2^-20
-        const float sx = (__builtin_fabsf(Bx) + 255.f * __builtin_fabsf(Ax)) * kSl;
-        const float sy = (__builtin_fabsf(By) + 255.f * __builtin_fabsf(Ay)) * kSl;
-        const float sz = (__builtin_fabsf(Bz) + 255.f * __builtin_fabsf(Az)) * kSl;
-        const float Bnx = Bx - sx, Bfx = Bx + sx, Bny = By - sy, Bfy = By + sy, Bnz = Bz - sz, Bfz = Bz + sz;
-        const uint32_t mx = (uint32_t)(__float_as_int(inv.x) >> 31), my = (uint32_t)(__float_as_int(inv.y) >> 31), mz = (uint32_t)(__float_as_int(inv.z) >> 31);
-        const uint32_t swx = (n2.x ^ n2.w) & mx, swy = (n2.y ^ n3.x) & my, swz = (n2.z ^ n3.y) & mz;
-        const uint32_t nqx = n2.x ^ swx, fqx = n2.w ^ swx, nqy = n2.y ^ swy, fqy = n3.x ^ swy, nqz = n2.z ^ swz, fqz = n3.y ^ swz;
-        const float cullT = bestT * cscale;
-        int key[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float tnx = __builtin_fmaf((float)((nqx >> (8 * k)) & 0xffu), Ax, Bnx);
-            const float tny = __builtin_fmaf((float)((nqy >> (8 * k)) & 0xffu), Ay, Bny);
-            const float tnz = __builtin_fmaf((float)((nqz >> (8 * k)) & 0xffu), Az, Bnz);
-            const float tfx = __builtin_fmaf((float)((fqx >> (8 * k)) & 0xffu), Ax, Bfx);
-            const float tfy = __builtin_fmaf((float)((fqy >> (8 * k)) & 0xffu), Ay, Bfy);
-            const float tfz = __builtin_fmaf((float)((fqz >> (8 * k)) & 0xffu), Az, Bfz);
-            const float tn = __builtin_fmaxf(__builtin_fmaxf(tnx, tny), __builtin_fmaxf(tnz, 0.f));
-            const float tf = __builtin_fminf(__builtin_fminf(tfx, tfy), __builtin_fminf(tfz, cullT));
-            key[k] = (tn <= tf) ? __float_as_int(tn) : 0x7fffffff;
-        }
-        int k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3], r0 = (int)n1.x, r1 = (int)n1.y, r2 = (int)n1.z, r3 = (int)n1.w;
-#define PT_CE(ka, ra, kb, rb) { const bool sw = ka > kb; const int tk = sw ? kb : ka, tr = sw ? rb : ra; kb = sw ? ka : kb; rb = sw ? ra : rb; ka = tk; ra = tr; }
-        PT_CE(k0, r0, k1, r1) PT_CE(k2, r2, k3, r3) PT_CE(k0, r0, k2, r2) PT_CE(k1, r1, k3, r3) PT_CE(k1, r1, k2, r2)
-#undef PT_CE
-        if (k0 != 0x7fffffff) {
-            if (k3 != 0x7fffffff) { stack[sp * 64] = r3; sp++; }
-            if (k2 != 0x7fffffff) { stack[sp * 64] = r2; sp++; }
-            if (k1 != 0x7fffffff) { stack[sp * 64] = r1; sp++; }
-            cur = r0;
-            return false;
-        }
+        int k0, k1, k2, k3, r0, r1, r2, r3;
+        quad_order(n0, n1, n2, n3, org, inv, bestT * cscale, k0, k1, k2, k3, r0, r1, r2, r3);
+        if (quad_descend(k0, k1, k2, k3, r0, r1, r2, r3, cur, [&](int ref) { stack[sp * 64] = ref; sp++; })) return false;
     } else {
         const int code = ~cur;
         int first = code >> 3, cnt = code & 7;

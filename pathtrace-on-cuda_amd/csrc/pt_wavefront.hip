@@ -33,6 +33,7 @@
 #include "pt_math.h"
 #include "pt_bxdf.h"
 #include "pt_trace.h"
+#include "pt_trace_probe.h"
 #include "pt_shade.h"
 #include "pt_stream.h"
 #include "pt_internal.h"
@@ -42,12 +43,37 @@ namespace ptd {
 constexpr int kWfLdsStack = 16;      // stack entries per lane kept in LDS (4 KB / wave)
 constexpr int kWfOvfLevels = 48;     // further levels spill to global memory (never needed on the config scenes: 4-wide depth 12 -> at most 38 entries; tests/test_needle_scene.py renders a scene whose rays do need them)
 constexpr int kWfChunk = 128;        // most ray ids a wave takes from a queue shard per atomic (measured optimum 116-229)
-constexpr int kWfRefill = 24;        // refill lanes once this many are idle (measured: 8..16 -2 %, 32 -0.4 %)
 constexpr int kDone = (int)0x80000000;
+// Scheduling constants of wf_trace.  None of them can change a result; each is the measured optimum on MI355X, and a sweep builds a
+// variant of the library with another value (tools/build_variant.sh NAME "-DWF_REFILL=16 ...").
 #ifndef SHARD_BLOCK
 #define SHARD_BLOCK 2048
 #endif
 constexpr uint32_t kShardBlock = SHARD_BLOCK;   // queue indices per block of the shard interleave (a power of two)
+#ifndef WF_CHUNK_SHIFT
+#define WF_CHUNK_SHIFT 12
+#endif
+constexpr int kWfChunkShift = WF_CHUNK_SHIFT;   // chunk = clamp(n >> this, 16, kWfChunk) ray ids per queue access
+#ifndef WF_GUIDE_SHIFT
+#define WF_GUIDE_SHIFT 9
+#endif
+constexpr int kWfGuideShift = WF_GUIDE_SHIFT;   // guided self-scheduling: the chunk shrinks to (rays left in the shard) >> this
+#ifndef WF_REFILL
+#define WF_REFILL 24
+#endif
+constexpr int kWfRefill = WF_REFILL;            // refill lanes once this many are idle (measured: 8..16 -2 %, 32 -0.4 %)
+#ifndef WF_TRI_TRIG
+#define WF_TRI_TRIG 64
+#endif
+constexpr int kWfTriTrig = WF_TRI_TRIG;         // parked leaves that force a triangle trip (64 = only when blocked rays outnumber walking ones)
+// Shards a wave tries (its own included) before it takes the queue to be dry: 4 (16 = all: every wave then spends 16 returning atomics
+// on hot words at the end of every launch; the shards are interleaved and equally long, so there is little to help with: 16 -> 4 is
+// +1 % on configs[2], +3 % on configs[1], +4.5 % for an 8-way rank, r03_b20.log)
+#ifndef WF_HELP_SHARDS
+#define WF_HELP_SHARDS 4
+#endif
+constexpr int kWfHelpShards = WF_HELP_SHARDS;
+static_assert(kWfHelpShards >= 1 && kWfHelpShards <= kWfShards, "a wave tries between one and all of the shards");
 // wf_trace's waves per SIMD.  7 (72 VGPRs) rather than 8 (64): the two-triangle leaf test needs the room, and
 // the kernel is bound by VALU issue, not by latency hiding (measured: 8 waves with 6-9 spilled registers and 6 waves
 // with none are both slower; round 2 again: 8 waves +5 % kernel time).
@@ -67,7 +93,7 @@ constexpr int kSuspInts = 4 + kWfLdsStack + kWfOvfLevels;
 // per launch on one cache line serialise at ~88 per microsecond; with one atomic per 256-thread block and the
 // counters on separate lines they no longer show.)
 // Must be called by every thread of the block.
-constexpr int kShadeThreads = 1024;      // largest wf_shade workgroup (the default runs 512-thread workgroups, two per CU: 4 waves/SIMD at 126 VGPRs)
+constexpr int kShadeThreads = 1024;      // threads block_append's per-wave counts are sized for (wf_shade's launch bound; it runs 512-thread workgroups, two per CU, the init kernels 256)
 constexpr int kLists = 1 + 2 * kRayKinds;      // live streams + per ray kind a front list (through the core box / unknown) and a back list (short rays)
 template <int N>
 PT_DEV void block_append(const bool (&e)[N], const uint32_t (&id)[N], uint32_t* const (&c)[N], uint32_t* const (&l)[N], const uint32_t (&top)[N])
@@ -99,6 +125,30 @@ PT_DEV void block_append(const bool (&e)[N], const uint32_t (&id)[N], uint32_t* 
     }
 }
 
+// The seven lists a kernel appends to, in the order of e[] / ids[]: the live streams (list 0: `liveList`, counted by nActive), then per
+// ray kind k the front list (rays through the core box, or of unknown length: grows upwards from index 0 of rq[k], counted by
+// nRays[k][0]) and, last, per kind the back list (short rays: grows DOWNWARDS from the last entry of the same array, counted by
+// nRays[k][kShortWord]).  wf_trace's queue index space is these six ray lists in a row (QueueSegments).  The caller says which lists
+// its thread joins (e) and with what entry (ids: the stream, for a suspended traversal with kResumeBit); where the lists and their
+// counters live is known here alone.  Must be called by every thread of the block.
+PT_DEV void append_lists(const WfBuf& b, int slot, uint32_t* liveList, const bool (&e)[kLists], const uint32_t (&ids)[kLists])
+{
+    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1: the last entry of a queue array
+    uint32_t* const c[kLists] = {&b.cnt[slot].nActive, &b.cnt[slot].nRays[0][0], &b.cnt[slot].nRays[1][0], &b.cnt[slot].nRays[2][0],
+                                 &b.cnt[slot].nRays[0][kShortWord], &b.cnt[slot].nRays[1][kShortWord], &b.cnt[slot].nRays[2][kShortWord]};
+    uint32_t* const l[kLists] = {liveList, b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
+    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
+    block_append<kLists>(e, ids, c, l, top);
+}
+
+// The end of every init kernel: stream sid, if live, joins the live list, and its first ray is queued by class (shortRay implies live).
+PT_DEV void append_first_ray(const WfBuf& b, uint32_t sid, bool live, bool shortRay)
+{
+    const bool e[kLists] = {live, live && !shortRay, false, false, shortRay, false, false};
+    const uint32_t ids[kLists] = {sid, sid, sid, sid, sid, sid, sid};
+    append_lists(b, 0, b.active[0], e, ids);
+}
+
 // ---------------------------------------------------------------------------------------
 // wf_init, wf_init_list, wf_init_views, wf_init_rays: StartRender prologue for every stream (pathtracer.cu:70-74).
 // This is the only place of the pipeline that turns a stream into a pixel: from here on a stream is its slot, so wf_trace, wf_shade
@@ -127,15 +177,7 @@ PT_DEV void init_streams(const DevScene& sc, const DevParams& prm, const WfBuf& 
         }
     }
     // the camera ray: queued by class like every other ray (a pixel that looks past the mesh has a short ray)
-    const bool shortRay = live && camShort;
-    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1: the last entry of a queue array
-    const bool e[kLists] = {live, live && !shortRay, false, false, shortRay, false, false};
-    uint32_t* const c[kLists] = {&b.cnt[0].nActive, &b.cnt[0].nRays[0][0], &b.cnt[0].nRays[1][0], &b.cnt[0].nRays[2][0],
-                                 &b.cnt[0].nRays[0][kShortWord], &b.cnt[0].nRays[1][kShortWord], &b.cnt[0].nRays[2][kShortWord]};
-    uint32_t* const l[kLists] = {b.active[0], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
-    const uint32_t ids[kLists] = {sid, sid, sid, sid, sid, sid, sid};
-    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
-    block_append<kLists>(e, ids, c, l, top);
+    append_first_ray(b, sid, live, live && camShort);
 }
 
 // one camera, the fixed share of the frame: local tile lt is tile lt * world + rank
@@ -190,14 +232,44 @@ void wf_init_rays(DevScene sc, DevParams prm, WfBuf b, uint32_t nStreams, const 
             b.staging[3 * (size_t)sid + 0] = 0.f; b.staging[3 * (size_t)sid + 1] = 0.f; b.staging[3 * (size_t)sid + 2] = 0.f;
         }
     }
-    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1: the last entry of a queue array
-    const bool e[kLists] = {live, live && !shortRay, false, false, shortRay, false, false};
-    uint32_t* const c[kLists] = {&b.cnt[0].nActive, &b.cnt[0].nRays[0][0], &b.cnt[0].nRays[1][0], &b.cnt[0].nRays[2][0],
-                                 &b.cnt[0].nRays[0][kShortWord], &b.cnt[0].nRays[1][kShortWord], &b.cnt[0].nRays[2][kShortWord]};
-    uint32_t* const l[kLists] = {b.active[0], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
-    const uint32_t ids[kLists] = {sid, sid, sid, sid, sid, sid, sid};
-    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
-    block_append<kLists>(e, ids, c, l, top);
+    append_first_ray(b, sid, live, shortRay);
+}
+
+// wf_trace's queue index space for one launch, six segments in a row: the rays of kind 0 (path), 1 and 2 (shadow) queued from the front
+// of their arrays — rays through the scene's core box, or of unknown length —, then the SHORT rays of each kind, queued from the back of
+// the same arrays (pt_stream.h: ray_is_short; append_lists): what is in flight when the queue runs dry is then short, and so is the
+// launch tail.  p1..p5 are where segments 1..5 start, n is the number of rays.
+struct QueueSegments {
+    uint32_t p1, p2, p3, p4, p5, n;
+    PT_DEV explicit QueueSegments(const WfCounters& c)
+    {
+        p1 = c.nRays[0][0];
+        p2 = p1 + c.nRays[1][0];
+        p3 = p2 + c.nRays[2][0];
+        p4 = p3 + c.nRays[0][kShortWord];
+        p5 = p4 + c.nRays[1][kShortWord];
+        n = p5 + c.nRays[2][kShortWord];
+    }
+    // queue index q -> kn = kind * n16 and the entry of rq[0] (the per-kind arrays lie back to back) that holds the ray: the front part of a
+    // kind's array upwards, its short part downwards from n16 - 1
+    PT_DEV uint32_t entry(uint32_t q, uint32_t n16, uint32_t& kn) const
+    {
+        const bool shortSeg = q >= p3;
+        const uint32_t b0 = shortSeg ? p3 : 0u, b1 = shortSeg ? p4 : p1, b2 = shortSeg ? p5 : p2;      // segment starts of kinds 0, 1, 2
+        const bool k0 = q < b1, k1 = q < b2;                                   // kind 0 / kind 0 or 1
+        kn = k0 ? 0u : (k1 ? n16 : 2u * n16);
+        const uint32_t local = q - (k0 ? b0 : (k1 ? b1 : b2));
+        return kn + (shortSeg ? n16 - 1u - local : local);
+    }
+};
+
+// A ray's hit record: (t, primitive), or for a suspended traversal (t, -2 - record).  PUBLISH: stored device-coherently, wf_shade's early
+// phase reads it while this kernel drains.
+template <bool PUBLISH>
+PT_DEV void store_hit(const WfBuf& b, uint32_t hs, float t, int prim)
+{
+    if (PUBLISH) __hip_atomic_store((unsigned long long*)&b.hit[0][hs], (unsigned long long)__float_as_uint(t) | ((unsigned long long)(uint32_t)prim << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else b.hit[0][hs] = make_float2(t, __int_as_float(prim));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -210,49 +282,20 @@ void wf_init_rays(DevScene sc, DevParams prm, WfBuf b, uint32_t nStreams, const 
 // closest one.  That test is made here, in the ray's epilogue (pt_shade.h: nee_verdict): the hit
 // record of a shadow ray carries the primitive only if it is the light point.
 // ---------------------------------------------------------------------------------------
-// STAT: a diagnostic build that also counts trips and the lanes they serve (pt_last_counters; PTAMD_TSTAT=1).
-template <int MODE, bool PUBLISH = false>      // PUBLISH: hits are stored device-coherently (wf_shade PHASE 1 reads them while this kernel drains);  MODE: 0 production, 1 trip counters + histograms + timeline (PTAMD_TSTAT=1), 2 timeline only (PTAMD_TSTAT=2), 3 trip counters + section clocks, no per-step atomics (PTAMD_TSTAT=3)
+// MODE: 0 production; 1, 2, 3 the diagnostic builds of PTAMD_TSTAT — all they add is in `probe` (pt_trace_probe.h), and so is the
+// kernel argument they read.  PUBLISH: hits are stored device-coherently (wf_shade PHASE 1 reads them while this kernel drains).
+// budgetShift, budgetMin, lateBudget: WfTuning.
+template <int MODE, bool PUBLISH = false>
 __global__ __launch_bounds__(256, TRACE_WAVES)
-void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chunkShift, int budgetShift, int budgetMin, int guideShift, int triTrig, int refillMin,
-              unsigned long long* stat, int statLaunch, int helpShards, int lateBudget)
+void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int budgetShift, int budgetMin, int lateBudget, typename TraceProbe<MODE>::Args probeArgs)
 {
-    constexpr bool STAT = MODE == 1 || MODE == 3, HIST = MODE == 1, timeline = MODE != 0;
-    // PUBLISH launches share the chip with wf_shade's early phase: the traversal is the critical path of the iteration (its last waves
-    // run a serial chain), so its waves issue ahead of the shading waves (statLaunch carries the priority in the production build)
-    if (PUBLISH && MODE == 0) { if (statLaunch == 1) __builtin_amdgcn_s_setprio(1); else if (statLaunch == 2) __builtin_amdgcn_s_setprio(2); else if (statLaunch == 3) __builtin_amdgcn_s_setprio(3); }
-    const unsigned long long stT0 = timeline ? __builtin_amdgcn_s_memrealtime() : 0ull;      // 100 MHz
-    unsigned long long stTExh = 0;
-    unsigned long long stClk[5] = {0, 0, 0, 0, 0}, stMark = 0;      // STAT: shader clocks in refill / vote + budget / node step / triangle step / ray epilogue
-    unsigned long long stNodeTrips = 0, stNodeLanes = 0, stTriTrips = 0, stTriLanes = 0, stRefills = 0, stRefillLanes = 0, stNoRayLanes = 0, stRays = 0;
-    unsigned int stTrips = 0, stTripsDry = 0;      // MODE 2: trips of this wave in all, and after it found the queue dry
-    // MODE 2, one chosen launch (PTAMD_TDUMP; stat[6] = launch + 1): a record per wave (kStatWaveRec) and a per-trip log of every 112th wave
-    const bool stDump = MODE == 2 && stat[6] == (unsigned long long)statLaunch + 1ull;
-    const uint32_t stWave = blockIdx.x * 4u + (threadIdx.x >> 6);
-    const bool stLog = stDump && stWave % kStatLogEvery == 0 && stWave / kStatLogEvery < (uint32_t)kStatLogWaves;
+    TraceProbe<MODE> probe(probeArgs);
     __shared__ int lds_stack[4][kWfLdsStack * 64];
-    // one queue index space, six segments: the rays of kind 0 (path), 1 and 2 (shadow) queued from the front of their arrays — rays through
-    // the scene's core box, or of unknown length —, then the SHORT rays of each kind, queued from the back of the same arrays
-    // (pt_stream.h: ray_is_short): what is in flight when the queue runs dry is then short, and so is the launch tail
-    const uint32_t p1 = b.cnt[slot].nRays[0][0];
-    const uint32_t p2 = p1 + b.cnt[slot].nRays[1][0];
-    const uint32_t p3 = p2 + b.cnt[slot].nRays[2][0];
-    const uint32_t p4 = p3 + b.cnt[slot].nRays[0][kShortWord];
-    const uint32_t p5 = p4 + b.cnt[slot].nRays[1][kShortWord];
-    const uint32_t n = p5 + b.cnt[slot].nRays[2][kShortWord];
+    const QueueSegments seg(b.cnt[slot]);
+    const uint32_t n = seg.n;
     if ((uint32_t)blockIdx.x * 256u >= n) return;      // surplus blocks leave before touching the queue (fewer rays per workgroup: no faster, r02_b21.log)
 
     const int lane = threadIdx.x & 63;
-    int* stack = &lds_stack[threadIdx.x >> 6][lane];
-    int* ovf = b.ovf + (blockIdx.x * 256 + threadIdx.x);
-    // Stack entry k of this lane: LDS below kWfLdsStack, global memory above (5e-7 of the node steps).  Written as a plain select of
-    // the two places the compiler merges them into ONE flat_load (LDS through the texture path, waited for with vmcnt(0), i.e. behind
-    // every outstanding store); the empty asm pins the LDS read down as a ds_read of its own.
-    auto stack_at = [&](int k) -> int {
-        int v = stack[(k < kWfLdsStack ? k : 0) * 64];
-        asm volatile("" : "+v"(v));
-        if (k >= kWfLdsStack) v = ovf[(k - kWfLdsStack) * ovfStride];
-        return v;
-    };
     // node steps a ray may take in this launch before it is suspended: large launches hide long rays,
     // small (latency-bound) launches must not wait for them
     const int budget = (n >> budgetShift) < (uint32_t)budgetMin ? budgetMin : ((n >> budgetShift) > 1024u ? 1024 : (int)(n >> budgetShift));
@@ -260,7 +303,7 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
     int* __restrict__ suspOut = b.susp[parity];
     // rays a wave takes per queue access: ~n / (4 x resident waves), between 16 and kWfChunk (one word
     // saturates near 88 returning atomics per microsecond, so large launches take large chunks)
-    const uint32_t kChunk = (n >> chunkShift) < 16u ? 16u : ((n >> chunkShift) > (uint32_t)kWfChunk ? (uint32_t)kWfChunk : (n >> chunkShift));
+    const uint32_t kChunk = (n >> kWfChunkShift) < 16u ? 16u : ((n >> kWfChunkShift) > (uint32_t)kWfChunk ? (uint32_t)kWfChunk : (n >> kWfChunkShift));
 
     uint32_t chunkPos = 0, chunkEnd = 0;   // wave-uniform
     uint32_t seenLeft = 0xffffffffu;       // rays this wave last saw left in its current shard (wave-uniform)
@@ -281,20 +324,39 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
     const uint32_t n16 = (uint32_t)(b.hit[1] - b.hit[0]);
     uint32_t hs = 0;
 
+    // The ray's stack, sp entries: entry k of this lane lives in LDS below kWfLdsStack, in global memory above (5e-7 of the node steps).
+    // (an LDS pointer by type: were it a generic one, the compiler could merge the two stores of stack_put into ONE flat_store with a selected address)
+    typedef __attribute__((address_space(3))) int LdsInt;
+    LdsInt* stack = (LdsInt*)&lds_stack[threadIdx.x >> 6][lane];
+    int* ovf = b.ovf + (blockIdx.x * 256 + threadIdx.x);
+    // The read: written as a plain select of the two places the compiler merges them into ONE flat_load (LDS through the texture path,
+    // waited for with vmcnt(0), i.e. behind every outstanding store); the empty asm pins the LDS read down as a ds_read of its own.
+    auto stack_at = [&](int k) -> int {
+        int v = stack[(k < kWfLdsStack ? k : 0) * 64];
+        asm volatile("" : "+v"(v));
+        if (k >= kWfLdsStack) v = ovf[(k - kWfLdsStack) * ovfStride];
+        return v;
+    };
+    auto stack_put = [&](int k, int v) { if (k < kWfLdsStack) stack[k * 64] = v; else ovf[(k - kWfLdsStack) * ovfStride] = v; };
+    auto push = [&](int v) { stack_put(sp, v); sp++; };
+    // the next entry of the stack becomes the ray's position; an empty stack ends the walk
+    auto pop = [&] { if (sp == 0) cur = kDone; else { sp--; cur = stack_at(sp); } };
+    // the suspend record of a traversal (kSuspInts words): cur, sp, closest hit, then the stack
+    auto save_walk = [&](int* rec) {
+        rec[0] = cur; rec[1] = sp; rec[2] = __float_as_int(bestT); rec[3] = bestPrim;
+        for (int k = 0; k < sp; k++) rec[4 + k] = (k < kWfLdsStack) ? stack[k * 64] : ovf[(k - kWfLdsStack) * ovfStride];
+    };
+    auto restore_walk = [&](const int* rec) {
+        cur = rec[0]; sp = rec[1]; bestT = __int_as_float(rec[2]); bestPrim = rec[3];
+        for (int k = 0; k < sp; k++) stack_put(k, rec[4 + k]);
+    };
+
     for (;;) {
+        probe.trip_top();
         // ---- hand new rays to idle lanes (ballot + mbcnt compaction) ----
-        if (STAT) stMark = __builtin_amdgcn_s_memtime();
-#define PT_STCLK(k) if (STAT) { const unsigned long long now = __builtin_amdgcn_s_memtime(); stClk[k] += now - stMark; stMark = now; }
-        uint32_t stW0 = 0, stAtomics = 0, stTook = 0;      // MODE 2 trip log: time at the top of the loop, queue atomics and rays taken in this iteration
-        uint32_t stW1 = 0, stW3 = 0;
-        if (MODE == 2 && stLog) {
-            // A = top of the loop, on the constant 100 MHz clock, and the shader clock counter at the same moment (their ratio is the clock the SIMD runs at)
-            stW0 = (uint32_t)((__builtin_amdgcn_s_memrealtime() - stT0) & 0xfffffull);
-            stW1 = (uint32_t)__builtin_amdgcn_s_memtime();
-        }
         const unsigned long long idle = __ballot(!hasRay);
         const int nIdle = __builtin_popcountll(idle);
-        if (!exhausted && (nIdle >= refillMin)) {
+        if (!exhausted && (nIdle >= kWfRefill)) {
             if (chunkPos == chunkEnd) {
                 // The queue index space is cut into kWfShards ranges, each with its own head word (a
                 // single word saturates near 88 returning atomics per microsecond, which throttled
@@ -308,54 +370,41 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     const uint32_t cnt = rounds * kShardBlock + (part < kShardBlock ? part : kShardBlock);      // indices this shard owns
                     // guided self-scheduling: the chunk shrinks with what this wave last saw left in the shard, so the
                     // last rays of a launch are spread over many waves instead of queuing behind one
-                    uint32_t want = seenLeft >> guideShift;
+                    uint32_t want = seenLeft >> kWfGuideShift;
                     want = want < 16u ? 16u : (want > kChunk ? kChunk : want);
                     uint32_t start = 0;
                     if (lane == 0) start = atomicAdd(&b.cnt[slot].head[shard].v, want);
-                    if (MODE == 2) stAtomics++;
+                    probe.queue_atomic();
                     start = __builtin_amdgcn_readfirstlane(start);
                     if (start < cnt) {
                         chunkPos = start; chunkEnd = (cnt - start > want) ? start + want : cnt; seenLeft = cnt - start; break; }
                     seenLeft = 0xffffffffu;
                     shard = (shard + 1) % kWfShards;
-                    if (++shardsTried >= helpShards) { exhausted = true; if (timeline) stTExh = __builtin_amdgcn_s_memrealtime(); break; }
+                    if (++shardsTried >= kWfHelpShards) { exhausted = true; probe.queue_dry(); break; }
                 }
             }
             if (!exhausted) {
                 const uint32_t avail = chunkEnd - chunkPos;
                 const uint32_t take = ((uint32_t)nIdle < avail) ? (uint32_t)nIdle : avail;
-                if (STAT && take) { stRefills++; stRefillLanes += take; }
-                if (MODE == 2) stTook = take;
+                probe.refilled(take);
                 if (!hasRay) {
                     const uint32_t r = (uint32_t)__builtin_popcountll(idle & ((1ull << lane) - 1ull));
                     if (r < take) {
                         const uint32_t j = chunkPos + r;      // shard-local -> queue index
                         const uint32_t q = ((j / kShardBlock) * kWfShards + (uint32_t)shard) * kShardBlock + (j % kShardBlock);
-                        // segment of q -> kind, position in the kind's queue array (front part upwards, short part downwards from n16 - 1)
-                        const bool shortSeg = q >= p3;
-                        const uint32_t b0 = shortSeg ? p3 : 0u, b1 = shortSeg ? p4 : p1, b2 = shortSeg ? p5 : p2;      // segment starts of kinds 0, 1, 2
-                        const bool k0 = q < b1, k1 = q < b2;                                   // kind 0 / kind 0 or 1
-                        const uint32_t kn = k0 ? 0u : (k1 ? n16 : 2u * n16);                  // kind * n16
-                        const uint32_t local = q - (k0 ? b0 : (k1 ? b1 : b2));
-                        const uint32_t qid = b.rq[0][kn + (shortSeg ? n16 - 1u - local : local)];
+                        uint32_t kn;      // kind * n16
+                        const uint32_t qid = b.rq[0][seg.entry(q, n16, kn)];
                         hs = kn + (qid & ~kResumeBit);
                         const float4 o = b.ray_o[0][hs + kn], d = b.ray_d[0][hs + kn];
-                        const int kind = k0 ? 0 : 1;      // all that is still asked of it: path ray or not
                         org = f3(o.x, o.y, o.z); dir = f3(d.x, d.y, d.z);
                         ray_setup(dir, inv, cscale, degenerate);      // pt_trace.h
-                        stopBelow = kind != 0 ? d.w : -__builtin_inff();      // shadow rays: any hit below this t ends the traversal (pt_stream.h: shadow_stop_t)
+                        stopBelow = kn != 0u ? d.w : -__builtin_inff();      // shadow rays: any hit below this t ends the traversal (pt_stream.h: shadow_stop_t)
                         steps = 0;
                         if (qid & kResumeBit) {
                             // resume a suspended traversal (wf_shade flags the queue entry: the hit slot then holds the record number;
                             // a fresh ray's hit slot is not read at all — 8 scattered bytes per ray that nothing else would fetch)
                             const float2 prev = b.hit[0][hs];
-                            const int pp = __float_as_int(prev.y);
-                            const int* rec = suspIn + (size_t)(-2 - pp) * kSuspInts;
-                            cur = rec[0]; sp = rec[1]; bestT = __int_as_float(rec[2]); bestPrim = rec[3];
-                            for (int k = 0; k < sp; k++) {
-                                const int v = rec[4 + k];
-                                if (k < kWfLdsStack) stack[k * 64] = v; else ovf[(k - kWfLdsStack) * ovfStride] = v;
-                            }
+                            restore_walk(suspIn + (size_t)(-2 - __float_as_int(prev.y)) * kSuspInts);
                         } else {
                             bestT = o.w; bestPrim = -1; cur = 0; sp = 0;
                         }
@@ -366,23 +415,9 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                 chunkPos += take;
             }
         }
-        PT_STCLK(0)
+        probe.after_refill();
         if (__ballot(hasRay) == 0ull) { if (exhausted) break; else continue; }
-        if (MODE == 2) { stTrips++; if (exhausted) stTripsDry++; }
-        uint32_t* stLogAt = nullptr;
-        if (MODE == 2 && stLog && 4 * stTrips <= (unsigned)kStatLogTrips) {
-            // four words per trip (10-ns ticks since the wave started in the low 20 bits).  w0: A, top of the loop | lanes with a ray (7 bits) | queue
-            // already dry | queue atomics of the refill (2 bits, saturating); w1: the shader clock counter at A (low 32 bits);
-            // w2: C, after the refill | rays taken (7) | some lane holds a leaf; w3: D, node data of a node trip arrived (0 for a triangle trip)
-            const uint32_t lanesNow = (uint32_t)__builtin_popcountll(__ballot(hasRay)), pendNow = (uint32_t)__builtin_popcountll(__ballot(hasRay && pend != 0));
-            stLogAt = (uint32_t*)(stat + kStatWords + (size_t)kStatWaves * 8) + (size_t)(stWave / kStatLogEvery) * kStatLogTrips + 4 * (stTrips - 1);
-            if (lane == 0) {
-                stLogAt[0] = stW0 | (lanesNow << 20) | (exhausted ? 1u << 27 : 0u) | ((stAtomics > 3u ? 3u : stAtomics) << 28);
-                stLogAt[1] = stW1;
-                stLogAt[2] = (uint32_t)((__builtin_amdgcn_s_memrealtime() - stT0) & 0xfffffull) | ((stTook > 127u ? 127u : stTook) << 20) | (pendNow ? 1u << 27 : 0u);
-                stLogAt[3] = 0u;
-            }
-        }
+        probe.trip_begins(hasRay, pend, exhausted, lane);
         if (hasRay) {
             // Only one code path runs per trip: a node step or ONE triangle test per lane (the vote is below).
             // (The classic while-while shape made 64 lanes wait for the slowest lane to reach a leaf every
@@ -395,12 +430,9 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     // node budget spent: suspend (or, if the pool is full, carry on)
                     const uint32_t rec = atomicAdd(&b.cnt[slot].nSusp, 1u);
                     if (rec < b.suspCap) {
-                        int* r = suspOut + (size_t)rec * kSuspInts;
-                        if (pend != 0) { if (sp < kWfLdsStack) stack[sp * 64] = pend; else ovf[(sp - kWfLdsStack) * ovfStride] = pend; sp++; pend = 0; }
-                        r[0] = cur; r[1] = sp; r[2] = __float_as_int(bestT); r[3] = bestPrim;
-                        for (int k = 0; k < sp; k++) r[4 + k] = (k < kWfLdsStack) ? stack[k * 64] : ovf[(k - kWfLdsStack) * ovfStride];
-                        if (PUBLISH) __hip_atomic_store((unsigned long long*)&b.hit[0][hs], (unsigned long long)__float_as_uint(bestT) | ((unsigned long long)(uint32_t)(-2 - (int)rec) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        else b.hit[0][hs] = make_float2(bestT, __int_as_float(-2 - (int)rec));
+                        if (pend != 0) { push(pend); pend = 0; }
+                        save_walk(suspOut + (size_t)rec * kSuspInts);
+                        store_hit<PUBLISH>(b, hs, bestT, -2 - (int)rec);
                         hasRay = false;
                         cur = kDone;
                     } else {
@@ -418,84 +450,21 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
             const int nNode = __builtin_popcountll(__ballot(cur >= 0));
             const int nTri = __builtin_popcountll(__ballot(hasRay && pend != 0));
             const int nBlk = __builtin_popcountll(__ballot(hasRay && pend != 0 && cur < 0));
-            const bool doTri = nTri > 0 && (nTri >= triTrig || nBlk >= nNode);
+            const bool doTri = nTri > 0 && (nTri >= kWfTriTrig || nBlk >= nNode);
             const bool doNode = !doTri;
-            if (STAT) {
-                if (doNode) { stNodeTrips++; stNodeLanes += nNode; } else { stTriTrips++; stTriLanes += nTri; }
-                stNoRayLanes += 64 - __builtin_popcountll(__ballot(hasRay));
-            }
-            PT_STCLK(1)
+            probe.after_vote(doNode, nNode, nTri, hasRay);
             if (doNode && cur >= 0) {
+                // ---- one 4-wide node (pt_trace.h: quad_order): nearest child next, the other hit children to the stack ----
                 steps++;
-                // ---- one 4-wide node: conservative slab test of its four quantised child boxes ----
-                // Child box = origin + 2^e * q.  Along each axis t(q) = q*A + B with A = 2^e * inv and
-                // B = (origin - org) * inv; both are widened by `sl` (2^-20 of their magnitudes, ~16 ulps),
-                // the near/far bytes are picked by the sign of the direction once per node (all four children
-                // of a coordinate share a dword), and the far side is cut at the closest hit.  The boxes only
-                // steer the search — acceptance is Triangle::hit + the reference's leaf box — so all that
-                // matters is that no box containing a point the ray reaches is ever rejected.
                 const uint4* np = sc.quad + 4 * (size_t)cur;
                 uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
-                if (MODE == 2 && stLogAt) {
-                    asm volatile("s_waitcnt vmcnt(0)" : "+v"(n0.x), "+v"(n1.x), "+v"(n2.x), "+v"(n3.x) :: "memory");
-                    stW3 = (uint32_t)((__builtin_amdgcn_s_memrealtime() - stT0) & 0xfffffull);
-                    stLogAt[3] = stW3;      // every lane of the node trip writes the same word
-                }
-                const float Ax = inv.x * __uint_as_float(n0.w), Ay = inv.y * __uint_as_float(n3.z), Az = inv.z * __uint_as_float(n3.w);      // scales are powers of two
-                const float Bx = (__uint_as_float(n0.x) - org.x) * inv.x;
-                const float By = (__uint_as_float(n0.y) - org.y) * inv.y;
-                const float Bz = (__uint_as_float(n0.z) - org.z) * inv.z;
-                const float kSl = 9.5367431640625e-7f;                           // 2^-20
-                const float sx = (__builtin_fabsf(Bx) + 255.f * __builtin_fabsf(Ax)) * kSl;
-                const float sy = (__builtin_fabsf(By) + 255.f * __builtin_fabsf(Ay)) * kSl;
-                const float sz = (__builtin_fabsf(Bz) + 255.f * __builtin_fabsf(Az)) * kSl;
-                const float Bnx = Bx - sx, Bfx = Bx + sx, Bny = By - sy, Bfy = By + sy, Bnz = Bz - sz, Bfz = Bz + sz;
-                // near / far bytes by the sign of the direction, as a masked swap: on this chip a second v_cndmask on the same vcc costs
-                // ~23 clocks (tools/valu_probe.py), xor / and / arithmetic shift ~2.3 each.  (A zero component of either sign gives
-                // A = B = +-0 on that axis: both planes at t = 0, so either assignment is the same test.)
-                const uint32_t mx = (uint32_t)(__float_as_int(inv.x) >> 31), my = (uint32_t)(__float_as_int(inv.y) >> 31), mz = (uint32_t)(__float_as_int(inv.z) >> 31);
-                const uint32_t swx = (n2.x ^ n2.w) & mx, swy = (n2.y ^ n3.x) & my, swz = (n2.z ^ n3.y) & mz;
-                const uint32_t nqx = n2.x ^ swx, fqx = n2.w ^ swx;   // lo.x = n2.x, hi.x = n2.w
-                const uint32_t nqy = n2.y ^ swy, fqy = n3.x ^ swy;   // lo.y = n2.y, hi.y = n3.x
-                const uint32_t nqz = n2.z ^ swz, fqz = n3.y ^ swz;   // lo.z = n2.z, hi.z = n3.y
-                const float cullT = bestT * cscale;
-                int key[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const float tnx = __builtin_fmaf((float)((nqx >> (8 * k)) & 0xffu), Ax, Bnx);
-                    const float tny = __builtin_fmaf((float)((nqy >> (8 * k)) & 0xffu), Ay, Bny);
-                    const float tnz = __builtin_fmaf((float)((nqz >> (8 * k)) & 0xffu), Az, Bnz);
-                    const float tfx = __builtin_fmaf((float)((fqx >> (8 * k)) & 0xffu), Ax, Bfx);
-                    const float tfy = __builtin_fmaf((float)((fqy >> (8 * k)) & 0xffu), Ay, Bfy);
-                    const float tfz = __builtin_fmaf((float)((fqz >> (8 * k)) & 0xffu), Az, Bfz);
-                    const float tn = __builtin_fmaxf(__builtin_fmaxf(tnx, tny), __builtin_fmaxf(tnz, 0.f));
-                    const float tf = __builtin_fminf(__builtin_fminf(tfx, tfy), __builtin_fminf(tfz, cullT));
-                    key[k] = (tn <= tf) ? __float_as_int(tn) : 0x7fffffff;   // tn >= 0: its bits order like ints
-                }
-                // sort (entry distance, ref) pairs: 5 compare-exchanges, each one compare + four selects (equal distances: any order will do)
-                int k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3], r0 = (int)n1.x, r1 = (int)n1.y, r2 = (int)n1.z, r3 = (int)n1.w;
-#define PT_CE(ka, ra, kb, rb) { const bool sw = ka > kb; const int tk = sw ? kb : ka, tr = sw ? rb : ra; kb = sw ? ka : kb; rb = sw ? ra : rb; ka = tk; ra = tr; }
-                PT_CE(k0, r0, k1, r1) PT_CE(k2, r2, k3, r3) PT_CE(k0, r0, k2, r2) PT_CE(k1, r1, k3, r3) PT_CE(k1, r1, k2, r2)
-#undef PT_CE
-                if (k0 != 0x7fffffff) {
-                    // nearest child next; the other hit children go to the stack, farthest first
-                    if (k3 != 0x7fffffff) { if (sp < kWfLdsStack) stack[sp * 64] = r3; else ovf[(sp - kWfLdsStack) * ovfStride] = r3; sp++; }
-                    if (k2 != 0x7fffffff) { if (sp < kWfLdsStack) stack[sp * 64] = r2; else ovf[(sp - kWfLdsStack) * ovfStride] = r2; sp++; }
-                    if (k1 != 0x7fffffff) { if (sp < kWfLdsStack) stack[sp * 64] = r1; else ovf[(sp - kWfLdsStack) * ovfStride] = r1; sp++; }
-                    cur = r0;
-                } else if (sp == 0) {
-                    cur = kDone;
-                } else {
-                    sp--;
-                    cur = stack_at(sp);
-                }
-                if (HIST) atomicAdd(&stat[kStatDepthHist + (sp > 31 ? 31 : sp)], 1ull);      // stack depth after this node step
-                if (cur < 0 && cur != kDone && pend == 0) {
-                    // park the leaf, carry on with the next stack entry
-                    pend = cur;
-                    if (sp == 0) cur = kDone;
-                    else { sp--; cur = stack_at(sp); }
-                }
+                probe.node_arrived(n0, n1, n2, n3);
+                int k0, k1, k2, k3, r0, r1, r2, r3;
+                quad_order(n0, n1, n2, n3, org, inv, bestT * cscale, k0, k1, k2, k3, r0, r1, r2, r3);
+                if (!quad_descend(k0, k1, k2, k3, r0, r1, r2, r3, cur, push)) pop();
+                probe.after_node(sp);
+                // a leaf: park it, carry on with the next stack entry
+                if (cur < 0 && cur != kDone && pend == 0) { pend = cur; pop(); }
             } else if (doTri && hasRay && pend != 0) {
                 // ---- the parked leaf: its (up to) two triangles in one go ----
                 const int code = ~pend, first = code >> 3, cnt = code & 7;
@@ -505,21 +474,12 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     if (bestPrim >= 0 && bestT < stopBelow) { cur = kDone; sp = 0; }          // shadow ray: any occluder in front of the light will do
                     else if (cnt > 2) pend = ~(((first + 2) << 3) | (cnt - 2));
                 }
-                if (pend == 0 && cur < 0 && cur != kDone) {
-                    // the ray was waiting with a second leaf: park that one, take the next stack entry
-                    pend = cur;
-                    if (sp == 0) cur = kDone;
-                    else { sp--; cur = stack_at(sp); }
-                }
+                // the ray was waiting with a second leaf: park that one, take the next stack entry
+                if (pend == 0 && cur < 0 && cur != kDone) { pend = cur; pop(); }
             }
-            PT_STCLK(doNode ? 2 : 3)
+            probe.after_step(doNode);
             if (hasRay && cur == kDone && pend == 0) {
-                // spheres, in order, against the triangles' closest t (CudaUtil.cuh:137-145)
-                for (int s = 0; s < sc.n_spheres; s++) {
-                    const float4 c = sc.spheres[4 * s];
-                    float root;
-                    if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; }
-                }
+                spheres_closest(sc, org, dir, bestT, bestPrim);
                 // A shadow ray (hs >= n16) that hit something: the verdict is formed here, where org, dir and t are still in registers — is the
                 // hit the sampled light point? — and the record carries the primitive only if it is (pt_shade.h: nee_verdict).  wf_shade then
                 // needs neither the ray nor the light point.  lp and lpA lie back to back like every per-kind array: lp[(kind - 1) n16 + sid].
@@ -531,57 +491,14 @@ void wf_trace(DevScene sc, WfBuf b, int slot, int ovfStride, int parity, int chu
                     const float4 lq = b.lp[hs - n16];
                     bestPrim = nee_verdict(org, dir, f3(lq.x, lq.y, lq.z), bestT, bestPrim);
                 }
-                if (PUBLISH) __hip_atomic_store((unsigned long long*)&b.hit[0][hs], (unsigned long long)__float_as_uint(bestT) | ((unsigned long long)(uint32_t)bestPrim << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else b.hit[0][hs] = make_float2(bestT, __int_as_float(bestPrim));
+                store_hit<PUBLISH>(b, hs, bestT, bestPrim);
                 hasRay = false;
-                if (STAT || MODE == 2) stRays++;
-                // node steps of this ray (this launch), bins of 4.  steps < 0: the ray spent its budget while the suspend pool was full and carried
-                // on (steps = -(1 << 28) above) — the last bin, never an index below the buffer
-                if (HIST) atomicAdd(&stat[kStatStepHist + ((steps < 0 || steps >= 252) ? 63 : steps >> 2)], 1ull);
+                probe.ray_end(steps);
             }
-            PT_STCLK(4)
+            probe.trip_ends();
         }
     }
-#undef PT_STCLK
-    if (timeline) {
-        // per-lane ray count -> wave total
-        unsigned long long r = stRays;
-        if (STAT || MODE == 2) for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o);
-        if (lane == 0 && stDump) {
-            // the dumped launch: one record per wave and none of the pooled statistics below (their atomics on a few hot words come from
-            // every wave as it leaves, i.e. all through the launch tail that is being looked at)
-            if (stWave < (uint32_t)kStatWaves) {
-                unsigned long long* w = stat + kStatWords + (size_t)stWave * 8;
-                w[0] = stT0; w[1] = stTExh; w[2] = __builtin_amdgcn_s_memrealtime(); w[3] = stTrips; w[4] = stTripsDry; w[5] = r;
-                w[6] = __builtin_amdgcn_s_getreg(4 | (31 << 11));       // HW_ID: wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]
-                w[7] = __builtin_amdgcn_s_getreg(20 | (31 << 11));      // XCC_ID
-            }
-        } else if (lane == 0) {
-            if (STAT) { atomicAdd(&stat[0], stNodeTrips); atomicAdd(&stat[1], stNodeLanes); atomicAdd(&stat[2], stTriTrips); atomicAdd(&stat[3], stTriLanes); }
-            // launch timeline (100 MHz ticks): earliest wave start, earliest "queue empty", latest wave exit
-            // MODE 2 keeps it in kStatStripes copies and nothing else unless stat[5] asks for the pooled histograms (PTAMD_TPOOL=1): atomics from
-            // every leaving wave on a handful of words stretched the very tail they were meant to measure (r03_b27.log: a launch of 100 us
-            // became one of 287 us)
-            unsigned long long* tl = MODE == 2 ? stat + kStatStripeOff / 8 + 3 * ((size_t)statLaunch * kStatStripes + (blockIdx.x % kStatStripes)) : stat + kStatTimeline + 3 * (size_t)statLaunch;
-            const unsigned long long tEnd = __builtin_amdgcn_s_memrealtime();
-            atomicMax(&tl[0], ~stT0); if (stTExh) atomicMax(&tl[1], ~stTExh); atomicMax(&tl[2], tEnd);
-            if (blockIdx.x == 0 && threadIdx.x == 0) stat[kStatLaunchRays + statLaunch] = n;      // rays of this launch
-            if (MODE == 2 && stat[5] == 0ull) return;
-            // distribution of wave exit times over the launch, all launches pooled (absolute: 32 us bins)
-            unsigned long long* hist = stat + kStatLifeHist;
-            const unsigned long long dtk = (tEnd - stT0) / 3200ull;      // 32 us bins (100 MHz ticks)
-            atomicAdd(&hist[dtk < 31 ? dtk : 31], 1ull);
-            if (MODE == 2) {
-                // per-wave work, all launches pooled: trips per wave (64 bins of 4), trips after the wave found the queue dry (32 bins of 2: in the
-                // slots of MODE 1's per-ray histograms), and rays per wave summed into stat[7] / trips into stat[0] for averages
-                atomicAdd(&stat[kStatStepHist + (stTrips >= 252 ? 63 : stTrips >> 2)], 1ull);
-                atomicAdd(&stat[kStatDepthHist + (stTripsDry >= 62 ? 31 : stTripsDry >> 1)], 1ull);
-                atomicAdd(&stat[7], r); atomicAdd(&stat[0], (unsigned long long)stTrips); atomicAdd(&stat[2], (unsigned long long)stTripsDry);
-            }
-            if (STAT) { atomicAdd(&stat[4], stRefills); atomicAdd(&stat[5], stRefillLanes); atomicAdd(&stat[6], stNoRayLanes); atomicAdd(&stat[7], r); }
-            if (STAT) for (int k = 0; k < 5; k++) atomicAdd(&stat[kStatClocks + k], stClk[k]);
-        }
-    }
+    probe.wave_end(n, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -611,13 +528,16 @@ PT_DEV float2 load_hit(const float2* p)
 }
 
 // Cam: a DevCamera, the ViewTable of a batch of views (pt_render_views) or the RayTable of the caller's rays (pt_render_rays) — all that
-// differs is where a restarted camera ray takes its origin from (pt_stream.h: camera_origin).  A batch and a ray set are built for 4 waves
-// per SIMD only, the default shape (PTAMD_SW does not apply to them).
+// differs is where a restarted camera ray takes its origin from (pt_stream.h: camera_origin).
+// 4 waves/SIMD (126 VGPRs, nothing spilled since the library is built without the SLP vectoriser): 3 waves/SIMD is 9...13 % slower
+// (r02_t16_shade_shapes_after_noslp.log).
+// WAVES is 4 and MARK is PHASE != 0 in every instantiation the pipeline names (shade_kernel); both stay template parameters because
+// they are part of the kernels' names, which profiles and tests read.
 template <int WAVES, bool TWO, int PHASE = 0, bool MARK = false, class Cam = DevCamera>
 __global__ __launch_bounds__(WAVES * 256, WAVES)
 void wf_shade(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int slotOut, int slotClear, int listIn)
 {
-    static_assert(PHASE == 0 || MARK, "the two-phase step needs the not-ready marks");
+    static_assert(WAVES == 4 && MARK == (PHASE != 0), "the two-phase step needs the not-ready marks; one launch per step does not");
     const uint32_t nIn = b.cnt[slotIn].nActive;
     if (PHASE != 1 && blockIdx.x == 0) for (int k = threadIdx.x; k < kWfSlotBytes / 4; k += blockDim.x) ((uint32_t*)&b.cnt[slotClear])[k] = 0;
     if ((uint32_t)blockIdx.x * blockDim.x >= nIn) return;
@@ -679,14 +599,9 @@ void wf_shade(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int slot
     }
     // a re-queued suspended traversal is long by definition: cls = 0 for it (it never went through the step)
     const bool s0 = (cls & 1u) != 0, s1 = (cls & 2u) != 0, s2 = (cls & 4u) != 0;
-    const uint32_t topIdx = (uint32_t)(b.hit[1] - b.hit[0]) - 1u;      // n16 - 1
     const bool e[kLists] = {alive, emit[0] && !s0, emit[1] && !s1, emit[2] && !s2, emit[0] && s0, emit[1] && s1, emit[2] && s2};
-    uint32_t* const c[kLists] = {&b.cnt[slotOut].nActive, &b.cnt[slotOut].nRays[0][0], &b.cnt[slotOut].nRays[1][0], &b.cnt[slotOut].nRays[2][0],
-                                 &b.cnt[slotOut].nRays[0][kShortWord], &b.cnt[slotOut].nRays[1][kShortWord], &b.cnt[slotOut].nRays[2][kShortWord]};
-    uint32_t* const l[kLists] = {b.active[listIn ^ 1], b.rq[0], b.rq[1], b.rq[2], b.rq[0], b.rq[1], b.rq[2]};
     const uint32_t ids[kLists] = {sid, sid | resume, sid | resume, sid | resume, sid, sid, sid};
-    const uint32_t top[kLists] = {0u, 0u, 0u, 0u, topIdx, topIdx, topIdx};
-    block_append<kLists>(e, ids, c, l, top);
+    append_lists(b, slotOut, b.active[listIn ^ 1], e, ids);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -747,11 +662,7 @@ void wf_drain(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int list
                     bestPrim = -1; cur = 0; sp = 0;
                 }
                 if (quad_step(sc, org, dir, inv, cscale, degenerate, stopBelow, stack, cur, sp, bestT, bestPrim)) {
-                    for (int s = 0; s < sc.n_spheres; s++) {      // spheres, in order, against the triangles' closest t (CudaUtil.cuh:137-145)
-                        const float4 c = sc.spheres[4 * s];
-                        float root;
-                        if (sphere_root(f3(c.x, c.y, c.z), c.w, org, dir, bestT, root)) { bestT = root; bestPrim = sc.n_tris + s; }
-                    }
+                    spheres_closest(sc, org, dir, bestT, bestPrim);
                     if (kind != 2) bestPrim = nee_verdict(org, dir, lightP, bestT, bestPrim);      // a shadow ray's record carries the verdict
                     const float2 h = make_float2(bestT, __int_as_float(bestPrim));
                     if (kind == 0) hitA = h; else if (kind == 1) hitS = h; else hitP = h;
@@ -772,18 +683,12 @@ void wf_drain(DevScene sc, Cam cam, DevParams prm, WfBuf b, int slotIn, int list
     write_mean(b, prm, sid, st);
 }
 
-// The wf_shade instantiation for one step: every one the pipeline launches is named here, 12 for one camera and 8 each for a batch of
-// views and for a ray set (4 waves per SIMD only).  The early phases and every launch with marks run the default shape.
+// The wf_shade instantiation for one step: every one the pipeline launches is named here, 6 for each of the three camera types.
 template <class Cam>
-static auto shade_kernel(int waves, bool two, int phase, bool mark) -> void (*)(DevScene, Cam, DevParams, WfBuf, int, int, int, int)
+static auto shade_kernel(bool two, int phase) -> void (*)(DevScene, Cam, DevParams, WfBuf, int, int, int, int)
 {
     if (phase == 1) return two ? wf_shade<4, true, 1, true, Cam> : wf_shade<4, false, 1, true, Cam>;
     if (phase == 2) return two ? wf_shade<4, true, 2, true, Cam> : wf_shade<4, false, 2, true, Cam>;
-    if (mark) return two ? wf_shade<4, true, 0, true, Cam> : wf_shade<4, false, 0, true, Cam>;
-    if constexpr (std::is_same_v<Cam, DevCamera>) {
-        if (waves == 2) return two ? wf_shade<2, true> : wf_shade<2, false>;
-        if (waves == 3) return two ? wf_shade<3, true> : wf_shade<3, false>;
-    }
     return two ? wf_shade<4, true, 0, false, Cam> : wf_shade<4, false, 0, false, Cam>;
 }
 
@@ -891,36 +796,17 @@ static void carve(char* p, size_t nStreams, int traceBlocks, ptd::WfBuf& b)
 
 const float* ptk_wf_staging(void* work) { return (const float*)work; }
 
-// Scheduling constants of the pipeline, read from the environment ONCE per process (tuning and A/B sweeps only — none of them can
-// change a result).  Defaults are the measured optima on MI355X.
+// What the pipeline still reads from the environment, ONCE per process: the node budget of wf_trace, which tests set to force time
+// slicing, and the choice of its diagnostic build.  None of them can change a result.  Defaults are the measured
+// optima on MI355X.
 struct WfTuning {
-    int chunkShift;      // PTAMD_CS   chunk  = clamp(n >> CS, 16, kWfChunk) ray ids per queue access
-    int guideShift;      // PTAMD_GS   guided = the chunk shrinks to (rays left in the shard) >> GS
     int budgetShift;     // PTAMD_BS   node budget = clamp(n >> BS, BM, 1024) steps per launch
     int budgetMin;       // PTAMD_BM
-    int refillMin;       // PTAMD_RF   idle lanes that trigger a refill
-    int triTrig;         // PTAMD_TT   parked leaves that force a triangle trip (64 = only when blocked rays outnumber walking ones)
-    int helpShards;      // PTAMD_HELP shards a wave tries (its own included) before it takes the queue to be dry: 4 (16 = all: every wave then
-                         // spends 16 returning atomics on hot words at the end of every launch; the shards are interleaved and equally long, so
-                         // there is little to help with: 16 -> 4 is +1 % on configs[2], +3 % on configs[1], +4.5 % for an 8-way rank, r03_b20.log)
     int lateBudget;      // PTAMD_LB   node steps after which a ray is suspended once the queue is dry and its wave holds at most two rays: 64 (0 = never).
                          // An 8-way rank's big launches wait 15 us on average (20 % of them > 25 us, 3 % > 100 us) for the latest of their 64 stripes of
                          // waves — one ray of several hundred steps, alone on its SIMD (tools/straggler_cost.py, r03_b41.log); cut there it goes on in
                          // the next launch among full waves, and no iteration is added: 4-way rank +3 %, 8-way +0.4 ... +2.5 %, configs[2] / [3] / [4]
                          // +0.3 / +0.5 / +1.2 % (32: -4 %, 48 / 96 / 128 within 1 % of 64; r03_b42.log, r03_b43.log)
-    // wf_shade: 4 waves/SIMD (126 VGPRs, nothing spilled since the library is built without the SLP vectoriser) in 512-thread workgroups =
-    // two per CU; other shapes: 256 threads -4 %, 384 / 768 -13 %, 1024 -8 %, 3 waves/SIMD -9...-13 % (r02_t16_shade_shapes_after_noslp.log)
-    int shadeWaves;      // PTAMD_SW   (one camera only: a batch of views runs the default shape)
-    int shadeThreads;    // PTAMD_ST
-    // wf_shade: may a stream whose path has just ended start its next sample in the same step (a second trip through the bounce code)?
-    // It saves one iteration per sample but doubles the step's dependent chain: shadeRounds 0 / 1 forces it (pt_set_shade_rounds,
-    // PTAMD_TR), -1 switches at trStreams live streams.  The result does not depend on it (pt_stream.h: shade_step_t).
-    uint32_t trStreams;  // PTAMD_TRS
-    int earlyThreads;    // PTAMD_EST  threads per workgroup of wf_shade's early phase (64: one free wave slot is enough; 512 / 256 / 128 / 64 -> 0.488 / 0.481 / 0.473 / 0.472 s for an 8-way rank)
-    int earlyPrio;       // PTAMD_EPRIO issue priority of the traversal waves while the early phase runs beside them (no effect measured)
-    bool pubOnly;        // PTAMD_EPUB  A/B: device-scope hit stores and marks, but no early phase
-    int drainSpread;     // PTAMD_DSPREAD  wf_drain: at most every 2^this-th lane carries a stream (3)
-    int drainQuad;       // PTAMD_DQUAD    wf_drain walks the 4-wide tree (1; 0 = the binary tree of the one-kernel mode, A/B)
     bool tracePool;      // PTAMD_TPOOL with PTAMD_TSTAT=2: also the pooled per-wave histograms (tools/wave_exit_hist.py) — their atomics lengthen the launch tail
     int traceDump;       // PTAMD_TDUMP with PTAMD_TSTAT=2: the wf_trace launch (iteration) whose waves are dumped one by one (pt_dbg_trace_timeline -3003 / -3004)
     int traceStat;       // PTAMD_TSTAT 1 trip counters + histograms (slower build), 2 timeline only (production code path), 3 trip counters + section clocks
@@ -929,34 +815,45 @@ static const WfTuning& wf_tuning()
 {
     static const WfTuning t = [] {
         auto num = [](const char* name, long long def) -> long long { const char* v = getenv(name); return v ? atoll(v) : def; };
-        auto threads = [&](const char* name, int def) { const long long v = num(name, def); return (v >= 64 && v <= ptd::kShadeThreads) ? (int)(v & ~63LL) : def; };
         WfTuning w;
-        w.chunkShift = (int)num("PTAMD_CS", 12); w.guideShift = (int)num("PTAMD_GS", 9);
         w.budgetShift = (int)num("PTAMD_BS", 14); w.budgetMin = (int)num("PTAMD_BM", ptd::kWfBudget);
-        w.refillMin = (int)num("PTAMD_RF", ptd::kWfRefill); w.triTrig = (int)num("PTAMD_TT", 64);
         w.lateBudget = (int)num("PTAMD_LB", 64);
-        w.helpShards = (int)num("PTAMD_HELP", 4); if (w.helpShards < 1) w.helpShards = 1; if (w.helpShards > ptd::kWfShards) w.helpShards = ptd::kWfShards;
-        w.shadeWaves = (int)num("PTAMD_SW", 4); w.shadeThreads = threads("PTAMD_ST", 512);
-        w.trStreams = (uint32_t)num("PTAMD_TRS", 4000000);
-        w.earlyThreads = threads("PTAMD_EST", 64); w.earlyPrio = (int)num("PTAMD_EPRIO", 0); w.pubOnly = num("PTAMD_EPUB", 0) != 0;
         w.traceStat = (int)num("PTAMD_TSTAT", 0);
         w.traceDump = (int)num("PTAMD_TDUMP", -1);
         w.tracePool = num("PTAMD_TPOOL", 0) != 0;
-        w.drainQuad = num("PTAMD_DQUAD", 1) != 0 ? 1 : 0;
-        w.drainSpread = (int)num("PTAMD_DSPREAD", 3); if (w.drainSpread < 0) w.drainSpread = 0; if (w.drainSpread > 5) w.drainSpread = 5;
         return w;
     }();
     return t;
 }
+// The rest of the schedule is fixed; each figure is the measured optimum.
+// wf_shade runs 512-thread workgroups, two per CU; other shapes: 256 threads -4 %, 384 / 768 -13 %, 1024 -8 % (r02_t16_shade_shapes_after_noslp.log)
+constexpr int kShadeBlock = 512;
+// wf_shade's early phase runs one-wave workgroups: one free wave slot is enough (512 / 256 / 128 / 64 threads -> 0.488 / 0.481 / 0.473 / 0.472 s for an 8-way rank)
+constexpr int kEarlyBlock = 64;
+// wf_shade: may a stream whose path has just ended start its next sample in the same step (a second trip through the bounce code)?
+// It saves one iteration per sample but doubles the step's dependent chain: shadeRounds 0 / 1 forces it (pt_set_shade_rounds,
+// PTAMD_TR), -1 switches to it below this many live streams.  The result does not depend on it (pt_stream.h: shade_step_t).
+constexpr uint32_t kTwoRoundsBelow = 4000000;
+constexpr int kDrainSpread = 3;      // wf_drain: at most every 2^this-th lane carries a stream
 int ptk_wf_trace_stat(void) { return wf_tuning().traceStat; }
 
 }  // extern "C"
 
+// One launch of wf_trace<MODE, PUBLISH> for iteration `it`.  A diagnostic build also gets the counter buffer and the launch's slot of its
+// timeline (later launches share the last one); the production kernel has no such argument (pt_trace_probe.h).
+template <int MODE, bool PUBLISH = false>
+static void launch_trace(const ptd::WfJob& job, const ptd::WfBuf& b, int blocks, int ovfStride, int it, const WfTuning& tn)
+{
+    using namespace ptd;
+    const typename TraceProbe<MODE>::Args probeArgs{job.traceStat, it < kStatLaunches ? it : kStatLaunches - 1};
+    hipLaunchKernelGGL((wf_trace<MODE, PUBLISH>), dim3(blocks), dim3(256), 0, job.stream, *job.scene, b, it % 3, ovfStride, it & 1, tn.budgetShift, tn.budgetMin, tn.lateBudget, probeArgs);
+}
+
 // The pipeline for one job whose streams take their pixel and camera from `cam` (DevCamera: a frame share or a tile list; ViewTable; RayTable):
-// `init` launches the kind's init kernel, and every later launch names the Cam instantiation of its kernel.  shadeWaves: waves per SIMD of
-// wf_shade.  Blocks the host until the render has drained (it polls the live-stream count every 16..64 iterations).
+// `init` launches the kind's init kernel, and every later launch names the Cam instantiation of its kernel.
+// Blocks the host until the render has drained (it polls the live-stream count every 16..64 iterations).
 template <class Cam, class Init>
-static hipError_t pipeline(const ptd::WfJob& job, const ptd::WfBuf& b, const Cam& cam, int shadeWaves, Init init)
+static hipError_t pipeline(const ptd::WfJob& job, const ptd::WfBuf& b, const Cam& cam, Init init)
 {
     using namespace ptd;
     const DevParams& prm = job.prm;
@@ -987,10 +884,9 @@ static hipError_t pipeline(const ptd::WfJob& job, const ptd::WfBuf& b, const Cam
     // every iteration (one rank of an 8-way tile split), the shade step starts on `aux` beside the draining wf_trace and the rest
     // follows both (result-neutral).  Decided once per render: a large render gains nothing from it in its last iterations.
     // (not below ~1/8 of the limit either: a render that small is bound by launch latency, and this adds a launch and two waits per iteration)
-    const bool early = job.earlyBelow > 0 && nStreams <= (size_t)job.earlyBelow && nStreams >= (size_t)job.earlyBelow / 8 && !job.traceStat && !tn.pubOnly;
-    const bool marks = early || tn.pubOnly;
-    // one launch for every build of wf_trace
-    const auto trace = job.traceStat ? (tn.traceStat == 3 ? wf_trace<3> : tn.traceStat == 1 ? wf_trace<1> : wf_trace<2>) : marks ? wf_trace<0, true> : wf_trace<0>;
+    const bool early = job.earlyBelow > 0 && nStreams <= (size_t)job.earlyBelow && nStreams >= (size_t)job.earlyBelow / 8 && !job.traceStat;
+    // the production kernel (it publishes its hits when the early phase reads them), or the diagnostic build PTAMD_TSTAT names
+    const auto trace = job.traceStat ? (tn.traceStat == 3 ? launch_trace<3> : tn.traceStat == 1 ? launch_trace<1> : launch_trace<2>) : early ? launch_trace<0, true> : launch_trace<0>;
     int it = 0;
     int poll = 16;
     // streams only ever retire, so the live count of the last poll bounds every later one: the shade grid
@@ -1006,20 +902,18 @@ static hipError_t pipeline(const ptd::WfJob& job, const ptd::WfBuf& b, const Cam
                 if ((e = hipEventRecord(toAux[it & 1], stream)) != hipSuccess) return e;
                 if ((e = hipStreamWaitEvent(aux, toAux[it & 1], 0)) != hipSuccess) return e;
             }
-            // statLaunch is the timeline slot of a diagnostic build, the issue priority in production
-            const int statLaunch = job.traceStat ? (it < kStatLaunches ? it : kStatLaunches - 1) : marks ? tn.earlyPrio : 0;
-            hipLaunchKernelGGL(trace, dim3(tb), dim3(256), 0, stream, *job.scene, b, sIn, ovfStride, it & 1, tn.chunkShift, tn.budgetShift, tn.budgetMin, tn.guideShift, tn.triTrig, tn.refillMin, job.traceStat, statLaunch, tn.helpShards, tn.lateBudget);
+            trace(job, b, tb, ovfStride, it, tn);
             if (timed) (void)hipEventRecord(job.trace_ev[3 * it + 1], stream);
-            const dim3 sg((liveBound + tn.shadeThreads - 1) / tn.shadeThreads), sb(tn.shadeThreads);
-            const bool twoRounds = job.shadeRounds >= 0 ? (job.shadeRounds != 0) : (liveBound < tn.trStreams);
+            const dim3 sg((liveBound + kShadeBlock - 1) / kShadeBlock), sb(kShadeBlock);
+            const bool twoRounds = job.shadeRounds >= 0 ? (job.shadeRounds != 0) : (liveBound < kTwoRoundsBelow);
             // one launch for every instantiation of wf_shade
             auto shade = [&](int phase, hipStream_t s, dim3 g, dim3 blk) {
-                hipLaunchKernelGGL(shade_kernel<Cam>(shadeWaves, twoRounds, phase, marks), g, blk, 0, s, *job.scene, cam, prm, b, sIn, sOut, sClr, it & 1);
+                hipLaunchKernelGGL(shade_kernel<Cam>(twoRounds, phase), g, blk, 0, s, *job.scene, cam, prm, b, sIn, sOut, sClr, it & 1);
             };
             if (early) {
                 // phase 1 in small workgroups: a 256-thread workgroup needs one free wave slot per SIMD, i.e. two traversal workgroups of
                 // the CU gone, a 512-thread one four — it gets onto the chip earlier in the drain
-                shade(1, aux, dim3((liveBound + tn.earlyThreads - 1) / tn.earlyThreads), dim3(tn.earlyThreads));
+                shade(1, aux, dim3((liveBound + kEarlyBlock - 1) / kEarlyBlock), dim3(kEarlyBlock));
                 if ((e = hipEventRecord(toMain[it & 1], aux)) != hipSuccess) return e;
                 if ((e = hipStreamWaitEvent(stream, toMain[it & 1], 0)) != hipSuccess) return e;
                 shade(2, stream, sg, sb);
@@ -1036,11 +930,11 @@ static hipError_t pipeline(const ptd::WfJob& job, const ptd::WfBuf& b, const Cam
         if (live <= (uint32_t)job.drainBelow) {
             // few streams left: finish them in one launch instead of hundreds of latency-bound iterations
             // the 4-wide tree if its walk fits the per-lane stack (any tree the builder makes for the config scenes does), else the binary one
-            const bool quadWalk = tn.drainQuad && 3 * job.scene->quad_depth + 2 <= kDrainQuadStack;
+            const bool quadWalk = 3 * job.scene->quad_depth + 2 <= kDrainQuadStack;
             // 2 (4-wide walk: 189 VGPRs) or 3 (165) waves per SIMD of wf_drain fit: spread the streams over at most that many lanes
             const size_t drainLanes = (size_t)((quadWalk && DRAIN_MINBLOCKS < 3) ? 2 : 3) * 4 * 256 * 64;
             int spread = 0;
-            while (spread < tn.drainSpread && ((size_t)live << (spread + 1)) <= drainLanes) spread++;
+            while (spread < kDrainSpread && ((size_t)live << (spread + 1)) <= drainLanes) spread++;
             const int db = (int)((((size_t)live << spread) + kBlockThreads - 1) / kBlockThreads);
             hipLaunchKernelGGL((quadWalk ? wf_drain<true, Cam> : wf_drain<false, Cam>), dim3(db), dim3(kBlockThreads), 0, stream, *job.scene, cam, prm, b, it % 3, it & 1, spread);
             if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -1059,8 +953,7 @@ static hipError_t pipeline(const ptd::WfJob& job, const ptd::WfBuf& b, const Cam
 extern "C" {
 
 // Runs the whole pipeline for one job (pt_internal.h: WfJob) on the caller's stream and blocks the host until the render has drained.
-// The pixel source is decided here, once: its init kernel and its camera type.  A batch of views and a ray set always run the
-// 4-waves-per-SIMD wf_shade (the only shape their instantiations are built for); one camera honours PTAMD_SW.
+// The pixel source is decided here, once: its init kernel and its camera type.
 hipError_t ptk_wf_render(const ptd::WfJob& job)
 {
     using namespace ptd;
@@ -1073,21 +966,20 @@ hipError_t ptk_wf_render(const ptd::WfJob& job)
     b.staging = (float*)job.work;
     hipError_t e;
     if ((e = hipEventRecord(job.ev_begin, stream)) != hipSuccess) return e;
-    const int sw = wf_tuning().shadeWaves;
     switch (src.kind) {
     case WfSource::kFrame:
-        e = pipeline(job, b, src.frame.cam, sw, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init, g, dim3(256), 0, stream, *job.scene, src.frame.cam, prm, b, n); });
+        e = pipeline(job, b, src.frame.cam, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init, g, dim3(256), 0, stream, *job.scene, src.frame.cam, prm, b, n); });
         break;
     case WfSource::kTileList:
-        e = pipeline(job, b, src.list.cam, sw, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init_list, g, dim3(256), 0, stream, *job.scene, src.list.cam, prm, b, n, src.list.tiles); });
+        e = pipeline(job, b, src.list.cam, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init_list, g, dim3(256), 0, stream, *job.scene, src.list.cam, prm, b, n, src.list.tiles); });
         break;
     case WfSource::kViews: {
         const ViewTable views{src.views.org, (uint32_t)prm.n_tiles_total};
-        e = pipeline(job, b, views, 4, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init_views, g, dim3(256), 0, stream, *job.scene, prm, b, n, src.views.cams, src.views.firstPass, views.tilesPerView); });
+        e = pipeline(job, b, views, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init_views, g, dim3(256), 0, stream, *job.scene, prm, b, n, src.views.cams, src.views.firstPass, views.tilesPerView); });
         break;
     }
     case WfSource::kRays:
-        e = pipeline(job, b, RayTable{src.rays.rays8}, 4, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init_rays, g, dim3(256), 0, stream, *job.scene, prm, b, n, src.rays.rays8, src.rays.seed, (uint32_t)src.rays.seedStride, src.rays.nRays); });
+        e = pipeline(job, b, RayTable{src.rays.rays8}, [&](dim3 g, uint32_t n) { hipLaunchKernelGGL(wf_init_rays, g, dim3(256), 0, stream, *job.scene, prm, b, n, src.rays.rays8, src.rays.seed, (uint32_t)src.rays.seedStride, src.rays.nRays); });
         break;
     }
     if (e != hipSuccess) {

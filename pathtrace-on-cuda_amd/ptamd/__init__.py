@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("PTAMD_LIB") or os.path.join(PKG_ROOT, "libptamd.so")      # PTAMD_LIB: A/B builds of the same library
 
+TRACE_STAT_LAUNCHES = 2700      # csrc/pt_device.h: kStatLaunches, the wf_trace launches the diagnostic counter buffer has a slot for (later ones share the last)
 PRIM_FLOATS = 84      # sizeof(PtPrimitive) / 4   (3 x 112-byte Vertex, include/mesh.h:21-37)
 TRI_FLOATS = 88       # sizeof(PtTriangle) / 4
 NODE_BYTES = 40       # sizeof(PtBVHNode)        (CudaBVHNode, include/CudaPrimitive.cuh:237-247)
@@ -417,6 +418,13 @@ class Scene:
         with 0 .. 30 and with 31 or more entries (32 x int64).  Entries 16 and up lie in the stack's global-memory overflow."""
         raw = np.zeros(32, np.int64)
         _check(lib().pt_dbg_trace_timeline(self._h, _ptr(raw), -3001), "pt_dbg_trace_timeline")
+        return raw
+
+    def trace_step_hist(self):
+        """Diagnostic (PTAMD_TSTAT=1): node steps per finished ray over the wf_trace launches of the last render, 64 bins of 4 steps
+        (the last bin: 252 or more)."""
+        raw = np.zeros(64, np.int64)
+        _check(lib().pt_dbg_trace_timeline(self._h, _ptr(raw), -3000), "pt_dbg_trace_timeline")
         return raw
 
     def nee(self, in5):

@@ -195,7 +195,9 @@ from test_needle_scene import camera, params, scene
 sc = scene()
 sc.set_drain_threshold(0)
 img = sc.render(camera(), params())
-np.savez(sys.argv[3], img=img, hist=sc.trace_depth_hist(), iterations=sc.last_iterations())
+it = sc.last_iterations()
+np.savez(sys.argv[3], img=img, hist=sc.trace_depth_hist(), iterations=it, counters=sc.counters(), launch_rays=sc.trace_launch_rays(it),
+         step_hist=sc.trace_step_hist())
 """
 
 
@@ -203,7 +205,14 @@ def test_the_stack_overflow_path_runs(needle, tmp_path):
     """The counting build of wf_trace (PTAMD_TSTAT=1) bins the stack depth after every node step.  At least 1 % of the node steps of the
     frame's render must leave the stack at 16 entries or more (the CPU walk of tools/stack_lab.cpp gives 2.9 % for the camera rays;
     the margin is for the kernel's cull, which parked leaves delay), and some step at 20 or more.
-    Measured on an MI355X: see DESIGN.md, "The needle scene"."""
+    Measured on an MI355X: see DESIGN.md, "The needle scene".
+    What the counting build's own counters must satisfy, by construction (pt_trace_probe.h): every queue index of a launch is handed to
+    exactly one lane, so counters()[5], the lanes refilled, is the sum of the launches' ray counts; a node trip (counters()[0]) serves
+    at most 64 lanes (counters()[1]), and so does a triangle trip ([2], [3]); every finished ray adds one to the histogram of node steps
+    per ray and one to counters()[7].  The stack-depth histogram gets one count from every lane of every node trip; counters()[0..3]
+    are lane 0's accumulators, and lane 0 counts a trip only while it holds a ray itself, so they are a part of the trips: the
+    histogram's sum is an upper bound of counters()[1], not equal to it (MI355X, this render: 32.7 M steps in the histogram, 26.3 M
+    lanes in counters()[1], 35,870 finished rays)."""
     out = tmp_path / "hist.npz"
     _child(tmp_path, _HIST_CHILD, [out], {"PTAMD_TSTAT": "1"})
     g = np.load(out)
@@ -215,6 +224,14 @@ def test_the_stack_overflow_path_runs(needle, tmp_path):
     assert hist.sum() > 0
     assert share >= 0.01
     assert hist[20:].any()
+    counters, launch_rays, iterations = g["counters"].astype(np.int64), g["launch_rays"].astype(np.int64), int(g["iterations"])
+    print(f"counters {counters.tolist()}, rays of {iterations} launches {int(launch_rays.sum())}")
+    assert 0 < iterations < ptamd.TRACE_STAT_LAUNCHES and launch_rays.shape == (iterations,)
+    assert (counters > 0).all()
+    assert int(counters[5]) == int(launch_rays.sum())
+    assert int(counters[1]) <= 64 * int(counters[0]) and int(counters[3]) <= 64 * int(counters[2])
+    assert int(counters[1]) <= int(hist.sum())
+    assert int(g["step_hist"].sum()) == int(counters[7])
     _assert_same(g["img"], frame(), "counting build of wf_trace")
 
 

@@ -433,15 +433,15 @@ PT_API int  pt_render_views_host(PtScene* s, const PtCamera* h_cams, int32_t n_v
  * pt_scene_update_spheres: a HOST array of the scene's sphere count; centre and radius may change, the material bytes must be
  *   those uploaded, or those of the last pt_scene_update_sphere_materials (else PT_ERR_INVALID).  A stream-ordered copy on the NULL stream.
  * pt_scene_tree_inflation: *ratio = sum of the surface areas (float32 each, summed in float64 in a fixed order) of all boxes of
- *   the binary traversal tree now / the same sum at upload: the caller's signal that refits have degraded the tree and a new
- *   pt_scene_create is due.  Exactly 1.0 for a scene never updated.  Otherwise waits for the whole device (hipDeviceSynchronize: the
+ *   the binary traversal tree now / the same sum at upload or at the last pt_scene_rebuild_tree: the caller's signal that refits
+ *   have degraded the tree (what to do about it: "Tree rebuild" below).  Exactly 1.0 for a scene never updated.  Otherwise waits for the whole device (hipDeviceSynchronize: the
  *   stream of the last update need not exist any more) and reduces on the NULL stream.
  * pt_dbg_scene_array (parity hook, tests only): copies one device array of the scene to the host after a device synchronisation;
  *   which = 0 nodes, 1 quad, 2 tri, 3 tripair, 4 leafbox, 5 surf, 6 lights, 7 spheres, 8 core (0 bytes if none; layouts:
  *   csrc/pt_device.h).  Returns the array's size in bytes and writes at most cap_bytes (h_out may be NULL when cap_bytes is 0).
  * NULL scene, NULL d_pos / h_pos / h_spheres / ratio, n_spheres different from the scene's and an unknown `which` return
  * PT_ERR_INVALID before any HIP call.
- * Out of scope: a change of the triangle count; a rebuild on the GPU or an automatic one; a tile-split update (every rank updates
+ * Out of scope: a change of the triangle count; an automatic rebuild; a tile-split update (every rank updates
  * its own scene).  The materials and the set of emissive triangles change through the calls of the next section.
  * -------------------------------------------------------------------------------- */
 PT_API int  pt_scene_update_vertices(PtScene* s, const float* d_pos, const float* d_frames, void* hip_stream);
@@ -492,6 +492,67 @@ PT_API int  pt_scene_update_materials(PtScene* s, const float* d_mat12, void* hi
 PT_API int  pt_scene_update_materials_host(PtScene* s, const float* h_mat12);
 PT_API int  pt_scene_update_sphere_materials(PtScene* s, const PtSphere* h_spheres, int32_t n_spheres);
 PT_API int32_t pt_scene_nee_prune(const PtScene* s);
+
+/* ----------------------------------------------------------------------------------
+ * Tree rebuild (new: the reference builds its tree once, on the host).  Opt-in: every call above is as it was.
+ * pt_scene_update_vertices keeps the topology of both traversal trees, so they degrade as the mesh deforms
+ * (pt_scene_tree_inflation).  pt_scene_rebuild_tree builds both trees anew on the GPU from the scene's CURRENT positions — as
+ * uploaded, or as the last pt_scene_update_vertices left them — on `hip_stream`, on the scene's device, without
+ * pt_bvh_build_sah + pt_scene_create and without losing what the scene has accumulated (materials, the light set, the position
+ * mirror).  The tree is a linear BVH over 30-bit Morton codes of the triangle centroids (csrc/pt_rebuild.hip, DESIGN.md
+ * section 23).
+ *
+ * Results: a render is defined by the triangles and the reference leaf boxes alone, so after the call the scene is, for every
+ *   entry point (pt_render*, pt_render_aov, pt_render_views, pt_render_rays, pt_render_tile_list, pt_render_adaptive,
+ *   pt_trace_rays closest hit with surface records, pt_dbg_raycast, pt_dbg_nee, both render modes, wf_drain on either tree), bit
+ *   for bit the scene it was before the call.  PT_QUERY_ANY keeps its own contract: the same hit / no-hit verdict; which hit is
+ *   returned may change.
+ * Arrays: leafbox, surf, lights, spheres, core, the light set and the pruning flag are not touched.  nodes, quad, tri and tripair
+ *   are replaced and the record counts of nodes and quad may change; tri is a permutation of its records.
+ * Function of the geometry alone: the four rebuilt arrays depend only on the current positions and the triangle -> reference
+ *   leaf assignment.  A scene moved to positions P and rebuilt has byte for byte the nodes, quad, tri and tripair of a scene
+ *   created at P and rebuilt; two rebuilds in a row change nothing.  No atomic operation decides an index or an order.
+ * Later updates: pt_scene_update_vertices, pt_scene_update_materials and pt_scene_update_spheres work on the new trees exactly
+ *   as specified above.  pt_scene_tree_inflation returns exactly 1.0 right after a rebuild: its denominator becomes the new
+ *   tree's area sum, from the same reduction in the same fixed order.
+ * Limits: those pt_scene_create enforces — binary depth <= 32, and 3 * (4-wide depth) + 2 <= the traversal kernel's stack
+ *   capacity.  A rebuilt topology that breaks one returns PT_ERR_UNSUPPORTED WITH THE SCENE EXACTLY AS IT WAS: the topology is
+ *   built and checked in buffers of its own before the first write to an array a render reads.  "As it was" is what a render,
+ *   a query or an update sees: the refused call has still run and waited for the whole build (every retry does), and what the
+ *   first rebuild allocated stays allocated (Memory).  After PT_ERR_DEVICE the trees are unspecified: rebuild again or destroy
+ *   the scene.
+ * Waiting: the call waits for `hip_stream` TWICE: once for the level offsets, the record counts and the two depths (they are
+ *   checked, steer the per-height launches and become kernel arguments of every later render), once for the area sums.  The
+ *   first rebuild of a scene waits a third time, before it frees the smaller blocks it replaces.  A render enqueued on the same
+ *   stream afterwards sees the new trees.  One update, query, render or rebuild at a time per scene.
+ * Memory: the first rebuild allocates for the worst case (2 n - 1 nodes of the binary tree, n - 1 `nodes` records, n - 1 `quad`
+ *   records, the sort's temporary storage) and moves nodes, quad and the maps of the build into blocks of that size; a failed
+ *   allocation leaves the scene as it was.  Later rebuilds allocate nothing.  pt_scene_device_bytes reports what is held: it
+ *   grows with the first rebuild, whether that rebuild is accepted or refused (the 278,268-triangle scene: 126 MB at upload,
+ *   259 MB from the first rebuild on), and does not shrink again.
+ * When to call it (measured on the MI355X): on the scenes measured, NOT YET instead of the refit tree.  The
+ *   call itself is cheap (0.5 ms for 69,576 triangles, 0.8 ms for 278,268; the host rebuild takes 114 ms and 506 ms), but a
+ *   Morton-order tree is weaker than the upload's size-aware SAH tree where big triangles sit among small ones: after turns of
+ *   10, 25 and 90 degrees of the stand-in mesh (inflation 1.06 - 1.12) the rebuilt tree rendered 13 - 18 % SLOWER than the refit
+ *   tree and 19 - 20 % slower than a fresh host upload, with 35 - 40 % more node records fetched.  At no inflation reached there
+ *   does a GPU rebuild pay; it can only win where refits have cost more than that, so time a render before and after.  Its 4-wide
+ *   tree has no depth cap either (14 - 15 levels against 11 - 12): pt_trace_rays and the render's drain walk the 4-wide tree
+ *   only up to level 12 and the binary tree beyond, with the same results but not the same speed (a closest-hit query ran
+ *   4 x slower).  And the tree can be too deep altogether: the 278,268-triangle scene turned by 25 degrees reaches binary depth
+ *   33 and is refused.  The remedies (a depth budget, a SAH top level over Morton clusters) are the section's next leads.
+ * pt_scene_tree_info (host only, no HIP call): the current counts of `nodes` and `quad` records, the depth of the binary and of
+ *   the 4-wide tree, from upload or from the last rebuild, and the number of rebuilds so far.
+ * pt_dbg_tree_limits (parity hook, host only): the limit check as pt_scene_create and pt_scene_rebuild_tree apply it to a pair
+ *   of depths — PT_OK or PT_ERR_UNSUPPORTED — and, through the non-NULL pointers, the largest depths it accepts.
+ * A NULL scene (pt_scene_tree_info: or a NULL out) returns PT_ERR_INVALID before any HIP call.
+ * Out of scope: a change of the triangle count; an automatic rebuild (the caller decides from pt_scene_tree_inflation); a SAH or
+ * PLOC quality pass on the GPU; a rebuild of the reference leaf assignment (it defines the result); a tile-split rebuild (every
+ * rank rebuilds its own scene and, the tree being a function of the positions alone, gets the same one); a ptrender option.
+ * -------------------------------------------------------------------------------- */
+typedef struct PtTreeInfo { int32_t n_wide, n_quad, depth, quad_depth, rebuilds; } PtTreeInfo;
+PT_API int  pt_scene_rebuild_tree(PtScene* s, void* hip_stream);
+PT_API int  pt_scene_tree_info(const PtScene* s, PtTreeInfo* out);   /* host only, no HIP call */
+PT_API int  pt_dbg_tree_limits(int32_t depth, int32_t quad_depth, int32_t* max_depth, int32_t* max_quad_depth);
 
 /* ----------------------------------------------------------------------------------
  * Ray queries (new: the reference casts rays only from inside its integrator).  Opt-in: every call above is as it was.

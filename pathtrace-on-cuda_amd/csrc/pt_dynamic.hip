@@ -290,14 +290,17 @@ inline unsigned blocks_of(int n, int per) { return (unsigned)((n + per - 1) / pe
 static_assert(ptd::kCoreBlocks == 256, "dyn_core_final reads one partial per thread of a 256-thread block");
 static_assert(kAreaBlock == 1024, "dyn_area folds 4 boxes per thread of a 256-thread block");
 
-// Enqueues the whole update on `stream`.  level_start: host array of n_levels + 1 offsets into `order` (height h = one launch).
-static hipError_t launch_update(const DynScene& s, const float* d_pos, const float* d_frames, float* d_keep, const int32_t* level_start, int n_levels, hipStream_t stream)
+// Enqueues the whole update on `stream` (pt_scene.h).  level_start: host array of n_levels + 1 offsets into `order` (height h = one launch).
+hipError_t pt_dyn_launch_update(const DynScene& s, const float* d_pos, const float* d_frames, float* d_keep, const int32_t* level_start, int n_levels,
+                                bool trees_only, hipStream_t stream)
 {
     // records: the leaf boxes first, the pair records carry them inline
-    hipLaunchKernelGGL(dyn_leafbox, dim3(blocks_of(s.n_leaves, 256)), dim3(256), 0, stream, s, d_pos);
-    hipLaunchKernelGGL(dyn_surf, dim3(blocks_of(s.n_tris, 256)), dim3(256), 0, stream, s, d_pos, d_frames, d_keep);
+    if (!trees_only) {
+        hipLaunchKernelGGL(dyn_leafbox, dim3(blocks_of(s.n_leaves, 256)), dim3(256), 0, stream, s, d_pos);
+        hipLaunchKernelGGL(dyn_surf, dim3(blocks_of(s.n_tris, 256)), dim3(256), 0, stream, s, d_pos, d_frames, d_keep);
+    }
     hipLaunchKernelGGL(dyn_tri, dim3(blocks_of(s.n_tris, 256)), dim3(256), 0, stream, s, d_pos);
-    if (s.n_lights > 0) hipLaunchKernelGGL(dyn_lights, dim3(blocks_of(s.n_lights, 64)), dim3(64), 0, stream, s, d_pos);
+    if (!trees_only && s.n_lights > 0) hipLaunchKernelGGL(dyn_lights, dim3(blocks_of(s.n_lights, 64)), dim3(64), 0, stream, s, d_pos);
     // binary tree, bottom up
     for (int h = 0; h < n_levels; h++) {
         const int first = level_start[h], count = level_start[h + 1] - first;
@@ -305,10 +308,16 @@ static hipError_t launch_update(const DynScene& s, const float* d_pos, const flo
     }
     hipLaunchKernelGGL(dyn_nodes, dim3(blocks_of(s.n_wide, 256)), dim3(256), 0, stream, s);
     hipLaunchKernelGGL(dyn_quad, dim3(blocks_of(s.n_quad, 256)), dim3(256), 0, stream, s);
-    if (s.core && s.small) {
+    if (!trees_only && s.core && s.small) {
         hipLaunchKernelGGL(dyn_core_partial, dim3(ptd::kCoreBlocks), dim3(256), 0, stream, s, d_pos);
         hipLaunchKernelGGL(dyn_core_final, dim3(1), dim3(256), 0, stream, s);
     }
+    return hipGetLastError();
+}
+
+hipError_t pt_dyn_launch_area(const DynScene& s, hipStream_t stream)
+{
+    hipLaunchKernelGGL(dyn_area, dim3(blocks_of(s.n_bn, kAreaBlock)), dim3(256), 0, stream, s);
     return hipGetLastError();
 }
 
@@ -363,7 +372,8 @@ int pt_scene_update_vertices(PtScene* s, const float* d_pos, const float* d_fram
     int rc;
     if ((rc = pt_dyn_prepare(s)) != PT_OK) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(launch_update(s->dyn, d_pos, d_frames, s->dyn_buf[kDynPos].as<float>(), s->dyn_host.level_start.data(), (int)s->dyn_host.level_start.size() - 1, st));
+    HIPCHK(pt_dyn_launch_update(s->dyn, d_pos, d_frames, s->dyn_buf[kDynPos].as<float>(), s->dyn_host.level_start.data(), (int)s->dyn_host.level_start.size() - 1,
+                                /*trees_only=*/false, st));
     s->updated = true;
     return PT_OK;
 }
@@ -410,8 +420,7 @@ int pt_scene_tree_inflation(PtScene* s, double* ratio)
     if (!s->updated) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipDeviceSynchronize());      // the stream of the last update may be gone by now: wait for the device, reduce on the NULL stream
-    hipLaunchKernelGGL(dyn_area, dim3(blocks_of(s->dyn.n_bn, kAreaBlock)), dim3(256), 0, nullptr, s->dyn);
-    HIPCHK(hipGetLastError());
+    HIPCHK(pt_dyn_launch_area(s->dyn, nullptr));
     HIPCHK(hipMemcpy(s->h_area.data(), s->dyn.area_partial, s->h_area.size() * 8, hipMemcpyDeviceToHost));
     double sum = 0.0;
     for (double v : s->h_area) sum += v;      // block sums in index order (host/accel_build.cpp: pt_accel_area_sum)

@@ -15,10 +15,17 @@ constexpr int kMatBlock = 256;      // triangles per block of the material updat
 enum DynAlloc { kDynBn, kDynOrder, kDynWideBn, kDynQuadBn, kDynLeafRange, kDynTmap, kDynLightPrim, kDynSmall, kDynPos,
                 kDynBbox, kDynMaxabs, kDynCorePartial, kDynAreaPartial, kDynMatPartial, kDynAllocs };
 
+// The allocations of the first tree rebuild (pt_rebuild.hip: rb_prepare), in the order of its plan: what the build works in, the
+// rocPRIM temporary storage, then the staged maps and refs.
+enum RbAlloc { kRbPrimLeaf, kRbBoxPartial, kRbCbox, kRbKeys, kRbSorted, kRbChild, kRbRange, kRbParent, kRbDepth, kRbHeight, kRbLive, kRbNewId, kRbWFlag, kRbWidx,
+               kRbKeyIn, kRbKeyOut, kRbIota, kRbQSorted, kRbQidx, kRbLevels, kRbTemp,
+               kRbBn, kRbOrder, kRbWideBn, kRbQuadBn, kRbTmap, kRbNodeRef, kRbQuadRef, kRbAllocs };
+
 struct PtScene {
     int device = 0;
     ptd::DevScene dev{};
-    DevBuf arr[kSceneArrays];            // as uploaded; an empty array holds 16 bytes, kArrCore is null when the scene has no core box
+    DevBuf arr[kSceneArrays];            // as uploaded; an empty array holds 16 bytes, kArrCore is null when the scene has no core box; nodes and quad have
+                                         // room for n_tris - 1 records once a tree rebuild has run (dev.n_nodes / dev.n_quad are the counts)
     DevBuf uv;                           // u0 v0 u1 v1 u2 v2 per triangle (reference order): HitResult::u / v of the HIT record (parity hook, surface pass of the queries)
     DevBuf unit_counter;
     DevBuf counters;
@@ -27,7 +34,7 @@ struct PtScene {
     std::vector<char> h_views;           // host image of `views` (the source of its stream-ordered copy)
     int64_t bytes = 0;
     int n_lights = 0;
-    int max_depth = 0;
+    int max_depth = 0;       // deepest node of the binary traversal tree, from upload or from the last rebuild
     int num_cus = 256;
     bool count_next = false;
     int mode = 1;            // 1 = wavefront pipeline (default), 0 = one-kernel state machine
@@ -59,6 +66,11 @@ struct PtScene {
     bool dyn_ready = false;
     bool updated = false;
     std::vector<double> h_area;          // host image of dyn.area_partial
+    // ---- tree rebuild (pt_scene_rebuild_tree, csrc/pt_rebuild.hip) ----
+    DevBuf rb_buf[kRbAllocs];            // allocated by the first rebuild, worst case: later rebuilds allocate nothing
+    size_t rb_temp_bytes = 0;            // size of kRbTemp, the rocPRIM temporary storage (queried once)
+    bool rb_ready = false;
+    int rebuilds = 0;
     // ---- materials and lights (pt_scene_update_materials, csrc/pt_material.hip) ----
     bool tri_emit_ok = true;             // emittance_ok's test over the triangles alone, from pt_scene_create or the last material update (the spheres' part: h_spheres)
     int32_t* h_mat = nullptr;            // pinned, 2 words: the light count and the flag a material update reads back (pt_dyn_prepare)
@@ -78,3 +90,12 @@ struct PtScene {
 inline bool pt_prune_allowed() { const char* m = getenv("PTAMD_PRUNE"); return !(m && atoi(m) == 0); }
 // pt_dynamic.hip: the first update of either kind brings the maps and the position mirror to the device (no-op afterwards)
 int pt_dyn_prepare(PtScene* s);
+// pt_dynamic.hip: enqueues a vertex update on `stream`.  level_start: host array of n_levels + 1 offsets into `order`.  trees_only: the
+// records and boxes of the two traversal trees alone (tri, tripair, nodes, quad) — leafbox, surf, lights, the core box and the
+// position mirror d_keep are not touched (a tree rebuild: the positions are the scene's own)
+hipError_t pt_dyn_launch_update(const ptd::DynScene& s, const float* d_pos, const float* d_frames, float* d_keep, const int32_t* level_start, int n_levels,
+                                bool trees_only, hipStream_t stream);
+// pt_dynamic.hip: enqueues dyn_area, the block sums of the box areas of all n_bn builder nodes into s.area_partial
+hipError_t pt_dyn_launch_area(const ptd::DynScene& s, hipStream_t stream);
+// pt_rebuild.hip: the stack limits of the traversal kernels (host only): PT_OK, or PT_ERR_UNSUPPORTED with the error text set
+int pt_tree_limits(const char* who, int depth, int quad_depth);

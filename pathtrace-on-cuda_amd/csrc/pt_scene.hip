@@ -204,15 +204,7 @@ int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* t
     // ---- traversal tree over the triangles (host/accel_build.cpp) ----
     PtAccel accel;
     pt_build_accel(nodes, n_nodes, tris, n_tris, accel);
-    if (accel.depth > ptd::kStackDepth) {
-        pt_set_error("pt_scene_create: traversal tree depth %d exceeds the traversal stack (%d)", accel.depth, ptd::kStackDepth);
-        return PT_ERR_UNSUPPORTED;
-    }
-    if (3 * accel.quad_depth + 2 > ptk_wf_stack_capacity()) {
-        pt_set_error("pt_scene_create: 4-wide traversal tree depth %d needs more than the %d stack entries of the traversal kernel",
-                     accel.quad_depth, ptk_wf_stack_capacity());
-        return PT_ERR_UNSUPPORTED;
-    }
+    if ((rc = pt_tree_limits("pt_scene_create", accel.depth, accel.quad_depth)) != PT_OK) return rc;
     std::vector<float> surf, lights, core;
     std::vector<int32_t> light_prim;
     std::vector<uint8_t> small;
@@ -275,8 +267,10 @@ int64_t pt_dbg_scene_array(PtScene* s, int32_t which, void* h_out, int64_t cap_b
         pt_set_error("pt_dbg_scene_array: %s", !s ? "NULL scene" : (which < 0 || which > 8) ? "which must be 0..8" : "bad output buffer");
         return PT_ERR_INVALID;
     }
-    // `lights` keeps its largest size through the material updates: what a render reads is the current n_lights records
-    const int64_t size = which == kArrLights ? (int64_t)s->n_lights * 64 : (int64_t)s->arr[which].bytes();
+    // `lights` keeps its largest size through the material updates, `nodes` and `quad` have worst-case room once a tree rebuild has
+    // run: what a render reads is the current number of records
+    const int64_t size = which == kArrLights ? (int64_t)s->n_lights * 64 : which == kArrNodes ? (int64_t)s->dev.n_nodes * 64 :
+                         which == kArrQuad ? (int64_t)s->dev.n_quad * 64 : (int64_t)s->arr[which].bytes();
     const int64_t n = size < cap_bytes ? size : cap_bytes;
     if (n > 0) {
         HIPCHK(hipSetDevice(s->device));

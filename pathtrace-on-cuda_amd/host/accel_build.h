@@ -19,7 +19,10 @@ struct PtAccel {
     int n_quad = 0, quad_depth = 0;
     // ---- maps of the build, for a refit of the arrays above from new vertex positions (csrc/pt_dynamic.hip) ----
     // The five arrays above do not depend on them.  A "builder node" is a node of the binary traversal tree in the builder's
-    // depth-first numbering (0 = root, a child's index is above its parent's).
+    // depth-first numbering (0 = root, a child's index is above its parent's).  That order of the indices is used by host code only
+    // (accel_build.cpp: the height passes; tests/dynamic_ref.py: refit_nodes on the REFERENCE tree): no dyn_* kernel relies on it — they go
+    // through `order` / `level_start` (dyn_refit_level), or visit every node on its own (dyn_nodes, dyn_quad, dyn_area) — and the maps
+    // a GPU rebuild writes (csrc/pt_rebuild.hip) number a node by its rank in the radix tree, the root at 0, children in no such order.
     std::vector<int32_t> bn;             // n_bn x 4: l, r, first, count — count > 0: a leaf over tri[first .. first + count), else its two children
     std::vector<int32_t> order;          // n_bn builder nodes sorted by height (0 = leaf), ascending index within a height
     std::vector<int32_t> level_start;    // heights + 2 offsets into `order`: height h is order[level_start[h] .. level_start[h + 1])

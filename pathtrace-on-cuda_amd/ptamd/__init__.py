@@ -63,6 +63,10 @@ class PtAdaptiveReport(C.Structure):
 TILE_ERROR_DTYPE = np.dtype([("mean_rel_se", "<f8"), ("pixels", "<i4"), ("skipped", "<i4")])      # PtTileError as a numpy record
 
 
+class PtTreeInfo(C.Structure):
+    _fields_ = [("n_wide", C.c_int32), ("n_quad", C.c_int32), ("depth", C.c_int32), ("quad_depth", C.c_int32), ("rebuilds", C.c_int32)]
+
+
 class PtRayHit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_int32)]
 
@@ -167,6 +171,9 @@ API = [
     ("pt_scene_update_spheres", C.c_int, [_P, _P, C.c_int32]),
     ("pt_scene_tree_inflation", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("pt_dbg_scene_array", C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
+    ("pt_scene_rebuild_tree", C.c_int, [_P, _P]),
+    ("pt_scene_tree_info", C.c_int, [_P, C.POINTER(PtTreeInfo)]),
+    ("pt_dbg_tree_limits", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("pt_scene_update_materials", C.c_int, [_P, _P, _P]),
     ("pt_scene_update_materials_host", C.c_int, [_P, _P]),
     ("pt_scene_update_sphere_materials", C.c_int, [_P, _P, C.c_int32]),
@@ -620,6 +627,18 @@ class Scene:
         r = C.c_double(0.0)
         _check(lib().pt_scene_tree_inflation(self._h, C.byref(r)), "pt_scene_tree_inflation")
         return r.value
+
+    def rebuild_tree(self, stream_ptr=0):
+        """Build both traversal trees anew on the GPU from the scene's current positions (include/pt_api.h: pt_scene_rebuild_tree),
+        enqueued on stream_ptr; the call waits for that stream.  Every result stays bit for bit what it was."""
+        _check(lib().pt_scene_rebuild_tree(self._h, C.c_void_p(stream_ptr)), "pt_scene_rebuild_tree")
+
+    def tree_info(self):
+        """The traversal trees as they are now, from upload or from the last rebuild_tree: a dict with n_wide, n_quad, depth,
+        quad_depth and the number of rebuilds so far.  No device call."""
+        info = PtTreeInfo()
+        _check(lib().pt_scene_tree_info(self._h, C.byref(info)), "pt_scene_tree_info")
+        return {name: int(getattr(info, name)) for name, _ in PtTreeInfo._fields_}
 
     def trace_rays(self, rays, any_hit=False, surface=False, stream_ptr=0):
         """Cast the caller's rays (include/pt_api.h: pt_trace_rays).  rays: (n, 8) float32 RAY8 records, org.xyz dir.xyz 0 tmax.

@@ -530,16 +530,20 @@ PT_API int32_t pt_scene_nee_prune(const PtScene* s);
  *   allocation leaves the scene as it was.  Later rebuilds allocate nothing.  pt_scene_device_bytes reports what is held: it
  *   grows with the first rebuild, whether that rebuild is accepted or refused (the 278,268-triangle scene: 126 MB at upload,
  *   259 MB from the first rebuild on), and does not shrink again.
- * When to call it (measured on the MI355X): on the scenes measured, NOT YET instead of the refit tree.  The
- *   call itself is cheap (0.5 ms for 69,576 triangles, 0.8 ms for 278,268; the host rebuild takes 114 ms and 506 ms), but a
- *   Morton-order tree is weaker than the upload's size-aware SAH tree where big triangles sit among small ones: after turns of
- *   10, 25 and 90 degrees of the stand-in mesh (inflation 1.06 - 1.12) the rebuilt tree rendered 13 - 18 % SLOWER than the refit
- *   tree and 19 - 20 % slower than a fresh host upload, with 35 - 40 % more node records fetched.  At no inflation reached there
- *   does a GPU rebuild pay; it can only win where refits have cost more than that, so time a render before and after.  Its 4-wide
- *   tree has no depth cap either (14 - 15 levels against 11 - 12): pt_trace_rays and the render's drain walk the 4-wide tree
- *   only up to level 12 and the binary tree beyond, with the same results but not the same speed (a closest-hit query ran
- *   4 x slower).  And the tree can be too deep altogether: the 278,268-triangle scene turned by 25 degrees reaches binary depth
- *   33 and is refused.  The remedies (a depth budget, a SAH top level over Morton clusters) are the section's next leads.
+ * When to call it (measured on the MI355X, DESIGN.md sections 23 and 24): prefer pt_scene_rebuild_tree_ex with its defaults
+ *   (below) to this call, and neither to the refit tree while pt_scene_tree_inflation is small.  Both calls are cheap (this one
+ *   0.5 ms for 69,576 triangles and 0.8 ms for 278,268, the extended one 12 - 18 % more; the host rebuild takes 114 ms and
+ *   506 ms).  After turns of 10, 25 and 90 degrees of the stand-in mesh (inflation 1.06 - 1.12) the tree of THIS call rendered
+ *   12 - 18 % slower than the refit tree and 19 - 20 % slower than a fresh host upload, with 35 - 40 % more node records fetched:
+ *   a Morton-order tree files the room's big triangles among the mesh's small ones.  Its 4-wide tree has no depth cap (14 - 15
+ *   levels against 11 - 12): pt_trace_rays and the render's drain walk the 4-wide tree only up to level 12 and the binary tree
+ *   beyond, with the same results but not the same speed (a closest-hit query of 2.07 M rays: 0.63 - 0.73 ms against 0.20 -
+ *   0.22 ms).  And the tree can be too deep altogether: the 278,268-triangle scene turned by 25 degrees reaches binary depth 33
+ *   and is refused.  The tree of pt_scene_rebuild_tree_ex with {26, 1/16} has none of the last two problems - depth 25 / 12 on
+ *   every scene measured, the 25 degree pose accepted, the query at 0.19 - 0.24 ms - and a smaller first one: it rendered
+ *   2.7 - 7.4 % slower than the refit tree and 7.0 - 9.6 % slower than a fresh host upload (the refit tree: 1 - 6 % slower than
+ *   the fresh one).  So the new tree does NOT beat the refit tree at any inflation reached there; a GPU rebuild pays where refits
+ *   have cost more than about 8 - 10 % of render time against a fresh tree, so time a render before and after.
  * pt_scene_tree_info (host only, no HIP call): the current counts of `nodes` and `quad` records, the depth of the binary and of
  *   the 4-wide tree, from upload or from the last rebuild, and the number of rebuilds so far.
  * pt_dbg_tree_limits (parity hook, host only): the limit check as pt_scene_create and pt_scene_rebuild_tree apply it to a pair
@@ -553,6 +557,44 @@ typedef struct PtTreeInfo { int32_t n_wide, n_quad, depth, quad_depth, rebuilds;
 PT_API int  pt_scene_rebuild_tree(PtScene* s, void* hip_stream);
 PT_API int  pt_scene_tree_info(const PtScene* s, PtTreeInfo* out);   /* host only, no HIP call */
 PT_API int  pt_dbg_tree_limits(int32_t depth, int32_t quad_depth, int32_t* max_depth, int32_t* max_quad_depth);
+
+/* ----------------------------------------------------------------------------------
+ * Tree rebuild with a depth budget and two size classes (new).  Opt-in: pt_scene_rebuild_tree is exactly what it was.
+ * pt_scene_rebuild_tree_ex is pt_scene_rebuild_tree with two parameters that answer its three weaknesses (csrc/pt_rebuild.hip,
+ * DESIGN.md section 24).  Everything "Tree rebuild" above promises holds for it unchanged: bit-for-bit results of every entry
+ * point (PT_QUERY_ANY: the same verdict), the untouched arrays, staging before commit with the limit check before the first
+ * write to anything a render reads, the two waits (three for a scene's first rebuild), `rebuilds`, inflation of exactly 1.0
+ * afterwards.  The four rebuilt arrays are a function of the current positions, the reference leaf assignment and the two
+ * parameters alone.  With {0, 0} the call produces byte for byte what pt_scene_rebuild_tree produces.
+ *
+ * depth_budget D (0 = none): the binary tree is at most D deep, a leaf counting as a node — PtTreeInfo::depth <= D - 1 — and the
+ *   4-wide tree at most (D - 1) / 2.  The radix tree is built as before; then every subtree v over more than two triangles with
+ *   depth(v) + clog2(size(v)) >= D nearest the root is replaced by the balanced tree over the ranks of its triangles in Morton
+ *   order (each triangle walks its parent links, rewrites its key below the bits v's keys share, and the radix tree is built a
+ *   second time over the new keys; clog2(m) = the bit length of m - 1).  The tree above such a v is unchanged.  With D > 0 the
+ *   call never returns PT_ERR_UNSUPPORTED (D <= 32 gives a 4-wide depth <= 15, the limit is 20), and with D <= 26 the 4-wide
+ *   tree has at most 12 levels, which pt_trace_rays and the render's drain walk 4-wide throughout.  The budget adds no wait.
+ * large_fraction f (0 = one class): a triangle whose own box is longer, on its longest axis, than f times the longest side of
+ *   the box of all centroids is "large".  Each class quantises its centroids in a centroid box of its own (the same two-stage
+ *   reduction, no float atomics) and the class is bit 62 of the sort key, so the root of the tree joins the tree of the small
+ *   triangles and the tree of the large ones and the room's walls no longer sit among the mesh's triangles.  An empty class
+ *   changes nothing.  All in float32, every operation rounded once.
+ * report (may be NULL): n_large, the number of large triangles (0 when f = 0), and n_flattened_tris, the number of triangles
+ *   whose key the budget changed.  Both are read back with the words the first wait already reads, and are valid for a refused
+ *   call too.
+ * Errors, before any HIP call: PT_ERR_INVALID for a NULL scene or params, D < 0 or D > 32, f negative, NaN or infinite, and
+ *   D > 0 with D < clog2(n) for a scene of n >= 3 triangles (no tree over n triangles is that shallow).
+ * Memory: the first call of a scene allocates 18 KB more than pt_scene_rebuild_tree does, once.
+ * When to call it: "When to call it" above; the call costs 0.53 ms for 69,576 triangles and 0.95 ms for 278,268.
+ * Out of scope: more than two classes; an automatic choice of the parameters; a SAH or PLOC pass; a ptrender option.
+ * -------------------------------------------------------------------------------- */
+typedef struct PtRebuildParams {
+    int32_t depth_budget;    /* 0: none (today's tree).  Else the binary tree is at most this deep (a leaf counts as a node), <= 32 */
+    float   large_fraction;  /* 0: one class.  Else a triangle whose box is longer than this fraction of the centroid box is "large" */
+} PtRebuildParams;
+typedef struct PtRebuildReport { int32_t n_large, n_flattened_tris; } PtRebuildReport;
+PT_API void pt_rebuild_params_default(PtRebuildParams* p);          /* 26, 0.0625f */
+PT_API int  pt_scene_rebuild_tree_ex(PtScene* s, const PtRebuildParams* p, PtRebuildReport* report /* may be NULL */, void* hip_stream);
 
 /* ----------------------------------------------------------------------------------
  * Ray queries (new: the reference casts rays only from inside its integrator).  Opt-in: every call above is as it was.

@@ -19,8 +19,13 @@
 //
 // Everything is built in buffers of its own and checked against the kernels' stack limits on the host BEFORE the first write to an
 // array a render reads: a topology that is too deep leaves the scene exactly as it was.
+//
+// pt_scene_rebuild_tree_ex is the same build with two opt-in steps: the triangles' size class as bit 62 of
+// the key, each class quantised in a centroid box of its own, and a depth budget — every triangle rewrites its key below the
+// topmost ancestor that would reach below the budget, and the radix tree is built a second time over the new keys.
 #include <hip/hip_runtime.h>
 #include <cfloat>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <utility>
@@ -341,6 +346,128 @@ __global__ __launch_bounds__(256) void rb_refs(DynScene s, RbDev r)
     }
 }
 
+// ---- pt_scene_rebuild_tree_ex: two size classes and a depth budget (include/pt_api.h: "Tree rebuild with a depth budget")
+// What only the extended call works in (PtScene::rbx_buf, one block): the partial and the final centroid boxes of the two classes, and
+// its own copy of the read-back words with the report's two counts behind them (they travel with wait 1).
+constexpr int kRxClassPartial = 0, kRxClassBox = ptd::kCoreBlocks * 16 * 4, kRxLevels = kRxClassBox + 16 * 4;
+constexpr int kLvLarge = kLvWords, kLvFlattened = kLvWords + 1, kLvWordsEx = kLvWords + 2;
+constexpr int kRxBytes = kRxLevels + kLvWordsEx * 4;
+
+struct RbEx {
+    float* class_partial;      // kCoreBlocks x 16: small lo.xyz hi.xyz, pad, large lo.xyz hi.xyz, pad
+    float* class_box;          // 16, the same layout
+    float large_fraction;
+};
+
+// the triangle's centroid and the longest side of its own box
+__device__ __forceinline__ float centroid_extent(const float* __restrict__ pos, int prim, float* c)
+{
+    const Tri9 t = load_tri(pos, prim);
+    float ext = 0.f;
+    for (int a = 0; a < 3; a++) {
+        const float mn = min2(t.v0[a], min2(t.v1[a], t.v2[a]));
+        const float mx = max2(t.v0[a], max2(t.v1[a], t.v2[a]));
+        c[a] = 0.5f * (mn + mx);
+        ext = max2(ext, mx - mn);
+    }
+    return ext;
+}
+
+// f * E, E the longest side of the box of all centroids (rb_box_final has written it)
+__device__ __forceinline__ float large_bound(const RbDev& r, float f)
+{
+    const float E = max2(r.cbox[3] - r.cbox[0], max2(r.cbox[4] - r.cbox[1], r.cbox[5] - r.cbox[2]));
+    return f * E;
+}
+
+__global__ __launch_bounds__(256) void rb_class_partial(RbDev r, RbEx x, const float* __restrict__ pos)
+{
+    __shared__ float lds[256][6];
+    __shared__ int n_large;
+    float v[12] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
+    if (threadIdx.x == 0) n_large = 0;
+    const float bound = large_bound(r, x.large_fraction);
+    int mine = 0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < r.n; i += ptd::kCoreBlocks * 256) {
+        float c[3];
+        const bool large = centroid_extent(pos, i, c) > bound;
+        mine += large ? 1 : 0;
+        for (int a = 0; a < 3; a++) {
+            const float lo_s = large ? v[a] : min2(v[a], c[a]), hi_s = large ? v[3 + a] : max2(v[3 + a], c[a]);
+            const float lo_l = large ? min2(v[6 + a], c[a]) : v[6 + a], hi_l = large ? max2(v[9 + a], c[a]) : v[9 + a];
+            v[a] = lo_s; v[3 + a] = hi_s; v[6 + a] = lo_l; v[9 + a] = hi_l;
+        }
+    }
+    for (int cls = 0; cls < 2; cls++) {      // after block_box only thread 0 reads lds, and only the row it alone writes
+        block_box(v + 6 * cls, lds);
+        if (threadIdx.x == 0) for (int k = 0; k < 6; k++) x.class_partial[blockIdx.x * 16 + cls * 8 + k] = lds[0][k];
+    }
+    if (mine) atomicAdd(&n_large, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && n_large) atomicAdd(&r.levels[kLvLarge], n_large);      // a count: it decides no index
+}
+
+__global__ __launch_bounds__(256) void rb_class_final(RbEx x)
+{
+    __shared__ float lds[256][6];
+    for (int cls = 0; cls < 2; cls++) {
+        float v[6];
+        for (int k = 0; k < 6; k++) v[k] = x.class_partial[threadIdx.x * 16 + cls * 8 + k];      // kCoreBlocks == the block size
+        block_box(v, lds);
+        if (threadIdx.x == 0) for (int k = 0; k < 6; k++) x.class_box[cls * 8 + k] = lds[0][k];
+    }
+}
+
+// rb_keys with the cell taken in the box of the triangle's own class, and the class above the Morton code
+__global__ __launch_bounds__(256) void rb_keys_classes(RbDev r, RbEx x, const float* __restrict__ pos)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= r.n) return;
+    float c[3];
+    const bool large = centroid_extent(pos, i, c) > large_bound(r, x.large_fraction);
+    const float* __restrict__ box = x.class_box + (large ? 8 : 0);
+    uint32_t q[3];
+    for (int a = 0; a < 3; a++) {
+        const float lo = box[a], ext = box[3 + a] - lo;
+        int v = 0;
+        if (ext > 0.f) { v = (int)(((c[a] - lo) / ext) * 1024.0f); if (v > 1023) v = 1023; }
+        q[a] = (uint32_t)v;
+    }
+    const uint32_t morton = (spread3(q[0]) << 2) | (spread3(q[1]) << 1) | spread3(q[2]);
+    r.keys[i] = ((uint64_t)(large ? 1 : 0) << 62) | ((uint64_t)morton << 32) | (uint32_t)i;
+}
+
+__device__ __forceinline__ int clog2(int m) { return 32 - __clz(m - 1); }      // bit length of m - 1, m >= 1
+
+// The depth budget: every sorted triangle finds the topmost ancestor v over more than two triangles with depth(v) + clog2(size(v))
+// >= budget and, below the bits all of v's keys share, replaces its key by its rank in v.  Reads the first tree (child links are not
+// needed: parent, range, depth) and `sorted`; writes `keys`, which nothing reads after the sort.
+__global__ __launch_bounds__(256) void rb_rekey(RbDev r, int budget)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int n = r.n;
+    int changed = 0;
+    if (i < n) {
+        int top = -1;
+        for (int p = r.parent[(n - 1) + i]; p >= 0; p = r.parent[p]) {
+            const int2 rg = r.range[p];
+            const int size = rg.y - rg.x + 1;
+            if (size > 2 && r.depth[p] + clog2(size) >= budget) top = p;
+        }
+        const uint64_t key = r.sorted[i];
+        uint64_t out = key;
+        if (top >= 0) {
+            const int2 rg = r.range[top];
+            const int low = 64 - __clzll((long long)(r.sorted[rg.x] ^ r.sorted[rg.y]));      // 1 .. 63: the keys differ and bit 63 is clear
+            out = ((key >> low) << low) | (uint64_t)(i - rg.x);
+        }
+        r.keys[i] = out;
+        changed = out != key ? 1 : 0;
+    }
+    const int total = __syncthreads_count(changed);
+    if (threadIdx.x == 0 && total) atomicAdd(&r.levels[kLvFlattened], total);      // a count: it decides no index
+}
+
 inline unsigned blocks_of(int n) { return (unsigned)((n + 255) / 256); }
 
 // temporary storage of the largest of the rocPRIM calls below (sizes only: nothing is launched with a null storage pointer)
@@ -422,6 +549,22 @@ static int rb_prepare(PtScene* s, hipStream_t st)
     return PT_OK;
 }
 
+// First extended rebuild of a scene: the block only pt_scene_rebuild_tree_ex works in, and temporary storage of its own where the
+// sort over all 64 key bits asks for more than the build's has.  pt_scene_rebuild_tree never allocates either.
+static int rbx_prepare(PtScene* s)
+{
+    if (s->rbx_buf) return PT_OK;
+    size_t b64 = 0;
+    HIPCHK(rocprim::radix_sort_keys(nullptr, b64, (uint64_t*)nullptr, (uint64_t*)nullptr, s->dyn.n_tris, 0, 64));
+    DevBuf block, temp;
+    HIPCHK(block.alloc(kRxBytes));
+    if (b64 > s->rb_temp_bytes) HIPCHK(temp.alloc(b64));
+    s->bytes += (int64_t)block.held() + (int64_t)temp.held();
+    s->rbx_buf = std::move(block);
+    s->rbx_temp = std::move(temp);
+    return PT_OK;
+}
+
 static RbDev rb_args(PtScene* s)
 {
     DevBuf* b = s->rb_buf;
@@ -438,27 +581,48 @@ static RbDev rb_args(PtScene* s)
     return r;
 }
 
-// Enqueues the whole build of the topology into the staging buffers.  Nothing a render reads is written.
-static int rb_build(PtScene* s, const RbDev& r, hipStream_t st)
+// Enqueues the whole build of the topology into the staging buffers.  Nothing a render reads is written.  x: the extended call
+// (pt_scene_rebuild_tree_ex) with its depth budget, NULL for pt_scene_rebuild_tree.
+static int rb_build(PtScene* s, const RbDev& r, hipStream_t st, const RbEx* x = nullptr, int budget = 0)
 {
     const int n = r.n, N = 2 * n - 1;
     const float* pos = s->dyn_buf[kDynPos].as<const float>();
     void* temp = s->rb_buf[kRbTemp].as<>();
     size_t tb = s->rb_temp_bytes;
+    if (x) HIPCHK(hipMemsetAsync(r.levels, 0, (size_t)kLvWordsEx * 4, st));      // the report's counts are summed from here on
     hipLaunchKernelGGL(rb_box_partial, dim3(ptd::kCoreBlocks), dim3(256), 0, st, r, pos);
     hipLaunchKernelGGL(rb_box_final, dim3(1), dim3(256), 0, st, r);
-    hipLaunchKernelGGL(rb_keys, dim3(blocks_of(n)), dim3(256), 0, st, r, pos);
-    HIPCHK(hipGetLastError());
-    HIPCHK(rocprim::radix_sort_keys(temp, tb, r.keys, r.sorted, n, 0, 62, st));
+    if (x && x->large_fraction > 0.f) {      // a centroid box per size class; the class is bit 62 of the key
+        hipLaunchKernelGGL(rb_class_partial, dim3(ptd::kCoreBlocks), dim3(256), 0, st, r, *x, pos);
+        hipLaunchKernelGGL(rb_class_final, dim3(1), dim3(256), 0, st, *x);
+        hipLaunchKernelGGL(rb_keys_classes, dim3(blocks_of(n)), dim3(256), 0, st, r, *x, pos);
+        HIPCHK(hipGetLastError());
+        void* temp64 = s->rbx_temp ? s->rbx_temp.as<>() : temp;
+        tb = s->rbx_temp ? s->rbx_temp.bytes() : s->rb_temp_bytes;
+        HIPCHK(rocprim::radix_sort_keys(temp64, tb, r.keys, r.sorted, n, 0, 64, st));
+    } else {
+        hipLaunchKernelGGL(rb_keys, dim3(blocks_of(n)), dim3(256), 0, st, r, pos);
+        HIPCHK(hipGetLastError());
+        HIPCHK(rocprim::radix_sort_keys(temp, tb, r.keys, r.sorted, n, 0, 62, st));
+    }
     hipLaunchKernelGGL(rb_tmap, dim3(blocks_of(n)), dim3(256), 0, st, r);
     if (n <= 2) {
         hipLaunchKernelGGL(rb_single, dim3(1), dim3(64), 0, st, r);
         HIPCHK(hipGetLastError());
         return PT_OK;
     }
-    HIPCHK(hipMemsetAsync(r.levels, 0, (size_t)kLvWords * 4, st));
+    if (!x) HIPCHK(hipMemsetAsync(r.levels, 0, (size_t)kLvWords * 4, st));
     hipLaunchKernelGGL(rb_karras, dim3(blocks_of(n - 1)), dim3(256), 0, st, r);
     hipLaunchKernelGGL(rb_depth, dim3(blocks_of(N)), dim3(256), 0, st, r);
+    if (budget > 0) {      // flatten what would be deeper than the budget, then the tree over the new keys (they are in `keys`)
+        RbDev again = r;
+        again.sorted = r.keys;
+        hipLaunchKernelGGL(rb_rekey, dim3(blocks_of(n)), dim3(256), 0, st, r, budget);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(r.levels + kLvDepth, 0, 4, st));
+        hipLaunchKernelGGL(rb_karras, dim3(blocks_of(n - 1)), dim3(256), 0, st, again);
+        hipLaunchKernelGGL(rb_depth, dim3(blocks_of(N)), dim3(256), 0, st, again);
+    }
     hipLaunchKernelGGL(rb_height, dim3(blocks_of(N)), dim3(256), 0, st, r);
     HIPCHK(hipGetLastError());
     // numbering: builder nodes and `nodes` records by rank, `order` by height, `quad` records by level
@@ -480,28 +644,34 @@ static int rb_build(PtScene* s, const RbDev& r, hipStream_t st)
     return PT_OK;
 }
 
-extern "C" {
-
-int pt_scene_rebuild_tree(PtScene* s, void* hip_stream)
+// The rebuild behind both entry points.  p: the parameters of pt_scene_rebuild_tree_ex (checked by the caller), NULL for
+// pt_scene_rebuild_tree, whose launches, waits and allocations are exactly what they were before the extended call existed.
+static int rb_run(PtScene* s, const char* who, const PtRebuildParams* p, PtRebuildReport* report, hipStream_t st)
 {
-    if (!s) { pt_set_error("pt_scene_rebuild_tree: NULL scene"); return PT_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
-    hipStream_t st = (hipStream_t)hip_stream;
     int rc;
     if ((rc = pt_dyn_prepare(s)) != PT_OK) return rc;
     if ((rc = rb_prepare(s, st)) != PT_OK) return rc;
-    const RbDev r = rb_args(s);
-    if ((rc = rb_build(s, r, st)) != PT_OK) return rc;
-    // wait 1: the level offsets, the counts and the depths
-    int32_t lv[kLvWords];
-    HIPCHK(hipMemcpyAsync(lv, r.levels, sizeof(lv), hipMemcpyDeviceToHost, st));
+    if (p && (rc = rbx_prepare(s)) != PT_OK) return rc;
+    RbDev r = rb_args(s);
+    RbEx x{};
+    if (p) {
+        char* base = s->rbx_buf.as<char>();
+        x.class_partial = (float*)(base + kRxClassPartial); x.class_box = (float*)(base + kRxClassBox); x.large_fraction = p->large_fraction;
+        r.levels = (int32_t*)(base + kRxLevels);
+    }
+    if ((rc = rb_build(s, r, st, p ? &x : nullptr, p ? p->depth_budget : 0)) != PT_OK) return rc;
+    // wait 1: the level offsets, the counts and the depths (and, behind them, the two counts of the extended call's report)
+    int32_t lv[kLvWordsEx] = {};
+    HIPCHK(hipMemcpyAsync(lv, r.levels, (size_t)(p ? kLvWordsEx : kLvWords) * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    if (report) { report->n_large = lv[kLvLarge]; report->n_flattened_tris = lv[kLvFlattened]; }
     const int n_bn = lv[kLvOrder + kDead], n_quad = lv[kLvQuad + kDead], n_wide = n_bn > 1 ? (n_bn - 1) / 2 : 1;
     int top = 0, quad_depth = 0;
     while (lv[kLvOrder + top + 1] < n_bn) top++;                 // heights 0 .. top
     while (lv[kLvQuad + quad_depth + 1] < n_quad) quad_depth++;      // levels 0 .. quad_depth
     const int depth = lv[kLvDepth];
-    if ((rc = pt_tree_limits("pt_scene_rebuild_tree", depth, quad_depth)) != PT_OK) return rc;      // nothing a render, a query or an update reads has been written
+    if ((rc = pt_tree_limits(who, depth, quad_depth)) != PT_OK) return rc;      // nothing a render, a query or an update reads has been written
     // ---- commit ----
     ptd::DynScene& d = s->dyn;
     const struct { int dst, src; size_t bytes; } maps[] = {{kDynBn, kRbBn, (size_t)n_bn * 16}, {kDynOrder, kRbOrder, (size_t)n_bn * 4}, {kDynWideBn, kRbWideBn, (size_t)n_wide * 8},
@@ -525,6 +695,40 @@ int pt_scene_rebuild_tree(PtScene* s, void* hip_stream)
     s->dyn_host.area_sum = sum;
     s->rebuilds++;
     return PT_OK;
+}
+
+extern "C" {
+
+int pt_scene_rebuild_tree(PtScene* s, void* hip_stream)
+{
+    if (!s) { pt_set_error("pt_scene_rebuild_tree: NULL scene"); return PT_ERR_INVALID; }
+    return rb_run(s, "pt_scene_rebuild_tree", nullptr, nullptr, (hipStream_t)hip_stream);
+}
+
+void pt_rebuild_params_default(PtRebuildParams* p)
+{
+    if (p) { p->depth_budget = 26; p->large_fraction = 0.0625f; }
+}
+
+int pt_scene_rebuild_tree_ex(PtScene* s, const PtRebuildParams* p, PtRebuildReport* report, void* hip_stream)
+{
+    if (!s || !p) { pt_set_error("pt_scene_rebuild_tree_ex: NULL %s", !s ? "scene" : "params"); return PT_ERR_INVALID; }
+    if (p->depth_budget < 0 || p->depth_budget > ptd::kStackDepth) {
+        pt_set_error("pt_scene_rebuild_tree_ex: depth_budget %d is not in 0 .. %d", p->depth_budget, ptd::kStackDepth);
+        return PT_ERR_INVALID;
+    }
+    if (!(p->large_fraction >= 0.f) || std::isinf(p->large_fraction)) {
+        pt_set_error("pt_scene_rebuild_tree_ex: large_fraction %g is not a finite number >= 0", (double)p->large_fraction);
+        return PT_ERR_INVALID;
+    }
+    const int n = s->dyn.n_tris;
+    int need = 0;
+    while (n >= 3 && need < 32 && ((int64_t)1 << need) < n) need++;      // clog2(n): a tree over n triangles is at least that deep
+    if (p->depth_budget > 0 && p->depth_budget < need) {
+        pt_set_error("pt_scene_rebuild_tree_ex: depth_budget %d is below %d, the depth of a balanced tree over %d triangles", p->depth_budget, need, n);
+        return PT_ERR_INVALID;
+    }
+    return rb_run(s, "pt_scene_rebuild_tree_ex", p, report, (hipStream_t)hip_stream);
 }
 
 int pt_scene_tree_info(const PtScene* s, PtTreeInfo* out)

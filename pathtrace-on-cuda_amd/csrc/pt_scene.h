@@ -71,6 +71,7 @@ struct PtScene {
     size_t rb_temp_bytes = 0;            // size of kRbTemp, the rocPRIM temporary storage (queried once)
     bool rb_ready = false;
     int rebuilds = 0;
+    DevBuf rbx_buf, rbx_temp;            // pt_scene_rebuild_tree_ex alone: its class boxes and read-back words; its sort's storage where kRbTemp is too small
     // ---- materials and lights (pt_scene_update_materials, csrc/pt_material.hip) ----
     bool tri_emit_ok = true;             // emittance_ok's test over the triangles alone, from pt_scene_create or the last material update (the spheres' part: h_spheres)
     int32_t* h_mat = nullptr;            // pinned, 2 words: the light count and the flag a material update reads back (pt_dyn_prepare)

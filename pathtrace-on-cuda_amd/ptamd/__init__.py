@@ -67,6 +67,14 @@ class PtTreeInfo(C.Structure):
     _fields_ = [("n_wide", C.c_int32), ("n_quad", C.c_int32), ("depth", C.c_int32), ("quad_depth", C.c_int32), ("rebuilds", C.c_int32)]
 
 
+class PtRebuildParams(C.Structure):
+    _fields_ = [("depth_budget", C.c_int32), ("large_fraction", C.c_float)]
+
+
+class PtRebuildReport(C.Structure):
+    _fields_ = [("n_large", C.c_int32), ("n_flattened_tris", C.c_int32)]
+
+
 class PtRayHit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_int32)]
 
@@ -173,6 +181,8 @@ API = [
     ("pt_dbg_scene_array", C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
     ("pt_scene_rebuild_tree", C.c_int, [_P, _P]),
     ("pt_scene_tree_info", C.c_int, [_P, C.POINTER(PtTreeInfo)]),
+    ("pt_rebuild_params_default", None, [C.POINTER(PtRebuildParams)]),
+    ("pt_scene_rebuild_tree_ex", C.c_int, [_P, C.POINTER(PtRebuildParams), C.POINTER(PtRebuildReport), _P]),
     ("pt_dbg_tree_limits", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("pt_scene_update_materials", C.c_int, [_P, _P, _P]),
     ("pt_scene_update_materials_host", C.c_int, [_P, _P]),
@@ -628,10 +638,21 @@ class Scene:
         _check(lib().pt_scene_tree_inflation(self._h, C.byref(r)), "pt_scene_tree_inflation")
         return r.value
 
-    def rebuild_tree(self, stream_ptr=0):
+    def rebuild_tree(self, stream_ptr=0, depth_budget=None, large_fraction=None):
         """Build both traversal trees anew on the GPU from the scene's current positions (include/pt_api.h: pt_scene_rebuild_tree),
-        enqueued on stream_ptr; the call waits for that stream.  Every result stays bit for bit what it was."""
-        _check(lib().pt_scene_rebuild_tree(self._h, C.c_void_p(stream_ptr)), "pt_scene_rebuild_tree")
+        enqueued on stream_ptr; the call waits for that stream.  Every result stays bit for bit what it was.
+        With a depth_budget or a large_fraction the call is pt_scene_rebuild_tree_ex (a None among the two takes its default,
+        pt_rebuild_params_default) and returns its report as a dict: n_large, n_flattened_tris."""
+        if depth_budget is None and large_fraction is None:
+            return _check(lib().pt_scene_rebuild_tree(self._h, C.c_void_p(stream_ptr)), "pt_scene_rebuild_tree")
+        prm, report = PtRebuildParams(), PtRebuildReport()
+        lib().pt_rebuild_params_default(C.byref(prm))
+        if depth_budget is not None:
+            prm.depth_budget = depth_budget
+        if large_fraction is not None:
+            prm.large_fraction = large_fraction
+        _check(lib().pt_scene_rebuild_tree_ex(self._h, C.byref(prm), C.byref(report), C.c_void_p(stream_ptr)), "pt_scene_rebuild_tree_ex")
+        return {name: int(getattr(report, name)) for name, _ in PtRebuildReport._fields_}
 
     def tree_info(self):
         """The traversal trees as they are now, from upload or from the last rebuild_tree: a dict with n_wide, n_quad, depth,

@@ -542,16 +542,19 @@ PT_API int32_t pt_scene_nee_prune(const PtScene* s);
  *   and is refused.  The tree of pt_scene_rebuild_tree_ex with {26, 1/16} has none of the last two problems - depth 25 / 12 on
  *   every scene measured, the 25 degree pose accepted, the query at 0.19 - 0.24 ms - and a smaller first one: it rendered
  *   2.7 - 7.4 % slower than the refit tree and 7.0 - 9.6 % slower than a fresh host upload (the refit tree: 1 - 6 % slower than
- *   the fresh one).  So the new tree does NOT beat the refit tree at any inflation reached there; a GPU rebuild pays where refits
- *   have cost more than about 8 - 10 % of render time against a fresh tree, so time a render before and after.
+ *   the fresh one).  So that tree does NOT beat the refit tree at any inflation reached there.  pt_scene_rebuild_tree_opt
+ *   ("Tree rebuild with treelet restructuring" below) improves it by surface area: 2 - 4 % faster to render, ahead of the refit
+ *   tree at the 25 degree pose (inflation 1.12) and 2 - 5 % behind it at the other two.  A GPU rebuild pays where refits have cost
+ *   more than about 4 - 7 % of render time against a fresh tree, so time a render before and after.
  * pt_scene_tree_info (host only, no HIP call): the current counts of `nodes` and `quad` records, the depth of the binary and of
  *   the 4-wide tree, from upload or from the last rebuild, and the number of rebuilds so far.
  * pt_dbg_tree_limits (parity hook, host only): the limit check as pt_scene_create and pt_scene_rebuild_tree apply it to a pair
  *   of depths — PT_OK or PT_ERR_UNSUPPORTED — and, through the non-NULL pointers, the largest depths it accepts.
  * A NULL scene (pt_scene_tree_info: or a NULL out) returns PT_ERR_INVALID before any HIP call.
- * Out of scope: a change of the triangle count; an automatic rebuild (the caller decides from pt_scene_tree_inflation); a SAH or
- * PLOC quality pass on the GPU; a rebuild of the reference leaf assignment (it defines the result); a tile-split rebuild (every
- * rank rebuilds its own scene and, the tree being a function of the positions alone, gets the same one); a ptrender option.
+ * Out of scope: a change of the triangle count; an automatic rebuild (the caller decides from pt_scene_tree_inflation); a full
+ * SAH or PLOC build on the GPU (the treelet pass of pt_scene_rebuild_tree_opt is the quality step there is); a rebuild of the
+ * reference leaf assignment (it defines the result); a tile-split rebuild (every rank rebuilds its own scene and, the tree being
+ * a function of the positions alone, gets the same one); a ptrender option.
  * -------------------------------------------------------------------------------- */
 typedef struct PtTreeInfo { int32_t n_wide, n_quad, depth, quad_depth, rebuilds; } PtTreeInfo;
 PT_API int  pt_scene_rebuild_tree(PtScene* s, void* hip_stream);
@@ -585,8 +588,9 @@ PT_API int  pt_dbg_tree_limits(int32_t depth, int32_t quad_depth, int32_t* max_d
  * Errors, before any HIP call: PT_ERR_INVALID for a NULL scene or params, D < 0 or D > 32, f negative, NaN or infinite, and
  *   D > 0 with D < clog2(n) for a scene of n >= 3 triangles (no tree over n triangles is that shallow).
  * Memory: the first call of a scene allocates 18 KB more than pt_scene_rebuild_tree does, once.
- * When to call it: "When to call it" above; the call costs 0.53 ms for 69,576 triangles and 0.95 ms for 278,268.
- * Out of scope: more than two classes; an automatic choice of the parameters; a SAH or PLOC pass; a ptrender option.
+ * When to call it: "When to call it" above; the call costs 0.53 ms for 69,576 triangles and 0.95 ms for 278,268.  Its tree is
+ *   the starting point of pt_scene_rebuild_tree_opt (below), whose tree rendered 2 - 4 % faster for 2.5 - 4 ms more per call.
+ * Out of scope: more than two classes; an automatic choice of the parameters; a ptrender option.
  * -------------------------------------------------------------------------------- */
 typedef struct PtRebuildParams {
     int32_t depth_budget;    /* 0: none (today's tree).  Else the binary tree is at most this deep (a leaf counts as a node), <= 32 */
@@ -595,6 +599,74 @@ typedef struct PtRebuildParams {
 typedef struct PtRebuildReport { int32_t n_large, n_flattened_tris; } PtRebuildReport;
 PT_API void pt_rebuild_params_default(PtRebuildParams* p);          /* 26, 0.0625f */
 PT_API int  pt_scene_rebuild_tree_ex(PtScene* s, const PtRebuildParams* p, PtRebuildReport* report /* may be NULL */, void* hip_stream);
+
+/* ----------------------------------------------------------------------------------
+ * Tree rebuild with treelet restructuring (new).  Opt-in: pt_scene_rebuild_tree and pt_scene_rebuild_tree_ex are exactly what
+ * they were, including what they allocate.
+ * pt_scene_rebuild_tree_opt is pt_scene_rebuild_tree_ex(s, p, ...) with `passes` restructuring passes over the binary topology by
+ * surface area (Karras and Aila 2013, "Fast parallel construction of high-quality bounding volume hierarchies";
+ * csrc/pt_rebuild.hip).  The passes run after the last radix tree is built (after the rekey where there is a
+ * budget) and before the numbering.  Everything "Tree rebuild" and "Tree rebuild with a depth budget" promise holds unchanged:
+ * bit-for-bit results of every entry point (PT_QUERY_ANY: the same verdict), the untouched arrays, staging before commit with the
+ * limit check before the first write to anything a render reads, `rebuilds`, inflation of exactly 1.0 afterwards, later updates on
+ * the new trees.  The four rebuilt arrays are a function of the current positions, the reference leaf assignment, p and passes
+ * alone.  passes == 0 is pt_scene_rebuild_tree_ex byte for byte.  Scenes of n <= 2 triangles take the single-leaf path and passes
+ * is ignored.
+ *
+ * The pass.  Nodes are the raw nodes of the radix tree.  A LEAF is a singleton or an internal node over exactly two triangles;
+ *   leaves are never opened, moved into or changed, so the order of tri, the maps and every leaf ref are those of
+ *   pt_scene_rebuild_tree_ex.  An INTERIOR node is an internal node over more than two triangles.
+ *   Boxes: a singleton's is the min / max of its three vertices, every other node's the min / max of (left child, right child);
+ *   the box of a subset of a treelet's entries is the entry of the lowest bit joined with the others in ascending order (min2(so
+ *   far, entry)).  Area is 2 * (dx * dy + dy * dz + dz * dx) in float32, every operation rounded once, no contraction.
+ *   Levels: heights (leaf = 0), depths and the depth of the tree are those of the topology a pass starts from.  Interior nodes
+ *   are processed in ascending start-of-pass height, one launch per height.  Nodes of one height are roots of disjoint subtrees
+ *   and a restructure rearranges nodes inside its root's subtree only, so a node's subtree is complete and the node still sits at
+ *   its start-of-pass depth when its turn comes, and no data passes between workgroups within a launch.
+ *   Per interior node v: (1) box and height of v from its current children.  (2) The treelet: L = [left, right]; while |L| < 7
+ *   and an entry is interior, the interior entry of largest area (the first of them in list order unless a later one is strictly
+ *   larger) is replaced by its left child and its right child is appended; the opened node joins the list I.  Fewer than 3
+ *   entries: nothing to do, the treelet is not counted.  (3) For every non-empty subset S of L (bit k = entry k): a[S] = area of
+ *   its box; c[S] = 0 for one entry, else (S == full ? 0 : a[S]) + min over P of (c[P] + c[S \ P]), P the proper subsets of S
+ *   that contain S's lowest bit, in ascending numeric order, a later P taken only where strictly smaller; h[S] = the height of
+ *   the entry, else 1 + max(h[P], h[S \ P]) of the chosen P.  (4) Accept only if c[full] < area(I[0]) + area(I[1]) + ... (summed
+ *   in opening order), strictly, and h[full] <= max(height(v), H_lim - depth(v)); H_lim = D - 1 for a budget D > 0, else the
+ *   depth of the tree THIS PASS started from (PtTreeInfo::depth of that topology).  So the tree never gets deeper than the budget,
+ *   or than it was, and a pass never turns an accepted rebuild into a refused one.  (5) Rewire: v stands for the full set, the
+ *   node of S has the node of P on its left and the node of S \ P on its right, and every other subset of two or more entries
+ *   takes the next unused node of I in pre-order (node, left subtree, right subtree).
+ * report (may be NULL): n_large and n_flattened_tris as pt_scene_rebuild_tree_ex reports them; n_roots, the treelets solved,
+ *   and n_restructured, the treelets accepted, both summed over all passes.  They travel with the words the first wait already
+ *   reads (integer atomic sums; no atomic decides an index) and are valid for a refused call too.
+ * Errors, before any HIP call: those of pt_scene_rebuild_tree_ex, and PT_ERR_INVALID for passes < 0 or passes > 8.  The report
+ *   is left untouched on that path.
+ * Waiting: as pt_scene_rebuild_tree_ex — the passes add no wait: the per-height launches are steered by level offsets that stay
+ *   in device memory (a fixed grid walks the slice of its height; heights 1 .. D - 1, or 1 .. 63 without a budget, are launched
+ *   whatever the tree's height is). Without a budget every pass enqueues 63 such launches, most over an empty
+ *   slice: (0, 1/16) with 2 passes cost 4.44 - 4.47 ms for 69,576 triangles against 3.04 - 3.06 ms with the budget of 26.
+ * Memory: the first call of a scene allocates, once, 28 bytes per raw node (a height and a box; 2 n - 1 raw nodes) and 1.6 KB
+ *   beside what pt_scene_rebuild_tree_ex allocates: 15.6 MB for 278,268 triangles.  Later calls allocate nothing;
+ *   pt_scene_device_bytes follows.
+ * When to call it (measured on the MI355X): whenever you rebuild on the GPU, prefer this call with its
+ *   defaults to pt_scene_rebuild_tree_ex; against the refit tree, still time a render before and after.  Two passes take 8 - 9 %
+ *   off the sum of the interior boxes' areas on the stand-in scene at 18,252 triangles (a third pass 0.2 %, so 2 is the default).
+ *   After turns of 10, 25 and 90 degrees of the stand-in mesh (69,576 triangles, inflation 1.06 - 1.12) the tree of this call
+ *   rendered 2.4 - 4.4 % faster than the tree of pt_scene_rebuild_tree_ex and fetched 5.1 - 6.9 % fewer node records - fewer
+ *   than the refit tree on all three poses (1.7 - 6.9 %), 2.2 - 2.6 % more than a fresh host upload.  In render time it beat the
+ *   refit tree at 25 degrees (2.8 % faster, inflation 1.12) and not at 10 and 90 degrees (1.8 % and 5.1 % slower); it stayed
+ *   3.5 - 7.3 % behind a fresh host upload (pt_scene_rebuild_tree_ex: 6.2 - 10.2 %).  So a GPU rebuild now pays from an inflation
+ *   of about 1.1 on, or wherever refits have cost more than about 4 - 7 % of render time against a fresh tree.  The call costs
+ *   more than estimated: 3.0 - 3.1 ms for 69,576 triangles and 4.8 ms for 278,268 (pt_scene_rebuild_tree_ex: 0.55 - 0.57 ms and
+ *   0.94 - 0.99 ms, so 4.8 - 5.6 times), 1.1 - 1.4 ms and 1.6 - 2.2 ms per pass: a pass is up to 25 launches one after the other,
+ *   each as long as its slowest treelet.  That is 37 and 106 times below the host rebuild (114 ms and 506 ms).  The closest-hit
+ *   query of 2.07 M rays stays where it was (0.22 - 0.28 ms; depth 25 / 12 on every pose).
+ * Out of scope: optimising a refit or an uploaded tree in place; the host build's area-driven 4-wide collapse (the 4-wide tree
+ *   is still every second level of the binary one); an automatic choice of passes; a ptrender option.
+ * -------------------------------------------------------------------------------- */
+typedef struct PtRebuildOptReport { int32_t n_large, n_flattened_tris, n_roots, n_restructured; } PtRebuildOptReport;
+PT_API int32_t pt_rebuild_opt_passes_default(void);   /* 2 */
+PT_API int  pt_scene_rebuild_tree_opt(PtScene* s, const PtRebuildParams* p, int32_t passes,
+                                      PtRebuildOptReport* report /* may be NULL */, void* hip_stream);
 
 /* ----------------------------------------------------------------------------------
  * Ray queries (new: the reference casts rays only from inside its integrator).  Opt-in: every call above is as it was.

@@ -23,6 +23,7 @@
 // pt_scene_rebuild_tree_ex is the same build with two opt-in steps: the triangles' size class as bit 62 of
 // the key, each class quantised in a centroid box of its own, and a depth budget — every triangle rewrites its key below the
 // topmost ancestor that would reach below the budget, and the radix tree is built a second time over the new keys.
+// pt_scene_rebuild_tree_opt adds treelet restructuring passes by surface area between that tree and the numbering.
 #include <hip/hip_runtime.h>
 #include <cfloat>
 #include <cmath>
@@ -46,7 +47,7 @@ using ptd::load_tri;
 __device__ __forceinline__ float min2(float x, float y) { return (y < x) ? y : x; }      // as pt_dynamic.hip
 __device__ __forceinline__ float max2(float x, float y) { return (x < y) ? y : x; }
 
-constexpr int kDead = 127;           // sort key of a raw node that gets no number (heights and levels are below 64: the keys have 62 bits)
+constexpr int kDead = 127;           // sort key of a raw node that gets no number (heights and levels are below 64: unique keys with at most 63 significant bits)
 constexpr int kLevelSlots = 129;     // first index with key >= h, h = 0 .. 128
 // the words read back before the commit: level offsets of `order`, level offsets of the 4-wide numbering, deepest builder node
 constexpr int kLvOrder = 0, kLvQuad = kLevelSlots, kLvDepth = 2 * kLevelSlots, kLvWords = 2 * kLevelSlots + 2;
@@ -468,6 +469,206 @@ __global__ __launch_bounds__(256) void rb_rekey(RbDev r, int budget)
     if (threadIdx.x == 0 && total) atomicAdd(&r.levels[kLvFlattened], total);      // a count: it decides no index
 }
 
+// ---- pt_scene_rebuild_tree_opt: treelet restructuring passes over the radix tree (include/pt_api.h: "Tree rebuild with treelet
+// restructuring"; Karras and Aila 2013).  A pass runs between the last rb_karras / rb_depth and the numbering and
+// rewires `child` / `parent` of interior nodes only: leaves (singletons and internal nodes over two triangles) are never opened, so
+// everything below — rb_depth, rb_height, the scans, rb_emit — runs as it is.  Interior nodes are taken in ascending start-of-pass height,
+// one launch per height; the nodes of one height are roots of disjoint subtrees and a restructure stays inside its root's subtree, so no
+// data passes between workgroups within a launch.
+// What only this call works in (PtScene::rbo_buf, one block): its own copy of the read-back words with the report's four counts behind
+// them, the level offsets of a pass (device only: they steer the per-height launches), a height and a box per raw node.
+constexpr int kTreelet = 7, kOptMaxPasses = 8, kOptPassesDefault = 2;
+constexpr int kOptBlock = 64;        // ro_solve: a workgroup is one wave64, two of the 128 subsets per lane
+constexpr int kOptGrid = 4096;      // one wave per treelet, grid-stride over the level's slice (its size is known on the device only)
+constexpr int kLvRoots = kLvWordsEx, kLvRestructured = kLvWordsEx + 1, kLvWordsOpt = kLvWordsEx + 2;
+constexpr size_t kRoLevels = 0, kRoPassLevels = (size_t)kLvWordsOpt * 4, kRoHeights = (kRoPassLevels + (size_t)kLevelSlots * 4 + 15) / 16 * 16;
+
+struct RbOpt {
+    float* box;          // N x 6: lo.xyz hi.xyz
+    int32_t* hcur;       // N: height now (leaf = 0)
+    int32_t* lvl;        // kLevelSlots: first index of `qsorted` with start-of-pass height >= h
+    int32_t h_lim;       // budget - 1, or -1: the depth of the tree the pass started from (levels[kLvDepth])
+};
+
+__device__ __forceinline__ float box_area(const float* b)      // dyn_area's expression
+{
+    const float d0 = b[3] - b[0], d1 = b[4] - b[1], d2 = b[5] - b[2];
+    return 2.f * (d0 * d1 + d1 * d2 + d2 * d0);
+}
+
+__device__ __forceinline__ void tri_box(const float* __restrict__ pos, int prim, float* b)
+{
+    const Tri9 t = load_tri(pos, prim);
+    for (int a = 0; a < 3; a++) {
+        b[a] = min2(t.v0[a], min2(t.v1[a], t.v2[a]));
+        b[3 + a] = max2(t.v0[a], max2(t.v1[a], t.v2[a]));
+    }
+}
+
+// boxes and heights of the leaves: singletons, and internal nodes over two triangles (rb_depth has written wflag)
+__global__ __launch_bounds__(256) void ro_init(RbDev r, RbOpt o, const float* __restrict__ pos)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    const int n = r.n, N = 2 * n - 1;
+    if (v >= N) return;
+    float b[6];
+    if (v >= n - 1) {
+        tri_box(pos, r.tmap[v - (n - 1)].x, b);
+    } else {
+        if (r.wflag[v]) return;
+        const int2 c = r.child[v];
+        float b1[6];
+        tri_box(pos, r.tmap[c.x - (n - 1)].x, b);
+        tri_box(pos, r.tmap[c.y - (n - 1)].x, b1);
+        for (int a = 0; a < 3; a++) { b[a] = min2(b[a], b1[a]); b[3 + a] = max2(b[3 + a], b1[3 + a]); }
+    }
+    for (int k = 0; k < 6; k++) o.box[(size_t)v * 6 + k] = b[k];
+    o.hcur[v] = 0;
+}
+
+__global__ __launch_bounds__(256) void ro_keys(RbDev r)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= r.n - 1) return;
+    r.key_in[v] = r.wflag[v] ? (uint32_t)r.height[v] : (uint32_t)kDead;
+}
+
+// One wave per interior node of start-of-pass height `level`: the treelet of up to 7 entries below it, the optimal topology over
+// them by dynamic programming over the 127 subsets (two per lane, rounds by subset size), and the rewiring by lane 0.
+__global__ __launch_bounds__(kOptBlock) void ro_solve(RbDev r, RbOpt o, int level)
+{
+    static_assert(kOptBlock == 64 && (1 << kTreelet) == 2 * kOptBlock, "the subsets of a treelet are dealt two per lane of one wave64");
+    __shared__ float lbox[kTreelet][6];
+    __shared__ float larea[kTreelet];
+    __shared__ float sa[128], sc[128];
+    __shared__ uint8_t spart[128], sh[128];
+    __shared__ int sL[kTreelet], sI[kTreelet], stS[16], stP[16], stSide[16];
+    __shared__ int sm;
+    const int lane = threadIdx.x;
+    const int first = o.lvl[level], last = o.lvl[level + 1];
+    int roots = 0, done = 0;
+    for (int idx = first + (int)blockIdx.x; idx < last; idx += (int)gridDim.x) {
+        __syncthreads();      // the treelet before is done with the shared arrays
+        const int v = r.qsorted[idx];
+        int hv = 0;
+        float was = 0.f;
+        if (lane == 0) {
+            // 1: box and height of v from its current children
+            const int2 c = r.child[v];
+            float bv[6];
+            for (int k = 0; k < 6; k++) { lbox[0][k] = o.box[(size_t)c.x * 6 + k]; lbox[1][k] = o.box[(size_t)c.y * 6 + k]; }
+            for (int a = 0; a < 3; a++) { bv[a] = min2(lbox[0][a], lbox[1][a]); bv[3 + a] = max2(lbox[0][3 + a], lbox[1][3 + a]); }
+            for (int k = 0; k < 6; k++) o.box[(size_t)v * 6 + k] = bv[k];
+            const int hl = o.hcur[c.x], hr = o.hcur[c.y];
+            hv = 1 + (hl > hr ? hl : hr);
+            o.hcur[v] = hv;
+            // 2: the treelet
+            sL[0] = c.x; sL[1] = c.y;
+            larea[0] = box_area(lbox[0]); larea[1] = box_area(lbox[1]);
+            int m = 2, ni = 0;
+            while (m < kTreelet) {
+                int pick = -1;
+                for (int k = 0; k < m; k++)
+                    if (rb_is_interior(r, sL[k]) && (pick < 0 || larea[k] > larea[pick])) pick = k;
+                if (pick < 0) break;
+                const int e = sL[pick];
+                was = ni == 0 ? larea[pick] : was + larea[pick];
+                sI[ni++] = e;
+                const int2 ec = r.child[e];
+                for (int k = 0; k < 6; k++) { lbox[pick][k] = o.box[(size_t)ec.x * 6 + k]; lbox[m][k] = o.box[(size_t)ec.y * 6 + k]; }
+                sL[pick] = ec.x; sL[m] = ec.y;
+                larea[pick] = box_area(lbox[pick]); larea[m] = box_area(lbox[m]);
+                m++;
+            }
+            for (int k = 0; k < m; k++) sh[1 << k] = (uint8_t)o.hcur[sL[k]];
+            sm = m;
+        }
+        __syncthreads();
+        const int m = sm;
+        if (m < 3) continue;
+        const int full = (1 << m) - 1;
+        // 3: areas of all subsets, then the cheapest partition of each by rounds of subset size
+        for (int S = lane; S <= full; S += kOptBlock) {
+            if (S == 0) continue;
+            float b[6];
+            bool any = false;
+            for (int k = 0; k < m; k++) {
+                if (!((S >> k) & 1)) continue;
+                for (int a = 0; a < 3; a++) {
+                    b[a] = any ? min2(b[a], lbox[k][a]) : lbox[k][a];
+                    b[3 + a] = any ? max2(b[3 + a], lbox[k][3 + a]) : lbox[k][3 + a];
+                }
+                any = true;
+            }
+            sa[S] = box_area(b);
+            if ((S & (S - 1)) == 0) sc[S] = 0.f;
+        }
+        __syncthreads();
+        for (int size = 2; size <= m; size++) {
+            for (int S = lane; S <= full; S += kOptBlock) {
+                if (__popc(S) != size) continue;
+                const int low = S & -S, rest = S ^ low;
+                int bp = low, sub = (0 - rest) & rest;
+                float best = sc[low] + sc[rest];
+                while (sub != rest) {      // P = low | sub ascends with sub; a later P only where strictly cheaper
+                    const int P = low | sub;
+                    const float cand = sc[P] + sc[S ^ P];
+                    if (cand < best) { best = cand; bp = P; }
+                    sub = (sub - rest) & rest;
+                }
+                spart[S] = (uint8_t)bp;
+                sc[S] = (S == full ? 0.f : sa[S]) + best;
+                const int h0 = sh[bp], h1 = sh[S ^ bp];
+                sh[S] = (uint8_t)(1 + (h0 > h1 ? h0 : h1));
+            }
+            __syncthreads();
+        }
+        if (lane == 0) {      // the other lanes go on to the barrier at the top of the loop: every barrier is reached by the whole workgroup
+            // 4: cheaper, and no deeper than the budget (or than the tree was) allows
+            roots++;
+            const int room = (o.h_lim >= 0 ? o.h_lim : r.levels[kLvDepth]) - r.depth[v];
+            if (sc[full] < was && (int)sh[full] <= (hv > room ? hv : room)) {
+                done++;
+                // 5: rewire in pre-order; the nodes of I are handed out as the subsets of two or more entries are met
+                int sp = 0, nxt = 0;
+                stS[0] = full; stP[0] = -1; stSide[0] = 0; sp = 1;
+                while (sp > 0) {
+                    sp--;
+                    const int S = stS[sp], pid = stP[sp], side = stSide[sp];
+                    const bool single = (S & (S - 1)) == 0;
+                    const int node = single ? sL[31 - __clz(S)] : pid < 0 ? v : sI[nxt++];
+                    if (pid >= 0) {
+                        reinterpret_cast<int32_t*>(&r.child[pid])[side] = node;
+                        r.parent[node] = pid;
+                    }
+                    if (single) continue;
+                    o.hcur[node] = sh[S];
+                    if (pid >= 0) {
+                        float b[6];
+                        bool any = false;
+                        for (int k = 0; k < m; k++) {
+                            if (!((S >> k) & 1)) continue;
+                            for (int a = 0; a < 3; a++) {
+                                b[a] = any ? min2(b[a], lbox[k][a]) : lbox[k][a];
+                                b[3 + a] = any ? max2(b[3 + a], lbox[k][3 + a]) : lbox[k][3 + a];
+                            }
+                            any = true;
+                        }
+                        for (int k = 0; k < 6; k++) o.box[(size_t)node * 6 + k] = b[k];
+                    }
+                    const int P = spart[S];
+                    stS[sp] = S ^ P; stP[sp] = node; stSide[sp] = 1; sp++;
+                    stS[sp] = P; stP[sp] = node; stSide[sp] = 0; sp++;
+                }
+            }
+        }
+    }
+    if (lane == 0) {      // counts: they decide no index
+        if (roots) atomicAdd(&r.levels[kLvRoots], roots);
+        if (done) atomicAdd(&r.levels[kLvRestructured], done);
+    }
+}
+
 inline unsigned blocks_of(int n) { return (unsigned)((n + 255) / 256); }
 
 // temporary storage of the largest of the rocPRIM calls below (sizes only: nothing is launched with a null storage pointer)
@@ -565,6 +766,20 @@ static int rbx_prepare(PtScene* s)
     return PT_OK;
 }
 
+// First optimised rebuild of a scene: the block only pt_scene_rebuild_tree_opt works in (28 bytes per raw node and 1.6 KB).  The two
+// older calls never allocate it.
+static size_t rbo_bytes(size_t n) { return kRoHeights + (2 * n - 1) * 4 + (2 * n - 1) * 24; }
+
+static int rbo_prepare(PtScene* s)
+{
+    if (s->rbo_buf) return PT_OK;
+    DevBuf block;
+    HIPCHK(block.alloc(rbo_bytes((size_t)s->dyn.n_tris)));
+    s->bytes += (int64_t)block.held();
+    s->rbo_buf = std::move(block);
+    return PT_OK;
+}
+
 static RbDev rb_args(PtScene* s)
 {
     DevBuf* b = s->rb_buf;
@@ -582,14 +797,15 @@ static RbDev rb_args(PtScene* s)
 }
 
 // Enqueues the whole build of the topology into the staging buffers.  Nothing a render reads is written.  x: the extended call
-// (pt_scene_rebuild_tree_ex) with its depth budget, NULL for pt_scene_rebuild_tree.
-static int rb_build(PtScene* s, const RbDev& r, hipStream_t st, const RbEx* x = nullptr, int budget = 0)
+// (pt_scene_rebuild_tree_ex) with its depth budget, NULL for pt_scene_rebuild_tree.  o: the optimised call
+// (pt_scene_rebuild_tree_opt) with its number of restructuring passes, NULL for the other two.
+static int rb_build(PtScene* s, const RbDev& r, hipStream_t st, const RbEx* x = nullptr, int budget = 0, const RbOpt* o = nullptr, int passes = 0)
 {
     const int n = r.n, N = 2 * n - 1;
     const float* pos = s->dyn_buf[kDynPos].as<const float>();
     void* temp = s->rb_buf[kRbTemp].as<>();
     size_t tb = s->rb_temp_bytes;
-    if (x) HIPCHK(hipMemsetAsync(r.levels, 0, (size_t)kLvWordsEx * 4, st));      // the report's counts are summed from here on
+    if (x) HIPCHK(hipMemsetAsync(r.levels, 0, (size_t)(o ? kLvWordsOpt : kLvWordsEx) * 4, st));      // the report's counts are summed from here on
     hipLaunchKernelGGL(rb_box_partial, dim3(ptd::kCoreBlocks), dim3(256), 0, st, r, pos);
     hipLaunchKernelGGL(rb_box_final, dim3(1), dim3(256), 0, st, r);
     if (x && x->large_fraction > 0.f) {      // a centroid box per size class; the class is bit 62 of the key
@@ -623,6 +839,22 @@ static int rb_build(PtScene* s, const RbDev& r, hipStream_t st, const RbEx* x = 
         hipLaunchKernelGGL(rb_karras, dim3(blocks_of(n - 1)), dim3(256), 0, st, again);
         hipLaunchKernelGGL(rb_depth, dim3(blocks_of(N)), dim3(256), 0, st, again);
     }
+    if (o && passes > 0) {      // treelet restructuring: per pass the heights, the interior nodes by height, one launch per height, the depths anew
+        const int top = budget > 0 ? budget - 1 : 63;      // no interior node is higher: the tree keeps the budget, and a radix tree over unique keys of at most 63 significant bits is at most 63 deep
+        hipLaunchKernelGGL(ro_init, dim3(blocks_of(N)), dim3(256), 0, st, r, *o, pos);
+        for (int pass = 0; pass < passes; pass++) {
+            hipLaunchKernelGGL(rb_height, dim3(blocks_of(N)), dim3(256), 0, st, r);
+            hipLaunchKernelGGL(ro_keys, dim3(blocks_of(n - 1)), dim3(256), 0, st, r);
+            HIPCHK(hipGetLastError());
+            tb = s->rb_temp_bytes;
+            HIPCHK(rocprim::radix_sort_pairs(temp, tb, r.key_in, r.key_out, r.iota, r.qsorted, n - 1, 0, 8, st));
+            hipLaunchKernelGGL(rb_level_start, dim3(blocks_of(n - 1)), dim3(256), 0, st, r.key_out, n - 1, o->lvl);
+            for (int h = 1; h <= top; h++) hipLaunchKernelGGL(ro_solve, dim3(kOptGrid), dim3(kOptBlock), 0, st, r, *o, h);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemsetAsync(r.levels + kLvDepth, 0, 4, st));
+            hipLaunchKernelGGL(rb_depth, dim3(blocks_of(N)), dim3(256), 0, st, r);
+        }
+    }
     hipLaunchKernelGGL(rb_height, dim3(blocks_of(N)), dim3(256), 0, st, r);
     HIPCHK(hipGetLastError());
     // numbering: builder nodes and `nodes` records by rank, `order` by height, `quad` records by level
@@ -644,28 +876,40 @@ static int rb_build(PtScene* s, const RbDev& r, hipStream_t st, const RbEx* x = 
     return PT_OK;
 }
 
-// The rebuild behind both entry points.  p: the parameters of pt_scene_rebuild_tree_ex (checked by the caller), NULL for
+// The rebuild behind the three entry points.  p: the parameters of pt_scene_rebuild_tree_ex (checked by the caller), NULL for
 // pt_scene_rebuild_tree, whose launches, waits and allocations are exactly what they were before the extended call existed.
-static int rb_run(PtScene* s, const char* who, const PtRebuildParams* p, PtRebuildReport* report, hipStream_t st)
+// passes >= 0: pt_scene_rebuild_tree_opt (p is not NULL), with its own report; -1 for the other two, which are what they were too.
+static int rb_run(PtScene* s, const char* who, const PtRebuildParams* p, PtRebuildReport* report, hipStream_t st, int passes = -1,
+                  PtRebuildOptReport* opt_report = nullptr)
 {
     HIPCHK(hipSetDevice(s->device));
     int rc;
     if ((rc = pt_dyn_prepare(s)) != PT_OK) return rc;
     if ((rc = rb_prepare(s, st)) != PT_OK) return rc;
     if (p && (rc = rbx_prepare(s)) != PT_OK) return rc;
+    const bool opt = passes >= 0;
+    if (opt && (rc = rbo_prepare(s)) != PT_OK) return rc;
     RbDev r = rb_args(s);
     RbEx x{};
+    RbOpt o{};
     if (p) {
         char* base = s->rbx_buf.as<char>();
         x.class_partial = (float*)(base + kRxClassPartial); x.class_box = (float*)(base + kRxClassBox); x.large_fraction = p->large_fraction;
         r.levels = (int32_t*)(base + kRxLevels);
     }
-    if ((rc = rb_build(s, r, st, p ? &x : nullptr, p ? p->depth_budget : 0)) != PT_OK) return rc;
+    if (opt) {
+        char* base = s->rbo_buf.as<char>();
+        r.levels = (int32_t*)(base + kRoLevels);
+        o.lvl = (int32_t*)(base + kRoPassLevels); o.hcur = (int32_t*)(base + kRoHeights); o.box = (float*)(base + kRoHeights + (2 * (size_t)r.n - 1) * 4);
+        o.h_lim = p->depth_budget > 0 ? p->depth_budget - 1 : -1;
+    }
+    if ((rc = rb_build(s, r, st, p ? &x : nullptr, p ? p->depth_budget : 0, opt ? &o : nullptr, opt ? passes : 0)) != PT_OK) return rc;
     // wait 1: the level offsets, the counts and the depths (and, behind them, the two counts of the extended call's report)
-    int32_t lv[kLvWordsEx] = {};
-    HIPCHK(hipMemcpyAsync(lv, r.levels, (size_t)(p ? kLvWordsEx : kLvWords) * 4, hipMemcpyDeviceToHost, st));
+    int32_t lv[kLvWordsOpt] = {};
+    HIPCHK(hipMemcpyAsync(lv, r.levels, (size_t)(opt ? kLvWordsOpt : p ? kLvWordsEx : kLvWords) * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (report) { report->n_large = lv[kLvLarge]; report->n_flattened_tris = lv[kLvFlattened]; }
+    if (opt_report) { opt_report->n_large = lv[kLvLarge]; opt_report->n_flattened_tris = lv[kLvFlattened]; opt_report->n_roots = lv[kLvRoots]; opt_report->n_restructured = lv[kLvRestructured]; }
     const int n_bn = lv[kLvOrder + kDead], n_quad = lv[kLvQuad + kDead], n_wide = n_bn > 1 ? (n_bn - 1) / 2 : 1;
     int top = 0, quad_depth = 0;
     while (lv[kLvOrder + top + 1] < n_bn) top++;                 // heights 0 .. top
@@ -710,25 +954,54 @@ void pt_rebuild_params_default(PtRebuildParams* p)
     if (p) { p->depth_budget = 26; p->large_fraction = 0.0625f; }
 }
 
-int pt_scene_rebuild_tree_ex(PtScene* s, const PtRebuildParams* p, PtRebuildReport* report, void* hip_stream)
+// The parameter checks of pt_scene_rebuild_tree_ex, under the name of the entry point that applies them.  No HIP call.
+static int rb_check_params(const char* who, const PtScene* s, const PtRebuildParams* p)
 {
-    if (!s || !p) { pt_set_error("pt_scene_rebuild_tree_ex: NULL %s", !s ? "scene" : "params"); return PT_ERR_INVALID; }
+    if (!s || !p) { pt_set_error("%s: NULL %s", who, !s ? "scene" : "params"); return PT_ERR_INVALID; }
     if (p->depth_budget < 0 || p->depth_budget > ptd::kStackDepth) {
-        pt_set_error("pt_scene_rebuild_tree_ex: depth_budget %d is not in 0 .. %d", p->depth_budget, ptd::kStackDepth);
+        pt_set_error("%s: depth_budget %d is not in 0 .. %d", who, p->depth_budget, ptd::kStackDepth);
         return PT_ERR_INVALID;
     }
     if (!(p->large_fraction >= 0.f) || std::isinf(p->large_fraction)) {
-        pt_set_error("pt_scene_rebuild_tree_ex: large_fraction %g is not a finite number >= 0", (double)p->large_fraction);
+        pt_set_error("%s: large_fraction %g is not a finite number >= 0", who, (double)p->large_fraction);
         return PT_ERR_INVALID;
     }
+    return PT_OK;
+}
+
+static int rb_check_budget(const char* who, const PtScene* s, const PtRebuildParams* p)
+{
     const int n = s->dyn.n_tris;
     int need = 0;
     while (n >= 3 && need < 32 && ((int64_t)1 << need) < n) need++;      // clog2(n): a tree over n triangles is at least that deep
     if (p->depth_budget > 0 && p->depth_budget < need) {
-        pt_set_error("pt_scene_rebuild_tree_ex: depth_budget %d is below %d, the depth of a balanced tree over %d triangles", p->depth_budget, need, n);
+        pt_set_error("%s: depth_budget %d is below %d, the depth of a balanced tree over %d triangles", who, p->depth_budget, need, n);
         return PT_ERR_INVALID;
     }
-    return rb_run(s, "pt_scene_rebuild_tree_ex", p, report, (hipStream_t)hip_stream);
+    return PT_OK;
+}
+
+int pt_scene_rebuild_tree_ex(PtScene* s, const PtRebuildParams* p, PtRebuildReport* report, void* hip_stream)
+{
+    const char* who = "pt_scene_rebuild_tree_ex";
+    int rc;
+    if ((rc = rb_check_params(who, s, p)) != PT_OK || (rc = rb_check_budget(who, s, p)) != PT_OK) return rc;
+    return rb_run(s, who, p, report, (hipStream_t)hip_stream);
+}
+
+int32_t pt_rebuild_opt_passes_default(void) { return kOptPassesDefault; }
+
+int pt_scene_rebuild_tree_opt(PtScene* s, const PtRebuildParams* p, int32_t passes, PtRebuildOptReport* report, void* hip_stream)
+{
+    const char* who = "pt_scene_rebuild_tree_opt";
+    int rc;
+    if ((rc = rb_check_params(who, s, p)) != PT_OK) return rc;
+    if (passes < 0 || passes > kOptMaxPasses) {      // before the scene is read: the checks above and this one need no scene
+        pt_set_error("%s: passes %d is not in 0 .. %d", who, passes, kOptMaxPasses);
+        return PT_ERR_INVALID;
+    }
+    if ((rc = rb_check_budget(who, s, p)) != PT_OK) return rc;
+    return rb_run(s, who, p, nullptr, (hipStream_t)hip_stream, passes, report);
 }
 
 int pt_scene_tree_info(const PtScene* s, PtTreeInfo* out)

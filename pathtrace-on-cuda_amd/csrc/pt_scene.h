@@ -72,6 +72,7 @@ struct PtScene {
     bool rb_ready = false;
     int rebuilds = 0;
     DevBuf rbx_buf, rbx_temp;            // pt_scene_rebuild_tree_ex alone: its class boxes and read-back words; its sort's storage where kRbTemp is too small
+    DevBuf rbo_buf;                      // pt_scene_rebuild_tree_opt alone: its read-back words, the level offsets of a pass, a height and a box per raw node
     // ---- materials and lights (pt_scene_update_materials, csrc/pt_material.hip) ----
     bool tri_emit_ok = true;             // emittance_ok's test over the triangles alone, from pt_scene_create or the last material update (the spheres' part: h_spheres)
     int32_t* h_mat = nullptr;            // pinned, 2 words: the light count and the flag a material update reads back (pt_dyn_prepare)

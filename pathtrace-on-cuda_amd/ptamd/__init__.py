@@ -75,6 +75,10 @@ class PtRebuildReport(C.Structure):
     _fields_ = [("n_large", C.c_int32), ("n_flattened_tris", C.c_int32)]
 
 
+class PtRebuildOptReport(C.Structure):
+    _fields_ = [("n_large", C.c_int32), ("n_flattened_tris", C.c_int32), ("n_roots", C.c_int32), ("n_restructured", C.c_int32)]
+
+
 class PtRayHit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_int32)]
 
@@ -183,6 +187,8 @@ API = [
     ("pt_scene_tree_info", C.c_int, [_P, C.POINTER(PtTreeInfo)]),
     ("pt_rebuild_params_default", None, [C.POINTER(PtRebuildParams)]),
     ("pt_scene_rebuild_tree_ex", C.c_int, [_P, C.POINTER(PtRebuildParams), C.POINTER(PtRebuildReport), _P]),
+    ("pt_rebuild_opt_passes_default", C.c_int32, []),
+    ("pt_scene_rebuild_tree_opt", C.c_int, [_P, C.POINTER(PtRebuildParams), C.c_int32, C.POINTER(PtRebuildOptReport), _P]),
     ("pt_dbg_tree_limits", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("pt_scene_update_materials", C.c_int, [_P, _P, _P]),
     ("pt_scene_update_materials_host", C.c_int, [_P, _P]),
@@ -653,6 +659,21 @@ class Scene:
             prm.large_fraction = large_fraction
         _check(lib().pt_scene_rebuild_tree_ex(self._h, C.byref(prm), C.byref(report), C.c_void_p(stream_ptr)), "pt_scene_rebuild_tree_ex")
         return {name: int(getattr(report, name)) for name, _ in PtRebuildReport._fields_}
+
+    def rebuild_tree_optimized(self, passes=None, depth_budget=None, large_fraction=None, stream_ptr=0):
+        """rebuild_tree with a depth budget and size classes, then `passes` treelet restructuring passes by surface area
+        (include/pt_api.h: pt_scene_rebuild_tree_opt).  A None takes its default (pt_rebuild_opt_passes_default,
+        pt_rebuild_params_default).  Returns the report as a dict: n_large, n_flattened_tris, n_roots, n_restructured."""
+        prm, report = PtRebuildParams(), PtRebuildOptReport()
+        lib().pt_rebuild_params_default(C.byref(prm))
+        if depth_budget is not None:
+            prm.depth_budget = depth_budget
+        if large_fraction is not None:
+            prm.large_fraction = large_fraction
+        if passes is None:
+            passes = lib().pt_rebuild_opt_passes_default()
+        _check(lib().pt_scene_rebuild_tree_opt(self._h, C.byref(prm), passes, C.byref(report), C.c_void_p(stream_ptr)), "pt_scene_rebuild_tree_opt")
+        return {name: int(getattr(report, name)) for name, _ in PtRebuildOptReport._fields_}
 
     def tree_info(self):
         """The traversal trees as they are now, from upload or from the last rebuild_tree: a dict with n_wide, n_quad, depth,

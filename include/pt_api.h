@@ -527,9 +527,12 @@ PT_API int32_t pt_scene_nee_prune(const PtScene* s);
  *   stream afterwards sees the new trees.  One update, query, render or rebuild at a time per scene.
  * Memory: the first rebuild allocates for the worst case (2 n - 1 nodes of the binary tree, n - 1 `nodes` records, n - 1 `quad`
  *   records, the sort's temporary storage) and moves nodes, quad and the maps of the build into blocks of that size; a failed
- *   allocation leaves the scene as it was.  Later rebuilds allocate nothing.  pt_scene_device_bytes reports what is held: it
- *   grows with the first rebuild, whether that rebuild is accepted or refused (the 278,268-triangle scene: 126 MB at upload,
- *   259 MB from the first rebuild on), and does not shrink again.
+ *   allocation leaves the scene as it was.  What a scene holds for rebuilding follows the PARAMETERS of the rebuilds it has seen,
+ *   through whichever of the three entry points they came: a later rebuild allocates only what its parameters need and no
+ *   earlier call did — for large_fraction > 0 and for passes > 0, see the two "Memory" paragraphs below — and a call with
+ *   parameters already seen allocates nothing.  pt_scene_device_bytes reports what is held: it grows with the first rebuild,
+ *   whether that rebuild is accepted or refused (the 278,268-triangle scene: 126 MB at upload, 259 MB from the first rebuild
+ *   on), and does not shrink again.
  * When to call it (measured on the MI355X, DESIGN.md sections 23 and 24): prefer pt_scene_rebuild_tree_ex with its defaults
  *   (below) to this call, and neither to the refit tree while pt_scene_tree_inflation is small.  Both calls are cheap (this one
  *   0.5 ms for 69,576 triangles and 0.8 ms for 278,268, the extended one 12 - 18 % more; the host rebuild takes 114 ms and
@@ -587,7 +590,10 @@ PT_API int  pt_dbg_tree_limits(int32_t depth, int32_t quad_depth, int32_t* max_d
  *   call too.
  * Errors, before any HIP call: PT_ERR_INVALID for a NULL scene or params, D < 0 or D > 32, f negative, NaN or infinite, and
  *   D > 0 with D < clog2(n) for a scene of n >= 3 triangles (no tree over n triangles is that shallow).
- * Memory: the first call of a scene allocates 18 KB more than pt_scene_rebuild_tree does, once.
+ * Memory: by the parameters ("Memory" above).  large_fraction > 0 needs the boxes of the two classes, 16,384 + 64 bytes, and
+ *   where the sort over all 64 key bits asks for more temporary storage than the rebuild already holds, storage of that size;
+ *   the first such call of a scene allocates them.  depth_budget needs nothing: with large_fraction == 0 the call holds exactly
+ *   what pt_scene_rebuild_tree holds.
  * When to call it: "When to call it" above; the call costs 0.53 ms for 69,576 triangles and 0.95 ms for 278,268.  Its tree is
  *   the starting point of pt_scene_rebuild_tree_opt (below), whose tree rendered 2 - 4 % faster for 2.5 - 4 ms more per call.
  * Out of scope: more than two classes; an automatic choice of the parameters; a ptrender option.
@@ -601,8 +607,8 @@ PT_API void pt_rebuild_params_default(PtRebuildParams* p);          /* 26, 0.062
 PT_API int  pt_scene_rebuild_tree_ex(PtScene* s, const PtRebuildParams* p, PtRebuildReport* report /* may be NULL */, void* hip_stream);
 
 /* ----------------------------------------------------------------------------------
- * Tree rebuild with treelet restructuring (new).  Opt-in: pt_scene_rebuild_tree and pt_scene_rebuild_tree_ex are exactly what
- * they were, including what they allocate.
+ * Tree rebuild with treelet restructuring (new).  Opt-in: pt_scene_rebuild_tree and pt_scene_rebuild_tree_ex build exactly what
+ * they did, and a scene that never asks for a pass holds nothing of a pass's ("Memory" below).
  * pt_scene_rebuild_tree_opt is pt_scene_rebuild_tree_ex(s, p, ...) with `passes` restructuring passes over the binary topology by
  * surface area (Karras and Aila 2013, "Fast parallel construction of high-quality bounding volume hierarchies";
  * csrc/pt_rebuild.hip).  The passes run after the last radix tree is built (after the rekey where there is a
@@ -644,9 +650,9 @@ PT_API int  pt_scene_rebuild_tree_ex(PtScene* s, const PtRebuildParams* p, PtReb
  *   in device memory (a fixed grid walks the slice of its height; heights 1 .. D - 1, or 1 .. 63 without a budget, are launched
  *   whatever the tree's height is). Without a budget every pass enqueues 63 such launches, most over an empty
  *   slice: (0, 1/16) with 2 passes cost 4.44 - 4.47 ms for 69,576 triangles against 3.04 - 3.06 ms with the budget of 26.
- * Memory: the first call of a scene allocates, once, 28 bytes per raw node (a height and a box; 2 n - 1 raw nodes) and 1.6 KB
- *   beside what pt_scene_rebuild_tree_ex allocates: 15.6 MB for 278,268 triangles.  Later calls allocate nothing;
- *   pt_scene_device_bytes follows.
+ * Memory: by the parameters ("Memory" of "Tree rebuild").  passes > 0 needs 28 bytes per raw node (a height and a box; 2 n - 1
+ *   raw nodes) and the 516 bytes of a pass's level offsets — 15.6 MB for 278,268 triangles — which the first such call of a
+ *   scene allocates; with passes == 0 the call holds exactly what pt_scene_rebuild_tree_ex with the same p holds.
  * When to call it (measured on the MI355X): whenever you rebuild on the GPU, prefer this call with its
  *   defaults to pt_scene_rebuild_tree_ex; against the refit tree, still time a render before and after.  Two passes take 8 - 9 %
  *   off the sum of the interior boxes' areas on the stand-in scene at 18,252 triangles (a third pass 0.2 %, so 2 is the default).

@@ -1,10 +1,17 @@
-// pt_dyn_device.h — the device expressions that the vertex update (pt_dynamic.hip) and the material update (pt_material.hip) share:
-// a triangle's nine position floats, its edges and its light record.  They are the host's own expressions (host/bvh_build.cpp:
-// flatten_tri) and are stated once, so that a light record comes out with the same bits whichever update writes it.
+// pt_dyn_device.h — the device expressions that the vertex update (pt_dynamic.hip), the material update (pt_material.hip) and the tree
+// rebuild (pt_rebuild.hip) share: a triangle's nine position floats, its edges and its light record, and the selections and the area
+// of a box.  They are the host's own expressions (host/bvh_build.cpp: flatten_tri; host/accel_build.cpp) and are stated once, so that a
+// light record or an area comes out with the same bits whichever file computes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace ptd {
+
+// Selections are written as comparisons, not fminf, so that the sign of a zero comes out as on the host.
+__device__ __forceinline__ float min2(float x, float y) { return (y < x) ? y : x; }      // glm::min / std::min
+__device__ __forceinline__ float max2(float x, float y) { return (x < y) ? y : x; }      // glm::max / std::max
+// surface area of a box with sides d0 d1 d2 (host/accel_build.cpp: Builder::area)
+__device__ __forceinline__ float box_area(float d0, float d1, float d2) { return 2.f * (d0 * d1 + d1 * d2 + d2 * d0); }
 
 struct Tri9 { float v0[3], v1[3], v2[3]; };
 struct Edges { float e1[3], e2[3]; };

@@ -11,7 +11,7 @@
 //   * `nodes` and `quad` are re-derived from the unpadded boxes with the padding and the outward 8-bit quantisation of
 //     host/accel_build.cpp (Emit::run), one thread per record, child refs untouched;
 //   * the core box (scheduling hint) is recomputed over the triangles classified small at upload.
-// Selections are written as comparisons (min2 / max2), not fminf, so that the sign of a zero comes out as on the host.
+// Selections are written as comparisons (pt_dyn_device.h: min2 / max2), not fminf, so that the sign of a zero comes out as on the host.
 #include <hip/hip_runtime.h>
 #include <cfloat>
 #include <cmath>
@@ -30,9 +30,9 @@ using ptd::Tri9;
 using ptd::Edges;
 using ptd::load_tri;
 using ptd::edges_of;
+using ptd::min2;
+using ptd::max2;
 
-__device__ __forceinline__ float min2(float x, float y) { return (y < x) ? y : x; }      // glm::min / std::min
-__device__ __forceinline__ float max2(float x, float y) { return (x < y) ? y : x; }      // glm::max / std::max
 __device__ __forceinline__ float pad_lo(float v) { return v - (fabsf(v) * 1.52587890625e-5f + 1e-30f); }      // accel_build.cpp
 __device__ __forceinline__ float pad_hi(float v) { return v + (fabsf(v) * 1.52587890625e-5f + 1e-30f); }
 
@@ -270,8 +270,7 @@ __global__ __launch_bounds__(256) void dyn_area(DynScene s)
         const int i = base + j;
         if (i < s.n_bn) {
             const float4 b0 = s.bbox[(size_t)i * 2], b1 = s.bbox[(size_t)i * 2 + 1];
-            const float d0 = b1.x - b0.x, d1 = b1.y - b0.y, d2 = b1.z - b0.z;
-            acc += (double)(2.f * (d0 * d1 + d1 * d2 + d2 * d0));      // Builder::area
+            acc += (double)ptd::box_area(b1.x - b0.x, b1.y - b0.y, b1.z - b0.z);
         }
     }
     v[threadIdx.x] = acc;

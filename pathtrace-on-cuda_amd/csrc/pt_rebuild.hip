@@ -20,10 +20,12 @@
 // Everything is built in buffers of its own and checked against the kernels' stack limits on the host BEFORE the first write to an
 // array a render reads: a topology that is too deep leaves the scene exactly as it was.
 //
-// pt_scene_rebuild_tree_ex is the same build with two opt-in steps: the triangles' size class as bit 62 of
-// the key, each class quantised in a centroid box of its own, and a depth budget — every triangle rewrites its key below the
-// topmost ancestor that would reach below the budget, and the radix tree is built a second time over the new keys.
-// pt_scene_rebuild_tree_opt adds treelet restructuring passes by surface area between that tree and the numbering.
+// One build serves the three entry points; it is a function of (depth_budget, large_fraction, passes).  large_fraction > 0 (DESIGN.md
+// section 24): the triangles' size class is bit 62 of the key, each class quantised in a centroid box of its own.  depth_budget > 0:
+// every triangle rewrites its key below the topmost ancestor that would reach below the budget, and the radix tree is built a second
+// time over the new keys.  passes > 0: treelet restructuring passes by surface area between that tree and the
+// numbering.  {0, 0, 0} is the plain rebuild.  What a scene holds follows the same three numbers (the workspace table below; DESIGN.md
+// section 26).
 #include <hip/hip_runtime.h>
 #include <cfloat>
 #include <cmath>
@@ -43,40 +45,75 @@ namespace {
 using ptd::DynScene;
 using ptd::Tri9;
 using ptd::load_tri;
-
-__device__ __forceinline__ float min2(float x, float y) { return (y < x) ? y : x; }      // as pt_dynamic.hip
-__device__ __forceinline__ float max2(float x, float y) { return (x < y) ? y : x; }
+using ptd::min2;
+using ptd::max2;
 
 constexpr int kDead = 127;           // sort key of a raw node that gets no number (heights and levels are below 64: unique keys with at most 63 significant bits)
 constexpr int kLevelSlots = 129;     // first index with key >= h, h = 0 .. 128
-// the words read back before the commit: level offsets of `order`, level offsets of the 4-wide numbering, deepest builder node
-constexpr int kLvOrder = 0, kLvQuad = kLevelSlots, kLvDepth = 2 * kLevelSlots, kLvWords = 2 * kLevelSlots + 2;
+// The words read back before the commit, one block: level offsets of `order`, level offsets of the 4-wide numbering, deepest builder
+// node, the report's four counts.  Cleared once at the start of every build, always read back whole.
+constexpr int kLvOrder = 0, kLvQuad = kLevelSlots, kLvDepth = 2 * kLevelSlots, kLvLarge = kLvDepth + 2, kLvFlattened = kLvLarge + 1, kLvRoots = kLvLarge + 2,
+              kLvRestructured = kLvLarge + 3, kLvWords = kLvLarge + 4;
+constexpr int kTreelet = 7, kOptMaxPasses = 8, kOptPassesDefault = 2;
+constexpr int kOptBlock = 64;        // ro_solve: a workgroup is one wave64, two of the 128 subsets per lane
+constexpr int kOptGrid = 4096;      // one wave per treelet, grid-stride over the level's slice (its size is known on the device only)
 
-// What the build works in (PtScene::rb_buf, in this order).  n = triangles, N = 2 n - 1 raw nodes, I = max(n - 1, 1) internal nodes.
+// What a build is a function of, beside the positions (the entry points check the ranges), and the four counts it reports.
+struct RbParams { int depth_budget; float large_fraction; int passes; };
+struct RbReport { int n_large, n_flattened_tris, n_roots, n_restructured; bool known; };      // known: wait 1 came back (a refused build reports too)
+
+// ---- the workspace: every buffer of a build stated once — element type, name, elements, when it is needed ------------------------------
+// RbDev's pointers, the slots of PtScene::rb_buf and rb_prepare's allocations all follow from this list, whatever its order.
+// The counts are evaluated in rb_prepare: n = triangles, N = 2 n - 1 raw nodes, I = max(n - 1, 1) internal nodes, temp_bytes and
+// temp64_bytes from rocprim_temp_bytes.  A buffer of no elements is not allocated.
+enum RbNeed { kAlways = 1, kClasses = 2 /* large_fraction > 0 */, kPasses = 4 /* passes > 0 */ };
+#define RB_WORKSPACE(X)                                                                                                                          \
+    X(int32_t,  prim_leaf,     n,                     kAlways)  /* reference leaf of every prim (written once per scene) */                      \
+    X(float,    box_partial,   ptd::kCoreBlocks * 8,  kAlways)                                                                                   \
+    X(float,    cbox,          8,                     kAlways)  /* lo.xyz hi.xyz of the centroids */                                             \
+    X(uint64_t, keys,          n,                     kAlways)  /* unsorted */                                                                   \
+    X(uint64_t, sorted,        n,                     kAlways)                                                                                   \
+    X(int2,     child,         I,                     kAlways)  /* raw l, r */                                                                   \
+    X(int2,     range,         I,                     kAlways)  /* first, last sorted triangle */                                                \
+    X(int32_t,  parent,        N,                     kAlways)                                                                                   \
+    X(int32_t,  depth,         N,                     kAlways)                                                                                   \
+    X(int32_t,  height,        N,                     kAlways)                                                                                   \
+    X(int32_t,  live,          N,                     kAlways)  /* 1 = gets a builder node */                                                    \
+    X(int32_t,  newid,         N,                     kAlways)  /* builder node */                                                               \
+    X(int32_t,  wflag,         I,                     kAlways)  /* 1 = interior (more than two triangles) */                                     \
+    X(int32_t,  widx,          I,                     kAlways)  /* `nodes` record */                                                             \
+    X(uint32_t, key_in,        N,                     kAlways)  /* sort keys (height, then level) */                                             \
+    X(uint32_t, key_out,       N,                     kAlways)                                                                                   \
+    X(int32_t,  iota,          I,                     kAlways)                                                                                   \
+    X(int32_t,  qsorted,       I,                     kAlways)  /* raw internal nodes by level (in a pass: by height) */                         \
+    X(int32_t,  qidx,          I,                     kAlways)  /* `quad` record */                                                              \
+    X(int32_t,  levels,        kLvWords,              kAlways)  /* the words read back */                                                        \
+    X(char,     temp,          temp_bytes,            kAlways)  /* rocPRIM temporary storage */                                                  \
+    X(int4,     bn,            N,                     kAlways)  /* the new maps and refs, staged: this line and the six below */                 \
+    X(int32_t,  order,         N,                     kAlways)                                                                                   \
+    X(int2,     wide_bn,       I,                     kAlways)                                                                                   \
+    X(int4,     quad_bn,       I,                     kAlways)                                                                                   \
+    X(int2,     tmap,          n,                     kAlways)                                                                                   \
+    X(int2,     node_ref,      I,                     kAlways)                                                                                   \
+    X(int4,     quad_ref,      I,                     kAlways)                                                                                   \
+    X(float,    class_partial, ptd::kCoreBlocks * 16, kClasses) /* per block: small lo.xyz hi.xyz, pad, large lo.xyz hi.xyz, pad */              \
+    X(float,    class_box,     16,                    kClasses) /* the same layout */                                                            \
+    X(char,     temp64,        temp64_bytes,          kClasses) /* only where the sort over all 64 key bits asks for more than `temp` has */     \
+    X(int32_t,  lvl,           kLevelSlots,           kPasses)  /* first index of `qsorted` with start-of-pass height >= h (device only) */      \
+    X(int32_t,  hcur,          N,                     kPasses)  /* height now (leaf = 0) */                                                      \
+    X(float,    box,           N * 6,                 kPasses)  /* lo.xyz hi.xyz */
+
+#define X(T, name, count, need) kRb_##name,
+enum RbSlot { RB_WORKSPACE(X) kRbSlots };
+#undef X
+
 struct RbDev {
-    int32_t* prim_leaf;      // n: reference leaf of every prim
-    float* box_partial;      // kCoreBlocks x 8
-    float* cbox;             // 8: lo.xyz hi.xyz of the centroids
-    uint64_t* keys;          // n, unsorted
-    uint64_t* sorted;        // n
-    int2* child;             // I: raw l, r
-    int2* range;             // I: first, last sorted triangle
-    int32_t* parent;         // N
-    int32_t* depth;          // N
-    int32_t* height;         // N
-    int32_t* live;           // N: 1 = gets a builder node
-    int32_t* newid;          // N: builder node
-    int32_t* wflag;          // I: 1 = interior (more than two triangles)
-    int32_t* widx;           // I: `nodes` record
-    uint32_t* key_in;        // N: sort keys (height, then level)
-    uint32_t* key_out;       // N
-    int32_t* iota;           // I
-    int32_t* qsorted;        // I: raw internal nodes by level
-    int32_t* qidx;           // I: `quad` record
-    int32_t* levels;         // kLvWords
-    // the new maps and refs, staged
-    int4* bn; int32_t* order; int2* wide_bn; int4* quad_bn; int2* tmap; int2* node_ref; int4* quad_ref;
+#define X(T, name, count, need) T* name;
+    RB_WORKSPACE(X)
+#undef X
     int32_t n;
+    float large_fraction;      // > 0 where the kernels of the size classes run
+    int32_t h_lim;             // a pass: budget - 1, or -1: the depth of the tree the pass started from (levels[kLvDepth])
 };
 
 // ---- prim -> reference leaf (once per scene) ------------------------------------------------------------------------------------
@@ -88,17 +125,20 @@ __global__ __launch_bounds__(256) void rb_prim_leaf(DynScene s, RbDev r)
     for (int k = 0; k < lr.y; k++) r.prim_leaf[lr.x + k] = i;
 }
 
-// ---- centroid box: two stages in the shape of dyn_core_partial / dyn_core_final, no float atomics ------------------------------
-__device__ __forceinline__ void centroid(const float* __restrict__ pos, int prim, float* c)
+// ---- a triangle's own box; its centroid and its longest side follow from it --------------------------------------------------------
+__device__ __forceinline__ void tri_box(const float* __restrict__ pos, int prim, float* b)
 {
     const Tri9 t = load_tri(pos, prim);
     for (int a = 0; a < 3; a++) {
-        const float mn = min2(t.v0[a], min2(t.v1[a], t.v2[a]));
-        const float mx = max2(t.v0[a], max2(t.v1[a], t.v2[a]));
-        c[a] = 0.5f * (mn + mx);
+        b[a] = min2(t.v0[a], min2(t.v1[a], t.v2[a]));
+        b[3 + a] = max2(t.v0[a], max2(t.v1[a], t.v2[a]));
     }
 }
+__device__ __forceinline__ void centroid(const float* b, float* c) { for (int a = 0; a < 3; a++) c[a] = 0.5f * (b[a] + b[3 + a]); }
+__device__ __forceinline__ float longest_side(const float* b) { return max2(max2(max2(0.f, b[3] - b[0]), b[4] - b[1]), b[5] - b[2]); }
+__device__ __forceinline__ float box_area(const float* b) { return ptd::box_area(b[3] - b[0], b[4] - b[1], b[5] - b[2]); }
 
+// ---- centroid box: two stages in the shape of dyn_core_partial / dyn_core_final, no float atomics ------------------------------
 __device__ __forceinline__ void block_box(float* v, float (*lds)[6])      // v[0..2] min, v[3..5] max over the block, in lds[0]
 {
     for (int k = 0; k < 6; k++) lds[threadIdx.x][k] = v[k];
@@ -113,13 +153,23 @@ __device__ __forceinline__ void block_box(float* v, float (*lds)[6])      // v[0
     }
 }
 
+// the 256 partial boxes of the first stage (one per thread, `stride` floats apart) into one box
+__device__ __forceinline__ void reduce_partials(const float* __restrict__ partial, int stride, float* __restrict__ box, float (*lds)[6])
+{
+    float v[6];
+    for (int k = 0; k < 6; k++) v[k] = partial[threadIdx.x * stride + k];      // kCoreBlocks == the block size
+    block_box(v, lds);
+    if (threadIdx.x == 0) for (int k = 0; k < 6; k++) box[k] = lds[0][k];
+}
+
 __global__ __launch_bounds__(256) void rb_box_partial(RbDev r, const float* __restrict__ pos)
 {
     __shared__ float lds[256][6];
     float v[6] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (int i = blockIdx.x * 256 + threadIdx.x; i < r.n; i += ptd::kCoreBlocks * 256) {
-        float c[3];
-        centroid(pos, i, c);
+        float b[6], c[3];
+        tri_box(pos, i, b);
+        centroid(b, c);
         for (int a = 0; a < 3; a++) { v[a] = min2(v[a], c[a]); v[3 + a] = max2(v[3 + a], c[a]); }
     }
     block_box(v, lds);
@@ -129,10 +179,50 @@ __global__ __launch_bounds__(256) void rb_box_partial(RbDev r, const float* __re
 __global__ __launch_bounds__(256) void rb_box_final(RbDev r)
 {
     __shared__ float lds[256][6];
-    float v[6];
-    for (int k = 0; k < 6; k++) v[k] = r.box_partial[threadIdx.x * 8 + k];      // kCoreBlocks == the block size
-    block_box(v, lds);
-    if (threadIdx.x == 0) for (int k = 0; k < 6; k++) r.cbox[k] = lds[0][k];
+    reduce_partials(r.box_partial, 8, r.cbox, lds);
+}
+
+// the same per size class.  A triangle is large where its longest side exceeds f * E, E the longest side of the box of all centroids
+// (rb_box_final has written it)
+__device__ __forceinline__ float large_bound(const RbDev& r)
+{
+    const float E = max2(r.cbox[3] - r.cbox[0], max2(r.cbox[4] - r.cbox[1], r.cbox[5] - r.cbox[2]));
+    return r.large_fraction * E;
+}
+
+__global__ __launch_bounds__(256) void rb_class_partial(RbDev r, const float* __restrict__ pos)
+{
+    __shared__ float lds[256][6];
+    __shared__ int n_large;
+    float v[12] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
+    if (threadIdx.x == 0) n_large = 0;
+    const float bound = large_bound(r);
+    int mine = 0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < r.n; i += ptd::kCoreBlocks * 256) {
+        float b[6], c[3];
+        tri_box(pos, i, b);
+        centroid(b, c);
+        const bool large = longest_side(b) > bound;
+        mine += large ? 1 : 0;
+        for (int a = 0; a < 3; a++) {
+            const float lo_s = large ? v[a] : min2(v[a], c[a]), hi_s = large ? v[3 + a] : max2(v[3 + a], c[a]);
+            const float lo_l = large ? min2(v[6 + a], c[a]) : v[6 + a], hi_l = large ? max2(v[9 + a], c[a]) : v[9 + a];
+            v[a] = lo_s; v[3 + a] = hi_s; v[6 + a] = lo_l; v[9 + a] = hi_l;
+        }
+    }
+    for (int cls = 0; cls < 2; cls++) {      // after block_box only thread 0 reads lds, and only the row it alone writes
+        block_box(v + 6 * cls, lds);
+        if (threadIdx.x == 0) for (int k = 0; k < 6; k++) r.class_partial[blockIdx.x * 16 + cls * 8 + k] = lds[0][k];
+    }
+    if (mine) atomicAdd(&n_large, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && n_large) atomicAdd(&r.levels[kLvLarge], n_large);      // a count: it decides no index
+}
+
+__global__ __launch_bounds__(256) void rb_class_final(RbDev r)
+{
+    __shared__ float lds[256][6];
+    for (int cls = 0; cls < 2; cls++) reduce_partials(r.class_partial + cls * 8, 16, r.class_box + cls * 8, lds);
 }
 
 // ---- keys: 10 bits per axis, x the most significant of every triple; the prim below makes the key unique -----------------------
@@ -146,21 +236,32 @@ __device__ __forceinline__ uint32_t spread3(uint32_t q)      // bit k of q -> bi
     return q;
 }
 
-__global__ __launch_bounds__(256) void rb_keys(RbDev r, const float* __restrict__ pos)
+// the Morton code of the cell of centroid c in `box` (lo.xyz hi.xyz)
+__device__ __forceinline__ uint32_t morton_cell(const float* __restrict__ box, const float* c)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= r.n) return;
-    float c[3];
-    centroid(pos, i, c);
     uint32_t q[3];
     for (int a = 0; a < 3; a++) {
-        const float lo = r.cbox[a], ext = r.cbox[3 + a] - lo;
+        const float lo = box[a], ext = box[3 + a] - lo;
         int v = 0;
         if (ext > 0.f) { v = (int)(((c[a] - lo) / ext) * 1024.0f); if (v > 1023) v = 1023; }
         q[a] = (uint32_t)v;
     }
-    const uint32_t morton = (spread3(q[0]) << 2) | (spread3(q[1]) << 1) | spread3(q[2]);
-    r.keys[i] = ((uint64_t)morton << 32) | (uint32_t)i;
+    return (spread3(q[0]) << 2) | (spread3(q[1]) << 1) | spread3(q[2]);
+}
+
+// kClasses: the cell is taken in the box of the triangle's own class, and the class goes above the Morton code.  Without classes the
+// size test is not evaluated at all: with a fraction of 0 it would call every non-degenerate triangle large.
+template <bool kClasses>
+__global__ __launch_bounds__(256) void rb_keys(RbDev r, const float* __restrict__ pos)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= r.n) return;
+    float b[6], c[3];
+    tri_box(pos, i, b);
+    centroid(b, c);
+    const bool large = kClasses && longest_side(b) > large_bound(r);
+    const float* __restrict__ box = kClasses ? r.class_box + (large ? 8 : 0) : r.cbox;
+    r.keys[i] = ((uint64_t)(large ? 1 : 0) << 62) | ((uint64_t)morton_cell(box, c) << 32) | (uint32_t)i;
 }
 
 __global__ __launch_bounds__(256) void rb_tmap(RbDev r)
@@ -347,97 +448,6 @@ __global__ __launch_bounds__(256) void rb_refs(DynScene s, RbDev r)
     }
 }
 
-// ---- pt_scene_rebuild_tree_ex: two size classes and a depth budget (include/pt_api.h: "Tree rebuild with a depth budget")
-// What only the extended call works in (PtScene::rbx_buf, one block): the partial and the final centroid boxes of the two classes, and
-// its own copy of the read-back words with the report's two counts behind them (they travel with wait 1).
-constexpr int kRxClassPartial = 0, kRxClassBox = ptd::kCoreBlocks * 16 * 4, kRxLevels = kRxClassBox + 16 * 4;
-constexpr int kLvLarge = kLvWords, kLvFlattened = kLvWords + 1, kLvWordsEx = kLvWords + 2;
-constexpr int kRxBytes = kRxLevels + kLvWordsEx * 4;
-
-struct RbEx {
-    float* class_partial;      // kCoreBlocks x 16: small lo.xyz hi.xyz, pad, large lo.xyz hi.xyz, pad
-    float* class_box;          // 16, the same layout
-    float large_fraction;
-};
-
-// the triangle's centroid and the longest side of its own box
-__device__ __forceinline__ float centroid_extent(const float* __restrict__ pos, int prim, float* c)
-{
-    const Tri9 t = load_tri(pos, prim);
-    float ext = 0.f;
-    for (int a = 0; a < 3; a++) {
-        const float mn = min2(t.v0[a], min2(t.v1[a], t.v2[a]));
-        const float mx = max2(t.v0[a], max2(t.v1[a], t.v2[a]));
-        c[a] = 0.5f * (mn + mx);
-        ext = max2(ext, mx - mn);
-    }
-    return ext;
-}
-
-// f * E, E the longest side of the box of all centroids (rb_box_final has written it)
-__device__ __forceinline__ float large_bound(const RbDev& r, float f)
-{
-    const float E = max2(r.cbox[3] - r.cbox[0], max2(r.cbox[4] - r.cbox[1], r.cbox[5] - r.cbox[2]));
-    return f * E;
-}
-
-__global__ __launch_bounds__(256) void rb_class_partial(RbDev r, RbEx x, const float* __restrict__ pos)
-{
-    __shared__ float lds[256][6];
-    __shared__ int n_large;
-    float v[12] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
-    if (threadIdx.x == 0) n_large = 0;
-    const float bound = large_bound(r, x.large_fraction);
-    int mine = 0;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < r.n; i += ptd::kCoreBlocks * 256) {
-        float c[3];
-        const bool large = centroid_extent(pos, i, c) > bound;
-        mine += large ? 1 : 0;
-        for (int a = 0; a < 3; a++) {
-            const float lo_s = large ? v[a] : min2(v[a], c[a]), hi_s = large ? v[3 + a] : max2(v[3 + a], c[a]);
-            const float lo_l = large ? min2(v[6 + a], c[a]) : v[6 + a], hi_l = large ? max2(v[9 + a], c[a]) : v[9 + a];
-            v[a] = lo_s; v[3 + a] = hi_s; v[6 + a] = lo_l; v[9 + a] = hi_l;
-        }
-    }
-    for (int cls = 0; cls < 2; cls++) {      // after block_box only thread 0 reads lds, and only the row it alone writes
-        block_box(v + 6 * cls, lds);
-        if (threadIdx.x == 0) for (int k = 0; k < 6; k++) x.class_partial[blockIdx.x * 16 + cls * 8 + k] = lds[0][k];
-    }
-    if (mine) atomicAdd(&n_large, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && n_large) atomicAdd(&r.levels[kLvLarge], n_large);      // a count: it decides no index
-}
-
-__global__ __launch_bounds__(256) void rb_class_final(RbEx x)
-{
-    __shared__ float lds[256][6];
-    for (int cls = 0; cls < 2; cls++) {
-        float v[6];
-        for (int k = 0; k < 6; k++) v[k] = x.class_partial[threadIdx.x * 16 + cls * 8 + k];      // kCoreBlocks == the block size
-        block_box(v, lds);
-        if (threadIdx.x == 0) for (int k = 0; k < 6; k++) x.class_box[cls * 8 + k] = lds[0][k];
-    }
-}
-
-// rb_keys with the cell taken in the box of the triangle's own class, and the class above the Morton code
-__global__ __launch_bounds__(256) void rb_keys_classes(RbDev r, RbEx x, const float* __restrict__ pos)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= r.n) return;
-    float c[3];
-    const bool large = centroid_extent(pos, i, c) > large_bound(r, x.large_fraction);
-    const float* __restrict__ box = x.class_box + (large ? 8 : 0);
-    uint32_t q[3];
-    for (int a = 0; a < 3; a++) {
-        const float lo = box[a], ext = box[3 + a] - lo;
-        int v = 0;
-        if (ext > 0.f) { v = (int)(((c[a] - lo) / ext) * 1024.0f); if (v > 1023) v = 1023; }
-        q[a] = (uint32_t)v;
-    }
-    const uint32_t morton = (spread3(q[0]) << 2) | (spread3(q[1]) << 1) | spread3(q[2]);
-    r.keys[i] = ((uint64_t)(large ? 1 : 0) << 62) | ((uint64_t)morton << 32) | (uint32_t)i;
-}
-
 __device__ __forceinline__ int clog2(int m) { return 32 - __clz(m - 1); }      // bit length of m - 1, m >= 1
 
 // The depth budget: every sorted triangle finds the topmost ancestor v over more than two triangles with depth(v) + clog2(size(v))
@@ -469,44 +479,15 @@ __global__ __launch_bounds__(256) void rb_rekey(RbDev r, int budget)
     if (threadIdx.x == 0 && total) atomicAdd(&r.levels[kLvFlattened], total);      // a count: it decides no index
 }
 
-// ---- pt_scene_rebuild_tree_opt: treelet restructuring passes over the radix tree (include/pt_api.h: "Tree rebuild with treelet
-// restructuring"; Karras and Aila 2013).  A pass runs between the last rb_karras / rb_depth and the numbering and
+// ---- treelet restructuring passes over the radix tree (include/pt_api.h: "Tree rebuild with treelet restructuring"; DESIGN.md section
+// 25; Karras and Aila 2013).  A pass runs between the last rb_karras / rb_depth and the numbering and
 // rewires `child` / `parent` of interior nodes only: leaves (singletons and internal nodes over two triangles) are never opened, so
 // everything below — rb_depth, rb_height, the scans, rb_emit — runs as it is.  Interior nodes are taken in ascending start-of-pass height,
 // one launch per height; the nodes of one height are roots of disjoint subtrees and a restructure stays inside its root's subtree, so no
 // data passes between workgroups within a launch.
-// What only this call works in (PtScene::rbo_buf, one block): its own copy of the read-back words with the report's four counts behind
-// them, the level offsets of a pass (device only: they steer the per-height launches), a height and a box per raw node.
-constexpr int kTreelet = 7, kOptMaxPasses = 8, kOptPassesDefault = 2;
-constexpr int kOptBlock = 64;        // ro_solve: a workgroup is one wave64, two of the 128 subsets per lane
-constexpr int kOptGrid = 4096;      // one wave per treelet, grid-stride over the level's slice (its size is known on the device only)
-constexpr int kLvRoots = kLvWordsEx, kLvRestructured = kLvWordsEx + 1, kLvWordsOpt = kLvWordsEx + 2;
-constexpr size_t kRoLevels = 0, kRoPassLevels = (size_t)kLvWordsOpt * 4, kRoHeights = (kRoPassLevels + (size_t)kLevelSlots * 4 + 15) / 16 * 16;
-
-struct RbOpt {
-    float* box;          // N x 6: lo.xyz hi.xyz
-    int32_t* hcur;       // N: height now (leaf = 0)
-    int32_t* lvl;        // kLevelSlots: first index of `qsorted` with start-of-pass height >= h
-    int32_t h_lim;       // budget - 1, or -1: the depth of the tree the pass started from (levels[kLvDepth])
-};
-
-__device__ __forceinline__ float box_area(const float* b)      // dyn_area's expression
-{
-    const float d0 = b[3] - b[0], d1 = b[4] - b[1], d2 = b[5] - b[2];
-    return 2.f * (d0 * d1 + d1 * d2 + d2 * d0);
-}
-
-__device__ __forceinline__ void tri_box(const float* __restrict__ pos, int prim, float* b)
-{
-    const Tri9 t = load_tri(pos, prim);
-    for (int a = 0; a < 3; a++) {
-        b[a] = min2(t.v0[a], min2(t.v1[a], t.v2[a]));
-        b[3 + a] = max2(t.v0[a], max2(t.v1[a], t.v2[a]));
-    }
-}
 
 // boxes and heights of the leaves: singletons, and internal nodes over two triangles (rb_depth has written wflag)
-__global__ __launch_bounds__(256) void ro_init(RbDev r, RbOpt o, const float* __restrict__ pos)
+__global__ __launch_bounds__(256) void ro_init(RbDev r, const float* __restrict__ pos)
 {
     const int v = blockIdx.x * 256 + threadIdx.x;
     const int n = r.n, N = 2 * n - 1;
@@ -522,8 +503,8 @@ __global__ __launch_bounds__(256) void ro_init(RbDev r, RbOpt o, const float* __
         tri_box(pos, r.tmap[c.y - (n - 1)].x, b1);
         for (int a = 0; a < 3; a++) { b[a] = min2(b[a], b1[a]); b[3 + a] = max2(b[3 + a], b1[3 + a]); }
     }
-    for (int k = 0; k < 6; k++) o.box[(size_t)v * 6 + k] = b[k];
-    o.hcur[v] = 0;
+    for (int k = 0; k < 6; k++) r.box[(size_t)v * 6 + k] = b[k];
+    r.hcur[v] = 0;
 }
 
 __global__ __launch_bounds__(256) void ro_keys(RbDev r)
@@ -533,134 +514,147 @@ __global__ __launch_bounds__(256) void ro_keys(RbDev r)
     r.key_in[v] = r.wflag[v] ? (uint32_t)r.height[v] : (uint32_t)kDead;
 }
 
-// One wave per interior node of start-of-pass height `level`: the treelet of up to 7 entries below it, the optimal topology over
-// them by dynamic programming over the 127 subsets (two per lane, rounds by subset size), and the rewiring by lane 0.
-__global__ __launch_bounds__(kOptBlock) void ro_solve(RbDev r, RbOpt o, int level)
+// One wave per interior node of start-of-pass height `level`: the treelet of up to 7 entries below it (lane 0), the optimal topology
+// over them by dynamic programming over the 127 subsets (two per lane, rounds by subset size), and the rewiring (lane 0).
+struct Treelet {      // the shared arrays of one workgroup
+    float lbox[kTreelet][6], larea[kTreelet];      // box and area of every entry
+    float sa[128], sc[128];                        // per subset: area of its box, cost of its cheapest topology
+    uint8_t spart[128], sh[128];                   // per subset: one side of its cheapest partition, height of that topology
+    int sL[kTreelet], sI[kTreelet];                // raw nodes: the entries, the interior nodes opened
+    int stS[16], stP[16], stSide[16];              // the rewiring's stack: subset, parent, side
+    int sm;                                        // entries
+};
+
+// box of the entries in S: the lowest first, then ascending (include/pt_api.h fixes the order)
+__device__ __forceinline__ void subset_box(int S, int m, const float (*lbox)[6], float* b)
+{
+    int k = __ffs(S) - 1;
+    for (int j = 0; j < 6; j++) b[j] = lbox[k][j];
+    for (k++; k < m; k++) {
+        if (!((S >> k) & 1)) continue;
+        for (int a = 0; a < 3; a++) { b[a] = min2(b[a], lbox[k][a]); b[3 + a] = max2(b[3 + a], lbox[k][3 + a]); }
+    }
+}
+
+// Lane 0.  Box and height of v from its current children, then the treelet: the interior entry of the largest area is opened until
+// there are 7 entries or none is interior.  Returns v's height; was = the summed area of the opened nodes.
+__device__ __forceinline__ int ro_form(const RbDev& r, Treelet& t, int v, float& was)
+{
+    const int2 c = r.child[v];
+    float bv[6];
+    for (int k = 0; k < 6; k++) { t.lbox[0][k] = r.box[(size_t)c.x * 6 + k]; t.lbox[1][k] = r.box[(size_t)c.y * 6 + k]; }
+    for (int a = 0; a < 3; a++) { bv[a] = min2(t.lbox[0][a], t.lbox[1][a]); bv[3 + a] = max2(t.lbox[0][3 + a], t.lbox[1][3 + a]); }
+    for (int k = 0; k < 6; k++) r.box[(size_t)v * 6 + k] = bv[k];
+    const int hl = r.hcur[c.x], hr = r.hcur[c.y];
+    const int hv = 1 + (hl > hr ? hl : hr);
+    r.hcur[v] = hv;
+    t.sL[0] = c.x; t.sL[1] = c.y;
+    t.larea[0] = box_area(t.lbox[0]); t.larea[1] = box_area(t.lbox[1]);
+    int m = 2, ni = 0;
+    while (m < kTreelet) {
+        int pick = -1;
+        for (int k = 0; k < m; k++)
+            if (rb_is_interior(r, t.sL[k]) && (pick < 0 || t.larea[k] > t.larea[pick])) pick = k;
+        if (pick < 0) break;
+        const int e = t.sL[pick];
+        was = ni == 0 ? t.larea[pick] : was + t.larea[pick];
+        t.sI[ni++] = e;
+        const int2 ec = r.child[e];
+        for (int k = 0; k < 6; k++) { t.lbox[pick][k] = r.box[(size_t)ec.x * 6 + k]; t.lbox[m][k] = r.box[(size_t)ec.y * 6 + k]; }
+        t.sL[pick] = ec.x; t.sL[m] = ec.y;
+        t.larea[pick] = box_area(t.lbox[pick]); t.larea[m] = box_area(t.lbox[m]);
+        m++;
+    }
+    for (int k = 0; k < m; k++) t.sh[1 << k] = (uint8_t)r.hcur[t.sL[k]];
+    t.sm = m;
+    return hv;
+}
+
+// The wave.  Areas of all subsets, then the cheapest partition of each by rounds of subset size.
+__device__ __forceinline__ void ro_cheapest(Treelet& t, int m, int lane)
+{
+    const int full = (1 << m) - 1;
+    for (int S = lane; S <= full; S += kOptBlock) {
+        if (S == 0) continue;
+        float b[6];
+        subset_box(S, m, t.lbox, b);
+        t.sa[S] = box_area(b);
+        if ((S & (S - 1)) == 0) t.sc[S] = 0.f;
+    }
+    __syncthreads();
+    for (int size = 2; size <= m; size++) {
+        for (int S = lane; S <= full; S += kOptBlock) {
+            if (__popc(S) != size) continue;
+            const int low = S & -S, rest = S ^ low;
+            int bp = low, sub = (0 - rest) & rest;
+            float best = t.sc[low] + t.sc[rest];
+            while (sub != rest) {      // P = low | sub ascends with sub; a later P only where strictly cheaper
+                const int P = low | sub;
+                const float cand = t.sc[P] + t.sc[S ^ P];
+                if (cand < best) { best = cand; bp = P; }
+                sub = (sub - rest) & rest;
+            }
+            t.spart[S] = (uint8_t)bp;
+            t.sc[S] = (S == full ? 0.f : t.sa[S]) + best;
+            const int h0 = t.sh[bp], h1 = t.sh[S ^ bp];
+            t.sh[S] = (uint8_t)(1 + (h0 > h1 ? h0 : h1));
+        }
+        __syncthreads();
+    }
+}
+
+// Lane 0.  Accepted where cheaper, and no deeper than the budget (or than the tree was) allows; then rewired in pre-order, the nodes of
+// I handed out as the subsets of two or more entries are met.  Returns whether v's treelet was restructured.
+__device__ __forceinline__ bool ro_rewire(const RbDev& r, Treelet& t, int v, int m, int hv, float was)
+{
+    const int full = (1 << m) - 1;
+    const int room = (r.h_lim >= 0 ? r.h_lim : r.levels[kLvDepth]) - r.depth[v];
+    if (!(t.sc[full] < was && (int)t.sh[full] <= (hv > room ? hv : room))) return false;
+    int sp = 0, nxt = 0;
+    t.stS[0] = full; t.stP[0] = -1; t.stSide[0] = 0; sp = 1;
+    while (sp > 0) {
+        sp--;
+        const int S = t.stS[sp], pid = t.stP[sp], side = t.stSide[sp];
+        const bool single = (S & (S - 1)) == 0;
+        const int node = single ? t.sL[31 - __clz(S)] : pid < 0 ? v : t.sI[nxt++];
+        if (pid >= 0) {
+            reinterpret_cast<int32_t*>(&r.child[pid])[side] = node;
+            r.parent[node] = pid;
+        }
+        if (single) continue;
+        r.hcur[node] = t.sh[S];
+        if (pid >= 0) {
+            float b[6];
+            subset_box(S, m, t.lbox, b);
+            for (int k = 0; k < 6; k++) r.box[(size_t)node * 6 + k] = b[k];
+        }
+        const int P = t.spart[S];
+        t.stS[sp] = S ^ P; t.stP[sp] = node; t.stSide[sp] = 1; sp++;
+        t.stS[sp] = P; t.stP[sp] = node; t.stSide[sp] = 0; sp++;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(kOptBlock) void ro_solve(RbDev r, int level)
 {
     static_assert(kOptBlock == 64 && (1 << kTreelet) == 2 * kOptBlock, "the subsets of a treelet are dealt two per lane of one wave64");
-    __shared__ float lbox[kTreelet][6];
-    __shared__ float larea[kTreelet];
-    __shared__ float sa[128], sc[128];
-    __shared__ uint8_t spart[128], sh[128];
-    __shared__ int sL[kTreelet], sI[kTreelet], stS[16], stP[16], stSide[16];
-    __shared__ int sm;
+    __shared__ Treelet t;
     const int lane = threadIdx.x;
-    const int first = o.lvl[level], last = o.lvl[level + 1];
+    const int first = r.lvl[level], last = r.lvl[level + 1];
     int roots = 0, done = 0;
     for (int idx = first + (int)blockIdx.x; idx < last; idx += (int)gridDim.x) {
         __syncthreads();      // the treelet before is done with the shared arrays
         const int v = r.qsorted[idx];
         int hv = 0;
         float was = 0.f;
-        if (lane == 0) {
-            // 1: box and height of v from its current children
-            const int2 c = r.child[v];
-            float bv[6];
-            for (int k = 0; k < 6; k++) { lbox[0][k] = o.box[(size_t)c.x * 6 + k]; lbox[1][k] = o.box[(size_t)c.y * 6 + k]; }
-            for (int a = 0; a < 3; a++) { bv[a] = min2(lbox[0][a], lbox[1][a]); bv[3 + a] = max2(lbox[0][3 + a], lbox[1][3 + a]); }
-            for (int k = 0; k < 6; k++) o.box[(size_t)v * 6 + k] = bv[k];
-            const int hl = o.hcur[c.x], hr = o.hcur[c.y];
-            hv = 1 + (hl > hr ? hl : hr);
-            o.hcur[v] = hv;
-            // 2: the treelet
-            sL[0] = c.x; sL[1] = c.y;
-            larea[0] = box_area(lbox[0]); larea[1] = box_area(lbox[1]);
-            int m = 2, ni = 0;
-            while (m < kTreelet) {
-                int pick = -1;
-                for (int k = 0; k < m; k++)
-                    if (rb_is_interior(r, sL[k]) && (pick < 0 || larea[k] > larea[pick])) pick = k;
-                if (pick < 0) break;
-                const int e = sL[pick];
-                was = ni == 0 ? larea[pick] : was + larea[pick];
-                sI[ni++] = e;
-                const int2 ec = r.child[e];
-                for (int k = 0; k < 6; k++) { lbox[pick][k] = o.box[(size_t)ec.x * 6 + k]; lbox[m][k] = o.box[(size_t)ec.y * 6 + k]; }
-                sL[pick] = ec.x; sL[m] = ec.y;
-                larea[pick] = box_area(lbox[pick]); larea[m] = box_area(lbox[m]);
-                m++;
-            }
-            for (int k = 0; k < m; k++) sh[1 << k] = (uint8_t)o.hcur[sL[k]];
-            sm = m;
-        }
+        if (lane == 0) hv = ro_form(r, t, v, was);
         __syncthreads();
-        const int m = sm;
+        const int m = t.sm;
         if (m < 3) continue;
-        const int full = (1 << m) - 1;
-        // 3: areas of all subsets, then the cheapest partition of each by rounds of subset size
-        for (int S = lane; S <= full; S += kOptBlock) {
-            if (S == 0) continue;
-            float b[6];
-            bool any = false;
-            for (int k = 0; k < m; k++) {
-                if (!((S >> k) & 1)) continue;
-                for (int a = 0; a < 3; a++) {
-                    b[a] = any ? min2(b[a], lbox[k][a]) : lbox[k][a];
-                    b[3 + a] = any ? max2(b[3 + a], lbox[k][3 + a]) : lbox[k][3 + a];
-                }
-                any = true;
-            }
-            sa[S] = box_area(b);
-            if ((S & (S - 1)) == 0) sc[S] = 0.f;
-        }
-        __syncthreads();
-        for (int size = 2; size <= m; size++) {
-            for (int S = lane; S <= full; S += kOptBlock) {
-                if (__popc(S) != size) continue;
-                const int low = S & -S, rest = S ^ low;
-                int bp = low, sub = (0 - rest) & rest;
-                float best = sc[low] + sc[rest];
-                while (sub != rest) {      // P = low | sub ascends with sub; a later P only where strictly cheaper
-                    const int P = low | sub;
-                    const float cand = sc[P] + sc[S ^ P];
-                    if (cand < best) { best = cand; bp = P; }
-                    sub = (sub - rest) & rest;
-                }
-                spart[S] = (uint8_t)bp;
-                sc[S] = (S == full ? 0.f : sa[S]) + best;
-                const int h0 = sh[bp], h1 = sh[S ^ bp];
-                sh[S] = (uint8_t)(1 + (h0 > h1 ? h0 : h1));
-            }
-            __syncthreads();
-        }
+        ro_cheapest(t, m, lane);
         if (lane == 0) {      // the other lanes go on to the barrier at the top of the loop: every barrier is reached by the whole workgroup
-            // 4: cheaper, and no deeper than the budget (or than the tree was) allows
             roots++;
-            const int room = (o.h_lim >= 0 ? o.h_lim : r.levels[kLvDepth]) - r.depth[v];
-            if (sc[full] < was && (int)sh[full] <= (hv > room ? hv : room)) {
-                done++;
-                // 5: rewire in pre-order; the nodes of I are handed out as the subsets of two or more entries are met
-                int sp = 0, nxt = 0;
-                stS[0] = full; stP[0] = -1; stSide[0] = 0; sp = 1;
-                while (sp > 0) {
-                    sp--;
-                    const int S = stS[sp], pid = stP[sp], side = stSide[sp];
-                    const bool single = (S & (S - 1)) == 0;
-                    const int node = single ? sL[31 - __clz(S)] : pid < 0 ? v : sI[nxt++];
-                    if (pid >= 0) {
-                        reinterpret_cast<int32_t*>(&r.child[pid])[side] = node;
-                        r.parent[node] = pid;
-                    }
-                    if (single) continue;
-                    o.hcur[node] = sh[S];
-                    if (pid >= 0) {
-                        float b[6];
-                        bool any = false;
-                        for (int k = 0; k < m; k++) {
-                            if (!((S >> k) & 1)) continue;
-                            for (int a = 0; a < 3; a++) {
-                                b[a] = any ? min2(b[a], lbox[k][a]) : lbox[k][a];
-                                b[3 + a] = any ? max2(b[3 + a], lbox[k][3 + a]) : lbox[k][3 + a];
-                            }
-                            any = true;
-                        }
-                        for (int k = 0; k < 6; k++) o.box[(size_t)node * 6 + k] = b[k];
-                    }
-                    const int P = spart[S];
-                    stS[sp] = S ^ P; stP[sp] = node; stSide[sp] = 1; sp++;
-                    stS[sp] = P; stP[sp] = node; stSide[sp] = 0; sp++;
-                }
-            }
+            done += ro_rewire(r, t, v, m, hv, was) ? 1 : 0;
         }
     }
     if (lane == 0) {      // counts: they decide no index
@@ -671,266 +665,213 @@ __global__ __launch_bounds__(kOptBlock) void ro_solve(RbDev r, RbOpt o, int leve
 
 inline unsigned blocks_of(int n) { return (unsigned)((n + 255) / 256); }
 
-// temporary storage of the largest of the rocPRIM calls below (sizes only: nothing is launched with a null storage pointer)
-hipError_t rocprim_temp_bytes(int n, size_t& bytes)
+// ---- rocPRIM: the temporary storage of the largest call of a build, and of the sort over all 64 key bits where that asks for more
+// (sizes only: nothing is launched with a null storage pointer).  temp64 = 0: `temp` serves that sort too.
+hipError_t rocprim_temp_bytes(int n, size_t& temp, size_t& temp64)
 {
     const int N = 2 * n - 1;
-    size_t b = 0;
-    bytes = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, n, 0, 62);
+    size_t b[4] = {};
+    hipError_t e = rocprim::radix_sort_keys(nullptr, b[0], (uint64_t*)nullptr, (uint64_t*)nullptr, n, 0, 62);
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, b[1], (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, N, 0, 8);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, b[2], (int32_t*)nullptr, (int32_t*)nullptr, 0, N, rocprim::plus<int32_t>());
+    if (e == hipSuccess) e = rocprim::radix_sort_keys(nullptr, b[3], (uint64_t*)nullptr, (uint64_t*)nullptr, n, 0, 64);
+    temp = b[0] > b[1] ? (b[0] > b[2] ? b[0] : b[2]) : (b[1] > b[2] ? b[1] : b[2]);
+    temp64 = b[3] > temp ? b[3] : 0;
+    return e;
+}
+
+// A rocPRIM call with its temporary storage: the size is an in/out argument, so every call gets a copy of it.
+struct RbTemp { void* p; size_t bytes; };
+template <class Call> hipError_t with_temp(RbTemp t, Call call) { return call(t.p, t.bytes); }
+
+// key_in (written by `keys`, one thread per item) sorted with a payload, and the level offsets of the sorted keys into `levels`
+hipError_t rb_sort_levels(void (*keys)(RbDev), const RbDev& r, RbTemp temp, int count, int32_t* payload, int32_t* sorted_payload, int32_t* levels, hipStream_t st)
+{
+    hipLaunchKernelGGL(keys, dim3(blocks_of(count)), dim3(256), 0, st, r);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = with_temp(temp, [&](void* p, size_t& b) { return rocprim::radix_sort_pairs(p, b, r.key_in, r.key_out, payload, sorted_payload, count, 0, 8, st); });
     if (e != hipSuccess) return e;
-    bytes = b > bytes ? b : bytes;
-    e = rocprim::radix_sort_pairs(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, N, 0, 8);
-    if (e != hipSuccess) return e;
-    bytes = b > bytes ? b : bytes;
-    e = rocprim::exclusive_scan(nullptr, b, (int32_t*)nullptr, (int32_t*)nullptr, 0, N, rocprim::plus<int32_t>());
-    if (e != hipSuccess) return e;
-    bytes = b > bytes ? b : bytes;
-    return hipSuccess;
+    hipLaunchKernelGGL(rb_level_start, dim3(blocks_of(count)), dim3(256), 0, st, r.key_out, count, levels);
+    return hipGetLastError();
+}
+
+// The depth of every raw node, after the radix tree over `sorted_keys` where that is not NULL.  Every call of a build but its first
+// counts the deepest level anew (the first finds the words as the build's memset left them).
+hipError_t rb_depths(RbDev r, uint64_t* sorted_keys, bool first, hipStream_t st)
+{
+    const int n = r.n;
+    if (!first) {
+        const hipError_t e = hipMemsetAsync(r.levels + kLvDepth, 0, 4, st);
+        if (e != hipSuccess) return e;
+    }
+    if (sorted_keys) {
+        r.sorted = sorted_keys;
+        hipLaunchKernelGGL(rb_karras, dim3(blocks_of(n - 1)), dim3(256), 0, st, r);
+    }
+    hipLaunchKernelGGL(rb_depth, dim3(blocks_of(2 * n - 1)), dim3(256), 0, st, r);
+    return hipGetLastError();
 }
 
 }  // namespace
 
-static_assert(ptd::kCoreBlocks == 256, "rb_box_final reads one partial per thread of a 256-thread block");
+static_assert(ptd::kCoreBlocks == 256, "reduce_partials reads one partial per thread of a 256-thread block");
 
-// The limits of the traversal kernels, as pt_scene_create enforces them.  Host only.
-int pt_tree_limits(const char* who, int depth, int quad_depth)
+// What this call needs and no earlier one allocated (the table's third kind of column).  On a scene's first rebuild also: the arrays
+// and maps whose record count a rebuild may change move into buffers of worst-case size (2 n - 1 builder nodes, n - 1 `nodes` and
+// `quad` records) with their contents.  All of it is built beside the scene and moved in only once every allocation exists (as
+// pt_dyn_prepare does); only the first rebuild waits, for its copies.
+static int rb_prepare(PtScene* s, int needs, hipStream_t st)
 {
-    if (depth > ptd::kStackDepth) {
-        pt_set_error("%s: traversal tree depth %d exceeds the traversal stack (%d)", who, depth, ptd::kStackDepth);
-        return PT_ERR_UNSUPPORTED;
-    }
-    if (3 * quad_depth + 2 > ptk_wf_stack_capacity()) {
-        pt_set_error("%s: 4-wide traversal tree depth %d needs more than the %d stack entries of the traversal kernel", who, quad_depth, ptk_wf_stack_capacity());
-        return PT_ERR_UNSUPPORTED;
-    }
-    return PT_OK;
-}
-
-// First rebuild of a scene: the arrays and maps whose record count a rebuild may change move into buffers of worst-case size
-// (2 n - 1 builder nodes, n - 1 `nodes` and `quad` records) with their contents, and the build's own buffers are allocated.  All
-// of it is built beside the scene and moved in only once every allocation exists (as pt_dyn_prepare does).
-static int rb_prepare(PtScene* s, hipStream_t st)
-{
-    if (s->rb_ready) return PT_OK;
+    const bool first = !s->rb_ready;
     const size_t n = (size_t)s->dyn.n_tris, N = 2 * n - 1, I = n > 1 ? n - 1 : 1;
-    size_t temp = 0;
-    HIPCHK(rocprim_temp_bytes((int)n, temp));
+    size_t temp_bytes = s->rb_temp_bytes, temp64_bytes = s->rb_temp64_bytes;
+    if (first) HIPCHK(rocprim_temp_bytes((int)n, temp_bytes, temp64_bytes));
+#define X(T, name, count, need) {(size_t)(count) * sizeof(T), need},
+    const struct { size_t bytes; int need; } plan[kRbSlots] = {RB_WORKSPACE(X)};
+#undef X
     struct { DevBuf* live; size_t bytes; } grow[] = {
         {&s->arr[kArrNodes], I * 64}, {&s->arr[kArrQuad], I * 64}, {&s->dyn_buf[kDynBn], N * 16}, {&s->dyn_buf[kDynOrder], N * 4},
         {&s->dyn_buf[kDynWideBn], I * 8}, {&s->dyn_buf[kDynQuadBn], I * 16}, {&s->dyn_buf[kDynBbox], N * 32},
         {&s->dyn_buf[kDynAreaPartial], ((N + kAreaBlock - 1) / kAreaBlock) * 8}};
     constexpr int kGrow = (int)(sizeof(grow) / sizeof(grow[0]));
-    const size_t plan[kRbAllocs] = {n * 4, (size_t)ptd::kCoreBlocks * 32, 32, n * 8, n * 8, I * 8, I * 8, N * 4, N * 4, N * 4, N * 4, N * 4, I * 4, I * 4,
-                                    N * 4, N * 4, I * 4, I * 4, I * 4, (size_t)kLvWords * 4, temp,
-                                    N * 16, N * 4, I * 8, I * 16, n * 8, I * 8, I * 16};
-    DevBuf fresh[kGrow], mine[kRbAllocs];
+    DevBuf fresh[kGrow], mine[kRbSlots];
     int64_t bytes = 0;
-    for (int k = 0; k < kGrow; k++) {
+    for (int k = 0; first && k < kGrow; k++) {
         HIPCHK(fresh[k].alloc(grow[k].bytes));
         bytes += (int64_t)fresh[k].held() - (int64_t)grow[k].live->held();
         if (grow[k].live->bytes()) HIPCHK(hipMemcpyAsync(fresh[k].as<>(), grow[k].live->as<>(), grow[k].live->bytes(), hipMemcpyDeviceToDevice, st));
     }
-    for (int k = 0; k < kRbAllocs; k++) { HIPCHK(mine[k].alloc(plan[k])); bytes += (int64_t)mine[k].held(); }
-    HIPCHK(hipStreamSynchronize(st));      // the copies are done, and so is whatever the stream still read from the old blocks
-    for (int k = 0; k < kGrow; k++) *grow[k].live = std::move(fresh[k]);      // the old blocks are freed with `fresh`
-    for (int k = 0; k < kRbAllocs; k++) s->rb_buf[k] = std::move(mine[k]);
+    for (int k = 0; k < kRbSlots; k++) {
+        if (!(plan[k].need & needs) || !plan[k].bytes || (!first && s->rb_buf[k])) continue;
+        HIPCHK(mine[k].alloc(plan[k].bytes));
+        bytes += (int64_t)mine[k].held();
+    }
+    if (first) {
+        HIPCHK(hipStreamSynchronize(st));      // the copies are done, and so is whatever the stream still read from the old blocks
+        for (int k = 0; k < kGrow; k++) *grow[k].live = std::move(fresh[k]);      // the old blocks are freed with `fresh`
+        s->rb_buf.resize(kRbSlots);
+    }
+    for (int k = 0; k < kRbSlots; k++) if (mine[k]) s->rb_buf[k] = std::move(mine[k]);
     s->bytes += bytes;
-    s->rb_temp_bytes = temp;
+    if (!first) return PT_OK;
+    s->rb_temp_bytes = temp_bytes; s->rb_temp64_bytes = temp64_bytes;
     ptd::DynScene& d = s->dyn;
     s->dev.nodes = d.nodes = s->arr[kArrNodes].as<float4>(); s->dev.quad = d.quad = s->arr[kArrQuad].as<uint4>();
     d.bn = s->dyn_buf[kDynBn].as<const int4>(); d.order = s->dyn_buf[kDynOrder].as<const int32_t>(); d.wide_bn = s->dyn_buf[kDynWideBn].as<const int2>();
     d.quad_bn = s->dyn_buf[kDynQuadBn].as<const int4>(); d.bbox = s->dyn_buf[kDynBbox].as<float4>(); d.area_partial = s->dyn_buf[kDynAreaPartial].as<double>();
     // prim -> reference leaf: the assignment defines the result and never changes
     RbDev r{};
-    r.prim_leaf = s->rb_buf[kRbPrimLeaf].as<int32_t>();
+    r.prim_leaf = s->rb_buf[kRb_prim_leaf].as<int32_t>();
     hipLaunchKernelGGL(rb_prim_leaf, dim3(blocks_of(d.n_leaves)), dim3(256), 0, st, d, r);
     HIPCHK(hipGetLastError());
     s->rb_ready = true;
     return PT_OK;
 }
 
-// First extended rebuild of a scene: the block only pt_scene_rebuild_tree_ex works in, and temporary storage of its own where the
-// sort over all 64 key bits asks for more than the build's has.  pt_scene_rebuild_tree never allocates either.
-static int rbx_prepare(PtScene* s)
+static RbDev rb_args(const PtScene* s, const RbParams& p)
 {
-    if (s->rbx_buf) return PT_OK;
-    size_t b64 = 0;
-    HIPCHK(rocprim::radix_sort_keys(nullptr, b64, (uint64_t*)nullptr, (uint64_t*)nullptr, s->dyn.n_tris, 0, 64));
-    DevBuf block, temp;
-    HIPCHK(block.alloc(kRxBytes));
-    if (b64 > s->rb_temp_bytes) HIPCHK(temp.alloc(b64));
-    s->bytes += (int64_t)block.held() + (int64_t)temp.held();
-    s->rbx_buf = std::move(block);
-    s->rbx_temp = std::move(temp);
-    return PT_OK;
-}
-
-// First optimised rebuild of a scene: the block only pt_scene_rebuild_tree_opt works in (28 bytes per raw node and 1.6 KB).  The two
-// older calls never allocate it.
-static size_t rbo_bytes(size_t n) { return kRoHeights + (2 * n - 1) * 4 + (2 * n - 1) * 24; }
-
-static int rbo_prepare(PtScene* s)
-{
-    if (s->rbo_buf) return PT_OK;
-    DevBuf block;
-    HIPCHK(block.alloc(rbo_bytes((size_t)s->dyn.n_tris)));
-    s->bytes += (int64_t)block.held();
-    s->rbo_buf = std::move(block);
-    return PT_OK;
-}
-
-static RbDev rb_args(PtScene* s)
-{
-    DevBuf* b = s->rb_buf;
     RbDev r;
-    r.prim_leaf = b[kRbPrimLeaf].as<int32_t>(); r.box_partial = b[kRbBoxPartial].as<float>(); r.cbox = b[kRbCbox].as<float>();
-    r.keys = b[kRbKeys].as<uint64_t>(); r.sorted = b[kRbSorted].as<uint64_t>(); r.child = b[kRbChild].as<int2>(); r.range = b[kRbRange].as<int2>();
-    r.parent = b[kRbParent].as<int32_t>(); r.depth = b[kRbDepth].as<int32_t>(); r.height = b[kRbHeight].as<int32_t>(); r.live = b[kRbLive].as<int32_t>();
-    r.newid = b[kRbNewId].as<int32_t>(); r.wflag = b[kRbWFlag].as<int32_t>(); r.widx = b[kRbWidx].as<int32_t>();
-    r.key_in = b[kRbKeyIn].as<uint32_t>(); r.key_out = b[kRbKeyOut].as<uint32_t>(); r.iota = b[kRbIota].as<int32_t>(); r.qsorted = b[kRbQSorted].as<int32_t>();
-    r.qidx = b[kRbQidx].as<int32_t>(); r.levels = b[kRbLevels].as<int32_t>();
-    r.bn = b[kRbBn].as<int4>(); r.order = b[kRbOrder].as<int32_t>(); r.wide_bn = b[kRbWideBn].as<int2>(); r.quad_bn = b[kRbQuadBn].as<int4>();
-    r.tmap = b[kRbTmap].as<int2>(); r.node_ref = b[kRbNodeRef].as<int2>(); r.quad_ref = b[kRbQuadRef].as<int4>();
+#define X(T, name, count, need) r.name = s->rb_buf[kRb_##name].as<T>();
+    RB_WORKSPACE(X)
+#undef X
     r.n = s->dyn.n_tris;
+    r.large_fraction = p.large_fraction;
+    r.h_lim = p.depth_budget > 0 ? p.depth_budget - 1 : -1;
     return r;
 }
 
-// Enqueues the whole build of the topology into the staging buffers.  Nothing a render reads is written.  x: the extended call
-// (pt_scene_rebuild_tree_ex) with its depth budget, NULL for pt_scene_rebuild_tree.  o: the optimised call
-// (pt_scene_rebuild_tree_opt) with its number of restructuring passes, NULL for the other two.
-static int rb_build(PtScene* s, const RbDev& r, hipStream_t st, const RbEx* x = nullptr, int budget = 0, const RbOpt* o = nullptr, int passes = 0)
+// Enqueues the whole build of the topology into the staging buffers.  Nothing a render reads is written.
+static int rb_build(const PtScene* s, const RbDev& r, const RbParams& p, hipStream_t st)
 {
     const int n = r.n, N = 2 * n - 1;
     const float* pos = s->dyn_buf[kDynPos].as<const float>();
-    void* temp = s->rb_buf[kRbTemp].as<>();
-    size_t tb = s->rb_temp_bytes;
-    if (x) HIPCHK(hipMemsetAsync(r.levels, 0, (size_t)(o ? kLvWordsOpt : kLvWordsEx) * 4, st));      // the report's counts are summed from here on
+    const RbTemp temp{r.temp, s->rb_temp_bytes};
+    const bool classes = p.large_fraction > 0.f;
+    HIPCHK(hipMemsetAsync(r.levels, 0, (size_t)kLvWords * 4, st));      // the counts are summed, and the deepest level is raised, from here on
     hipLaunchKernelGGL(rb_box_partial, dim3(ptd::kCoreBlocks), dim3(256), 0, st, r, pos);
     hipLaunchKernelGGL(rb_box_final, dim3(1), dim3(256), 0, st, r);
-    if (x && x->large_fraction > 0.f) {      // a centroid box per size class; the class is bit 62 of the key
-        hipLaunchKernelGGL(rb_class_partial, dim3(ptd::kCoreBlocks), dim3(256), 0, st, r, *x, pos);
-        hipLaunchKernelGGL(rb_class_final, dim3(1), dim3(256), 0, st, *x);
-        hipLaunchKernelGGL(rb_keys_classes, dim3(blocks_of(n)), dim3(256), 0, st, r, *x, pos);
-        HIPCHK(hipGetLastError());
-        void* temp64 = s->rbx_temp ? s->rbx_temp.as<>() : temp;
-        tb = s->rbx_temp ? s->rbx_temp.bytes() : s->rb_temp_bytes;
-        HIPCHK(rocprim::radix_sort_keys(temp64, tb, r.keys, r.sorted, n, 0, 64, st));
-    } else {
-        hipLaunchKernelGGL(rb_keys, dim3(blocks_of(n)), dim3(256), 0, st, r, pos);
-        HIPCHK(hipGetLastError());
-        HIPCHK(rocprim::radix_sort_keys(temp, tb, r.keys, r.sorted, n, 0, 62, st));
+    if (classes) {      // a centroid box per size class; the class is bit 62 of the key
+        hipLaunchKernelGGL(rb_class_partial, dim3(ptd::kCoreBlocks), dim3(256), 0, st, r, pos);
+        hipLaunchKernelGGL(rb_class_final, dim3(1), dim3(256), 0, st, r);
     }
+    void (*const keys)(RbDev, const float*) = classes ? rb_keys<true> : rb_keys<false>;
+    hipLaunchKernelGGL(keys, dim3(blocks_of(n)), dim3(256), 0, st, r, pos);
+    HIPCHK(hipGetLastError());
+    HIPCHK(with_temp(classes && r.temp64 ? RbTemp{r.temp64, s->rb_temp64_bytes} : temp,
+                     [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, r.keys, r.sorted, n, 0, classes ? 64 : 62, st); }));
     hipLaunchKernelGGL(rb_tmap, dim3(blocks_of(n)), dim3(256), 0, st, r);
     if (n <= 2) {
         hipLaunchKernelGGL(rb_single, dim3(1), dim3(64), 0, st, r);
         HIPCHK(hipGetLastError());
         return PT_OK;
     }
-    if (!x) HIPCHK(hipMemsetAsync(r.levels, 0, (size_t)kLvWords * 4, st));
-    hipLaunchKernelGGL(rb_karras, dim3(blocks_of(n - 1)), dim3(256), 0, st, r);
-    hipLaunchKernelGGL(rb_depth, dim3(blocks_of(N)), dim3(256), 0, st, r);
-    if (budget > 0) {      // flatten what would be deeper than the budget, then the tree over the new keys (they are in `keys`)
-        RbDev again = r;
-        again.sorted = r.keys;
-        hipLaunchKernelGGL(rb_rekey, dim3(blocks_of(n)), dim3(256), 0, st, r, budget);
+    HIPCHK(rb_depths(r, r.sorted, /*first=*/true, st));
+    if (p.depth_budget > 0) {      // flatten what would be deeper than the budget, then the tree over the new keys (they are in `keys`)
+        hipLaunchKernelGGL(rb_rekey, dim3(blocks_of(n)), dim3(256), 0, st, r, p.depth_budget);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemsetAsync(r.levels + kLvDepth, 0, 4, st));
-        hipLaunchKernelGGL(rb_karras, dim3(blocks_of(n - 1)), dim3(256), 0, st, again);
-        hipLaunchKernelGGL(rb_depth, dim3(blocks_of(N)), dim3(256), 0, st, again);
+        HIPCHK(rb_depths(r, r.keys, false, st));
     }
-    if (o && passes > 0) {      // treelet restructuring: per pass the heights, the interior nodes by height, one launch per height, the depths anew
-        const int top = budget > 0 ? budget - 1 : 63;      // no interior node is higher: the tree keeps the budget, and a radix tree over unique keys of at most 63 significant bits is at most 63 deep
-        hipLaunchKernelGGL(ro_init, dim3(blocks_of(N)), dim3(256), 0, st, r, *o, pos);
-        for (int pass = 0; pass < passes; pass++) {
+    if (p.passes > 0) {      // treelet restructuring: per pass the heights, the interior nodes by height, one launch per height, the depths anew
+        const int top = p.depth_budget > 0 ? p.depth_budget - 1 : 63;      // no interior node is higher: the tree keeps the budget, and a radix tree over unique keys of at most 63 significant bits is at most 63 deep
+        hipLaunchKernelGGL(ro_init, dim3(blocks_of(N)), dim3(256), 0, st, r, pos);
+        for (int pass = 0; pass < p.passes; pass++) {
             hipLaunchKernelGGL(rb_height, dim3(blocks_of(N)), dim3(256), 0, st, r);
-            hipLaunchKernelGGL(ro_keys, dim3(blocks_of(n - 1)), dim3(256), 0, st, r);
+            HIPCHK(rb_sort_levels(ro_keys, r, temp, n - 1, r.iota, r.qsorted, r.lvl, st));
+            for (int h = 1; h <= top; h++) hipLaunchKernelGGL(ro_solve, dim3(kOptGrid), dim3(kOptBlock), 0, st, r, h);
             HIPCHK(hipGetLastError());
-            tb = s->rb_temp_bytes;
-            HIPCHK(rocprim::radix_sort_pairs(temp, tb, r.key_in, r.key_out, r.iota, r.qsorted, n - 1, 0, 8, st));
-            hipLaunchKernelGGL(rb_level_start, dim3(blocks_of(n - 1)), dim3(256), 0, st, r.key_out, n - 1, o->lvl);
-            for (int h = 1; h <= top; h++) hipLaunchKernelGGL(ro_solve, dim3(kOptGrid), dim3(kOptBlock), 0, st, r, *o, h);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemsetAsync(r.levels + kLvDepth, 0, 4, st));
-            hipLaunchKernelGGL(rb_depth, dim3(blocks_of(N)), dim3(256), 0, st, r);
+            HIPCHK(rb_depths(r, nullptr, false, st));
         }
     }
     hipLaunchKernelGGL(rb_height, dim3(blocks_of(N)), dim3(256), 0, st, r);
     HIPCHK(hipGetLastError());
     // numbering: builder nodes and `nodes` records by rank, `order` by height, `quad` records by level
-    tb = s->rb_temp_bytes;
-    HIPCHK(rocprim::exclusive_scan(temp, tb, r.live, r.newid, 0, N, rocprim::plus<int32_t>(), st));
-    tb = s->rb_temp_bytes;
-    HIPCHK(rocprim::exclusive_scan(temp, tb, r.wflag, r.widx, 0, n - 1, rocprim::plus<int32_t>(), st));
-    hipLaunchKernelGGL(rb_height_keys, dim3(blocks_of(N)), dim3(256), 0, st, r);
-    tb = s->rb_temp_bytes;
-    HIPCHK(rocprim::radix_sort_pairs(temp, tb, r.key_in, r.key_out, r.newid, r.order, N, 0, 8, st));
-    hipLaunchKernelGGL(rb_level_start, dim3(blocks_of(N)), dim3(256), 0, st, r.key_out, N, r.levels + kLvOrder);
-    hipLaunchKernelGGL(rb_level_keys, dim3(blocks_of(n - 1)), dim3(256), 0, st, r);
-    tb = s->rb_temp_bytes;
-    HIPCHK(rocprim::radix_sort_pairs(temp, tb, r.key_in, r.key_out, r.iota, r.qsorted, n - 1, 0, 8, st));
-    hipLaunchKernelGGL(rb_level_start, dim3(blocks_of(n - 1)), dim3(256), 0, st, r.key_out, n - 1, r.levels + kLvQuad);
+    HIPCHK(with_temp(temp, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, r.live, r.newid, 0, N, rocprim::plus<int32_t>(), st); }));
+    HIPCHK(with_temp(temp, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, r.wflag, r.widx, 0, n - 1, rocprim::plus<int32_t>(), st); }));
+    HIPCHK(rb_sort_levels(rb_height_keys, r, temp, N, r.newid, r.order, r.levels + kLvOrder, st));
+    HIPCHK(rb_sort_levels(rb_level_keys, r, temp, n - 1, r.iota, r.qsorted, r.levels + kLvQuad, st));
     hipLaunchKernelGGL(rb_qidx, dim3(blocks_of(n - 1)), dim3(256), 0, st, r);
     hipLaunchKernelGGL(rb_emit, dim3(blocks_of(N)), dim3(256), 0, st, r);
     HIPCHK(hipGetLastError());
     return PT_OK;
 }
 
-// The rebuild behind the three entry points.  p: the parameters of pt_scene_rebuild_tree_ex (checked by the caller), NULL for
-// pt_scene_rebuild_tree, whose launches, waits and allocations are exactly what they were before the extended call existed.
-// passes >= 0: pt_scene_rebuild_tree_opt (p is not NULL), with its own report; -1 for the other two, which are what they were too.
-static int rb_run(PtScene* s, const char* who, const PtRebuildParams* p, PtRebuildReport* report, hipStream_t st, int passes = -1,
-                  PtRebuildOptReport* opt_report = nullptr)
+// The numbers of a built topology, from the words.
+struct RbTree { int32_t lv[kLvWords]; int n_bn, n_wide, n_quad, top, depth, quad_depth; };
+
+// Wait 1: the words come back, the report is filled, and the tree is checked against the kernels' stack limits.  Nothing a render, a
+// query or an update reads has been written when this refuses.
+static int rb_read_back(const char* who, const RbDev& r, hipStream_t st, RbReport& report, RbTree& t)
 {
-    HIPCHK(hipSetDevice(s->device));
-    int rc;
-    if ((rc = pt_dyn_prepare(s)) != PT_OK) return rc;
-    if ((rc = rb_prepare(s, st)) != PT_OK) return rc;
-    if (p && (rc = rbx_prepare(s)) != PT_OK) return rc;
-    const bool opt = passes >= 0;
-    if (opt && (rc = rbo_prepare(s)) != PT_OK) return rc;
-    RbDev r = rb_args(s);
-    RbEx x{};
-    RbOpt o{};
-    if (p) {
-        char* base = s->rbx_buf.as<char>();
-        x.class_partial = (float*)(base + kRxClassPartial); x.class_box = (float*)(base + kRxClassBox); x.large_fraction = p->large_fraction;
-        r.levels = (int32_t*)(base + kRxLevels);
-    }
-    if (opt) {
-        char* base = s->rbo_buf.as<char>();
-        r.levels = (int32_t*)(base + kRoLevels);
-        o.lvl = (int32_t*)(base + kRoPassLevels); o.hcur = (int32_t*)(base + kRoHeights); o.box = (float*)(base + kRoHeights + (2 * (size_t)r.n - 1) * 4);
-        o.h_lim = p->depth_budget > 0 ? p->depth_budget - 1 : -1;
-    }
-    if ((rc = rb_build(s, r, st, p ? &x : nullptr, p ? p->depth_budget : 0, opt ? &o : nullptr, opt ? passes : 0)) != PT_OK) return rc;
-    // wait 1: the level offsets, the counts and the depths (and, behind them, the two counts of the extended call's report)
-    int32_t lv[kLvWordsOpt] = {};
-    HIPCHK(hipMemcpyAsync(lv, r.levels, (size_t)(opt ? kLvWordsOpt : p ? kLvWordsEx : kLvWords) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(t.lv, r.levels, sizeof(t.lv), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (report) { report->n_large = lv[kLvLarge]; report->n_flattened_tris = lv[kLvFlattened]; }
-    if (opt_report) { opt_report->n_large = lv[kLvLarge]; opt_report->n_flattened_tris = lv[kLvFlattened]; opt_report->n_roots = lv[kLvRoots]; opt_report->n_restructured = lv[kLvRestructured]; }
-    const int n_bn = lv[kLvOrder + kDead], n_quad = lv[kLvQuad + kDead], n_wide = n_bn > 1 ? (n_bn - 1) / 2 : 1;
-    int top = 0, quad_depth = 0;
-    while (lv[kLvOrder + top + 1] < n_bn) top++;                 // heights 0 .. top
-    while (lv[kLvQuad + quad_depth + 1] < n_quad) quad_depth++;      // levels 0 .. quad_depth
-    const int depth = lv[kLvDepth];
-    if ((rc = pt_tree_limits(who, depth, quad_depth)) != PT_OK) return rc;      // nothing a render, a query or an update reads has been written
-    // ---- commit ----
+    report = {t.lv[kLvLarge], t.lv[kLvFlattened], t.lv[kLvRoots], t.lv[kLvRestructured], true};
+    t.n_bn = t.lv[kLvOrder + kDead]; t.n_quad = t.lv[kLvQuad + kDead]; t.n_wide = t.n_bn > 1 ? (t.n_bn - 1) / 2 : 1;
+    t.top = t.quad_depth = 0;
+    while (t.lv[kLvOrder + t.top + 1] < t.n_bn) t.top++;                    // heights 0 .. top
+    while (t.lv[kLvQuad + t.quad_depth + 1] < t.n_quad) t.quad_depth++;      // levels 0 .. quad_depth
+    t.depth = t.lv[kLvDepth];
+    return pt_tree_limits(who, t.depth, t.quad_depth);
+}
+
+// The commit: the staged maps and refs go into the scene, the vertex update's kernels write the boxes, and wait 2 brings the new
+// denominator of pt_scene_tree_inflation.
+static int rb_commit(PtScene* s, const RbDev& r, const RbTree& t, hipStream_t st)
+{
     ptd::DynScene& d = s->dyn;
-    const struct { int dst, src; size_t bytes; } maps[] = {{kDynBn, kRbBn, (size_t)n_bn * 16}, {kDynOrder, kRbOrder, (size_t)n_bn * 4}, {kDynWideBn, kRbWideBn, (size_t)n_wide * 8},
-                                                           {kDynQuadBn, kRbQuadBn, (size_t)n_quad * 16}, {kDynTmap, kRbTmap, (size_t)d.n_tris * 8}};
-    for (const auto& m : maps) HIPCHK(hipMemcpyAsync(s->dyn_buf[m.dst].as<>(), s->rb_buf[m.src].as<>(), m.bytes, hipMemcpyDeviceToDevice, st));
-    d.n_bn = n_bn; d.n_wide = n_wide; d.n_quad = n_quad;
-    s->dev.n_nodes = n_wide; s->dev.n_quad = n_quad; s->dev.quad_depth = quad_depth;
-    s->max_depth = depth;
-    s->dyn_host.level_start.assign(lv + kLvOrder, lv + kLvOrder + top + 2);
-    hipLaunchKernelGGL(rb_refs, dim3(blocks_of(n_wide > n_quad ? n_wide : n_quad)), dim3(256), 0, st, d, r);
+    const struct { int dst; const void* src; size_t bytes; } maps[] = {{kDynBn, r.bn, (size_t)t.n_bn * 16}, {kDynOrder, r.order, (size_t)t.n_bn * 4}, {kDynWideBn, r.wide_bn, (size_t)t.n_wide * 8},
+                                                                        {kDynQuadBn, r.quad_bn, (size_t)t.n_quad * 16}, {kDynTmap, r.tmap, (size_t)d.n_tris * 8}};
+    for (const auto& m : maps) HIPCHK(hipMemcpyAsync(s->dyn_buf[m.dst].as<>(), m.src, m.bytes, hipMemcpyDeviceToDevice, st));
+    d.n_bn = t.n_bn; d.n_wide = t.n_wide; d.n_quad = t.n_quad;
+    s->dev.n_nodes = t.n_wide; s->dev.n_quad = t.n_quad; s->dev.quad_depth = t.quad_depth;
+    s->max_depth = t.depth;
+    s->dyn_host.level_start.assign(t.lv + kLvOrder, t.lv + kLvOrder + t.top + 2);
+    hipLaunchKernelGGL(rb_refs, dim3(blocks_of(t.n_wide > t.n_quad ? t.n_wide : t.n_quad)), dim3(256), 0, st, d, r);
     HIPCHK(hipGetLastError());
     // tri, tripair, every box of `nodes`, origin / scales / quantised boxes of `quad`, from the scene's own positions
-    HIPCHK(pt_dyn_launch_update(d, s->dyn_buf[kDynPos].as<const float>(), nullptr, nullptr, s->dyn_host.level_start.data(), top + 1, /*trees_only=*/true, st));
-    // wait 2: the new denominator of pt_scene_tree_inflation, by the same reduction in the same order
-    s->h_area.assign(((size_t)n_bn + kAreaBlock - 1) / kAreaBlock, 0.0);
+    HIPCHK(pt_dyn_launch_update(d, s->dyn_buf[kDynPos].as<const float>(), nullptr, nullptr, s->dyn_host.level_start.data(), t.top + 1, /*trees_only=*/true, st));
+    // wait 2: by the same reduction in the same order as at upload
+    s->h_area.assign(((size_t)t.n_bn + kAreaBlock - 1) / kAreaBlock, 0.0);
     HIPCHK(pt_dyn_launch_area(d, st));
     HIPCHK(hipMemcpyAsync(s->h_area.data(), d.area_partial, s->h_area.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -941,12 +882,26 @@ static int rb_run(PtScene* s, const char* who, const PtRebuildParams* p, PtRebui
     return PT_OK;
 }
 
+// The rebuild behind the three entry points, which have checked p.
+static int rb_run(PtScene* s, const char* who, const RbParams& p, RbReport& report, hipStream_t st)
+{
+    HIPCHK(hipSetDevice(s->device));
+    int rc;
+    if ((rc = pt_dyn_prepare(s)) != PT_OK) return rc;
+    if ((rc = rb_prepare(s, kAlways | (p.large_fraction > 0.f ? kClasses : 0) | (p.passes > 0 ? kPasses : 0), st)) != PT_OK) return rc;
+    const RbDev r = rb_args(s, p);
+    RbTree t;
+    if ((rc = rb_build(s, r, p, st)) != PT_OK || (rc = rb_read_back(who, r, st, report, t)) != PT_OK) return rc;
+    return rb_commit(s, r, t, st);
+}
+
 extern "C" {
 
 int pt_scene_rebuild_tree(PtScene* s, void* hip_stream)
 {
     if (!s) { pt_set_error("pt_scene_rebuild_tree: NULL scene"); return PT_ERR_INVALID; }
-    return rb_run(s, "pt_scene_rebuild_tree", nullptr, nullptr, (hipStream_t)hip_stream);
+    RbReport rep{};
+    return rb_run(s, "pt_scene_rebuild_tree", RbParams{0, 0.f, 0}, rep, (hipStream_t)hip_stream);
 }
 
 void pt_rebuild_params_default(PtRebuildParams* p)
@@ -986,7 +941,10 @@ int pt_scene_rebuild_tree_ex(PtScene* s, const PtRebuildParams* p, PtRebuildRepo
     const char* who = "pt_scene_rebuild_tree_ex";
     int rc;
     if ((rc = rb_check_params(who, s, p)) != PT_OK || (rc = rb_check_budget(who, s, p)) != PT_OK) return rc;
-    return rb_run(s, who, p, report, (hipStream_t)hip_stream);
+    RbReport rep{};
+    rc = rb_run(s, who, RbParams{p->depth_budget, p->large_fraction, 0}, rep, (hipStream_t)hip_stream);
+    if (report && rep.known) { report->n_large = rep.n_large; report->n_flattened_tris = rep.n_flattened_tris; }
+    return rc;
 }
 
 int32_t pt_rebuild_opt_passes_default(void) { return kOptPassesDefault; }
@@ -1001,21 +959,10 @@ int pt_scene_rebuild_tree_opt(PtScene* s, const PtRebuildParams* p, int32_t pass
         return PT_ERR_INVALID;
     }
     if ((rc = rb_check_budget(who, s, p)) != PT_OK) return rc;
-    return rb_run(s, who, p, nullptr, (hipStream_t)hip_stream, passes, report);
-}
-
-int pt_scene_tree_info(const PtScene* s, PtTreeInfo* out)
-{
-    if (!s || !out) { pt_set_error("pt_scene_tree_info: NULL %s", !s ? "scene" : "out"); return PT_ERR_INVALID; }
-    out->n_wide = s->dev.n_nodes; out->n_quad = s->dev.n_quad; out->depth = s->max_depth; out->quad_depth = s->dev.quad_depth; out->rebuilds = s->rebuilds;
-    return PT_OK;
-}
-
-int pt_dbg_tree_limits(int32_t depth, int32_t quad_depth, int32_t* max_depth, int32_t* max_quad_depth)
-{
-    if (max_depth) *max_depth = ptd::kStackDepth;
-    if (max_quad_depth) *max_quad_depth = (ptk_wf_stack_capacity() - 2) / 3;
-    return pt_tree_limits("pt_dbg_tree_limits", depth, quad_depth);
+    RbReport rep{};
+    rc = rb_run(s, who, RbParams{p->depth_budget, p->large_fraction, passes}, rep, (hipStream_t)hip_stream);
+    if (report && rep.known) { report->n_large = rep.n_large; report->n_flattened_tris = rep.n_flattened_tris; report->n_roots = rep.n_roots; report->n_restructured = rep.n_restructured; }
+    return rc;
 }
 
 }  // extern "C"

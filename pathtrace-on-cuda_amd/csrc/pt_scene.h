@@ -15,12 +15,6 @@ constexpr int kMatBlock = 256;      // triangles per block of the material updat
 enum DynAlloc { kDynBn, kDynOrder, kDynWideBn, kDynQuadBn, kDynLeafRange, kDynTmap, kDynLightPrim, kDynSmall, kDynPos,
                 kDynBbox, kDynMaxabs, kDynCorePartial, kDynAreaPartial, kDynMatPartial, kDynAllocs };
 
-// The allocations of the first tree rebuild (pt_rebuild.hip: rb_prepare), in the order of its plan: what the build works in, the
-// rocPRIM temporary storage, then the staged maps and refs.
-enum RbAlloc { kRbPrimLeaf, kRbBoxPartial, kRbCbox, kRbKeys, kRbSorted, kRbChild, kRbRange, kRbParent, kRbDepth, kRbHeight, kRbLive, kRbNewId, kRbWFlag, kRbWidx,
-               kRbKeyIn, kRbKeyOut, kRbIota, kRbQSorted, kRbQidx, kRbLevels, kRbTemp,
-               kRbBn, kRbOrder, kRbWideBn, kRbQuadBn, kRbTmap, kRbNodeRef, kRbQuadRef, kRbAllocs };
-
 struct PtScene {
     int device = 0;
     ptd::DevScene dev{};
@@ -67,12 +61,11 @@ struct PtScene {
     bool updated = false;
     std::vector<double> h_area;          // host image of dyn.area_partial
     // ---- tree rebuild (pt_scene_rebuild_tree, csrc/pt_rebuild.hip) ----
-    DevBuf rb_buf[kRbAllocs];            // allocated by the first rebuild, worst case: later rebuilds allocate nothing
-    size_t rb_temp_bytes = 0;            // size of kRbTemp, the rocPRIM temporary storage (queried once)
+    std::vector<DevBuf> rb_buf;          // the build's workspace, one slot per line of pt_rebuild.hip's table, worst case: a rebuild allocates what its
+                                         // parameters need and no earlier call did (rb_prepare)
+    size_t rb_temp_bytes = 0, rb_temp64_bytes = 0;      // rocPRIM's temporary storage (queried once); the second is 0 where the first serves the 64-bit sort too
     bool rb_ready = false;
     int rebuilds = 0;
-    DevBuf rbx_buf, rbx_temp;            // pt_scene_rebuild_tree_ex alone: its class boxes and read-back words; its sort's storage where kRbTemp is too small
-    DevBuf rbo_buf;                      // pt_scene_rebuild_tree_opt alone: its read-back words, the level offsets of a pass, a height and a box per raw node
     // ---- materials and lights (pt_scene_update_materials, csrc/pt_material.hip) ----
     bool tri_emit_ok = true;             // emittance_ok's test over the triangles alone, from pt_scene_create or the last material update (the spheres' part: h_spheres)
     int32_t* h_mat = nullptr;            // pinned, 2 words: the light count and the flag a material update reads back (pt_dyn_prepare)
@@ -99,5 +92,5 @@ hipError_t pt_dyn_launch_update(const ptd::DynScene& s, const float* d_pos, cons
                                 bool trees_only, hipStream_t stream);
 // pt_dynamic.hip: enqueues dyn_area, the block sums of the box areas of all n_bn builder nodes into s.area_partial
 hipError_t pt_dyn_launch_area(const ptd::DynScene& s, hipStream_t stream);
-// pt_rebuild.hip: the stack limits of the traversal kernels (host only): PT_OK, or PT_ERR_UNSUPPORTED with the error text set
+// pt_scene.hip: the stack limits of the traversal kernels (host only): PT_OK, or PT_ERR_UNSUPPORTED with the error text set
 int pt_tree_limits(const char* who, int depth, int quad_depth);

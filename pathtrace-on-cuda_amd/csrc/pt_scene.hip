@@ -188,6 +188,20 @@ static void apply_defaults(PtScene* sc, int32_t n_tris, bool emitOk)
     sc->dev.nee_prune = (emitOk && pt_prune_allowed()) ? 1 : 0;
 }
 
+// The limits of the traversal kernels, for the tree of an upload and for a rebuilt one alike.  Host only.
+int pt_tree_limits(const char* who, int depth, int quad_depth)
+{
+    if (depth > ptd::kStackDepth) {
+        pt_set_error("%s: traversal tree depth %d exceeds the traversal stack (%d)", who, depth, ptd::kStackDepth);
+        return PT_ERR_UNSUPPORTED;
+    }
+    if (3 * quad_depth + 2 > ptk_wf_stack_capacity()) {
+        pt_set_error("%s: 4-wide traversal tree depth %d needs more than the %d stack entries of the traversal kernel", who, quad_depth, ptk_wf_stack_capacity());
+        return PT_ERR_UNSUPPORTED;
+    }
+    return PT_OK;
+}
+
 extern "C" {
 
 int pt_scene_create(const PtBVHNode* nodes, int32_t n_nodes, const PtTriangle* tris, int32_t n_tris,
@@ -260,6 +274,20 @@ void pt_scene_destroy(PtScene* s)
 
 int32_t pt_scene_num_lights(const PtScene* s) { return s ? s->n_lights : 0; }
 int64_t pt_scene_device_bytes(const PtScene* s) { return s ? s->bytes : 0; }
+
+int pt_scene_tree_info(const PtScene* s, PtTreeInfo* out)
+{
+    if (!s || !out) { pt_set_error("pt_scene_tree_info: NULL %s", !s ? "scene" : "out"); return PT_ERR_INVALID; }
+    out->n_wide = s->dev.n_nodes; out->n_quad = s->dev.n_quad; out->depth = s->max_depth; out->quad_depth = s->dev.quad_depth; out->rebuilds = s->rebuilds;
+    return PT_OK;
+}
+
+int pt_dbg_tree_limits(int32_t depth, int32_t quad_depth, int32_t* max_depth, int32_t* max_quad_depth)
+{
+    if (max_depth) *max_depth = ptd::kStackDepth;
+    if (max_quad_depth) *max_quad_depth = (ptk_wf_stack_capacity() - 2) / 3;
+    return pt_tree_limits("pt_dbg_tree_limits", depth, quad_depth);
+}
 
 int64_t pt_dbg_scene_array(PtScene* s, int32_t which, void* h_out, int64_t cap_bytes)
 {

@@ -232,6 +232,17 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _rebuild_params(depth_budget, large_fraction):
+    """PtRebuildParams of the two optional arguments of Scene.rebuild_tree / rebuild_tree_optimized: a None takes its default."""
+    prm = PtRebuildParams()
+    lib().pt_rebuild_params_default(C.byref(prm))
+    if depth_budget is not None:
+        prm.depth_budget = depth_budget
+    if large_fraction is not None:
+        prm.large_fraction = large_fraction
+    return prm
+
+
 def default_params(**kw):
     p = PtParams()
     lib().pt_params_default(C.byref(p))
@@ -651,12 +662,7 @@ class Scene:
         pt_rebuild_params_default) and returns its report as a dict: n_large, n_flattened_tris."""
         if depth_budget is None and large_fraction is None:
             return _check(lib().pt_scene_rebuild_tree(self._h, C.c_void_p(stream_ptr)), "pt_scene_rebuild_tree")
-        prm, report = PtRebuildParams(), PtRebuildReport()
-        lib().pt_rebuild_params_default(C.byref(prm))
-        if depth_budget is not None:
-            prm.depth_budget = depth_budget
-        if large_fraction is not None:
-            prm.large_fraction = large_fraction
+        prm, report = _rebuild_params(depth_budget, large_fraction), PtRebuildReport()
         _check(lib().pt_scene_rebuild_tree_ex(self._h, C.byref(prm), C.byref(report), C.c_void_p(stream_ptr)), "pt_scene_rebuild_tree_ex")
         return {name: int(getattr(report, name)) for name, _ in PtRebuildReport._fields_}
 
@@ -664,12 +670,7 @@ class Scene:
         """rebuild_tree with a depth budget and size classes, then `passes` treelet restructuring passes by surface area
         (include/pt_api.h: pt_scene_rebuild_tree_opt).  A None takes its default (pt_rebuild_opt_passes_default,
         pt_rebuild_params_default).  Returns the report as a dict: n_large, n_flattened_tris, n_roots, n_restructured."""
-        prm, report = PtRebuildParams(), PtRebuildOptReport()
-        lib().pt_rebuild_params_default(C.byref(prm))
-        if depth_budget is not None:
-            prm.depth_budget = depth_budget
-        if large_fraction is not None:
-            prm.large_fraction = large_fraction
+        prm, report = _rebuild_params(depth_budget, large_fraction), PtRebuildOptReport()
         if passes is None:
             passes = lib().pt_rebuild_opt_passes_default()
         _check(lib().pt_scene_rebuild_tree_opt(self._h, C.byref(prm), passes, C.byref(report), C.c_void_p(stream_ptr)), "pt_scene_rebuild_tree_opt")

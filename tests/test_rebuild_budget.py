@@ -323,6 +323,43 @@ def test_rebuilt_arrays_are_a_function_of_positions_and_parameters(_gpu):
 
 
 @pytest.mark.gpu
+def test_what_a_rebuild_holds_follows_its_parameters(_gpu):
+    """pt_scene_device_bytes after a rebuild follows the parameters of the calls a scene has seen, not the name of the entry point
+    (include/pt_api.h: "Memory"): the class boxes (16,384 + 64 bytes, and the 64-bit sort's storage where it applies) with a
+    large_fraction > 0, 28 bytes per raw node and the level offsets of a pass with passes > 0, and nothing else beyond the plain call."""
+    nodes, tris, sph = T._build("standin_spheres")
+    N = 2 * len(tris) - 1
+
+    def rebuilt(call):
+        sc = ptamd.Scene(nodes, tris, sph)
+        call(sc)
+        assert sc.tree_inflation() == 1.0
+        return sc, sc.device_bytes
+
+    def again(sc, call):
+        held = sc.device_bytes
+        call(sc)
+        assert sc.device_bytes == held and sc.tree_inflation() == 1.0
+
+    sc_plain, plain = rebuilt(lambda sc: sc.rebuild_tree())
+    for D, f in ((0, 0.0), (26, 0.0)):
+        assert rebuilt(lambda sc: sc.rebuild_tree(depth_budget=D, large_fraction=f))[1] == plain, (D, f)
+    assert rebuilt(lambda sc: sc.rebuild_tree_optimized(passes=0, depth_budget=26, large_fraction=0.0))[1] == plain
+    classes = lambda sc: sc.rebuild_tree(depth_budget=0, large_fraction=1 / 16)
+    sc_classes, with_classes = rebuilt(classes)
+    print(f"plain {plain}, classes + {with_classes - plain}")
+    assert with_classes - plain >= 16448 and rebuilt(classes)[1] == with_classes
+    passes = lambda sc: sc.rebuild_tree_optimized(passes=2, depth_budget=26, large_fraction=0.0)
+    sc_passes, with_passes = rebuilt(passes)
+    print(f"passes + {with_passes - plain}, 28 N = {28 * N}")
+    assert 28 * N <= with_passes - plain <= 28 * N + 8192
+    again(sc_plain, lambda sc: sc.rebuild_tree())
+    again(sc_classes, classes)
+    again(sc_passes, passes)
+    again(sc_passes, lambda sc: sc.rebuild_tree())      # a plain call after an opt call
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("env", [{"PTAMD_TREE": "0"}, {"PTAMD_LEAF": "4"}])
 def test_rebuild_does_not_depend_on_the_build_at_upload(_gpu, monkeypatch, env):
     nodes, tris, sph = T._build("standin")

@@ -73,6 +73,28 @@ void pt_fill_camera(const PtCamera* cam, ptd::DevCamera& c)
     c.tan_half_fovy = (float)std::tan((double)(fovy * 0.5f));
 }
 
+int pt_upload_views(PtScene* s, const PtCamera* h_cams, int32_t n_views, int32_t default_first, const int32_t* h_first_pass, hipStream_t stream,
+                    PtViewTable& t)
+{
+    HIPCHK(s->views.reserve(n_views, 64, 16 + sizeof(ptd::DevCamera) + 4));
+    // origins | cameras | first passes, each n_views long, packed for one copy (16-byte entries first: every part stays aligned)
+    const size_t offCam = (size_t)n_views * 16, offFirst = offCam + (size_t)n_views * sizeof(ptd::DevCamera), total = offFirst + (size_t)n_views * 4;
+    s->h_views.resize(total);
+    for (int32_t v = 0; v < n_views; v++) {
+        ptd::DevCamera c;
+        pt_fill_camera(&h_cams[v], c);
+        const float org[4] = {c.pos[0], c.pos[1], c.pos[2], 0.f};
+        const int32_t first = h_first_pass ? h_first_pass[v] : default_first;
+        memcpy(s->h_views.data() + (size_t)v * 16, org, 16);
+        memcpy(s->h_views.data() + offCam + (size_t)v * sizeof(ptd::DevCamera), &c, sizeof(c));
+        memcpy(s->h_views.data() + offFirst + (size_t)v * 4, &first, 4);
+    }
+    HIPCHK(hipMemcpyAsync(s->views.as<>(), s->h_views.data(), total, hipMemcpyHostToDevice, stream));
+    const char* dv = s->views.as<const char>();
+    t = {(const ptd::DevCamera*)(dv + offCam), (const int32_t*)(dv + offFirst), (const float4*)dv};
+    return PT_OK;
+}
+
 extern "C" {
 
 int64_t pt_tiles_floats(const PtCamera* cam, const PtParams* prm)
@@ -288,27 +310,15 @@ int pt_render_views(PtScene* s, const PtCamera* h_cams, int32_t n_views, const P
     if (!pt_has_light(s)) return PT_ERR_NO_LIGHT;
     job.stream = (hipStream_t)hip_stream;
     HIPCHK(hipSetDevice(s->device));
-    // the previous batch on this scene has drained (one render at a time per scene), so nothing reads the old buffer
-    HIPCHK(s->views.reserve(n_views, 64, 16 + sizeof(ptd::DevCamera) + 4));
-    // origins | cameras | first passes, each n_views long, packed for one copy (16-byte entries first: every part stays aligned)
-    const size_t offCam = (size_t)n_views * 16, offFirst = offCam + (size_t)n_views * sizeof(ptd::DevCamera), total = offFirst + (size_t)n_views * 4;
-    s->h_views.resize(total);
-    for (int32_t v = 0; v < n_views; v++) {
-        ptd::DevCamera c;
-        pt_fill_camera(&h_cams[v], c);
-        const float org[4] = {c.pos[0], c.pos[1], c.pos[2], 0.f};
-        const int32_t first = h_first_pass ? h_first_pass[v] : prm->first_pass;
-        memcpy(s->h_views.data() + (size_t)v * 16, org, 16);
-        memcpy(s->h_views.data() + offCam + (size_t)v * sizeof(ptd::DevCamera), &c, sizeof(c));
-        memcpy(s->h_views.data() + offFirst + (size_t)v * 4, &first, 4);
-    }
+    // the previous batch on this scene has drained (one render at a time per scene), so nothing reads the old buffer;
     // stream-ordered before wf_init_views; the render below returns only once it has drained, so the callers' arrays are not read after the call
-    HIPCHK(hipMemcpyAsync(s->views.as<>(), s->h_views.data(), total, hipMemcpyHostToDevice, job.stream));
-    const char* dv = s->views.as<const char>();
+    PtViewTable t;
+    const int urc = pt_upload_views(s, h_cams, n_views, prm->first_pass, h_first_pass, job.stream, t);
+    if (urc) return urc;
     // always the queue-driven pipeline (pt_set_mode, the counting build and the PTAMD_TSTAT diagnostics do not apply); per-launch trace events as for a frame
     job.work = d_work;
     job.src.kind = ptd::WfSource::kViews;
-    job.src.views = {(const ptd::DevCamera*)(dv + offCam), (const int32_t*)(dv + offFirst), (const float4*)dv};
+    job.src.views = {t.cams, t.firstPass, t.org};
     return pt_run_job(s, job, /*traceEvents=*/true, /*traceStat=*/false, d_tiles);
 }
 
@@ -338,6 +348,18 @@ int pt_untile(const float* d_gathered, const PtCamera* cam, int32_t world, float
     const ptd::TileGrid g = ptd::tile_grid(cam->W, cam->H, world);
     const long long per_rank = (long long)g.per_rank * ptd::kTilePixels * 3;
     HIPCHK(ptk_untile(d_gathered, cam->W, cam->H, g.tiles_x, g.total, world, per_rank, d_frame_rgb, (hipStream_t)hip_stream));
+    return PT_OK;
+}
+
+int pt_untile_views(const float* d_tiles, const PtCamera* cam0, int32_t n_views, float* d_frames_rgb, void* hip_stream)
+{
+    if (!d_tiles || !cam0 || !d_frames_rgb || n_views < 1) { pt_set_error("pt_untile_views: bad argument"); return PT_ERR_INVALID; }
+    if (!ptd::frame_ok(cam0->W, cam0->H) || (int64_t)n_views * cam0->W * cam0->H > ptd::kMaxPixels) {
+        pt_set_error("pt_untile_views: %d views of %dx%d: a frame below 2x2 or more than 2^28 pixels", n_views, cam0->W, cam0->H);
+        return PT_ERR_INVALID;
+    }
+    const ptd::TileGrid g = ptd::tile_grid(cam0->W, cam0->H);
+    HIPCHK(ptk_untile_views(d_tiles, cam0->W, cam0->H, g.tiles_x, g.total, n_views, d_frames_rgb, (hipStream_t)hip_stream));
     return PT_OK;
 }
 

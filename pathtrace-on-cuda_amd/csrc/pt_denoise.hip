@@ -1,13 +1,14 @@
-// pt_denoise.hip — first-hit feature buffers ("AOVs") and the edge-aware denoiser guided by them (include/pt_api.h:
+// pt_denoise.hip — first-hit feature buffers ("AOVs") of the full frame and the edge-aware denoiser guided by them (include/pt_api.h:
 // pt_render_aov, pt_denoise).  New ground: the reference has neither.  Nothing here touches a render's state.
 //
-// AOVs (aov_kernel): per pixel of the full frame, the camera ray of the FIRST path of each pass first_pass + j of the call
+// AOVs: per pixel of the full frame, the camera ray of the FIRST path of each pass first_pass + j of the call
 // (the render's seed expression, two jitter draws, pixel_direction, origin cam.pos, t_max 999999 — as dbg_pixel_dir), traced to
-// its closest hit with trace_closest + make_surf (as dbg_raycast).  Float32 sums in pass order, one IEEE division at the end:
+// its closest hit and given its surface by make_surf (as dbg_raycast).  Float32 sums in pass order, one IEEE division at the end:
 //   [0..2] sum albedo / passes   [3..5] sum shading normal (ray-facing, not renormalised) / passes
 //   [6] sum t / hits (0 if none) [7] hits / passes
-// The host restates it bit for bit from the oracle (tests/denoise_ref.py: aov_from_oracle).  One thread per pixel, one wave per
-// 8x8 tile (ray coherence), the LDS traversal stack of dbg_raycast.
+// The host restates it bit for bit from the oracle (tests/denoise_ref.py: aov_from_oracle).  The kernel is pt_aov.hip's, which takes its
+// pixels from any source: the full frame is the window of all its pixels (measured against the kernel this file used to hold, one
+// wave per tile in 256-thread workgroups on trace_closest: 0.89 against 2.91 ms at 1080p).
 //
 // Denoiser: edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with albedo demodulation.  Definition (tests/denoise_ref.py
 // states it in numpy, float64):
@@ -19,6 +20,8 @@
 //       + |z_p - z_q| / (sz max(z_p, z_q))  (0 when both depths are 0);   w = 0 exactly when E > 80
 //   e'_p = sum w e_q / sum w, or e_p when sum w = 0 (a NaN pixel with a finite neighbour becomes finite; a NaN is never spread);
 //   n (AOV 3..5) and z (AOV 6) are not filtered;  out_p = e_p^(L) div_p sample_cnt;  L = 0 is a plain copy.
+// A stack of n frames of one size (pt_denoise_batch) is filtered by the same launches: the frame is blockIdx.z, every buffer is offset by
+// frame x W*H at the top of a kernel, and a tap is tested against the frame's own W and H — it never crosses into a neighbour.
 // Kernels: pack (demodulate once: colour float4 (e.rgb, finite), feature float4 (n.xyz, z)), L x atrous (ping-pong of the colour
 // float4s in the work buffer), finish (remodulate, write RGB).  256-thread blocks, each wave an 8x8 pixel tile, plain 16-byte loads:
 // the 48 B/pixel working set (100 MB at 1080p) stays in the Infinity Cache, the 5x5 footprint of a wave in L2.
@@ -26,58 +29,18 @@
 #include <cmath>
 #include "pt_device.h"
 #include "pt_math.h"
-#include "pt_bxdf.h"
-#include "pt_trace.h"
-#include "pt_shade.h"
 #include "pt_scene.h"
 
 namespace ptd {
 
-__global__ __launch_bounds__(kBlockThreads)
-void aov_kernel(DevScene sc, DevCamera cam, int first_pass, int passes, int tiles_x, int n_tiles,
-                float4* __restrict__ aov, int* __restrict__ prim_out)
-{
-    __shared__ int lds_stack[kWavesPerBlock][kStackDepth * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int* stack = &lds_stack[wave][lane];
-    const int tile = blockIdx.x * kWavesPerBlock + wave;
-    const int px = (tile % tiles_x) * kTile + (lane & 7), py = (tile / tiles_x) * kTile + (lane >> 3);
-    if (tile >= n_tiles || px >= cam.W || py >= cam.H) return;
-    const f3 org(cam.pos[0], cam.pos[1], cam.pos[2]);
-    f3 alb(0.f, 0.f, 0.f), nrm(0.f, 0.f, 0.f);
-    float tsum = 0.f;
-    int hits = 0, prim0 = -1;
-    for (int j = 0; j < passes; j++) {
-        const int pass = first_pass + j;
-        Rng rng;
-        rng.init((uint64_t)(int64_t)(py * cam.W + px + pass * cam.W * cam.H));      // srcs/pathtracer.cu:70-71
-        float u1, u2;
-        const f3 dir = pixel_direction(cam, px, py, rng, u1, u2);
-        float t; TraceStats st{0, 0, 0};
-        const int prim = trace_closest<false>(sc, org, dir, 999999.f, stack, t, st);
-        if (j == 0) prim0 = prim;
-        if (prim >= 0) {
-            Surf s;
-            make_surf(sc, prim, t, org, dir, s);
-            alb += s.m.albedo;
-            nrm += s.fr.n;
-            tsum += t;
-            hits++;
-        }
-    }
-    const float fp = (float)passes;
-    const size_t i = (size_t)py * cam.W + px;
-    aov[2 * i] = make_float4(alb.x / fp, alb.y / fp, alb.z / fp, nrm.x / fp);
-    aov[2 * i + 1] = make_float4(nrm.y / fp, nrm.z / fp, hits ? tsum / (float)hits : 0.f, (float)hits / fp);
-    if (prim_out) prim_out[i] = prim0;
-}
-
-// pixel of this thread: blocks of 16x16 pixels, wave w of the block on the 8x8 quadrant (w & 1, w >> 1)
-PT_DEV void dn_pixel(int& px, int& py)
+// pixel of this thread: blocks of 16x16 pixels, wave w of the block on the 8x8 quadrant (w & 1, w >> 1); blockIdx.z is the frame of a
+// stack, `frame` the index of its pixel 0
+PT_DEV void dn_pixel(int W, int H, int& px, int& py, size_t& frame)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     px = blockIdx.x * 16 + (wave & 1) * kTile + (lane & 7);
     py = blockIdx.y * 16 + (wave >> 1) * kTile + (lane >> 3);
+    frame = (size_t)blockIdx.z * (size_t)W * (size_t)H;
 }
 
 PT_DEV bool finite3(float a, float b, float c) { return __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c); }
@@ -92,9 +55,9 @@ __global__ __launch_bounds__(256)
 void dn_pack(const float* __restrict__ rgb, const float4* __restrict__ aov, int W, int H, float sample_cnt, int demodulate,
              float4* __restrict__ color, float4* __restrict__ feat)
 {
-    int px, py; dn_pixel(px, py);
+    int px, py; size_t frame; dn_pixel(W, H, px, py, frame);
     if (px >= W || py >= H) return;
-    const size_t i = (size_t)py * W + px;
+    const size_t i = frame + (size_t)py * W + px;
     const float4 a0 = aov[2 * i], a1 = aov[2 * i + 1];
     const f3 c(rgb[3 * i] / sample_cnt, rgb[3 * i + 1] / sample_cnt, rgb[3 * i + 2] / sample_cnt);
     const f3 d = demod_div(a0, demodulate);
@@ -107,10 +70,10 @@ __global__ __launch_bounds__(256)
 void dn_atrous(const float4* __restrict__ cin, const float4* __restrict__ feat, int W, int H, int s, float kc, float kn, float kz,
                float4* __restrict__ cout)
 {
-    int px, py; dn_pixel(px, py);
+    int px, py; size_t frame; dn_pixel(W, H, px, py, frame);
     if (px >= W || py >= H) return;
     const float h[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
-    const size_t i = (size_t)py * W + px;
+    const size_t i = frame + (size_t)py * W + px;
     const float4 cp = cin[i], fp = feat[i];
     const bool finP = cp.w != 0.f;
     float ax = 0.f, ay = 0.f, az = 0.f, wsum = 0.f;
@@ -122,7 +85,7 @@ void dn_atrous(const float4* __restrict__ cin, const float4* __restrict__ feat, 
         for (int dx = -2; dx <= 2; dx++) {
             const int qx = px + s * dx;
             if (qx < 0 || qx >= W) continue;
-            const size_t q = (size_t)qy * W + qx;
+            const size_t q = frame + (size_t)qy * W + qx;
             const float4 cq = cin[q];
             if (cq.w == 0.f) continue;
             const float4 fq = feat[q];
@@ -153,9 +116,9 @@ __global__ __launch_bounds__(256)
 void dn_finish(const float4* __restrict__ color, const float4* __restrict__ aov, int W, int H, float sample_cnt, int demodulate,
                float* __restrict__ out)
 {
-    int px, py; dn_pixel(px, py);
+    int px, py; size_t frame; dn_pixel(W, H, px, py, frame);
     if (px >= W || py >= H) return;
-    const size_t i = (size_t)py * W + px;
+    const size_t i = frame + (size_t)py * W + px;
     const float4 e = color[i];
     const f3 d = demod_div(aov[2 * i], demodulate);
     out[3 * i] = (e.x * d.x) * sample_cnt;
@@ -166,11 +129,10 @@ void dn_finish(const float4* __restrict__ color, const float4* __restrict__ aov,
 }  // namespace ptd
 
 // ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
-static const int64_t kMaxPixels = (int64_t)1 << 28;      // keeps every per-pixel float offset (x 8) inside int64 and the pixel index inside int
+using ptd::frame_ok;
+using ptd::kMaxPixels;
 
-static bool frame_ok(int32_t W, int32_t H) { return W >= 2 && H >= 2 && (int64_t)W * H <= kMaxPixels; }
-
-static int aov_args(const PtCamera* cam, const PtParams* prm)
+int pt_aov_args(const PtCamera* cam, const PtParams* prm)
 {
     if (!cam || !prm) { pt_set_error("NULL camera/params"); return PT_ERR_INVALID; }
     if (!frame_ok(cam->W, cam->H)) { pt_set_error("frame %dx%d out of range", cam->W, cam->H); return PT_ERR_INVALID; }
@@ -185,18 +147,22 @@ static bool overlaps(const void* a, size_t na, const void* b, size_t nb)
     return x < y + nb && y < x + na;
 }
 
-static int denoise_args(const void* rgb, const void* aov, int32_t W, int32_t H, int32_t sample_cnt, const PtDenoiseParams* p,
+// n_frames frames of W x H, stacked: the checks of one frame with every extent multiplied by n_frames
+static int denoise_args(const void* rgb, const void* aov, int32_t W, int32_t H, int32_t n_frames, int32_t sample_cnt, const PtDenoiseParams* p,
                         const void* out, const void* work, bool device)
 {
     if (!rgb || !aov || !p || !out || (device && !work)) { pt_set_error("pt_denoise: NULL argument"); return PT_ERR_INVALID; }
     if (!frame_ok(W, H)) { pt_set_error("pt_denoise: frame %dx%d out of range", W, H); return PT_ERR_INVALID; }
+    if (n_frames < 1 || n_frames > 65535 || (int64_t)n_frames * W * H > kMaxPixels) {
+        pt_set_error("pt_denoise: %d frames of %dx%d: 1 .. 65535 frames, at most 2^28 pixels in all", n_frames, W, H); return PT_ERR_INVALID;
+    }
     if (sample_cnt <= 0) { pt_set_error("pt_denoise: sample_cnt %d <= 0", sample_cnt); return PT_ERR_INVALID; }
     if (p->iterations < 0 || p->iterations > 12) { pt_set_error("pt_denoise: iterations %d outside 0..12", p->iterations); return PT_ERR_INVALID; }
     if (!(p->sigma_color > 0.f) || !(p->sigma_normal > 0.f) || !(p->sigma_depth > 0.f) ||
         !std::isfinite(p->sigma_color) || !std::isfinite(p->sigma_normal) || !std::isfinite(p->sigma_depth)) {
         pt_set_error("pt_denoise: sigmas must be finite and > 0"); return PT_ERR_INVALID;
     }
-    const size_t n = (size_t)W * H;
+    const size_t n = (size_t)W * H * (size_t)n_frames;
     if (overlaps(out, n * 12, rgb, n * 12) || overlaps(out, n * 12, aov, n * 32) || (work && overlaps(out, n * 12, work, n * 48))) {
         pt_set_error("pt_denoise: the output overlaps an input or the work buffer"); return PT_ERR_INVALID;
     }
@@ -218,23 +184,16 @@ int pt_render_aov(PtScene* s, const PtCamera* cam, const PtParams* prm, float* d
 {
     if (!s || !d_aov) { pt_set_error("pt_render_aov: NULL argument"); return PT_ERR_INVALID; }
     if ((uintptr_t)d_aov % 16) { pt_set_error("pt_render_aov: d_aov is not 16-byte aligned"); return PT_ERR_INVALID; }
-    int rc = aov_args(cam, prm);
+    int rc = pt_aov_args(cam, prm);
     if (rc) return rc;
-    ptd::DevCamera c;
-    pt_fill_camera(cam, c);
-    HIPCHK(hipSetDevice(s->device));
-    const ptd::TileGrid g = ptd::tile_grid(cam->W, cam->H);
-    const int nb = (g.total + ptd::kWavesPerBlock - 1) / ptd::kWavesPerBlock;
-    if (nb > 0) hipLaunchKernelGGL(ptd::aov_kernel, dim3(nb), dim3(ptd::kBlockThreads), 0, (hipStream_t)hip_stream, s->dev, c, prm->first_pass, prm->passes,
-                                   g.tiles_x, g.total, (float4*)d_aov, d_prim);
-    HIPCHK(hipGetLastError());
-    return PT_OK;
+    // the whole frame is the window of all its pixels: one kernel for every pixel source (pt_aov.hip)
+    return pt_render_aov_window(s, cam, prm, 0, 0, cam->W, cam->H, d_aov, d_prim, hip_stream);
 }
 
 int pt_aov(PtScene* s, const PtCamera* cam, const PtParams* prm, float* h_aov, int32_t* h_prim)
 {
     if (!s || !h_aov) { pt_set_error("pt_aov: NULL argument"); return PT_ERR_INVALID; }
-    int rc = aov_args(cam, prm);
+    int rc = pt_aov_args(cam, prm);
     if (rc) return rc;
     const size_t n = (size_t)cam->W * cam->H;
     HIPCHK(hipSetDevice(s->device));
@@ -254,19 +213,27 @@ int64_t pt_denoise_work_bytes(int32_t W, int32_t H)
     return (int64_t)W * H * 48;
 }
 
-int pt_denoise(const float* d_rgb, const float* d_aov, int32_t W, int32_t H, int32_t sample_cnt, const PtDenoiseParams* p,
-               float* d_out, void* d_work, void* hip_stream)
+int64_t pt_denoise_batch_work_bytes(int32_t W, int32_t H, int32_t n_frames)
 {
-    const int rc = denoise_args(d_rgb, d_aov, W, H, sample_cnt, p, d_out, d_work, true);
+    if (!frame_ok(W, H) || n_frames < 1 || n_frames > 65535 || (int64_t)n_frames * W * H > kMaxPixels) {
+        pt_set_error("pt_denoise_batch_work_bytes: %d frames of %dx%d out of range", n_frames, W, H); return -1;
+    }
+    return (int64_t)W * H * 48 * n_frames;
+}
+
+int pt_denoise_batch(const float* d_rgb, const float* d_aov, int32_t W, int32_t H, int32_t n_frames, int32_t sample_cnt, const PtDenoiseParams* p,
+                     float* d_out, void* d_work, void* hip_stream)
+{
+    const int rc = denoise_args(d_rgb, d_aov, W, H, n_frames, sample_cnt, p, d_out, d_work, true);
     if (rc) return rc;
     const hipStream_t stream = (hipStream_t)hip_stream;
-    if (p->iterations == 0) { HIPCHK(hipMemcpyAsync(d_out, d_rgb, (size_t)W * H * 12, hipMemcpyDeviceToDevice, stream)); return PT_OK; }
-    // d_work: 3 x W*H float4 (colour ping, colour pong, features)
-    const size_t n = (size_t)W * H;
+    // d_work: 3 x n_frames*W*H float4 (colour ping, colour pong, features), each frame-major like the inputs
+    const size_t n = (size_t)W * H * (size_t)n_frames;
+    if (p->iterations == 0) { HIPCHK(hipMemcpyAsync(d_out, d_rgb, n * 12, hipMemcpyDeviceToDevice, stream)); return PT_OK; }
     float4* c0 = (float4*)d_work;
     float4* c1 = c0 + n;
     float4* feat = c1 + n;
-    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16)), block(256);
+    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16), (unsigned)n_frames), block(256);
     const float sc = (float)sample_cnt;
     const int demodulate = p->demodulate ? 1 : 0;
     hipLaunchKernelGGL(ptd::dn_pack, grid, block, 0, stream, d_rgb, (const float4*)d_aov, W, H, sc, demodulate, c0, feat);
@@ -282,12 +249,19 @@ int pt_denoise(const float* d_rgb, const float* d_aov, int32_t W, int32_t H, int
     return PT_OK;
 }
 
-int pt_denoise_host(int32_t device, const float* h_rgb, const float* h_aov, int32_t W, int32_t H, int32_t sample_cnt,
-                    const PtDenoiseParams* p, float* h_out)
+// one frame is the batch of one: one code path
+int pt_denoise(const float* d_rgb, const float* d_aov, int32_t W, int32_t H, int32_t sample_cnt, const PtDenoiseParams* p,
+               float* d_out, void* d_work, void* hip_stream)
 {
-    int rc = denoise_args(h_rgb, h_aov, W, H, sample_cnt, p, h_out, nullptr, false);
+    return pt_denoise_batch(d_rgb, d_aov, W, H, 1, sample_cnt, p, d_out, d_work, hip_stream);
+}
+
+int pt_denoise_batch_host(int32_t device, const float* h_rgb, const float* h_aov, int32_t W, int32_t H, int32_t n_frames, int32_t sample_cnt,
+                          const PtDenoiseParams* p, float* h_out)
+{
+    int rc = denoise_args(h_rgb, h_aov, W, H, n_frames, sample_cnt, p, h_out, nullptr, false);
     if (rc) return rc;
-    const size_t n = (size_t)W * H;
+    const size_t n = (size_t)W * H * (size_t)n_frames;
     HIPCHK(hipSetDevice(device));
     DevBuf buf;      // one allocation: rgb | aov | out | work
     HIPCHK(buf.alloc(n * (12 + 32 + 12 + 48) + 64));
@@ -298,9 +272,35 @@ int pt_denoise_host(int32_t device, const float* h_rgb, const float* h_aov, int3
     void* d_work = (char*)d_aov + ((n * 44 + 15) & ~(size_t)15);
     HIPCHK(hipMemcpy(d_rgb, h_rgb, n * 12, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_aov, h_aov, n * 32, hipMemcpyHostToDevice));
-    rc = pt_denoise(d_rgb, d_aov, W, H, sample_cnt, p, d_out, d_work, nullptr);
+    rc = pt_denoise_batch(d_rgb, d_aov, W, H, n_frames, sample_cnt, p, d_out, d_work, nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpy(h_out, d_out, n * 12, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_denoise_host(int32_t device, const float* h_rgb, const float* h_aov, int32_t W, int32_t H, int32_t sample_cnt,
+                    const PtDenoiseParams* p, float* h_out)
+{
+    return pt_denoise_batch_host(device, h_rgb, h_aov, W, H, 1, sample_cnt, p, h_out);
+}
+
+// ---- the exact windowed denoise (host only): how far a pixel of the L-iteration filter looks, and a window grown by that much ----
+int32_t pt_denoise_margin(int32_t iterations)
+{
+    if (iterations < 0 || iterations > 12) { pt_set_error("pt_denoise_margin: iterations %d outside 0..12", iterations); return -1; }
+    return 2 * ((1 << iterations) - 1);      // the sum of the reaches 2 * 2^i of iterations 0 .. L-1
+}
+
+int pt_window_expand(const PtCamera* cam, const int32_t window[4], int32_t margin, int32_t expanded[4])
+{
+    if (!window || !expanded) { pt_set_error("pt_window_expand: NULL argument"); return PT_ERR_INVALID; }
+    const int rc = pt_window_args("pt_window_expand", cam, window[0], window[1], window[2], window[3]);
+    if (rc) return rc;
+    if (margin < -1) { pt_set_error("pt_window_expand: margin %d (-1: the margin of the default iterations, else >= 0)", margin); return PT_ERR_INVALID; }
+    if (margin == -1) { PtDenoiseParams p; pt_denoise_params_default(&p); margin = pt_denoise_margin(p.iterations); }
+    const int64_t m = margin, x0 = window[0] - m, y0 = window[1] - m, x1 = window[2] + m, y1 = window[3] + m;
+    expanded[0] = (int32_t)(x0 < 0 ? 0 : x0); expanded[1] = (int32_t)(y0 < 0 ? 0 : y0);
+    expanded[2] = (int32_t)(x1 > cam->W ? cam->W : x1); expanded[3] = (int32_t)(y1 > cam->H ? cam->H : y1);
     return PT_OK;
 }
 

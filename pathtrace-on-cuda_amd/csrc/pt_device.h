@@ -47,6 +47,9 @@ constexpr int kTilePixels = 64;
 constexpr int kStackDepth = 32;          // per-lane traversal stack entries (LDS)
 constexpr int kWavesPerBlock = 4;
 constexpr int kBlockThreads = 64 * kWavesPerBlock;
+// the one-ray-per-lane kernels with one-wave workgroups (pt_query.hip: query_rays, pt_aov.hip: aov_source)
+constexpr int kQueryStack = 40;          // per-lane stack entries of their 4-wide walk: trees up to 12 levels (host/accel_build.h: kQuadDepthCap)
+constexpr int kQueryWaves = 4;           // waves per SIMD their register allocation must allow: 16 one-wave workgroups x 10 KB = the CU's 160 KB of LDS
 
 // Diagnostic counter buffer (PtScene::counters, PTAMD_TSTAT): kStatWords 64-bit words of counters, launch timeline and histograms,
 // then — for one chosen launch of wf_trace (PTAMD_TDUMP) — 8 words per wave (kStatWaves) and a per-trip log of every kStatLogEvery-th wave

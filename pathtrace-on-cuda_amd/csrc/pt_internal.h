@@ -73,6 +73,11 @@ inline TileGrid tile_grid(int W, int H, int world = 1)
     return g;
 }
 
+// The frames (and stacks of frames) the feature buffers and the denoiser take: every per-pixel float offset (x 8) stays inside int64
+// and the pixel index inside int
+constexpr int64_t kMaxPixels = (int64_t)1 << 28;
+inline bool frame_ok(int32_t W, int32_t H) { return W >= 2 && H >= 2 && (int64_t)W * H <= kMaxPixels; }
+
 // The render seeds a pixel's stream with offset + SampleIDX * W * H as an int: false, with the error text set, when the last pass overflows it.
 inline bool seed_in_range(const PtCamera* cam, int first_pass, int passes)
 {
@@ -186,6 +191,10 @@ struct DynScene {
 int pt_check_params(const PtParams* prm);                        // the parameter ranges alone (prm not NULL), the error text set
 int pt_fill_params(const PtCamera* cam, const PtParams* prm, ptd::DevParams& d);
 void pt_fill_camera(const PtCamera* cam, ptd::DevCamera& c);
+// pt_denoise.hip: what every feature-buffer call asks of its camera and params (the frame, passes >= 1, first_pass >= 0, the seed limit)
+int pt_aov_args(const PtCamera* cam, const PtParams* prm);
+// pt_region.hip: a half-open window inside the frame of cam (not NULL, W and H >= 2), the error text set
+int pt_window_args(const char* who, const PtCamera* cam, int32_t x0, int32_t y0, int32_t x1, int32_t y1);
 
 extern "C" {
 // pt_api.hip
@@ -196,6 +205,7 @@ int pt_run_job(PtScene* s, ptd::WfJob& job, bool traceEvents, bool traceStat, fl
 hipError_t ptk_render_units(const ptd::DevScene*, const ptd::DevCamera*, const ptd::DevParams*, float*, unsigned int*, void*, int, int, hipStream_t);
 hipError_t ptk_sum_passes(const float*, int, long long, float*, hipStream_t);
 hipError_t ptk_untile(const float*, int, int, int, int, int, long long, float*, hipStream_t);
+hipError_t ptk_untile_views(const float* tiles, int W, int H, int tiles_x, int n_tiles_total, int n_views, float* frames, hipStream_t);
 hipError_t ptk_dbg_raycast(const ptd::DevScene*, const float* uv, const float*, int, float*, int*, hipStream_t);
 hipError_t ptk_dbg_bxdf(int, const float*, int, float*, hipStream_t);
 hipError_t ptk_dbg_rng(unsigned long long, int, uint32_t*, float*, hipStream_t);

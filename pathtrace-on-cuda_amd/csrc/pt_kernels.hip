@@ -228,6 +228,19 @@ __global__ void untile(const float* __restrict__ gathered, int W, int H, int til
     frame[3 * i + 0] = src[0]; frame[3 * i + 1] = src[1]; frame[3 * i + 2] = src[2];
 }
 
+// view-major tile buffers of a batch (pt_render_views) -> n_views row-major frames, stacked: untile of a world of one per view, in one launch
+__global__ void untile_views(const float* __restrict__ tiles, int W, int H, int tiles_x, int n_tiles_total, long long n_pixels, float* __restrict__ frames)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    const long long view = i / ((long long)W * H), p = i % ((long long)W * H);
+    const int px = (int)(p % W), py = (int)(p / W);
+    const int tile = (py / kTile) * tiles_x + (px / kTile);
+    const int lane = (py % kTile) * kTile + (px % kTile);
+    const float* src = tiles + ((view * n_tiles_total + tile) * kTilePixels + lane) * 3;
+    frames[3 * i + 0] = src[0]; frames[3 * i + 1] = src[1]; frames[3 * i + 2] = src[2];
+}
+
 // ---------------------------------------------------------------------------------------
 // Parity hooks (pt_dbg_*): single device functions, one record per thread.
 // ---------------------------------------------------------------------------------------
@@ -352,6 +365,14 @@ hipError_t ptk_untile(const float* gathered, int W, int H, int tiles_x, int n_ti
     const long long n = (long long)W * H;
     const long long nb = (n + bs - 1) / bs;
     if (nb > 0) hipLaunchKernelGGL(ptd::untile, dim3((unsigned)nb), dim3(bs), 0, stream, gathered, W, H, tiles_x, n_tiles_total, world, floats_per_rank, frame);
+    return hipGetLastError();
+}
+
+hipError_t ptk_untile_views(const float* tiles, int W, int H, int tiles_x, int n_tiles_total, int n_views, float* frames, hipStream_t stream)
+{
+    const int bs = 256;
+    const long long n = (long long)W * H * n_views;
+    hipLaunchKernelGGL(ptd::untile_views, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, stream, tiles, W, H, tiles_x, n_tiles_total, n, frames);
     return hipGetLastError();
 }
 

@@ -22,9 +22,6 @@
 
 namespace ptd {
 
-constexpr int kQueryStack = 40;       // per-lane stack entries of the 4-wide walk: trees up to 12 levels (host/accel_build.h: kQuadDepthCap)
-constexpr int kQueryWaves = 4;        // waves per SIMD the register allocation must allow: 16 one-wave workgroups x 10 KB = the CU's 160 KB of LDS
-
 // RAY8: org.xyz dir.xyz reserved tmax, as two 16-byte loads
 PT_DEV void load_ray(const float4* __restrict__ rays, size_t i, f3& org, f3& dir, float& tmax)
 {
@@ -139,7 +136,7 @@ int pt_trace_rays(PtScene* s, const float* d_rays8, int64_t n, int32_t mode, PtR
     if ((rc = query_args_ok("pt_trace_rays", s, d_rays8, n, mode, d_hits, d_surface29, true)) != PT_OK) return rc;
     if (n == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
-    const bool quad = s->query_quad && 3 * s->dev.quad_depth + 2 <= ptd::kQueryStack;      // does the 4-wide walk of a tree this deep fit the per-lane stack?
+    const bool quad = pt_query_walks_quad(s);
     const int64_t kBatch = (int64_t)1 << 30;      // rays per launch: ray numbers are 32-bit
     for (int64_t off = 0; off < n; off += kBatch) {
         const uint32_t m = (uint32_t)(n - off < kBatch ? n - off : kBatch);

@@ -30,7 +30,7 @@ void untile_list(const float* __restrict__ tiles, const int32_t* __restrict__ ti
 
 }  // namespace ptd
 
-static int window_args(const char* who, const PtCamera* cam, int32_t x0, int32_t y0, int32_t x1, int32_t y1)
+int pt_window_args(const char* who, const PtCamera* cam, int32_t x0, int32_t y0, int32_t x1, int32_t y1)
 {
     if (!cam) { pt_set_error("%s: NULL camera", who); return PT_ERR_INVALID; }
     if (cam->W < 2 || cam->H < 2) { pt_set_error("%s: frame %dx%d too small", who, cam->W, cam->H); return PT_ERR_INVALID; }
@@ -45,7 +45,7 @@ extern "C" {
 
 int32_t pt_tiles_of_window(const PtCamera* cam, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t* h_tiles, int32_t cap)
 {
-    const int rc = window_args("pt_tiles_of_window", cam, x0, y0, x1, y1);
+    const int rc = pt_window_args("pt_tiles_of_window", cam, x0, y0, x1, y1);
     if (rc) return rc;
     if (cap < 0 || (cap > 0 && !h_tiles)) { pt_set_error("pt_tiles_of_window: cap=%d with%s a buffer", cap, h_tiles ? "" : "out"); return PT_ERR_INVALID; }
     const int tiles_x = ptd::tile_grid(cam->W, cam->H).tiles_x;
@@ -61,7 +61,7 @@ int pt_untile_list(const float* d_tiles, const int32_t* h_tiles, int32_t n_tiles
                    int32_t x0, int32_t y0, int32_t x1, int32_t y1, float* d_out, void* hip_stream)
 {
     if (!d_tiles || !h_tiles || !d_out) { pt_set_error("pt_untile_list: NULL argument"); return PT_ERR_INVALID; }
-    const int rc = window_args("pt_untile_list", cam, x0, y0, x1, y1);
+    const int rc = pt_window_args("pt_untile_list", cam, x0, y0, x1, y1);
     if (rc) return rc;
     const ptd::TileGrid g = ptd::tile_grid(cam->W, cam->H);
     const int tiles_x = g.tiles_x, n_total = g.total;

@@ -81,6 +81,17 @@ struct PtScene {
     }
 };
 
+// Which walk pt_trace_rays and the feature-buffer kernel of pt_aov.hip take: the 4-wide tree when its walk fits their per-lane stack
+// (and PTAMD_QUERY_QUAD=0 does not force the other), else the binary tree with trace_closest
+inline bool pt_query_walks_quad(const PtScene* s) { return s->query_quad && 3 * s->dev.quad_depth + 2 <= ptd::kQueryStack; }
+
+// pt_api.hip: the table of a batch of views in the scene's buffer `views` (grown on demand; the caller knows that nothing on the device
+// still reads the old one): origins | cameras | first passes, packed by way of the host image h_views and copied in stream order.
+// first = h_first_pass[v], or default_first for every view when h_first_pass is NULL.  PT_OK, or PT_ERR_DEVICE with the error text set.
+struct PtViewTable { const ptd::DevCamera* cams; const int32_t* firstPass; const float4* org; };
+int pt_upload_views(PtScene* s, const PtCamera* h_cams, int32_t n_views, int32_t default_first, const int32_t* h_first_pass, hipStream_t stream,
+                    PtViewTable& t);
+
 // DevScene::nee_prune may be 1 unless PTAMD_PRUNE=0 (A/B only); read whenever the flag is formed
 inline bool pt_prune_allowed() { const char* m = getenv("PTAMD_PRUNE"); return !(m && atoi(m) == 0); }
 // pt_dynamic.hip: the first update of either kind brings the maps and the position mirror to the device (no-op afterwards)

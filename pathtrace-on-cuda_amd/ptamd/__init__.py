@@ -157,6 +157,20 @@ API = [
     ("pt_denoise_work_bytes", C.c_int64, [C.c_int32, C.c_int32]),
     ("pt_denoise", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PtDenoiseParams), _P, _P, _P]),
     ("pt_denoise_host", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PtDenoiseParams), _P]),
+    ("pt_aov_window_floats", C.c_int64, [C.POINTER(PtCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("pt_render_aov_window", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("pt_aov_window", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    ("pt_aov_views_floats", C.c_int64, [C.POINTER(PtCamera), C.c_int32]),
+    ("pt_render_aov_views", C.c_int, [_P, C.POINTER(PtCamera), C.c_int32, C.POINTER(PtParams), _P, _P, _P, _P]),
+    ("pt_aov_views", C.c_int, [_P, C.POINTER(PtCamera), C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
+    ("pt_aov_rays", C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    ("pt_aov_rays_host", C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    ("pt_untile_views", C.c_int, [_P, C.POINTER(PtCamera), C.c_int32, _P, _P]),
+    ("pt_denoise_batch_work_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    ("pt_denoise_batch", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PtDenoiseParams), _P, _P, _P]),
+    ("pt_denoise_batch_host", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PtDenoiseParams), _P]),
+    ("pt_denoise_margin", C.c_int32, [C.c_int32]),
+    ("pt_window_expand", C.c_int, [C.POINTER(PtCamera), C.POINTER(C.c_int32 * 4), C.c_int32, C.POINTER(C.c_int32 * 4)]),
     ("pt_accumulate_passes", C.c_int, [_P, C.POINTER(PtCamera), C.POINTER(PtParams), C.c_int32, _P, _P, _P]),
     ("pt_variance", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
     ("pt_error_scratch_bytes", C.c_int64, [C.c_int64]),
@@ -487,6 +501,106 @@ class Scene:
         _check(lib().pt_render_aov(self._h, C.byref(cam), C.byref(prm), C.c_void_p(d_aov_ptr), C.c_void_p(d_prim_ptr or None),
                                    C.c_void_p(stream_ptr)), "pt_render_aov")
 
+    def aov_window(self, cam, prm, window):
+        """The feature buffers of the pixel window (x0, y0, x1, y1), half-open, synchronous (include/pt_api.h: pt_render_aov_window):
+        ((y1 - y0, x1 - x0, 8) float32, (y1 - y0, x1 - x0) int32), bit for bit aov(cam, prm)[...][y0:y1, x0:x1]."""
+        x0, y0, x1, y1 = (int(v) for v in window)
+        out = np.zeros((max(y1 - y0, 0), max(x1 - x0, 0), AOV_FLOATS), np.float32)
+        prim = np.zeros(out.shape[:2], np.int32)
+        _check(lib().pt_aov_window(self._h, C.byref(cam), C.byref(prm), x0, y0, x1, y1, _ptr(out), _ptr(prim)), "pt_aov_window")
+        return out, prim
+
+    def render_aov_window(self, cam, prm, window, d_aov_ptr, d_prim_ptr=0, stream_ptr=0):
+        """Device-resident pt_render_aov_window into raw device pointers (aov_window_floats(cam, window) floats; d_prim_ptr 0 = none),
+        enqueued on the given stream; nothing is allocated and nothing read back."""
+        x0, y0, x1, y1 = (int(v) for v in window)
+        _check(lib().pt_render_aov_window(self._h, C.byref(cam), C.byref(prm), x0, y0, x1, y1, C.c_void_p(d_aov_ptr), C.c_void_p(d_prim_ptr or None),
+                                          C.c_void_p(stream_ptr)), "pt_render_aov_window")
+
+    def aov_views(self, cams, prm, first_pass=None):
+        """The feature buffers of a batch of cameras of one size in one launch, synchronous (include/pt_api.h: pt_render_aov_views):
+        ((V, H, W, 8) float32, (V, H, W) int32), [v] bit for bit aov(cams[v], prm) (with first_pass[v] as its first pass where given)."""
+        arr = _camera_array(cams)
+        fp = _first_passes(first_pass, len(arr))
+        out = np.zeros((len(arr), arr[0].H, arr[0].W, AOV_FLOATS), np.float32)
+        prim = np.zeros(out.shape[:3], np.int32)
+        _check(lib().pt_aov_views(self._h, arr, len(arr), C.byref(prm), _ptr(fp) if fp is not None else None, _ptr(out), _ptr(prim)), "pt_aov_views")
+        return out, prim
+
+    def render_aov_views(self, cams, prm, d_aov_ptr, d_prim_ptr=0, stream_ptr=0, first_pass=None):
+        """Device-resident pt_render_aov_views into raw device pointers (aov_views_floats(cams[0], n) floats, view-major; d_prim_ptr 0 =
+        none).  Waits for the stream once (the camera table's upload); the kernel is asynchronous on it."""
+        arr = _camera_array(cams)
+        fp = _first_passes(first_pass, len(arr))
+        _check(lib().pt_render_aov_views(self._h, arr, len(arr), C.byref(prm), _ptr(fp) if fp is not None else None, C.c_void_p(d_aov_ptr),
+                                         C.c_void_p(d_prim_ptr or None), C.c_void_p(stream_ptr)), "pt_render_aov_views")
+
+    def aov_rays(self, rays, stream_ptr=0):
+        """The feature buffers of the caller's rays (include/pt_api.h: pt_aov_rays).  rays: (n, 8) float32 RAY8 records as in trace_rays.
+        Returns ((n, 8) float32 albedo.rgb | normal.xyz | t | 1, zeros for a miss, and (n,) int32 primitive, -1 = miss).  A torch float32
+        tensor on the scene's device is used in place (data_ptr()): the call is enqueued on stream_ptr, the results are torch tensors on
+        that device, valid once the stream has passed it, and `rays` must stay alive until then.  A numpy array goes through
+        pt_aov_rays_host (synchronous) and returns numpy arrays."""
+        if isinstance(rays, np.ndarray):
+            r = np.ascontiguousarray(rays, np.float32)
+            if r.ndim != 2 or r.shape[1] != 8:
+                raise PtError(f"aov_rays: rays has shape {r.shape}, want (n, 8)")
+            n = r.shape[0]
+            out, prim = np.zeros((n, AOV_FLOATS), np.float32), np.zeros(n, np.int32)
+            _check(lib().pt_aov_rays_host(self._h, _ptr(r), n, _ptr(out), _ptr(prim)), "pt_aov_rays_host")
+            return out, prim
+        if not (hasattr(rays, "data_ptr") and hasattr(rays, "is_contiguous")):
+            raise PtError("aov_rays: rays must be a torch tensor or a numpy array")
+        if str(rays.dtype) != "torch.float32" or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+            raise PtError(f"aov_rays: rays must be contiguous float32 of shape (n, 8), got {rays.dtype} {tuple(rays.shape)}")
+        if rays.device.type != "cuda" or rays.device.index != self.device:
+            raise PtError(f"aov_rays: rays is on {rays.device}, the scene is on device {self.device}")
+        import torch
+        n = rays.shape[0]
+        out = torch.empty((n, AOV_FLOATS), dtype=torch.float32, device=rays.device)
+        prim = torch.empty(n, dtype=torch.int32, device=rays.device)
+        self.aov_rays_device(rays.data_ptr(), n, out.data_ptr(), prim.data_ptr(), stream_ptr)
+        return out, prim
+
+    def aov_rays_device(self, d_rays_ptr, n_rays, d_aov_ptr, d_prim_ptr=0, stream_ptr=0):
+        """pt_aov_rays on raw device pointers (d_prim_ptr 0 = none), enqueued on the given stream."""
+        _check(lib().pt_aov_rays(self._h, C.c_void_p(d_rays_ptr), int(n_rays), C.c_void_p(d_aov_ptr), C.c_void_p(d_prim_ptr or None),
+                                 C.c_void_p(stream_ptr)), "pt_aov_rays")
+
+    def render_window_denoised(self, cam, prm, window, margin=None, **params):
+        """The pixel window (x0, y0, x1, y1) of the denoised frame without the full frame: the window grown by `margin` (None: what the
+        filter's iterations reach, denoise_margin — then the result is bit for bit denoise(render(cam, prm), aov(cam, prm)[0],
+        prm.passes, **params)[y0:y1, x0:x1]) is rendered, its feature buffers are made, denoised and cropped.  Synchronous;
+        (y1 - y0, x1 - x0, 3) float32.  A smaller margin is cheaper and makes no equality claim (include/pt_api.h: pt_window_expand)."""
+        p = denoise_params(**params)
+        x0, y0, x1, y1 = (int(v) for v in window)
+        ex = expand_window(cam, (x0, y0, x1, y1), denoise_margin(p.iterations) if margin is None else int(margin))
+        rgb = self.render_window(cam, prm, ex)
+        aov, _ = self.aov_window(cam, prm, ex)
+        out = denoise(rgb, aov, prm.passes, self.device, **params)
+        return np.ascontiguousarray(out[y0 - ex[1]:y1 - ex[1], x0 - ex[0]:x1 - ex[0]])
+
+    def render_views_denoised(self, cams, prm, first_pass=None, **params):
+        """A batch of cameras of one size rendered and denoised on one stream with one download: render_views_device, untile_views,
+        the feature buffers of the batch and denoise_batch.  (V, H, W, 3) float32, [v] bit for bit denoise(render(cams[v], ...),
+        aov(cams[v], ...)[0], prm.passes, **params).  torch provides the device buffers."""
+        import torch
+        arr = _camera_array(cams)
+        V, W, H = len(arr), arr[0].W, arr[0].H
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            tiles = torch.empty(views_floats(arr[0], V), dtype=torch.float32, device=dev)
+            work = torch.empty(max(views_work_bytes(arr[0], prm, V), denoise_batch_work_bytes(W, H, V)), dtype=torch.uint8, device=dev)
+            frames = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev)
+            aov = torch.empty((V, H, W, AOV_FLOATS), dtype=torch.float32, device=dev)
+            out = torch.empty_like(frames)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            self.render_views_device(arr, prm, tiles.data_ptr(), work.data_ptr(), st, first_pass)
+            untile_views(tiles.data_ptr(), arr[0], V, frames.data_ptr(), st)
+            self.render_aov_views(arr, prm, aov.data_ptr(), 0, st, first_pass)
+            denoise_batch_device(frames.data_ptr(), aov.data_ptr(), W, H, V, prm.passes, out.data_ptr(), work.data_ptr(), st, **params)
+            return out.cpu().numpy()
+
     def render_stats(self, cam, prm):
         """Whole frame with its per-pixel variance across the call's passes (prm.passes >= 2), synchronous: one pt_render_tiles,
         pt_accumulate_passes, pt_variance and two pt_untile.  Returns ((H, W, 3) float32 frame — bit for bit what render()
@@ -802,7 +916,14 @@ def untile(d_gathered_ptr, cam, world, d_frame_ptr, stream_ptr=0):
     _check(lib().pt_untile(C.c_void_p(d_gathered_ptr), C.byref(cam), world, C.c_void_p(d_frame_ptr), C.c_void_p(stream_ptr)), "pt_untile")
 
 
+def untile_views(d_tiles_ptr, cam0, n_views, d_frames_ptr, stream_ptr=0):
+    """pt_untile_views on raw device pointers: the view-major tile buffer of render_views_device -> (n_views, H, W, 3) frames, one launch."""
+    _check(lib().pt_untile_views(C.c_void_p(d_tiles_ptr), C.byref(cam0), int(n_views), C.c_void_p(d_frames_ptr), C.c_void_p(stream_ptr)), "pt_untile_views")
+
+
 def _camera_array(cams):
+    if isinstance(cams, C.Array):
+        return cams
     cams = list(cams)
     if not cams:
         raise PtError("a batch of views holds at least one camera")
@@ -963,6 +1084,65 @@ def denoise_device(d_rgb_ptr, d_aov_ptr, W, H, sample_cnt, d_out_ptr, d_work_ptr
     p = denoise_params(**params)
     _check(lib().pt_denoise(C.c_void_p(d_rgb_ptr), C.c_void_p(d_aov_ptr), W, H, int(sample_cnt), C.byref(p), C.c_void_p(d_out_ptr),
                             C.c_void_p(d_work_ptr), C.c_void_p(stream_ptr)), "pt_denoise")
+
+
+def aov_window_floats(cam, window):
+    x0, y0, x1, y1 = (int(v) for v in window)
+    n = lib().pt_aov_window_floats(C.byref(cam), x0, y0, x1, y1)
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def aov_views_floats(cam, n_views):
+    n = lib().pt_aov_views_floats(C.byref(cam), int(n_views))
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def denoise_batch_work_bytes(W, H, n_frames):
+    n = lib().pt_denoise_batch_work_bytes(W, H, int(n_frames))
+    if n < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return n
+
+
+def denoise_batch(rgb, aov, sample_cnt, device=0, **params):
+    """pt_denoise_batch_host: (n, H, W, 3) frames of one size + (n, H, W, 8) AOVs -> denoised (n, H, W, 3) float32; slice k is bit for bit
+    denoise(rgb[k], aov[k], sample_cnt, **params)."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    aov = np.ascontiguousarray(aov, np.float32)
+    if rgb.ndim != 4 or rgb.shape[3] != 3 or aov.shape != rgb.shape[:3] + (AOV_FLOATS,):
+        raise ValueError(f"shapes {rgb.shape} / {aov.shape}: want (n, H, W, 3) and (n, H, W, {AOV_FLOATS})")
+    n, H, W = rgb.shape[:3]
+    out = np.zeros_like(rgb)
+    p = denoise_params(**params)
+    _check(lib().pt_denoise_batch_host(device, _ptr(rgb), _ptr(aov), W, H, n, int(sample_cnt), C.byref(p), _ptr(out)), "pt_denoise_batch_host")
+    return out
+
+
+def denoise_batch_device(d_rgb_ptr, d_aov_ptr, W, H, n_frames, sample_cnt, d_out_ptr, d_work_ptr, stream_ptr=0, **params):
+    """pt_denoise_batch on raw device pointers (d_work: denoise_batch_work_bytes(W, H, n_frames) bytes), enqueued on the given stream."""
+    p = denoise_params(**params)
+    _check(lib().pt_denoise_batch(C.c_void_p(d_rgb_ptr), C.c_void_p(d_aov_ptr), W, H, int(n_frames), int(sample_cnt), C.byref(p),
+                                  C.c_void_p(d_out_ptr), C.c_void_p(d_work_ptr), C.c_void_p(stream_ptr)), "pt_denoise_batch")
+
+
+def denoise_margin(iterations=None):
+    """pt_denoise_margin: how far (in x and in y) a pixel of the filter with that many iterations looks, 2 * (2^L - 1); None: the default L."""
+    m = lib().pt_denoise_margin(denoise_params().iterations if iterations is None else int(iterations))
+    if m < 0:
+        raise PtError(lib().pt_last_error().decode())
+    return m
+
+
+def expand_window(cam, window, margin=-1):
+    """pt_window_expand: the half-open window (x0, y0, x1, y1) grown by `margin` pixels on every side (-1: denoise_margin of the default
+    iterations) and clipped to the frame, as a tuple."""
+    w, out = (C.c_int32 * 4)(*(int(v) for v in window)), (C.c_int32 * 4)()
+    _check(lib().pt_window_expand(C.byref(cam), C.byref(w), int(margin), C.byref(out)), "pt_window_expand")
+    return tuple(out[:])
 
 
 def _estimate_dict(e):

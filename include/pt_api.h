@@ -786,6 +786,76 @@ PT_API int  pt_trace_rays(PtScene* s, const float* d_rays8, int64_t n, int32_t m
 PT_API int  pt_trace_rays_host(PtScene* s, const float* h_rays8, int64_t n, int32_t mode, PtRayHit* h_hits, float* h_surface29);
 
 /* ----------------------------------------------------------------------------------
+ * Closest-point queries (new: the reference has no such query).  Opt-in: every call above is as it was.
+ * The other half of a BVH query set: what is near a POINT of the caller's, on the device and in stream order (csrc/pt_nearest.hip):
+ * distance and penetration probes against a mesh that pt_scene_update_vertices moves, snapping a picked point to the surface,
+ * signed-distance and proximity baking, "is anything within r of this sensor".
+ *
+ * Points are POINT4 records: p.xyz | radius.  The radius must be >= 0; +inf is allowed.  The search bound is r2 = radius * radius in
+ *   float32.  Primitives are numbered as in pt_trace_rays: triangles first, in the order of `tris`, spheres after them.  None of the
+ *   ray rules apply: distance is two-sided, nothing is culled by facing, and the reference leaf boxes play no part.
+ * Arithmetic: IEEE float32, every operation below rounded once and none contracted, in the order written;
+ *     dot(a, b)   = (ax*bx + ay*by) + az*bz
+ *     cross(a, b) = (ay*bz - az*by, -(ax*bz - az*bx), ax*by - ay*bx)
+ *     min / max of two floats (no NaN arises from finite input), component-wise on vectors.
+ * f(p, k) for triangle k, V0 E1 E2 = its vertex 0 and the float32 edges V1 - V0, V2 - V0 (the PtTriangle fields v0, E1, E2):
+ *     a = V0, ab = E1, ac = E2, bc = ac - ab, ap = p - a, bp = ap - ab
+ *     seg(q, e):  t = dot(q, e) / dot(e, e);  t = (t > 0) ? t : 0;  t = (t < 1) ? t : 1;      (a zero edge gives a NaN t: the first clamp makes it 0)
+ *                 r = q - t * e;  seg = dot(r, r)
+ *     d_edge = min(min(seg(ap, ab), seg(ap, ac)), seg(bp, bc))
+ *     n = cross(ab, ac);  nn = dot(n, n);  h = dot(ap, n)
+ *     inside = nn > 0 && dot(cross(ab, ap), n) >= 0 && dot(cross(bc, bp), n) >= 0 && dot(cross(ap, ac), n) >= 0
+ *     d_raw  = (inside && (h*h)/nn < d_edge) ? (h*h)/nn : d_edge
+ *     lo, hi = component-wise min(min(a, a + ab), a + ac), max(max(a, a + ab), a + ac)      (the box of the triangle the record describes)
+ *     boxdist2(p, lo, hi):  per axis g = max(max(lo - p, p - hi), 0);  boxdist2 = (gx*gx + gy*gy) + gz*gz
+ *     f = max(d_raw, boxdist2(p, lo, hi))
+ *   The edge candidates make a wrong inside / outside call near an edge harmless (the two meet there), and no input, zero-area
+ *   triangles included, gives a NaN.  The last line is a floor: the float32 normal of a thin triangle is tilted, so the plane term can
+ *   fall below the true distance; the floor moves f towards the true distance only, and it gives f(p, k) >= boxdist2(p, box of k)
+ *   EXACTLY — the inequality that lets a tree walk prune without ever disagreeing with the definition below.
+ * f(p, k) for sphere j (k = number of triangles + j):  pc = p - center;  l = sqrt(dot(pc, pc));  g = l - rad;  f = g * g.
+ * PT_NEAREST_CLOSEST: defined without reference to any tree.  Among the primitives k with f(p, k) <= r2, d_out[i] = (f(p, k), k) of
+ *   the smallest f; among equal f the largest k (the tie rule of the ray queries).  No such primitive: a miss, (0, -1).  The result
+ *   is therefore bit for bit the same before and after a refit or any rebuild, and equals a brute-force evaluation over the scene's
+ *   current positions.
+ * PT_NEAREST_ANY: prim >= 0 exactly when the closest query of the same record finds something.  The primitive returned is SOME k with
+ *   f(p, k) <= r2 and dist2 = f(p, k) bit for bit; which k is unspecified and may change between versions (the walk stops at the
+ *   first).  d_detail8 must be NULL.
+ * d_detail8 (PT_NEAREST_CLOSEST only; may be NULL): 8 floats per point about the winning primitive, zeros for a miss:
+ *     c.xyz | v | w | side | feature | 0
+ *   For a triangle, with t1, t2, t3 the clamped parameters and d1, d2, d3 the values of seg(ap, ab), seg(ap, ac), seg(bp, bc):
+ *     interior = inside && (h*h)/nn < d_edge
+ *     interior:            feature 0;  v = dot(cross(ap, ac), n) / nn;  w = dot(cross(ab, ap), n) / nn;  c = p - (h / nn) * n
+ *     else d1 == d_edge:   feature 1 (edge AB);  v = t1;  w = 0;  c = a + t1 * ab
+ *     else d2 == d_edge:   feature 2 (edge AC);  v = 0;  w = t2;  c = a + t2 * ac
+ *     else                 feature 3 (edge BC);  v = 1 - t3;  w = t3;  c = (a + ab) + t3 * bc
+ *     side = (h >= 0) ? +1 : -1      (h = dot(p - V0, cross(E1, E2)))
+ *   so that c ~ V0 + v E1 + w E2; a clamped parameter puts c on a vertex.  (c is the point d_raw measures to; where the floor decides f,
+ *   |p - c|^2 is below dist2 by the rounding the floor repairs.)  For a sphere: feature 4, v = w = 0, side = (l >= rad) ? +1 : -1 and
+ *   c = center + (rad / l) * pc, or (center.x + rad, center.y, center.z) when l == 0.
+ * pt_closest_points: d_points4 (16-byte aligned), d_out (8-byte aligned) and d_detail8 (4-byte aligned) are DEVICE pointers on the
+ *   scene's device holding n records.  Everything is enqueued on `hip_stream`: no host wait, nothing is read back, nothing is allocated
+ *   (pt_scene_device_bytes stays what it was); batches of at most 2^30 points go per launch.  A query enqueued after
+ *   pt_scene_update_vertices, pt_scene_rebuild_tree, pt_scene_rebuild_tree_ex or pt_scene_rebuild_tree_opt on the same stream sees
+ *   their result.  The buffers must stay valid until the stream has passed the query.  A query leaves every render state alone:
+ *   frames, pt_last_iterations, pt_last_counters, pt_last_render_ms.  Concurrency: ONE query, update or render at a time per scene.
+ * pt_closest_points_host: the same on HOST arrays: uploads, queries on the NULL stream, waits and downloads.
+ * NULL scene / points / out, n < 0, an unknown mode, misaligned d_points4 / d_out / d_detail8 and a detail buffer given with
+ *   PT_NEAREST_ANY return PT_ERR_INVALID before any HIP call, no pointer dereferenced; n = 0 returns PT_OK without one.
+ * A point with a non-finite coordinate, or a negative or NaN radius: the result for THAT point is unspecified (prim stays in [-1,
+ *   number of primitives)), the other points of the batch are unaffected, and the call ends by the argument of quad_step
+ *   (csrc/pt_trace.h): a depth-first walk over a finite tree, its stack bounded by the depth of the tree whatever the floats are.
+ * Out of scope: the k nearest, all primitives within a radius, per-primitive masks, a multi-GPU split, a CLI option, sorting the
+ * points for coherence.
+ * -------------------------------------------------------------------------------- */
+typedef struct PtNearest { float dist2; int32_t prim; } PtNearest;     /* 8 bytes */
+#define PT_NEAREST_CLOSEST 0
+#define PT_NEAREST_ANY     1
+PT_API int  pt_closest_points(PtScene* s, const float* d_points4, int64_t n, int32_t mode, PtNearest* d_out, float* d_detail8 /* may be NULL */,
+                              void* hip_stream);
+PT_API int  pt_closest_points_host(PtScene* s, const float* h_points4, int64_t n, int32_t mode, PtNearest* h_out, float* h_detail8 /* may be NULL */);
+
+/* ----------------------------------------------------------------------------------
  * Radiance along the caller's own rays (new: the reference reaches its integrator through a pinhole camera only).
  * Opt-in: every call above is as it was.  pt_trace_rays opened the geometry of an uploaded scene to the caller's rays; this opens
  * the light transport: a panorama, fisheye, orthographic or thin-lens camera, a light probe at a point, a lightmap texel, the

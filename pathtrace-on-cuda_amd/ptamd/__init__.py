@@ -85,6 +85,14 @@ class PtRayHit(C.Structure):
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4")])      # PtRayHit as a numpy record
 QUERY_CLOSEST, QUERY_ANY = 0, 1
+
+
+class PtNearest(C.Structure):
+    _fields_ = [("dist2", C.c_float), ("prim", C.c_int32)]
+
+
+NEAREST_DTYPE = np.dtype([("dist2", "<f4"), ("prim", "<i4")])      # PtNearest as a numpy record
+NEAREST_CLOSEST, NEAREST_ANY = 0, 1
 AOV_FLOATS = 8        # floats per pixel of pt_render_aov: albedo.rgb | normal.xyz | depth | coverage
 
 _lib = None
@@ -210,6 +218,8 @@ API = [
     ("pt_scene_nee_prune", C.c_int32, [_P]),
     ("pt_trace_rays", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     ("pt_trace_rays_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
+    ("pt_closest_points", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    ("pt_closest_points_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     ("pt_rays_floats", C.c_int64, [C.c_int64]),
     ("pt_rays_work_bytes", C.c_int64, [C.POINTER(PtParams), C.c_int64]),
     ("pt_render_rays", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
@@ -831,6 +841,42 @@ class Scene:
                                    C.c_void_p(surf.data_ptr()) if surface else None, C.c_void_p(stream_ptr)), "pt_trace_rays")
         out = (hits[:, 0].view(torch.float32), hits[:, 1])
         return out + (surf,) if surface else out
+
+    def closest_points(self, points, any_within=False, detail=False, stream_ptr=0):
+        """The primitive nearest to each of the caller's points (include/pt_api.h: pt_closest_points).  points: (n, 4) float32 POINT4
+        records, p.xyz radius (>= 0, inf allowed).  Returns (dist2, prim) — float32 and int32 of length n, a miss is (0, -1) — and, with
+        detail=True (closest only), the (n, 8) detail records c.xyz v w side feature 0 as a third item.  any_within=True: prim >= 0 iff
+        the closest query finds something within the radius; which primitive is unspecified.
+        A torch float32 tensor on the scene's device is used in place (data_ptr()): the query is enqueued on stream_ptr, the results
+        are torch tensors on that device, valid once the stream has passed the query, and `points` must stay alive until then.
+        A numpy array goes through pt_closest_points_host (synchronous) and returns numpy arrays."""
+        if any_within and detail:
+            raise PtError("closest_points: an any-within query has no detail record")
+        mode = NEAREST_ANY if any_within else NEAREST_CLOSEST
+        if isinstance(points, np.ndarray):
+            p = np.ascontiguousarray(points, np.float32)
+            if p.ndim != 2 or p.shape[1] != 4:
+                raise PtError(f"closest_points: points has shape {p.shape}, want (n, 4)")
+            n = p.shape[0]
+            res = np.zeros(n, NEAREST_DTYPE)
+            det = np.zeros((n, 8), np.float32) if detail else None
+            _check(lib().pt_closest_points_host(self._h, _ptr(p), n, mode, _ptr(res), _ptr(det) if detail else None), "pt_closest_points_host")
+            out = (np.ascontiguousarray(res["dist2"]), np.ascontiguousarray(res["prim"]))
+            return out + (det,) if detail else out
+        if not (hasattr(points, "data_ptr") and hasattr(points, "is_contiguous")):
+            raise PtError("closest_points: points must be a torch tensor or a numpy array")
+        if str(points.dtype) != "torch.float32" or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 4:
+            raise PtError(f"closest_points: points must be contiguous float32 of shape (n, 4), got {points.dtype} {tuple(points.shape)}")
+        if points.device.type != "cuda" or points.device.index != self.device:
+            raise PtError(f"closest_points: points is on {points.device}, the scene is on device {self.device}")
+        import torch
+        n = points.shape[0]
+        res = torch.empty((n, 2), dtype=torch.int32, device=points.device)      # PtNearest: dist2's bits | prim
+        det = torch.empty((n, 8), dtype=torch.float32, device=points.device) if detail else None
+        _check(lib().pt_closest_points(self._h, C.c_void_p(points.data_ptr()), n, mode, C.c_void_p(res.data_ptr()),
+                                       C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_closest_points")
+        out = (res[:, 0].view(torch.float32), res[:, 1])
+        return out + (det,) if detail else out
 
     def render_rays_device(self, d_rays_ptr, n_rays, prm, d_rgb_ptr, d_work_ptr, d_seed_ptr=0, seed_stride=None, stream_ptr=0):
         """Device-resident radiance along n_rays RAY8 records (raw device pointers: rays_floats(n) floats of output, rays_work_bytes(prm,

@@ -845,8 +845,8 @@ PT_API int  pt_trace_rays_host(PtScene* s, const float* h_rays8, int64_t n, int3
  * A point with a non-finite coordinate, or a negative or NaN radius: the result for THAT point is unspecified (prim stays in [-1,
  *   number of primitives)), the other points of the batch are unaffected, and the call ends by the argument of quad_step
  *   (csrc/pt_trace.h): a depth-first walk over a finite tree, its stack bounded by the depth of the tree whatever the floats are.
- * Out of scope: the k nearest, all primitives within a radius, per-primitive masks, a multi-GPU split, a CLI option, sorting the
- * points for coherence.
+ * Out of scope: per-primitive masks, a multi-GPU split, a CLI option, sorting the points for coherence.  The k nearest and the number
+ * of primitives within a radius: the next section.
  * -------------------------------------------------------------------------------- */
 typedef struct PtNearest { float dist2; int32_t prim; } PtNearest;     /* 8 bytes */
 #define PT_NEAREST_CLOSEST 0
@@ -854,6 +854,50 @@ typedef struct PtNearest { float dist2; int32_t prim; } PtNearest;     /* 8 byte
 PT_API int  pt_closest_points(PtScene* s, const float* d_points4, int64_t n, int32_t mode, PtNearest* d_out, float* d_detail8 /* may be NULL */,
                               void* hip_stream);
 PT_API int  pt_closest_points_host(PtScene* s, const float* h_points4, int64_t n, int32_t mode, PtNearest* h_out, float* h_detail8 /* may be NULL */);
+
+/* ----------------------------------------------------------------------------------
+ * K nearest and counts within a radius (new: the reference has no such query).  Opt-in: every call above is as it was.
+ * pt_closest_points returns one primitive per point; these return several (csrc/pt_knearest.hip): the contact set of a probe, the
+ * neighbours a smooth distance field is blended from, several candidates for registration or snapping, "how crowded is it around
+ * this sensor".
+ *
+ * Points are POINT4 records p.xyz | radius exactly as pt_closest_points takes them: r2 = radius * radius in float32, radius >= 0, +inf
+ *   allowed; triangles are numbered first, in the order of `tris`, spheres after them.  f(p, k) is the function of the section above,
+ *   operation for operation, for triangles and spheres.  Let C(p) = { k : f(p, k) <= r2 }.
+ * pt_nearest_k: the K nearest within the radius, sorted; defined without reference to any tree.  Order C(p_i) by f ascending, among
+ *   equal f the larger primitive index first (the tie rule of the closest query; no two members share both, so the order is total).
+ *   Slot j of point i, d_out[i * k + j], is (f, prim) of the j-th member for j < min(k, |C|); every later slot is the miss record
+ *   (0, -1).  Hence slot 0 is bit for bit what pt_closest_points(PT_NEAREST_CLOSEST) writes for the same record, k = 1 is that call,
+ *   the result equals a brute-force evaluation over the scene's current positions, and it is the same bits before and after a refit
+ *   or any rebuild.  1 <= k <= PT_NEAREST_KMAX.
+ * d_detail8 (may be NULL): one 8-float record per slot, d_detail8[(i * k + j) * 8 ..], in the layout of the section above,
+ *   c.xyz | v | w | side | feature | 0.  The record of a slot depends only on the point and the slot's primitive; a miss slot holds zeros.
+ * pt_count_within: d_count[i] = |C(p_i)|, uncapped.  With pt_nearest_k it tells whether the K slots were all there is; with k = 32 the
+ *   two calls together are "all primitives within a radius" for any neighbourhood of up to 32.  An infinite radius counts every
+ *   primitive by walking the whole tree: allowed, and the caller's cost.
+ * pt_nearest_k, pt_count_within: d_points4 (16-byte aligned), d_out (8-byte aligned), d_detail8 and d_count (4-byte aligned) are DEVICE
+ *   pointers on the scene's device holding n, n * k, n * k * 8 and n records.  Everything is enqueued on `hip_stream`: no host wait,
+ *   nothing is read back, nothing is allocated (pt_scene_device_bytes stays what it was); batches of at most 2^30 points go per
+ *   launch.  A query enqueued after pt_scene_update_vertices, pt_scene_rebuild_tree, pt_scene_rebuild_tree_ex or
+ *   pt_scene_rebuild_tree_opt on the same stream sees their result.  The buffers must stay valid until the stream has passed the
+ *   query.  A query leaves every render state alone: frames, pt_last_iterations, pt_last_counters, pt_last_render_ms.  Concurrency:
+ *   ONE query, update or render at a time per scene.
+ * pt_nearest_k_host, pt_count_within_host: the same on HOST arrays: upload, query on the NULL stream, wait and download.  h_out has
+ *   n * k records.
+ * NULL scene / points / out, n < 0, k < 1 or k > PT_NEAREST_KMAX and a misaligned device pointer return PT_ERR_INVALID before any
+ *   HIP call, no pointer dereferenced, the message naming the entry point; n = 0 returns PT_OK without one.
+ * A point with a non-finite coordinate, or a negative or NaN radius: the result for THAT point is unspecified (every prim stays in
+ *   [-1, number of primitives), every count in [0, number of primitives]), the other points of the batch are unaffected, and the
+ *   call ends by the argument of quad_step (csrc/pt_trace.h).
+ * Out of scope: k above 32, variable-length lists of all primitives within a radius, per-primitive masks, the k nearest along a ray,
+ * sorting the points for coherence, a multi-GPU split, a CLI option.
+ * -------------------------------------------------------------------------------- */
+#define PT_NEAREST_KMAX 32
+PT_API int  pt_nearest_k(PtScene* s, const float* d_points4, int64_t n, int32_t k, PtNearest* d_out /* n * k */,
+                         float* d_detail8 /* n * k * 8, may be NULL */, void* hip_stream);
+PT_API int  pt_nearest_k_host(PtScene* s, const float* h_points4, int64_t n, int32_t k, PtNearest* h_out, float* h_detail8 /* may be NULL */);
+PT_API int  pt_count_within(PtScene* s, const float* d_points4, int64_t n, int32_t* d_count, void* hip_stream);
+PT_API int  pt_count_within_host(PtScene* s, const float* h_points4, int64_t n, int32_t* h_count);
 
 /* ----------------------------------------------------------------------------------
  * Radiance along the caller's own rays (new: the reference reaches its integrator through a pinhole camera only).

@@ -93,6 +93,7 @@ class PtNearest(C.Structure):
 
 NEAREST_DTYPE = np.dtype([("dist2", "<f4"), ("prim", "<i4")])      # PtNearest as a numpy record
 NEAREST_CLOSEST, NEAREST_ANY = 0, 1
+NEAREST_KMAX = 32      # PT_NEAREST_KMAX: the most slots per point of pt_nearest_k
 AOV_FLOATS = 8        # floats per pixel of pt_render_aov: albedo.rgb | normal.xyz | depth | coverage
 
 _lib = None
@@ -220,6 +221,10 @@ API = [
     ("pt_trace_rays_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     ("pt_closest_points", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     ("pt_closest_points_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
+    ("pt_nearest_k", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    ("pt_nearest_k_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
+    ("pt_count_within", C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    ("pt_count_within_host", C.c_int, [_P, _P, C.c_int64, _P]),
     ("pt_rays_floats", C.c_int64, [C.c_int64]),
     ("pt_rays_work_bytes", C.c_int64, [C.POINTER(PtParams), C.c_int64]),
     ("pt_render_rays", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
@@ -254,6 +259,17 @@ def _check(rc, what):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _device_points(who, points, device):
+    """The host-side checks of a POINT4 tensor for the scene on `device`; returns n."""
+    if not (hasattr(points, "data_ptr") and hasattr(points, "is_contiguous")):
+        raise PtError(f"{who}: points must be a torch tensor or a numpy array")
+    if str(points.dtype) != "torch.float32" or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 4:
+        raise PtError(f"{who}: points must be contiguous float32 of shape (n, 4), got {points.dtype} {tuple(points.shape)}")
+    if points.device.type != "cuda" or points.device.index != device:
+        raise PtError(f"{who}: points is on {points.device}, the scene is on device {device}")
+    return points.shape[0]
 
 
 def _rebuild_params(depth_budget, large_fraction):
@@ -877,6 +893,53 @@ class Scene:
                                        C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_closest_points")
         out = (res[:, 0].view(torch.float32), res[:, 1])
         return out + (det,) if detail else out
+
+    def nearest_k(self, points, k, detail=False, stream_ptr=0):
+        """The k nearest primitives within each point's radius, sorted (include/pt_api.h: pt_nearest_k).  points: (n, 4) float32 POINT4
+        records, p.xyz radius (>= 0, inf allowed); 1 <= k <= NEAREST_KMAX.  Returns (dist2, prim) — float32 and int32 of shape (n, k),
+        nearest first, among equal dist2 the larger prim first, the slots past the last candidate (0, -1) — and, with detail=True, the
+        (n, k, 8) detail records c.xyz v w side feature 0 as a third item (zeros in a miss slot).
+        A torch float32 tensor on the scene's device is used in place (data_ptr()): the query is enqueued on stream_ptr, the results
+        are torch tensors on that device, valid once the stream has passed the query, and `points` must stay alive until then.
+        A numpy array goes through pt_nearest_k_host (synchronous) and returns numpy arrays."""
+        k = int(k)
+        if not 1 <= k <= NEAREST_KMAX:
+            raise PtError(f"nearest_k: k = {k}, want 1 .. {NEAREST_KMAX}")
+        if isinstance(points, np.ndarray):
+            p = np.ascontiguousarray(points, np.float32)
+            if p.ndim != 2 or p.shape[1] != 4:
+                raise PtError(f"nearest_k: points has shape {p.shape}, want (n, 4)")
+            n = p.shape[0]
+            res = np.zeros((n, k), NEAREST_DTYPE)
+            det = np.zeros((n, k, 8), np.float32) if detail else None
+            _check(lib().pt_nearest_k_host(self._h, _ptr(p), n, k, _ptr(res), _ptr(det) if detail else None), "pt_nearest_k_host")
+            out = (np.ascontiguousarray(res["dist2"]), np.ascontiguousarray(res["prim"]))
+            return out + (det,) if detail else out
+        n = _device_points("nearest_k", points, self.device)
+        import torch
+        res = torch.empty((n, k, 2), dtype=torch.int32, device=points.device)      # PtNearest: dist2's bits | prim
+        det = torch.empty((n, k, 8), dtype=torch.float32, device=points.device) if detail else None
+        _check(lib().pt_nearest_k(self._h, C.c_void_p(points.data_ptr()), n, k, C.c_void_p(res.data_ptr()),
+                                  C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_nearest_k")
+        out = (res[:, :, 0].view(torch.float32), res[:, :, 1])
+        return out + (det,) if detail else out
+
+    def count_within(self, points, stream_ptr=0):
+        """How many primitives lie within each point's radius (include/pt_api.h: pt_count_within), uncapped: (n,) int32.  points as in
+        nearest_k; an infinite radius counts every primitive, by walking the whole tree.  A torch tensor on the scene's device is
+        used in place and the count is a torch tensor there, in stream order; a numpy array goes through pt_count_within_host."""
+        if isinstance(points, np.ndarray):
+            p = np.ascontiguousarray(points, np.float32)
+            if p.ndim != 2 or p.shape[1] != 4:
+                raise PtError(f"count_within: points has shape {p.shape}, want (n, 4)")
+            cnt = np.zeros(p.shape[0], np.int32)
+            _check(lib().pt_count_within_host(self._h, _ptr(p), p.shape[0], _ptr(cnt)), "pt_count_within_host")
+            return cnt
+        n = _device_points("count_within", points, self.device)
+        import torch
+        cnt = torch.empty(n, dtype=torch.int32, device=points.device)
+        _check(lib().pt_count_within(self._h, C.c_void_p(points.data_ptr()), n, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_count_within")
+        return cnt
 
     def render_rays_device(self, d_rays_ptr, n_rays, prm, d_rgb_ptr, d_work_ptr, d_seed_ptr=0, seed_stride=None, stream_ptr=0):
         """Device-resident radiance along n_rays RAY8 records (raw device pointers: rays_floats(n) floats of output, rays_work_bytes(prm,

@@ -98,7 +98,9 @@ typedef struct PtParams {                                        /* the referenc
     int32_t spp_per_pass;     /* NUM_SAMPLE (1024)      */
     int32_t max_bounce;       /* MAX_BOUNCE (8)         */
     int32_t rr_bounce;        /* RUSSIAN_ROULETTE_BOUNCE (3) */
-    float   rr_floor;         /* PROB_STOP_BOUNCE (0.5) */
+    float   rr_floor;         /* PROB_STOP_BOUNCE (0.5).  Not validated: the roulette keeps a path with probability q = (m > floor) ? m : floor, m = min(maxcomp(weight), 1),
+                               * the reference's select-style max.  NaN: q is NaN and the path ends at the roulette; a negative floor is the same as 0;
+                               * above 1 the path always survives and its weight shrinks by 1 / floor per bounce. */
     int32_t max_refract;      /* the literal 8 of `RefractCnt++>8`, include/CudaUtil.cuh:354 */
     int32_t first_pass;       /* SampleIDX of the first pass of this call (seed = offset + SampleIDX*W*H, srcs/pathtracer.cu:71) */
     /* Tile split (new; the reference is single-device).  The frame is cut into 8x8-pixel
@@ -1102,7 +1104,9 @@ PT_API int  pt_dbg_trace_timeline(PtScene* s, int64_t* out3n, int32_t n_launches
 /* Render path: 1 = queue-driven wavefront pipeline (default: traversal and shading are
  * separate kernels, lanes refill from a ray queue), 0 = the one-kernel state machine.
  * Both produce bit-identical frames.  Environment PTAMD_MODE overrides the default.
- * pt_last_iterations: bounce iterations the pipeline needed for the last render. */
+ * pt_last_iterations: bounce iterations the pipeline launched for the last render.  The host reads the live-stream count every 16 to 64
+ * iterations (with wf_drain off: every 16), so this is the first such poll at or after the iteration that retired the last stream
+ * or handed the rest to wf_drain: with wf_drain off at most 15 more than the render needed. */
 PT_API int  pt_set_mode(PtScene* s, int32_t mode);
 /* Per-launch timing of the two pipeline kernels (mode 1): pt_enable_trace_timing makes every following render record HIP
  * events, on the launch stream, before and after each of its first max_launches wf_trace launches and after the wf_shade

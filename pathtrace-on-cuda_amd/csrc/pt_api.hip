@@ -34,12 +34,12 @@ static const int kTraceBlocks = (getenv("PTAMD_TB") && atoi(getenv("PTAMD_TB")) 
 // ---- geometry of the tile split --------------------------------------------------------
 int pt_check_params(const PtParams* prm)
 {
-    if (prm->spp_per_pass > 65535 || prm->max_bounce > 255 || prm->max_refract < 0 || prm->max_refract > 250) {
-        pt_set_error("params out of range: spp_per_pass <= 65535, max_bounce <= 255, 0 <= max_refract <= 250");
-        return PT_ERR_INVALID;
-    }
+    // the limits of the packed stream state (pt_stream.h: store_state)
+    if (prm->spp_per_pass > 65535) { pt_set_error("params out of range: spp_per_pass=%d, at most 65535", prm->spp_per_pass); return PT_ERR_INVALID; }
+    if (prm->max_bounce > 255) { pt_set_error("params out of range: max_bounce=%d, at most 255", prm->max_bounce); return PT_ERR_INVALID; }
+    if (prm->max_refract < 0 || prm->max_refract > 250) { pt_set_error("params out of range: max_refract=%d, 0 .. 250", prm->max_refract); return PT_ERR_INVALID; }
     if (prm->passes < 1 || prm->spp_per_pass < 1 || prm->max_bounce < 1 || prm->world < 1 || prm->rank < 0 || prm->rank >= prm->world) {
-        pt_set_error("bad params: passes=%d spp=%d max_bounce=%d rank=%d world=%d", prm->passes, prm->spp_per_pass, prm->max_bounce, prm->rank, prm->world);
+        pt_set_error("bad params: passes=%d spp_per_pass=%d max_bounce=%d rank=%d world=%d", prm->passes, prm->spp_per_pass, prm->max_bounce, prm->rank, prm->world);
         return PT_ERR_INVALID;
     }
     return PT_OK;

@@ -851,7 +851,7 @@ static void launch_trace(const ptd::WfJob& job, const ptd::WfBuf& b, int blocks,
 
 // The pipeline for one job whose streams take their pixel and camera from `cam` (DevCamera: a frame share or a tile list; ViewTable; RayTable):
 // `init` launches the kind's init kernel, and every later launch names the Cam instantiation of its kernel.
-// Blocks the host until the render has drained (it polls the live-stream count every 16..64 iterations).
+// Blocks the host until the render has drained (it polls the live-stream count every 16..64 iterations; every 16 with wf_drain off).
 template <class Cam, class Init>
 static hipError_t pipeline(const ptd::WfJob& job, const ptd::WfBuf& b, const Cam& cam, Init init)
 {
@@ -942,7 +942,9 @@ static hipError_t pipeline(const ptd::WfJob& job, const ptd::WfBuf& b, const Cam
             break;
         }
         if (it > hardCap) return hipErrorLaunchFailure;      // cannot happen for a well-formed scene; never spin forever
-        if (poll < 64) poll *= 2;
+        // with wf_drain off the render ends at the first poll that finds no stream alive, and every iteration launched after the last
+        // stream retired is an empty one: keep looking every 16, so that at most 15 of them are launched (and counted: pt_last_iterations)
+        if (poll < 64 && job.drainBelow != 0) poll *= 2;
         if (job.drainBelow > 0 && (unsigned long long)live <= (unsigned long long)job.drainBelow * 8ull) poll = 16;      // near the hand-over: look again soon
     }
     *job.iters = it;

@@ -760,7 +760,19 @@ PT_API int  pt_scene_rebuild_tree_opt(PtScene* s, const PtRebuildParams* p, int3
  *   |(1/dx, 1/dy, 1/dz)| >= 1 — every direction with components in [-1, 1] — that IS the reference's result; for longer directions
  *   the reference's box cull (a normalised entry distance against the un-scaled closest t) drops hits in an order-dependent way,
  *   which the device, here as in pt_dbg_raycast, does not imitate: it returns the closest hit in [0, tmax].
- * PT_QUERY_CLOSEST: d_hits[i] = (t, prim) of the closest hit, bit for bit what pt_dbg_raycast and the reference return; prim
+ *   Known defect (found by tests/test_slack.py, not yet fixed).  Float Moeller-Trumbore is ill-conditioned for thin
+ *   triangles and far origins: its barycentric error is about e = 2^-24 * kappa * |T|, kappa = |E1| |E2| / |E1 x E2|, T = org - V0.  Within
+ *   e of an edge it accepts rays that pass OUTSIDE the triangle's own box by more than the traversal trees' pads, while the
+ *   reference's leaf box (up to four triangles) still lets them through: the reference reports the hit and no walk of the trees here
+ *   reaches it.  Such a ray gets the closest hit among the triangles whose boxes it does enter (another primitive, or a miss), and
+ *   the 4-wide walk, the binary walk (PTAMD_QUERY_QUAD=0), pt_dbg_raycast and a tree after pt_scene_rebuild_tree need not agree on it.
+ *   The pads bound where it can happen: a ray is safe when e * (the triangle's longest edge) is within the absolute pad of the
+ *   4-wide boxes, maxabs * 2^-20 (maxabs: the scene's largest coordinate) — in a room 40 wide, an ordinary mesh triangle
+ *   (kappa 1.5, edge 2.6) seen from within about 160 units; the searches find the first such ray at e = 4.8 * 10^-5.  Outside that
+ *   it is rare, not absent: of 10^6 rays aimed at the ends and edges of 10 x 10^-3 slivers from inside the room 39, at box corners
+ *   of an ordinary mesh from 2^10 .. 2^19.5 away 34.  Every entry point that traces rays shares it.
+ * PT_QUERY_CLOSEST: d_hits[i] = (t, prim) of the closest hit, bit for bit what pt_dbg_raycast and the reference return (but for the
+ *   rays of the known defect above); prim
  *   counts triangles first (the order of `tris`) and spheres after them; a miss is prim = -1, t = 0.  d_surface29 is NULL or
  *   receives, per ray, the 29-float HIT record exactly as pt_dbg_raycast writes it (zeros for a miss).
  * PT_QUERY_ANY: prim >= 0 exactly when the closest-hit query of the same ray hits.  The hit returned is SOME hit the reference

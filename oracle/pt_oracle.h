@@ -83,6 +83,8 @@ int   o_scene_num_lights(void* scene);
 void o_raycast(void* scene, const float* rays8, int R, float* out_hits, int* out_prim,
                int64_t* counters);
 
+void o_render_rays(void* scene, const float* rays8, int n, const OParams* prm, const int* seeds, int stride, float* out_rgb);   /* ray i in the place of a pixel: include/pt_api.h, pt_render_rays */
+
 void o_camera_basis(const float rot_deg[3], float forward[3], float up[3], float right[3]);
 
 int  o_render(void* scene, const OCamera* cam, const OParams* prm, float* accum_rgb,

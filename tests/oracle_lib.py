@@ -62,6 +62,7 @@ def lib():
         l.o_camera_basis.argtypes = [P, P, P, P]
         l.o_render.restype = C.c_int
         l.o_render.argtypes = [P, C.POINTER(OCamera), C.POINTER(OParams), P, P, C.c_int]
+        l.o_render_rays.argtypes = [P, P, C.c_int, C.POINTER(OParams), P, C.c_int, P]
         l.o_tonemap.argtypes = [P, C.c_int, C.c_int, P]
         l.o_u8.argtypes = [P, C.c_int, P]
         l.o_pixel_dir.argtypes = [C.POINTER(OCamera), P, C.c_int, P]
@@ -183,6 +184,15 @@ class Scene:
         a = np.ascontiguousarray(in5, np.float32).reshape(-1, 5)
         out = np.zeros((a.shape[0], 12), np.float32)
         lib().o_nee(self._h, _p(a), a.shape[0], _p(out))
+        return out
+
+    def render_rays(self, rays8, prm, seeds=None, stride=None):
+        """(n, 3) float32: the radiance along RAY8 records as pt_render_rays defines it (ray i in the place of a pixel, the direction used as given)."""
+        rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
+        n = rays8.shape[0]
+        out = np.zeros((n, 3), np.float32)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, np.int32)
+        lib().o_render_rays(self._h, _p(rays8), n, C.byref(prm), None if sd is None else _p(sd), n if stride is None else int(stride), _p(out))
         return out
 
     def render(self, cam, prm, nthreads=8, accum=None):

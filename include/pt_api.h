@@ -903,7 +903,7 @@ PT_API int  pt_closest_points_host(PtScene* s, const float* h_points4, int64_t n
  * A point with a non-finite coordinate, or a negative or NaN radius: the result for THAT point is unspecified (every prim stays in
  *   [-1, number of primitives), every count in [0, number of primitives]), the other points of the batch are unaffected, and the
  *   call ends by the argument of quad_step (csrc/pt_trace.h).
- * Out of scope: k above 32, variable-length lists of all primitives within a radius, per-primitive masks, the k nearest along a ray,
+ * Out of scope: k above 32, variable-length lists of all primitives within a radius, per-primitive masks, the k nearest along a ray (the next section),
  * sorting the points for coherence, a multi-GPU split, a CLI option.
  * -------------------------------------------------------------------------------- */
 #define PT_NEAREST_KMAX 32
@@ -912,6 +912,73 @@ PT_API int  pt_nearest_k(PtScene* s, const float* d_points4, int64_t n, int32_t 
 PT_API int  pt_nearest_k_host(PtScene* s, const float* h_points4, int64_t n, int32_t k, PtNearest* h_out, float* h_detail8 /* may be NULL */);
 PT_API int  pt_count_within(PtScene* s, const float* d_points4, int64_t n, int32_t* d_count, void* hip_stream);
 PT_API int  pt_count_within_host(PtScene* s, const float* h_points4, int64_t n, int32_t* h_count);
+
+/* ----------------------------------------------------------------------------------
+ * First K hits along a ray and hit counts (new: the reference keeps the closest hit only).  Opt-in: every call above is as it was.
+ * pt_trace_rays returns one hit per ray; these return several, or their number (csrc/pt_rayhits.hip): what lies behind the first
+ * surface (x-ray, thickness, multi-return range simulation, transmission through several walls), how many surfaces a segment
+ * crosses (its parity is an inside / outside test), and what the back faces do, which every other ray entry point culls.
+ *
+ * Rays are RAY8 records exactly as pt_trace_rays takes them: org.xyz | dir.xyz | reserved (not read) | tmax; the direction is used as
+ *   given, t is the parameter along it, the range is [0, tmax]; primitives are numbered triangles first, in the order of `tris`, then
+ *   spheres.  flags is PT_HITS_FRONT (back faces culled, as everywhere else) or PT_HITS_BOTH_SIDES.
+ * Arithmetic: IEEE float32, every operation below rounded once and none contracted, in the order written;
+ *     dot(a, b)   = (ax*bx + ay*by) + az*bz
+ *     cross(a, b) = (ay*bz - az*by, -(ax*bz - az*bx), ax*by - ay*bx)
+ * Triangle k, V0 E1 E2 from its record (the PtTriangle fields v0, E1, E2), kEps = 1e-4f:
+ *     T = org - V0;  P = cross(dir, E2);  Q = cross(T, E1)
+ *     det = dot(P, E1);  t = dot(Q, E2) * (1 / det);  u = dot(P, T);  v = dot(Q, dir)
+ *   FRONT acceptance (Triangle::hit's, operation for operation, facing +1):
+ *     !(det < kEps)  &&  !(t < 0)  &&  !(t > tmax)  &&  !(u < 0 || u > det)  &&  !(v < 0 || v + u > det)
+ *     && the ray passes the reference's slab test of the triangle's reference leaf box, uncut (the rule of the ray-query section;
+ *        it passes always for a degenerate ray: one whose |(1/dx, 1/dy, 1/dz)| is not finite, i.e. a direction with a zero component).
+ *   BACK acceptance (counted only under PT_HITS_BOTH_SIDES, facing -1): !(-det < kEps), the same t, and the same four range tests
+ *     on -u, -v, -det (negation is exact); the same leaf-box condition.  No triangle is accepted on both sides.
+ * Sphere j (prim = number of triangles + j), center c, radius rad:
+ *     oc = org - c;  a = dot(dir, dir);  half_b = dot(oc, dir);  cc = dot(oc, oc) - rad * rad;  disc = half_b * half_b - a * cc
+ *     disc < 0: no hit.  sq = sqrt(disc);  r1 = (-half_b - sq) / a;  r2 = (-half_b + sq) / a;  a root r is valid when !(r < 0) && !(tmax < r)
+ *   PT_HITS_FRONT: the one root Sphere::hit returns for [0, tmax]: r1 if valid, else r2 if valid.
+ *   PT_HITS_BOTH_SIDES: r1 if valid (entering, facing +1), and r2 if valid and r2 != r1 (leaving, facing -1).
+ * H(ray) is the set of accepted (t, prim, facing) records; only a sphere under PT_HITS_BOTH_SIDES can contribute two records with one
+ *   prim, and they differ in t.  Order: t ascending, compared as floats (-0 equals +0); among equal t the larger prim first — the tie
+ *   rule of every ray entry point here.
+ * pt_trace_rays_k: slot j of ray i, d_hits[i * k + j], is the j-th member of H(ray i) for j < min(k, |H|); every later slot is the miss
+ *   record (0, -1).  1 <= k <= PT_RAY_HITS_KMAX.  t's bits are the float's own (a hit at -0.0 is reported as -0.0).  The definition
+ *   names no tree: the result is the same bits before and after a refit or any rebuild and equals a brute-force evaluation over the
+ *   scene's current positions.  With PT_HITS_FRONT slot 0 is bit for bit what pt_trace_rays(PT_QUERY_CLOSEST) writes for the same
+ *   ray, and k = 1 is that call.  The known defect of the ray-query section (rays that Moeller-Trumbore accepts
+ *   outside the boxes no tree lets them into) applies to every member of H as it does to the closest hit.
+ * d_detail4 (may be NULL): 4 floats per slot, d_detail4[(i * k + j) * 4 ..]:  u * (1 / det) | v * (1 / det) | facing | 0, so that the
+ *   hit point is approximately V0 + that * E1 + that * E2.  A sphere slot has 0 | 0 | facing | 0; a miss slot holds zeros.
+ * pt_count_hits: d_count[i] = |H(ray i)|, uncapped, int32.  With pt_trace_rays_k it tells whether the K slots were all there is.
+ * pt_trace_rays_k, pt_count_hits: d_rays8 (16-byte aligned), d_hits (8-byte aligned), d_detail4 and d_count (4-byte aligned) are DEVICE
+ *   pointers on the scene's device holding n, n * k, n * k * 4 and n records.  Everything is enqueued on `hip_stream`: no host wait,
+ *   nothing is read back, nothing is allocated (pt_scene_device_bytes stays what it was); batches of at most 2^30 rays go per launch.
+ *   A query enqueued after pt_scene_update_vertices, pt_scene_rebuild_tree, pt_scene_rebuild_tree_ex or pt_scene_rebuild_tree_opt on
+ *   the same stream sees their result.  The buffers must stay valid until the stream has passed the query.  A query leaves every render
+ *   state alone: frames, pt_last_iterations, pt_last_counters, pt_last_render_ms.  Concurrency: ONE query, update or render at a time
+ *   per scene.
+ * pt_trace_rays_k_host, pt_count_hits_host: the same on HOST arrays: upload, query on the NULL stream, wait and download.  h_hits has
+ *   n * k records.
+ * NULL scene / rays / hits / count, n < 0, k < 1 or k > PT_RAY_HITS_KMAX, flags other than the two values and a misaligned device
+ *   pointer return PT_ERR_INVALID before any HIP call, no pointer dereferenced, the message naming the entry point; n = 0 returns
+ *   PT_OK without one.
+ * A ray with a non-finite component or a zero direction: the result for THAT ray is unspecified (every prim stays in [-1, number of
+ *   primitives), every count in [0, number of triangles + 2 * number of spheres]), the other rays of the batch are unaffected, and the
+ *   call ends by the argument of quad_step (csrc/pt_trace.h).
+ * Cost: k = 1 costs more than the lean closest-hit kernel — measured 1.16 to 1.33 times pt_trace_rays(PT_QUERY_CLOSEST) on 2 M rays
+ *   (DESIGN.md section 34): for one hit per ray call pt_trace_rays.
+ * Out of scope: k above 32, variable-length lists, tmin other than 0, primitive masks, the 29-float surface record per slot, a CLI
+ * option, a multi-GPU split.
+ * -------------------------------------------------------------------------------- */
+#define PT_RAY_HITS_KMAX   32
+#define PT_HITS_FRONT      0
+#define PT_HITS_BOTH_SIDES 1
+PT_API int  pt_trace_rays_k(PtScene* s, const float* d_rays8, int64_t n, int32_t k, int32_t flags, PtRayHit* d_hits /* n * k */,
+                            float* d_detail4 /* n * k * 4, may be NULL */, void* hip_stream);
+PT_API int  pt_trace_rays_k_host(PtScene* s, const float* h_rays8, int64_t n, int32_t k, int32_t flags, PtRayHit* h_hits, float* h_detail4 /* may be NULL */);
+PT_API int  pt_count_hits(PtScene* s, const float* d_rays8, int64_t n, int32_t flags, int32_t* d_count, void* hip_stream);
+PT_API int  pt_count_hits_host(PtScene* s, const float* h_rays8, int64_t n, int32_t flags, int32_t* h_count);
 
 /* ----------------------------------------------------------------------------------
  * Radiance along the caller's own rays (new: the reference reaches its integrator through a pinhole camera only).

@@ -1,0 +1,440 @@
+// pt_rayhits.hip — the first K hits along each of the caller's rays, sorted, and the number of hits, on an uploaded scene
+// (include/pt_api.h: pt_trace_rays_k, pt_count_hits).  DESIGN.md section 34.
+//
+// Both are DEFINED without a tree, over H(ray) = the (t, prim, facing) records the header's acceptance rules admit in [0, tmax]: the
+// first K members of H in the order (t ascending as floats, among equal t the larger prim first), and |H|.  The walks only have to
+// find them.  A box on the way to a member at t is entered by the ray no later than t (in the walk's units, with the slack the
+// closest-hit walk already relies on), so a child culled at `bound` holds no member at t <= bound: quad_step's argument with the
+// closest hit replaced by the sink's bound — tmax while the list holds fewer than K, then the t of its last slot (it only ever
+// decreases); for the count it is tmax throughout.  The cull lets a box through whose entry EQUALS the bound, so a tie at the bound
+// is still met and the tie rule decides.  As in pt_knearest.hip every triangle must sit below exactly ONE leaf of the tree walked.
+//
+// Shape: query_rays' (pt_query.hip) — one ray per lane, one-wave workgroups, the per-lane int stack in LDS with entry e at
+// stack[e * 64].  Beside it nearest_k's per-lane list, sorted, slot j at list[j * kHitRow + lane] as int2 (t's bits, prim).  t is
+// compared as a FLOAT (-0 equals +0, and its bits go out as pt_trace_rays would write them).  Facing is not stored: the detail kernel
+// recomputes it from the sign of det (a triangle) or from which root the slot holds (a sphere).
+#include <hip/hip_runtime.h>
+#include "pt_device.h"
+#include "pt_math.h"
+#include "pt_trace.h"
+#include "pt_scene.h"
+
+namespace ptd {
+
+constexpr int kHitRow = 65;      // int2 entries from one slot of the list to the next: pt_knearest.hip's kListRow, for the same copy-out
+
+// What a walk hands its hits to.  `bound`: a box the ray enters beyond this holds nothing the sink would take.  wants(): the sink's
+// precondition, asked before the leaf box is fetched; take(): only after a wants() on the sink as it is now.
+// The list of the first K.  (bound, boundPrim) is (tmax, -1) while cnt < k and slot k - 1 from then on, so that ONE rule accepts:
+// t < bound, or t == bound and a larger prim — with fewer than k that is t <= tmax, with k it is "precedes the last slot".  A NaN t
+// passes neither comparison.  Every slot index is at most min(cnt, k - 1) <= k - 1, and the kernel has checked k <= KC.
+struct HitList {
+    int2* list;      // this lane's slot 0
+    int k, cnt;
+    float bound;
+    int boundPrim;
+    PT_DEV bool wants(float t, int prim) const { return (t < bound) | ((t == bound) & (prim > boundPrim)); }
+    PT_DEV void take(float t, int prim)
+    {
+        int j = (cnt < k) ? cnt : k - 1;      // the slot that opens: the next free one, or the last, whose hit drops out
+        while (j > 0) {                       // shift from the tail until the slot before precedes the hit
+            const int2 e = list[(j - 1) * kHitRow];
+            const float et = __int_as_float(e.x);
+            if ((et < t) | ((et == t) & (e.y > prim))) break;
+            list[j * kHitRow] = e;
+            j--;
+        }
+        list[j * kHitRow] = make_int2(__float_as_int(t), prim);
+        cnt += (cnt < k) ? 1 : 0;
+        if (cnt == k) {
+            const int2 last = list[(k - 1) * kHitRow];
+            bound = __int_as_float(last.x);
+            boundPrim = last.y;
+        }
+    }
+};
+
+// |H|: the bound stays tmax
+struct HitCount {
+    int cnt;
+    float bound;
+    PT_DEV bool wants(float t, int) const { return !(t > bound); }
+    PT_DEV void take(float, int) { cnt++; }
+};
+
+// One triangle of a binary-tree leaf, from its tri record: tri_test's arithmetic and test order (pt_trace.h), the two-sided rule of
+// tri_hits_pairrec, the sink's precondition before the reference leaf box.
+template <bool BOTH, class SINK>
+PT_DEV void tri_hits(const DevScene& sc, int q, const f3& org, const f3& dir, const f3& invD, bool degenerate, SINK& s)
+{
+    const float4 a = sc.tri[3 * (size_t)q], b = sc.tri[3 * (size_t)q + 1], c = sc.tri[3 * (size_t)q + 2];
+    const f3 V0(a.x, a.y, a.z), E1(b.x, b.y, b.z), E2(c.x, c.y, c.z);
+    const f3 T = org - V0;
+    const f3 P = cross(dir, E2);
+    const f3 Q = cross(T, E1);
+    float det = dot(P, E1);
+    const bool back = BOTH & (det < kEps);
+    const float t = dot(Q, E2) * (1.f / det);
+    float u = dot(P, T), v = dot(Q, dir);
+    if (back) { det = -det; u = -u; v = -v; }
+    if (det < kEps) return;
+    if (t < 0.f) return;
+    if (u < 0.f || u > det) return;
+    if (v < 0.f || (v + u) > det) return;
+    const int prim = __float_as_int(a.w);
+    if (!s.wants(t, prim)) return;
+    if (!degenerate) {
+        const int leaf = __float_as_int(b.w);
+        const float4 l0 = sc.leafbox[2 * leaf], l1 = sc.leafbox[2 * leaf + 1];
+        float tn;
+        if (!box_test(l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, org, invD, __builtin_inff(), tn)) return;
+    }
+    s.take(t, prim);
+}
+
+// The walk over the 4-wide quantised tree: quad_step's (pt_trace.h) with the sink's bound where the closest hit was, and no early
+// out.  A node pushes at most three of its children and descends into the fourth, a leaf pushes nothing: at most 3 entries per
+// level (the caller has checked 3 * quad_depth + 2 <= kQueryStack), and the walk ends whatever the floats are.
+template <bool BOTH, class SINK>
+PT_DEV void hits_walk_quad(const DevScene& sc, const f3& org, const f3& dir, int* stack, SINK& s)
+{
+    f3 inv; float cscale; bool degenerate;
+    ray_setup(dir, inv, cscale, degenerate);
+    int cur = 0, sp = 0;
+    for (;;) {
+        if (cur >= 0) {
+            const uint4* np = sc.quad + 4 * (size_t)cur;
+            const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
+            int k0, k1, k2, k3, r0, r1, r2, r3;
+            quad_order(n0, n1, n2, n3, org, inv, s.bound * cscale, k0, k1, k2, k3, r0, r1, r2, r3);
+            if (quad_descend(k0, k1, k2, k3, r0, r1, r2, r3, cur, [&](int ref) { stack[sp * 64] = ref; sp++; })) continue;
+        } else {
+            const int code = ~cur;
+            int first = code >> 3, cnt = code & 7;
+            while (cnt > 0) { tri_hits_pairrec<BOTH>(sc, first, cnt > 1, org, dir, inv, degenerate, s); first += 2; cnt -= 2; }
+        }
+        if (sp == 0) return;
+        sp--;
+        cur = stack[sp * 64];
+    }
+}
+
+// The walk over the binary tree, for a scene whose 4-wide walk would not fit kQueryStack (or PTAMD_QUERY_QUAD=0): trace_closest's
+// control flow (pt_trace.h) — leaves tested on the spot, an entry pushed only where both children are interior: at most
+// depth - 1 <= 31 entries — with the sink's bound in cullB.
+template <bool BOTH, class SINK>
+PT_DEV void hits_walk_binary(const DevScene& sc, const f3& org, const f3& dir, int* stack, SINK& s)
+{
+    const f3 inv(1.f / dir.x, 1.f / dir.y, 1.f / dir.z);
+    const float L = __builtin_sqrtf(inv.x * inv.x + inv.y * inv.y + inv.z * inv.z);
+    const f3 invD = inv / L;
+    const bool degenerate = !(L < __builtin_inff());
+    const float kcull = degenerate ? 1.0078125f : 1.0078125f / L;
+    float cullB = s.bound * kcull;
+    int sp = 0, cur = 0;
+    for (;;) {
+        const float4 q0 = sc.nodes[4 * (size_t)cur + 0], q1 = sc.nodes[4 * (size_t)cur + 1], q2 = sc.nodes[4 * (size_t)cur + 2], q3 = sc.nodes[4 * (size_t)cur + 3];
+        float tnL, tnR;
+        bool okL, okR;
+        if (!degenerate) {
+            okL = box_test(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, org, invD, cullB, tnL);
+            okR = box_test(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, org, invD, cullB, tnR);
+        } else {
+            okL = box_test_robust(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, org, dir, inv, cullB, tnL);
+            okR = box_test_robust(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, org, dir, inv, cullB, tnR);
+        }
+        const int refL = __float_as_int(q3.x), refR = __float_as_int(q3.y);
+        if (okL && refL < 0) {
+            const int code = ~refL, first = code >> 3, cnt = code & 7;
+            for (int k = 0; k < cnt; k++) tri_hits<BOTH>(sc, first + k, org, dir, invD, degenerate, s);
+            cullB = s.bound * kcull;
+            okL = false;
+        }
+        if (okR && refR < 0) {
+            if (tnR <= cullB) {      // against what the left leaf left
+                const int code = ~refR, first = code >> 3, cnt = code & 7;
+                for (int k = 0; k < cnt; k++) tri_hits<BOTH>(sc, first + k, org, dir, invD, degenerate, s);
+                cullB = s.bound * kcull;
+            }
+            okR = false;
+        }
+        if (okL & okR) {
+            const bool lNear = tnL <= tnR;
+            stack[sp * 64] = lNear ? refR : refL;
+            sp++;
+            cur = lNear ? refL : refR;
+        } else if (okL) {
+            cur = refL;
+        } else if (okR) {
+            cur = refR;
+        } else {
+            if (sp == 0) return;
+            sp--;
+            cur = stack[sp * 64];
+        }
+    }
+}
+
+// The spheres, in order, after the walk: sphere_root's values (pt_trace.h), both roots kept apart.  Front: the one root Sphere::hit
+// returns for [0, tmax].  Both sides: r1 if valid, and r2 if valid and not r1 again (r1 <= r2: the list takes them in that order).
+template <bool BOTH, class SINK>
+PT_DEV void sphere_hits(const DevScene& sc, const f3& org, const f3& dir, float tmax, SINK& s)
+{
+    for (int j = 0; j < sc.n_spheres; j++) {
+        const float4 c = sc.spheres[4 * j];
+        const f3 oc = org - f3(c.x, c.y, c.z);
+        const float a = sqlen(dir);
+        const float half_b = dot(oc, dir);
+        const float cc = sqlen(oc) - c.w * c.w;
+        const float disc = half_b * half_b - a * cc;
+        if (disc < 0.f) continue;
+        const float sq = __builtin_sqrtf(disc);
+        const float r1 = (-half_b - sq) / a, r2 = (-half_b + sq) / a;
+        const bool v1 = !(r1 < 0.f) & !(tmax < r1), v2 = !(r2 < 0.f) & !(tmax < r2);
+        const int prim = sc.n_tris + j;
+        if (BOTH) {
+            if (v1 && s.wants(r1, prim)) s.take(r1, prim);
+            if (v2 && r2 != r1 && s.wants(r2, prim)) s.take(r2, prim);
+        } else {
+            const float r = v1 ? r1 : r2;
+            if ((v1 | v2) && s.wants(r, prim)) s.take(r, prim);
+        }
+    }
+}
+
+PT_DEV void load_ray8(const float4* __restrict__ rays, size_t i, f3& org, f3& dir, float& tmax)
+{
+    const float4 a = rays[2 * i], b = rays[2 * i + 1];
+    org = f3(a.x, a.y, a.z); dir = f3(a.w, b.x, b.y); tmax = b.w;
+}
+
+template <bool QUAD, bool BOTH, class SINK>
+PT_DEV void hits_ray(const DevScene& sc, const f3& org, const f3& dir, float tmax, int* stack, SINK& s)
+{
+    if (QUAD) hits_walk_quad<BOTH>(sc, org, dir, stack, s);
+    else hits_walk_binary<BOTH>(sc, org, dir, stack, s);
+    sphere_hits<BOTH>(sc, org, dir, tmax, s);
+}
+
+// KC: the capacity class of the list, the smallest of 4, 8, 16, 32 that holds k (launch_rays_k).  The wave's 64 rays own the 64 * k
+// consecutive records from out[blockIdx.x * 64 * k]; every lane pads its list with miss records and the wave copies the block out
+// of LDS in record order, 64 consecutive records (512 bytes) per store, exactly as nearest_k does.
+// No waves-per-SIMD figure in the launch bounds, as in nearest_k: above KC = 4 the list's LDS, not the registers, decides how many
+// workgroups a CU holds (DESIGN.md section 34 has the table; the registers allow kQueryWaves in every instantiation).
+template <int KC, bool QUAD, bool BOTH>
+__global__ __launch_bounds__(64)
+void rays_k(DevScene sc, const float4* __restrict__ rays, uint32_t n, int k, int2* __restrict__ out)
+{
+    __shared__ int lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    __shared__ int2 lds_list[KC * kHitRow];
+    if (k < 1 || k > KC) return;      // the launcher's choice of KC, restated where the list is indexed
+    const uint32_t lane = threadIdx.x, base = blockIdx.x * 64u, i = base + lane;
+    int2* list = &lds_list[lane];
+    int cnt = 0;
+    if (i < n) {
+        f3 org, dir; float tmax;
+        load_ray8(rays, i, org, dir, tmax);
+        HitList s{list, k, 0, tmax, -1};
+        hits_ray<QUAD, BOTH>(sc, org, dir, tmax, &lds_stack[lane], s);
+        cnt = s.cnt;
+    }
+    for (int j = cnt; j < k; j++) list[j * kHitRow] = make_int2(0, -1);      // a miss is (0, -1)
+    __syncthreads();
+    const uint32_t live = (n - base < 64u) ? n - base : 64u, total = live * (uint32_t)k;
+    int2* dst = out + (size_t)base * (size_t)k;
+    const int q64 = 64 / k, m64 = 64 % k;
+    int t = (int)lane / k, j = (int)lane % k;      // record r is slot j of ray t: r = t * k + j, t < live <= 64
+    for (uint32_t r = lane; r < total; r += 64u) {
+        dst[r] = lds_list[j * kHitRow + t];
+        j += m64;
+        t += q64;
+        if (j >= k) { j -= k; t++; }
+    }
+}
+
+template <bool QUAD, bool BOTH>
+__global__ __launch_bounds__(64, kQueryWaves)
+void count_hits(DevScene sc, const float4* __restrict__ rays, uint32_t n, int32_t* __restrict__ out)
+{
+    __shared__ int lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    f3 org, dir; float tmax;
+    load_ray8(rays, i, org, dir, tmax);
+    HitCount s{0, tmax};
+    hits_ray<QUAD, BOTH>(sc, org, dir, tmax, &lds_stack[threadIdx.x], s);
+    out[i] = s.cnt;
+}
+
+// The 4-float detail record of the header for every finished slot, one thread per slot; zeros for a miss slot.  Slot t belongs to
+// ray t / k.  A triangle is read from its surface record (indexed by primitive in the reference's order), which starts with V0 E1 E2,
+// the floats its tri record holds.  Facing: a triangle was taken as a back face iff det < kEps; a sphere slot holds the entering
+// root iff r1 is valid and is the slot's t (r2 is only ever kept beside a valid r1 when it differs from it).
+// A launch covers the slots from `first` on (launch_rays_k: at most kHitDetailSlots of them, so that no grid exceeds 2^31 threads).
+__global__ __launch_bounds__(256)
+void rays_k_detail(DevScene sc, const float4* __restrict__ rays, uint64_t first, uint64_t slots, uint32_t k, const int2* __restrict__ res, float* __restrict__ out4)
+{
+    const uint64_t t = first + (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= slots) return;
+    const int2 h = res[t];
+    const int prim = h.y;
+    float* o = out4 + t * 4;      // 4-byte aligned: four stores
+    if (prim < 0) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; return; }
+    f3 org, dir; float tmax;
+    load_ray8(rays, t / k, org, dir, tmax);
+    if (prim >= sc.n_tris) {
+        const float4 c = sc.spheres[4 * (prim - sc.n_tris)];
+        const f3 oc = org - f3(c.x, c.y, c.z);
+        const float a = sqlen(dir);
+        const float half_b = dot(oc, dir);
+        const float cc = sqlen(oc) - c.w * c.w;
+        const float disc = half_b * half_b - a * cc;
+        const float r1 = (-half_b - __builtin_sqrtf(disc)) / a;
+        const bool entering = !(r1 < 0.f) & !(tmax < r1) & (r1 == __int_as_float(h.x));
+        o[0] = 0.f; o[1] = 0.f; o[2] = entering ? 1.f : -1.f; o[3] = 0.f;
+        return;
+    }
+    const float4* rec = sc.surf + 12 * (size_t)prim;
+    const float4 s0 = rec[0], s1 = rec[1], s2 = rec[2];
+    const f3 V0(s0.x, s0.y, s0.z), E1(s0.w, s1.x, s1.y), E2(s1.z, s1.w, s2.x);
+    const f3 T = org - V0;
+    const f3 P = cross(dir, E2);
+    const f3 Q = cross(T, E1);
+    const float det = dot(P, E1);
+    const float invDet = 1.f / det;
+    o[0] = dot(P, T) * invDet; o[1] = dot(Q, dir) * invDet; o[2] = (det < kEps) ? -1.f : 1.f; o[3] = 0.f;
+}
+
+}  // namespace ptd
+
+template <int KC>
+static void launch_rays_kc(const ptd::DevScene& sc, const float4* rays, uint32_t n, int k, bool quad, bool both, int2* out, hipStream_t stream)
+{
+    const dim3 blocks((n + 63u) / 64u);
+    if (quad) {
+        if (both) hipLaunchKernelGGL((ptd::rays_k<KC, true, true>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
+        else hipLaunchKernelGGL((ptd::rays_k<KC, true, false>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
+    } else {
+        if (both) hipLaunchKernelGGL((ptd::rays_k<KC, false, true>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
+        else hipLaunchKernelGGL((ptd::rays_k<KC, false, false>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
+    }
+}
+
+static const uint64_t kHitDetailSlots = (uint64_t)1 << 31;      // slots per launch of rays_k_detail (a multiple of its 256 threads)
+
+// Enqueues one batch of n <= 2^30 rays on `stream`: k records per ray, then the detail records if asked for
+static hipError_t launch_rays_k(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, int k, bool quad, bool both, PtRayHit* d_hits, float* d_detail4, hipStream_t stream)
+{
+    const float4* rays = (const float4*)d_rays8;
+    int2* out = (int2*)d_hits;
+    if (k <= 4) launch_rays_kc<4>(sc, rays, n, k, quad, both, out, stream);
+    else if (k <= 8) launch_rays_kc<8>(sc, rays, n, k, quad, both, out, stream);
+    else if (k <= 16) launch_rays_kc<16>(sc, rays, n, k, quad, both, out, stream);
+    else launch_rays_kc<32>(sc, rays, n, k, quad, both, out, stream);
+    if (d_detail4) {      // 2^30 rays are up to 2^35 slots: several launches, each of at most 2^31 threads
+        const uint64_t slots = (uint64_t)n * (uint64_t)k;
+        for (uint64_t first = 0; first < slots; first += kHitDetailSlots) {
+            const uint64_t m = slots - first < kHitDetailSlots ? slots - first : kHitDetailSlots;
+            hipLaunchKernelGGL(ptd::rays_k_detail, dim3((uint32_t)((m + 255u) / 256u)), dim3(256), 0, stream, sc, rays, first, slots, (uint32_t)k, (const int2*)out, d_detail4);
+        }
+    }
+    return hipGetLastError();
+}
+
+static hipError_t launch_count_hits(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, bool quad, bool both, int32_t* d_count, hipStream_t stream)
+{
+    const dim3 blocks((n + 63u) / 64u);
+    const float4* rays = (const float4*)d_rays8;
+    if (quad) {
+        if (both) hipLaunchKernelGGL((ptd::count_hits<true, true>), blocks, dim3(64), 0, stream, sc, rays, n, d_count);
+        else hipLaunchKernelGGL((ptd::count_hits<true, false>), blocks, dim3(64), 0, stream, sc, rays, n, d_count);
+    } else {
+        if (both) hipLaunchKernelGGL((ptd::count_hits<false, true>), blocks, dim3(64), 0, stream, sc, rays, n, d_count);
+        else hipLaunchKernelGGL((ptd::count_hits<false, false>), blocks, dim3(64), 0, stream, sc, rays, n, d_count);
+    }
+    return hipGetLastError();
+}
+
+// ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
+// out_align: 8 for PtRayHit records, 4 for counts.  has_k: pt_trace_rays_k and its host variant.
+static int hits_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, bool has_k, int32_t k, int32_t flags, const void* out, int out_align,
+                        const float* detail, bool device)
+{
+    const char* bad = !s ? "NULL scene" : !rays ? "NULL rays" : !out ? "NULL out" : n < 0 ? "n < 0" :
+                      (has_k && (k < 1 || k > PT_RAY_HITS_KMAX)) ? "k must be in 1 .. PT_RAY_HITS_KMAX" :
+                      (flags != PT_HITS_FRONT && flags != PT_HITS_BOTH_SIDES) ? "flags must be PT_HITS_FRONT or PT_HITS_BOTH_SIDES" :
+                      (device && ((uintptr_t)rays & 15)) ? "rays must be 16-byte aligned" :
+                      (device && ((uintptr_t)out & (uintptr_t)(out_align - 1))) ? (out_align == 8 ? "hits must be 8-byte aligned" : "count must be 4-byte aligned") :
+                      (device && ((uintptr_t)detail & 3)) ? "detail must be 4-byte aligned" : nullptr;
+    if (bad) { pt_set_error("%s: %s", who, bad); return PT_ERR_INVALID; }
+    return PT_OK;
+}
+
+static const int64_t kHitsBatch = (int64_t)1 << 30;      // rays per launch: ray numbers are 32-bit
+
+extern "C" {
+
+int pt_trace_rays_k(PtScene* s, const float* d_rays8, int64_t n, int32_t k, int32_t flags, PtRayHit* d_hits, float* d_detail4, void* hip_stream)
+{
+    int rc;
+    if ((rc = hits_args_ok("pt_trace_rays_k", s, d_rays8, n, true, k, flags, d_hits, 8, d_detail4, true)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s), both = flags == PT_HITS_BOTH_SIDES;
+    for (int64_t off = 0; off < n; off += kHitsBatch) {
+        const uint32_t m = (uint32_t)(n - off < kHitsBatch ? n - off : kHitsBatch);
+        HIPCHK(launch_rays_k(s->dev, d_rays8 + off * 8, m, k, quad, both, d_hits + off * k, d_detail4 ? d_detail4 + off * k * 4 : nullptr, (hipStream_t)hip_stream));
+    }
+    return PT_OK;
+}
+
+int pt_trace_rays_k_host(PtScene* s, const float* h_rays8, int64_t n, int32_t k, int32_t flags, PtRayHit* h_hits, float* h_detail4)
+{
+    int rc;
+    if ((rc = hits_args_ok("pt_trace_rays_k_host", s, h_rays8, n, true, k, flags, h_hits, 8, h_detail4, false)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    const size_t slots = (size_t)n * (size_t)k;
+    DevBuf d_rays, d_hits, d_det;      // d_det stays null when the caller asked for no detail records
+    HIPCHK(d_rays.alloc((size_t)n * 32));
+    HIPCHK(d_hits.alloc(slots * 8));
+    if (h_detail4) HIPCHK(d_det.alloc(slots * 16));
+    HIPCHK(hipMemcpy(d_rays.as<>(), h_rays8, (size_t)n * 32, hipMemcpyHostToDevice));
+    if ((rc = pt_trace_rays_k(s, d_rays.as<float>(), n, k, flags, d_hits.as<PtRayHit>(), d_det.as<float>(), nullptr)) != PT_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(h_hits, d_hits.as<>(), slots * 8, hipMemcpyDeviceToHost));
+    if (h_detail4) HIPCHK(hipMemcpy(h_detail4, d_det.as<>(), slots * 16, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_count_hits(PtScene* s, const float* d_rays8, int64_t n, int32_t flags, int32_t* d_count, void* hip_stream)
+{
+    int rc;
+    if ((rc = hits_args_ok("pt_count_hits", s, d_rays8, n, false, 0, flags, d_count, 4, nullptr, true)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s), both = flags == PT_HITS_BOTH_SIDES;
+    for (int64_t off = 0; off < n; off += kHitsBatch) {
+        const uint32_t m = (uint32_t)(n - off < kHitsBatch ? n - off : kHitsBatch);
+        HIPCHK(launch_count_hits(s->dev, d_rays8 + off * 8, m, quad, both, d_count + off, (hipStream_t)hip_stream));
+    }
+    return PT_OK;
+}
+
+int pt_count_hits_host(PtScene* s, const float* h_rays8, int64_t n, int32_t flags, int32_t* h_count)
+{
+    int rc;
+    if ((rc = hits_args_ok("pt_count_hits_host", s, h_rays8, n, false, 0, flags, h_count, 4, nullptr, false)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    DevBuf d_rays, d_count;
+    HIPCHK(d_rays.alloc((size_t)n * 32));
+    HIPCHK(d_count.alloc((size_t)n * 4));
+    HIPCHK(hipMemcpy(d_rays.as<>(), h_rays8, (size_t)n * 32, hipMemcpyHostToDevice));
+    if ((rc = pt_count_hits(s, d_rays.as<float>(), n, flags, d_count.as<int32_t>(), nullptr)) != PT_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(h_count, d_count.as<>(), (size_t)n * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+}  // extern "C"

@@ -190,6 +190,52 @@ PT_DEV void tri_test_pairrec(const DevScene& sc, int q, bool two, const f3& org,
     }
 }
 
+// The pair record's two triangles for a walk that collects hits instead of keeping the closest (pt_rayhits.hip; include/pt_api.h:
+// "First K hits along a ray").  det, t's numerator, u and v of both triangles come from the packed arithmetic of tri_test_pairrec,
+// operation for operation.  BOTH: a triangle whose det fails the front test is judged on -det, -u, -v (negation is exact), so that
+// at most one of the two sides accepts it.  g_j: triangle j passes the range tests that do not involve the sink; c_j: the sink would
+// take it now (SINK::wants — its bound, which for a list is the K-th hit so far).  The reference's leaf box is fetched only for a c_j,
+// once for most lanes; triangle 1 is asked again after triangle 0 has been taken, since that may have moved the bound.
+template <bool BOTH, class SINK>
+PT_DEV void tri_hits_pairrec(const DevScene& sc, int q, bool two, const f3& org, const f3& dir, const f3& invD, bool degenerate, SINK& s)
+{
+    typedef float f2v __attribute__((ext_vector_type(2)));
+    const float4* rec = sc.tripair + 8 * (size_t)q;
+    const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3], r4 = rec[4];
+    const f2v ox = {org.x, org.x}, oy = {org.y, org.y}, oz = {org.z, org.z};
+    const f2v dx = {dir.x, dir.x}, dy = {dir.y, dir.y}, dz = {dir.z, dir.z};
+    const f2v E1x = {r1.z, r1.w}, E1y = {r2.x, r2.y}, E1z = {r2.z, r2.w};
+    const f2v E2x = {r3.x, r3.y}, E2y = {r3.z, r3.w}, E2z = {r4.x, r4.y};
+    const f2v Tx = ox - (f2v){r0.x, r0.y}, Ty = oy - (f2v){r0.z, r0.w}, Tz = oz - (f2v){r1.x, r1.y};
+    const f2v Px = dy * E2z - dz * E2y, Py = -(dx * E2z - dz * E2x), Pz = dx * E2y - dy * E2x;
+    const f2v Qx = Ty * E1z - Tz * E1y, Qy = -(Tx * E1z - Tz * E1x), Qz = Tx * E1y - Ty * E1x;
+    const f2v det = Px * E1x + Py * E1y + Pz * E1z;
+    const f2v tnum = Qx * E2x + Qy * E2y + Qz * E2z;
+    const f2v uu = {Px.x * Tx.x + Py.x * Ty.x + Pz.x * Tz.x, Px.y * Tx.y + Py.y * Ty.y + Pz.y * Tz.y};
+    const f2v vv = {Qx.x * dir.x + Qy.x * dir.y + Qz.x * dir.z, Qx.y * dir.x + Qy.y * dir.y + Qz.y * dir.z};
+    const float t0 = tnum.x * (1.f / det.x), t1 = tnum.y * (1.f / det.y);
+    const int prim0 = __float_as_int(r4.z), prim1 = __float_as_int(r4.w);
+    const bool b0 = BOTH & (det.x < kEps), b1 = BOTH & (det.y < kEps);      // judged as a back face
+    const float d0 = b0 ? -det.x : det.x, u0 = b0 ? -uu.x : uu.x, v0 = b0 ? -vv.x : vv.x;
+    const float d1 = b1 ? -det.y : det.y, u1 = b1 ? -uu.y : uu.y, v1 = b1 ? -vv.y : vv.y;
+    const bool g0 = !(d0 < kEps) & !(t0 < 0.f) & !((u0 < 0.f) | (u0 > d0)) & !((v0 < 0.f) | ((v0 + u0) > d0));
+    const bool g1 = two & !(d1 < kEps) & !(t1 < 0.f) & !((u1 < 0.f) | (u1 > d1)) & !((v1 < 0.f) | ((v1 + u1) > d1));
+    const bool c0 = g0 && s.wants(t0, prim0);
+    const bool c1 = g1 && s.wants(t1, prim1);
+    if (c0 | c1) {
+        const bool okA = degenerate ? true : pair_box_ok((const float*)rec, !c0, org, invD);
+        if (c0 & c1) {
+            if (okA) s.take(t0, prim0);
+            if (s.wants(t1, prim1)) {
+                const bool okB = degenerate ? true : pair_box_ok((const float*)rec, true, org, invD);
+                if (okB) s.take(t1, prim1);
+            }
+        } else if (okA) {
+            s.take(c0 ? t0 : t1, c0 ? prim0 : prim1);
+        }
+    }
+}
+
 // Sphere::hit root selection, include/CudaPrimitive.cuh:255-272.
 PT_DEV bool sphere_root(const f3& center, float rad, const f3& org, const f3& dir, float tmax, float& root)
 {

@@ -94,6 +94,8 @@ class PtNearest(C.Structure):
 NEAREST_DTYPE = np.dtype([("dist2", "<f4"), ("prim", "<i4")])      # PtNearest as a numpy record
 NEAREST_CLOSEST, NEAREST_ANY = 0, 1
 NEAREST_KMAX = 32      # PT_NEAREST_KMAX: the most slots per point of pt_nearest_k
+RAY_HITS_KMAX = 32     # PT_RAY_HITS_KMAX: the most slots per ray of pt_trace_rays_k
+HITS_FRONT, HITS_BOTH_SIDES = 0, 1
 AOV_FLOATS = 8        # floats per pixel of pt_render_aov: albedo.rgb | normal.xyz | depth | coverage
 
 _lib = None
@@ -225,6 +227,10 @@ API = [
     ("pt_nearest_k_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     ("pt_count_within", C.c_int, [_P, _P, C.c_int64, _P, _P]),
     ("pt_count_within_host", C.c_int, [_P, _P, C.c_int64, _P]),
+    ("pt_trace_rays_k", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("pt_trace_rays_k_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
+    ("pt_count_hits", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
+    ("pt_count_hits_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     ("pt_rays_floats", C.c_int64, [C.c_int64]),
     ("pt_rays_work_bytes", C.c_int64, [C.POINTER(PtParams), C.c_int64]),
     ("pt_render_rays", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
@@ -270,6 +276,17 @@ def _device_points(who, points, device):
     if points.device.type != "cuda" or points.device.index != device:
         raise PtError(f"{who}: points is on {points.device}, the scene is on device {device}")
     return points.shape[0]
+
+
+def _device_rays(who, rays, device):
+    """The host-side checks of a RAY8 tensor for the scene on `device`; returns n."""
+    if not (hasattr(rays, "data_ptr") and hasattr(rays, "is_contiguous")):
+        raise PtError(f"{who}: rays must be a torch tensor or a numpy array")
+    if str(rays.dtype) != "torch.float32" or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
+        raise PtError(f"{who}: rays must be contiguous float32 of shape (n, 8), got {rays.dtype} {tuple(rays.shape)}")
+    if rays.device.type != "cuda" or rays.device.index != device:
+        raise PtError(f"{who}: rays is on {rays.device}, the scene is on device {device}")
+    return rays.shape[0]
 
 
 def _rebuild_params(depth_budget, large_fraction):
@@ -939,6 +956,56 @@ class Scene:
         import torch
         cnt = torch.empty(n, dtype=torch.int32, device=points.device)
         _check(lib().pt_count_within(self._h, C.c_void_p(points.data_ptr()), n, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_count_within")
+        return cnt
+
+    def trace_rays_k(self, rays, k, both_sides=False, detail=False, stream_ptr=0):
+        """The first k hits along each ray, sorted (include/pt_api.h: pt_trace_rays_k).  rays: (n, 8) float32 RAY8 records, org.xyz
+        dir.xyz 0 tmax, as trace_rays takes them; 1 <= k <= RAY_HITS_KMAX.  Returns (t, prim) — float32 and int32 of shape (n, k), nearest
+        first, among equal t the larger prim first, the slots past the last hit (0, -1) — and, with detail=True, the (n, k, 4) detail
+        records u/det v/det facing 0 as a third item (zeros in a miss slot).  both_sides=True: back faces and the far root of a sphere
+        count too (HITS_BOTH_SIDES); with False column 0 is trace_rays' closest hit.
+        A torch float32 tensor on the scene's device is used in place (data_ptr()): the query is enqueued on stream_ptr, the results
+        are torch tensors on that device, valid once the stream has passed the query, and `rays` must stay alive until then.
+        A numpy array goes through pt_trace_rays_k_host (synchronous) and returns numpy arrays."""
+        k = int(k)
+        if not 1 <= k <= RAY_HITS_KMAX:
+            raise PtError(f"trace_rays_k: k = {k}, want 1 .. {RAY_HITS_KMAX}")
+        flags = HITS_BOTH_SIDES if both_sides else HITS_FRONT
+        if isinstance(rays, np.ndarray):
+            r = np.ascontiguousarray(rays, np.float32)
+            if r.ndim != 2 or r.shape[1] != 8:
+                raise PtError(f"trace_rays_k: rays has shape {r.shape}, want (n, 8)")
+            n = r.shape[0]
+            hits = np.zeros((n, k), HIT_DTYPE)
+            det = np.zeros((n, k, 4), np.float32) if detail else None
+            _check(lib().pt_trace_rays_k_host(self._h, _ptr(r), n, k, flags, _ptr(hits), _ptr(det) if detail else None), "pt_trace_rays_k_host")
+            out = (np.ascontiguousarray(hits["t"]), np.ascontiguousarray(hits["prim"]))
+            return out + (det,) if detail else out
+        n = _device_rays("trace_rays_k", rays, self.device)
+        import torch
+        hits = torch.empty((n, k, 2), dtype=torch.int32, device=rays.device)      # PtRayHit: t's bits | prim
+        det = torch.empty((n, k, 4), dtype=torch.float32, device=rays.device) if detail else None
+        _check(lib().pt_trace_rays_k(self._h, C.c_void_p(rays.data_ptr()), n, k, flags, C.c_void_p(hits.data_ptr()),
+                                     C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_trace_rays_k")
+        out = (hits[:, :, 0].view(torch.float32), hits[:, :, 1])
+        return out + (det,) if detail else out
+
+    def count_hits(self, rays, both_sides=False, stream_ptr=0):
+        """How many hits each ray has in [0, tmax] (include/pt_api.h: pt_count_hits), uncapped: (n,) int32.  rays and both_sides as in
+        trace_rays_k.  A torch tensor on the scene's device is used in place and the count is a torch tensor there, in stream order; a
+        numpy array goes through pt_count_hits_host."""
+        flags = HITS_BOTH_SIDES if both_sides else HITS_FRONT
+        if isinstance(rays, np.ndarray):
+            r = np.ascontiguousarray(rays, np.float32)
+            if r.ndim != 2 or r.shape[1] != 8:
+                raise PtError(f"count_hits: rays has shape {r.shape}, want (n, 8)")
+            cnt = np.zeros(r.shape[0], np.int32)
+            _check(lib().pt_count_hits_host(self._h, _ptr(r), r.shape[0], flags, _ptr(cnt)), "pt_count_hits_host")
+            return cnt
+        n = _device_rays("count_hits", rays, self.device)
+        import torch
+        cnt = torch.empty(n, dtype=torch.int32, device=rays.device)
+        _check(lib().pt_count_hits(self._h, C.c_void_p(rays.data_ptr()), n, flags, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_count_hits")
         return cnt
 
     def render_rays_device(self, d_rays_ptr, n_rays, prm, d_rgb_ptr, d_work_ptr, d_seed_ptr=0, seed_stride=None, stream_ptr=0):

@@ -243,6 +243,22 @@ PT_API int  pt_render_split(PtScene* s, const PtCamera* cam, const PtParams* prm
  *         + |z_p - z_q| / (sigma_depth max(z_p, z_q)) (z = AOV 6; 0 when both are 0)
  *     e_p <- sum w e_q / sum w (kept when sum w = 0: a NaN pixel with a finite neighbour becomes finite, a NaN never spreads)
  *     out_p = e_p * div_p * sample_cnt after L iterations;  L = 0 copies d_rgb bit for bit.
+ *   All of it in float32, every operation rounded once (tests/denoise_ref.py: denoise32 restates it; on inputs whose every exp
+ *   argument is 0 the result is that restatement's bit for bit).  The edges of the definition:
+ *     - the albedo is compared in float32 against the float32 nearest 1e-3 (0x3A83126F = 0.001000000047...): an albedo of exactly
+ *       that value, or below it, divides by 1; the next float above divides by itself.
+ *     - the cutoff is inclusive: a tap with E == 80 is used, the next float above is not.  A tap whose E is NaN is not used.
+ *     - a pixel whose normal has a NaN (a zero-area triangle's normal, pt_scene_update_vertices below) has a NaN E against every
+ *       tap, itself included: sum w = 0 and it keeps its value.  It is no tap of another pixel either, as that pixel's E against it
+ *       is NaN.  A depth of +inf does the same (inf - inf at the centre tap, inf / inf against a finite neighbour).
+ *     - max(z_p, z_q) is z_p > z_q ? z_p : z_q, and the depth term is added only when that is > 0: a pair with max <= 0 (misses,
+ *       negative depths) adds no depth term.  A NaN depth is therefore no edge where it is the max (as a tap, and at its own centre
+ *       tap) and a NaN E against the positive depths around it when it is the centre: give misses depth 0, not NaN.
+ *     - kc = 1 / (sigma_color * sigma_color), times 4 per iteration, in float32.  A sigma_color whose square overflows (> 1.8e19)
+ *       makes kc zero: the colour term is switched off.  One whose square underflows to 0, or is small enough that kc overflows
+ *       (at once below 5.4e-20, after i iterations below 2^i times that), makes kc infinite: the centre tap's 0 * inf is NaN, no
+ *       tap is used and from that iteration on the filter keeps every finite pixel (a non-finite one has no colour term).
+ *     - sample_cnt is converted to float32 once (2^24 + 1 becomes 2^24, 2^31 - 1 becomes 2^31).
  *   d_work: pt_denoise_work_bytes(W, H) bytes; d_aov and d_work 16-byte aligned; d_out must not overlap d_rgb, d_aov or d_work,
  *   and the inputs are not modified.  Asynchronous on `hip_stream`.
  * pt_denoise_host: the same on host buffers, on HIP device `device`, synchronous.

@@ -11,8 +11,14 @@
 // wave per tile in 256-thread workgroups on trace_closest: 0.89 against 2.91 ms at 1080p).
 //
 // Denoiser: edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with albedo demodulation.  Definition (tests/denoise_ref.py
-// states it in numpy, float64):
-//   c_p = rgb_p / sample_cnt;  div_p = albedo_p where > 1e-3 else 1 (per channel; 1 without demodulation);  e_p = c_p / div_p
+// states it in numpy twice: `denoise` in float64, `denoise32` in float32 with every operation rounded once in the order of the code
+// below — on inputs whose every exp argument is 0 the kernels return denoise32's bits, tests/test_denoise_exact.py).  The albedo is
+// compared in float32 against the float32 nearest 1e-3 (1e-3f = 0.001000000047...: that value and below divide by 1); the cutoff is
+// inclusive (E == 80 is used, a NaN E is not); a NaN in the normal, or a depth of +inf, makes every E of the pixel NaN, so it keeps its
+// value and is nobody's tap; max(z_p, z_q) is the select of the code below and adds a depth term only when > 0 (misses, negative
+// depths: none; a NaN depth as a tap: none); kc = 0 (sc^2 overflows) switches the colour term off, kc = inf (sc^2 underflows, or kc
+// overflows on the way) makes the centre tap's 0 * inf NaN and keeps every finite pixel (include/pt_api.h has all of it).
+//   c_p = rgb_p / sample_cnt;  div_p = albedo_p where > 1e-3f else 1 (per channel; 1 without demodulation);  e_p = c_p / div_p
 //   finite_p = all three components of c_p are finite (after an iteration: of e'_p)
 //   iteration i = 0 .. L-1, step s = 2^i, taps q = p + s (dx, dy), dx, dy in -2..2 (dy outer, dx inner), inside the frame and finite_q:
 //     w = h(dx) h(dy) exp(-E),  h = (1/16, 1/4, 3/8, 1/4, 1/16)

@@ -919,7 +919,7 @@ PT_API int  pt_closest_points_host(PtScene* s, const float* h_points4, int64_t n
  * A point with a non-finite coordinate, or a negative or NaN radius: the result for THAT point is unspecified (every prim stays in
  *   [-1, number of primitives), every count in [0, number of primitives]), the other points of the batch are unaffected, and the
  *   call ends by the argument of quad_step (csrc/pt_trace.h).
- * Out of scope: k above 32, variable-length lists of all primitives within a radius, per-primitive masks, the k nearest along a ray (the next section),
+ * Out of scope: k above 32 (every primitive within a radius: pt_within_radius_list, two sections on), per-primitive masks, the k nearest along a ray (the next section),
  * sorting the points for coherence, a multi-GPU split, a CLI option.
  * -------------------------------------------------------------------------------- */
 #define PT_NEAREST_KMAX 32
@@ -984,8 +984,8 @@ PT_API int  pt_count_within_host(PtScene* s, const float* h_points4, int64_t n, 
  *   call ends by the argument of quad_step (csrc/pt_trace.h).
  * Cost: k = 1 costs more than the lean closest-hit kernel — measured 1.16 to 1.33 times pt_trace_rays(PT_QUERY_CLOSEST) on 2 M rays
  *   (DESIGN.md section 34): for one hit per ray call pt_trace_rays.
- * Out of scope: k above 32, variable-length lists, tmin other than 0, primitive masks, the 29-float surface record per slot, a CLI
- * option, a multi-GPU split.
+ * Out of scope: k above 32 (every hit: pt_trace_rays_list, the next section), tmin other than 0, primitive masks, the 29-float surface
+ * record per slot, a CLI option, a multi-GPU split.
  * -------------------------------------------------------------------------------- */
 #define PT_RAY_HITS_KMAX   32
 #define PT_HITS_FRONT      0
@@ -995,6 +995,64 @@ PT_API int  pt_trace_rays_k(PtScene* s, const float* d_rays8, int64_t n, int32_t
 PT_API int  pt_trace_rays_k_host(PtScene* s, const float* h_rays8, int64_t n, int32_t k, int32_t flags, PtRayHit* h_hits, float* h_detail4 /* may be NULL */);
 PT_API int  pt_count_hits(PtScene* s, const float* d_rays8, int64_t n, int32_t flags, int32_t* d_count, void* hip_stream);
 PT_API int  pt_count_hits_host(PtScene* s, const float* h_rays8, int64_t n, int32_t flags, int32_t* h_count);
+
+/* ----------------------------------------------------------------------------------
+ * Variable-length query results: all hits along a ray, all primitives in a radius (new: the reference has no such query).  Opt-in:
+ * every call above is as it was.  pt_trace_rays_k and pt_nearest_k return at most 32 per query; these return every member, in CSR form
+ * (csrc/pt_lists.hip, csrc/pt_rayhits.hip, csrc/pt_knearest.hip): the thickness of every wall a ray crosses, the full contact set of a
+ * probe, every triangle inside a brush radius.  DESIGN.md section 37.
+ *
+ * The protocol, three device calls in stream order, none of which allocates, waits or reads back:
+ *     pt_count_hits / pt_count_within     -> d_count[n]
+ *     pt_list_offsets(d_count, n)         -> d_offsets[n + 1]      (the caller reads the 8-byte total d_offsets[n] back, at its own cost,
+ *                                                                    and allocates)
+ *     pt_trace_rays_list / pt_within_radius_list(..., d_offsets, cap, records)      -> every segment filled, sorted
+ * pt_list_offsets: d_offsets[0] = 0 and d_offsets[i + 1] = d_offsets[i] + max(d_count[i], 0), in int64 (the sum does not wrap at 2^31).
+ *   n = 0 writes the single 0.  The result depends only on the counts: the same bits on every run.  It needs no scene and runs on the
+ *   current device.  d_scratch: pt_list_offsets_scratch_bytes(n) bytes of device memory (2 KB for any n > 0, 0 for n = 0; -1 for
+ *   n < 0), 8-byte aligned, not read before it is written.  Three launches: per-span sums over at most 256 workgroups (a span is a whole
+ *   number of 2,048-count chunks), one workgroup scanning those partials, a rescan of every span from its base; no workgroup waits on
+ *   another.
+ * pt_trace_rays_list: the segment of ray i is [b, e) with b = clamp(d_offsets[i], 0, cap) and e = clamp(d_offsets[i + 1], b, cap).  No
+ *   other record of d_hits or d_detail4 is written, whatever the offsets hold: garbage offsets give garbage segments (overlapping ones
+ *   among them), never a write outside [0, cap).  With m = e - b and H = H(ray i) under `flags`, exactly as pt_trace_rays_k defines it
+ *   (acceptance, arithmetic, order, tie rule):
+ *     m >= |H|: slots 0 .. |H| - 1 of the segment are the members of H in order; the later slots hold the miss record (0, -1).
+ *     m < |H|:  the m slots hold m distinct members of H, sorted among themselves; which members is unspecified.
+ *   Hence with offsets made from pt_count_hits of the same rays, flags and scene state, the records are the concatenation of every H,
+ *   bit for bit: brute force over the scene's current positions, before and after a refit or any rebuild.  Slot 0 of a non-empty
+ *   PT_HITS_FRONT list is pt_trace_rays(PT_QUERY_CLOSEST)'s record, and a ray with at most 32 hits has the slots pt_trace_rays_k(k = 32)
+ *   gives it.  d_detail4 (may be NULL): pt_trace_rays_k's 4 floats per slot, d_detail4[s * 4 ..] for record s; miss slots hold zeros.
+ * pt_within_radius_list: the same with C(p) and f of the section "K nearest and counts within a radius", its order (f ascending, among
+ *   equal f the larger index first) and pt_nearest_k's 8-float detail record, d_detail8[s * 8 ..].  An infinite radius lists every
+ *   primitive.
+ * Stream order, concurrency, batching (at most 2^30 queries per launch) and the treatment of non-finite input are those of
+ *   pt_trace_rays_k / pt_nearest_k (a query whose list is unspecified keeps every prim in [-1, number of primitives) and writes its own
+ *   segment only); the known defect of DESIGN.md section 33 applies unchanged.  Alignment: d_rays8 and d_points4 16 bytes; records,
+ *   offsets and scratch 8 bytes; counts and detail 4 bytes.  pt_scene_device_bytes stays what it was.
+ * NULL scene / rays / points / offsets / records / count, n < 0, cap < 0, unknown flags, a NULL scratch for n > 0 and a misaligned
+ *   device pointer return PT_ERR_INVALID before any HIP call, no pointer dereferenced, the message naming the entry point.  n = 0 returns
+ *   PT_OK without a HIP call, pt_list_offsets after writing its one 0.
+ * pt_trace_rays_list_host, pt_within_radius_list_host: upload, count, scan and fill on the NULL stream, wait and download.  h_offsets
+ *   (n + 1 records) is always written.  With the records pointer NULL the call stops after the offsets: the sizing call.  With
+ *   cap < h_offsets[n] it returns PT_ERR_INVALID, the offsets written.  The records of every segment go to h_hits / h_out [0, h_offsets[n]).
+ * Cost (measured on an MI355X, 69,576 triangles): the fill walks the tree again, so count + offsets + fill costs
+ *   1.7 to 2.3 times the count alone on 2 M rays (0.55 / 1.79 / 1.69 ms on camera / bounce / segment rays) and 2.7 times on 2 M points at
+ *   a median of 8 members (9.2 ms), 0.58 to 0.86 times count + pt_trace_rays_k / pt_nearest_k (k = 32).  Lists of the whole scene for
+ *   4,096 points (285 M records) take 248 ms, 3.7 times the count.  A segment smaller than its list still walks the whole tree.
+ * Out of scope: a defined choice of members for an undersized segment, tmin, primitive masks, the 29-float surface record per slot, a
+ * per-slot owner array, a CLI option, a multi-GPU split.
+ * -------------------------------------------------------------------------------- */
+PT_API int64_t pt_list_offsets_scratch_bytes(int64_t n);                 /* or -1 (n < 0) */
+PT_API int  pt_list_offsets(const int32_t* d_count, int64_t n, int64_t* d_offsets /* n + 1 */, void* d_scratch, void* hip_stream);
+PT_API int  pt_trace_rays_list(PtScene* s, const float* d_rays8, int64_t n, int32_t flags, const int64_t* d_offsets /* n + 1 */,
+                               int64_t cap, PtRayHit* d_hits /* cap */, float* d_detail4 /* cap * 4, may be NULL */, void* hip_stream);
+PT_API int  pt_within_radius_list(PtScene* s, const float* d_points4, int64_t n, const int64_t* d_offsets /* n + 1 */,
+                                  int64_t cap, PtNearest* d_out /* cap */, float* d_detail8 /* cap * 8, may be NULL */, void* hip_stream);
+PT_API int  pt_trace_rays_list_host(PtScene* s, const float* h_rays8, int64_t n, int32_t flags, int64_t* h_offsets /* n + 1, written */,
+                                    int64_t cap, PtRayHit* h_hits /* may be NULL */, float* h_detail4 /* may be NULL */);
+PT_API int  pt_within_radius_list_host(PtScene* s, const float* h_points4, int64_t n, int64_t* h_offsets, int64_t cap,
+                                       PtNearest* h_out /* may be NULL */, float* h_detail8 /* may be NULL */);
 
 /* ----------------------------------------------------------------------------------
  * Radiance along the caller's own rays (new: the reference reaches its integrator through a pinhole camera only).

@@ -17,6 +17,7 @@
 #include "pt_trace.h"
 #include "pt_scene.h"
 #include "pt_nearest.h"
+#include "pt_lists.h"
 
 namespace ptd {
 
@@ -225,6 +226,75 @@ void nearest_k_detail(DevScene sc, const float4* __restrict__ points, uint64_t f
     near_detail(sc, points[t / k], prim, o);
 }
 
+// ---- every primitive within the radius: the fill of pt_within_radius_list (pt_lists.h says which code sorts
+// which segment) ----
+// The sink of the fill.  A lane owns the segment [b, b + m) of the records.  m <= kListLds: KList itself, over the lane's LDS list with
+// k = m; the list goes out sorted after the walk.  m > kListLds: every member of C is appended to the segment in the order the walk
+// meets it, while fewer than m are stored, with KCount's bound (r2) and acceptance — so the members appended are the members
+// pt_count_within counts —, and ptk_list_sort sorts the segment afterwards.  Ordered: the nearer child first, for the list's sake.
+struct KSeg : KList {
+    int2* seg;
+    int64_t m;
+    bool append;
+    PT_DEV void take(float f, int prim)
+    {
+        if (!append) { KList::take(f, prim); return; }
+        if ((f <= bound) & (cnt < m)) { seg[cnt] = make_int2(__float_as_int(f), prim); cnt++; }
+    }
+};
+
+// One point per lane, nearest_k's shape with the list of class kListLds.  A lane whose segment is empty walks nothing.  Every record of
+// the segment is written once, by its lane: the members, then the miss record (0, -1) up to m.  Nothing outside [0, cap) is written.
+template <bool QUAD>
+__global__ __launch_bounds__(64)
+void near_list(DevScene sc, const float4* __restrict__ points, uint32_t n, const int64_t* __restrict__ off, int64_t cap, int2* __restrict__ out)
+{
+    __shared__ int2 lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    __shared__ int2 lds_list[kListLds * kListRow];
+    const uint32_t lane = threadIdx.x, i = blockIdx.x * 64u + lane;
+    if (i >= n) return;
+    int64_t b, e;
+    list_segment(off, i, cap, b, e);
+    const int64_t m = e - b;
+    if (m == 0) return;
+    const float4 q = points[i];
+    int2* list = &lds_list[lane];
+    int2* dst = out + b;
+    KSeg s;
+    s.list = list; s.k = m > kListLds ? 0 : (int)m; s.cnt = 0; s.bound = q.w * q.w; s.boundPrim = -1;
+    s.seg = dst; s.m = m; s.append = m > kListLds;
+    knear_point<QUAD>(sc, q, &lds_stack[lane], s);
+    int64_t j = 0;
+    if (!s.append)
+        for (; j < s.cnt; j++) dst[j] = list[j * kListRow];
+    else
+        j = s.cnt;
+    for (; j < m; j++) dst[j] = make_int2(0, -1);
+}
+
+// The detail records of every segment, after the sort: near_detail per member slot, zeros per miss slot.  A short segment by its query's
+// thread, a long one by the whole workgroup (pt_lists.h: for_each_segment).
+__global__ __launch_bounds__(kSegThreads)
+void near_list_detail(DevScene sc, const float4* __restrict__ points, uint32_t n, uint32_t per, const int64_t* __restrict__ off, int64_t cap,
+                      const int2* __restrict__ res, float* __restrict__ out8)
+{
+    auto slot = [&](const float4& q, int64_t t) {
+        const int prim = res[t].y;
+        float* o = out8 + t * 8;
+        if (prim < 0) { for (int c = 0; c < 8; c++) o[c] = 0.f; return; }
+        near_detail(sc, q, prim, o);
+    };
+    for_each_segment(off, n, per, cap,
+                     [&](uint32_t i, int64_t b, int64_t e) {
+                         const float4 q = points[i];
+                         for (int64_t t = b; t < e; t++) slot(q, t);
+                     },
+                     [&](uint32_t i, int64_t b, int64_t e) {
+                         const float4 q = points[i];
+                         for (int64_t t = b + threadIdx.x; t < e; t += kSegThreads) slot(q, t);
+                     });
+}
+
 }  // namespace ptd
 
 template <int KC>
@@ -264,6 +334,27 @@ static hipError_t launch_count_within(const ptd::DevScene& sc, const float* d_po
     return hipGetLastError();
 }
 
+// Enqueues one batch of n <= 2^30 points of pt_within_radius_list on `stream`: the fill, the sort of the segments longer than kListLds,
+// then the detail records if asked for.  off: the batch's first offset; the records are addressed from d_out whatever the batch.
+static hipError_t launch_near_list(const ptd::DevScene& sc, const float* d_points4, uint32_t n, bool quad, const int64_t* off, int64_t cap,
+                                   PtNearest* d_out, float* d_detail8, hipStream_t stream)
+{
+    const dim3 blocks((n + 63u) / 64u);
+    const float4* pts = (const float4*)d_points4;
+    int2* out = (int2*)d_out;
+    if (quad) hipLaunchKernelGGL((ptd::near_list<true>), blocks, dim3(64), 0, stream, sc, pts, n, off, cap, out);
+    else hipLaunchKernelGGL((ptd::near_list<false>), blocks, dim3(64), 0, stream, sc, pts, n, off, cap, out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = ptk_list_sort(off, n, cap, out, false, stream)) != hipSuccess) return e;
+    if (d_detail8) {
+        uint32_t per, grid;
+        pt_list_grid(n, per, grid);
+        hipLaunchKernelGGL(ptd::near_list_detail, dim3(grid), dim3(ptd::kSegThreads), 0, stream, sc, pts, n, per, off, cap, (const int2*)out, d_detail8);
+    }
+    return hipGetLastError();
+}
+
 // ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
 // out_align: 8 for PtNearest records, 4 for counts.  has_k: pt_nearest_k and its host variant.
 static int knear_args_ok(const char* who, const PtScene* s, const float* points, int64_t n, bool has_k, int32_t k, const void* out, int out_align,
@@ -273,6 +364,21 @@ static int knear_args_ok(const char* who, const PtScene* s, const float* points,
                       (has_k && (k < 1 || k > PT_NEAREST_KMAX)) ? "k must be in 1 .. PT_NEAREST_KMAX" :
                       (device && ((uintptr_t)points & 15)) ? "points must be 16-byte aligned" :
                       (device && ((uintptr_t)out & (uintptr_t)(out_align - 1))) ? (out_align == 8 ? "out must be 8-byte aligned" : "count must be 4-byte aligned") :
+                      (device && ((uintptr_t)detail & 3)) ? "detail must be 4-byte aligned" : nullptr;
+    if (bad) { pt_set_error("%s: %s", who, bad); return PT_ERR_INVALID; }
+    return PT_OK;
+}
+
+// pt_within_radius_list and its host variant.  device: the pointers are device pointers (alignment checked, out required); on the host
+// variant out may be NULL (the sizing call).
+static int near_list_args_ok(const char* who, const PtScene* s, const float* points, int64_t n, const int64_t* offsets, int64_t cap,
+                             const void* out, const float* detail, bool device)
+{
+    const char* bad = !s ? "NULL scene" : !points ? "NULL points" : !offsets ? "NULL offsets" : (device && !out) ? "NULL out" : n < 0 ? "n < 0" :
+                      cap < 0 ? "cap < 0" :
+                      (device && ((uintptr_t)points & 15)) ? "points must be 16-byte aligned" :
+                      (device && ((uintptr_t)offsets & 7)) ? "offsets must be 8-byte aligned" :
+                      (device && ((uintptr_t)out & 7)) ? "out must be 8-byte aligned" :
                       (device && ((uintptr_t)detail & 3)) ? "detail must be 4-byte aligned" : nullptr;
     if (bad) { pt_set_error("%s: %s", who, bad); return PT_ERR_INVALID; }
     return PT_OK;
@@ -342,6 +448,50 @@ int pt_count_within_host(PtScene* s, const float* h_points4, int64_t n, int32_t*
     if ((rc = pt_count_within(s, d_pts.as<float>(), n, d_count.as<int32_t>(), nullptr)) != PT_OK) return rc;
     HIPCHK(hipStreamSynchronize(nullptr));
     HIPCHK(hipMemcpy(h_count, d_count.as<>(), (size_t)n * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_within_radius_list(PtScene* s, const float* d_points4, int64_t n, const int64_t* d_offsets, int64_t cap, PtNearest* d_out, float* d_detail8,
+                          void* hip_stream)
+{
+    int rc;
+    if ((rc = near_list_args_ok("pt_within_radius_list", s, d_points4, n, d_offsets, cap, d_out, d_detail8, true)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s);
+    for (int64_t off = 0; off < n; off += kKnearBatch) {
+        const uint32_t m = (uint32_t)(n - off < kKnearBatch ? n - off : kKnearBatch);
+        HIPCHK(launch_near_list(s->dev, d_points4 + off * 4, m, quad, d_offsets + off, cap, d_out, d_detail8, (hipStream_t)hip_stream));
+    }
+    return PT_OK;
+}
+
+int pt_within_radius_list_host(PtScene* s, const float* h_points4, int64_t n, int64_t* h_offsets, int64_t cap, PtNearest* h_out, float* h_detail8)
+{
+    int rc;
+    if ((rc = near_list_args_ok("pt_within_radius_list_host", s, h_points4, n, h_offsets, cap, h_out, h_detail8, false)) != PT_OK) return rc;
+    if (n == 0) { h_offsets[0] = 0; return PT_OK; }
+    HIPCHK(hipSetDevice(s->device));
+    DevBuf d_pts, d_count, d_off, d_scratch, d_out, d_det;      // d_det stays null when the caller asked for no detail records
+    HIPCHK(d_pts.alloc((size_t)n * 16));
+    HIPCHK(d_count.alloc((size_t)n * 4));
+    HIPCHK(d_off.alloc((size_t)(n + 1) * 8));
+    HIPCHK(d_scratch.alloc((size_t)pt_list_offsets_scratch_bytes(n)));
+    HIPCHK(hipMemcpy(d_pts.as<>(), h_points4, (size_t)n * 16, hipMemcpyHostToDevice));
+    if ((rc = pt_count_within(s, d_pts.as<float>(), n, d_count.as<int32_t>(), nullptr)) != PT_OK) return rc;
+    if ((rc = pt_list_offsets(d_count.as<int32_t>(), n, d_off.as<int64_t>(), d_scratch.as<>(), nullptr)) != PT_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(h_offsets, d_off.as<>(), (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
+    if (!h_out) return PT_OK;      // the sizing call
+    const int64_t total = h_offsets[n];
+    if (cap < total) { pt_set_error("pt_within_radius_list_host: cap %lld < %lld records", (long long)cap, (long long)total); return PT_ERR_INVALID; }
+    HIPCHK(d_out.alloc((size_t)total * 8));
+    if (h_detail8) HIPCHK(d_det.alloc((size_t)total * 32));
+    if ((rc = pt_within_radius_list(s, d_pts.as<float>(), n, d_off.as<int64_t>(), total, d_out.as<PtNearest>(), d_det.as<float>(), nullptr)) != PT_OK)
+        return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(h_out, d_out.as<>(), (size_t)total * 8, hipMemcpyDeviceToHost));
+    if (h_detail8) HIPCHK(hipMemcpy(h_detail8, d_det.as<>(), (size_t)total * 32, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -18,6 +18,7 @@
 #include "pt_math.h"
 #include "pt_trace.h"
 #include "pt_scene.h"
+#include "pt_lists.h"
 
 namespace ptd {
 
@@ -270,18 +271,10 @@ void count_hits(DevScene sc, const float4* __restrict__ rays, uint32_t n, int32_
 // ray t / k.  A triangle is read from its surface record (indexed by primitive in the reference's order), which starts with V0 E1 E2,
 // the floats its tri record holds.  Facing: a triangle was taken as a back face iff det < kEps; a sphere slot holds the entering
 // root iff r1 is valid and is the slot's t (r2 is only ever kept beside a valid r1 when it differs from it).
-// A launch covers the slots from `first` on (launch_rays_k: at most kHitDetailSlots of them, so that no grid exceeds 2^31 threads).
-__global__ __launch_bounds__(256)
-void rays_k_detail(DevScene sc, const float4* __restrict__ rays, uint64_t first, uint64_t slots, uint32_t k, const int2* __restrict__ res, float* __restrict__ out4)
+// hit_detail: the record of a member h (h.y >= 0) of the ray's H, for rays_k_detail and rays_list_detail.
+PT_DEV void hit_detail(const DevScene& sc, const f3& org, const f3& dir, float tmax, int2 h, float* o)
 {
-    const uint64_t t = first + (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (t >= slots) return;
-    const int2 h = res[t];
     const int prim = h.y;
-    float* o = out4 + t * 4;      // 4-byte aligned: four stores
-    if (prim < 0) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; return; }
-    f3 org, dir; float tmax;
-    load_ray8(rays, t / k, org, dir, tmax);
     if (prim >= sc.n_tris) {
         const float4 c = sc.spheres[4 * (prim - sc.n_tris)];
         const f3 oc = org - f3(c.x, c.y, c.z);
@@ -303,6 +296,94 @@ void rays_k_detail(DevScene sc, const float4* __restrict__ rays, uint64_t first,
     const float det = dot(P, E1);
     const float invDet = 1.f / det;
     o[0] = dot(P, T) * invDet; o[1] = dot(Q, dir) * invDet; o[2] = (det < kEps) ? -1.f : 1.f; o[3] = 0.f;
+}
+
+// A launch covers the slots from `first` on (launch_rays_k: at most kHitDetailSlots of them, so that no grid exceeds 2^31 threads).
+__global__ __launch_bounds__(256)
+void rays_k_detail(DevScene sc, const float4* __restrict__ rays, uint64_t first, uint64_t slots, uint32_t k, const int2* __restrict__ res, float* __restrict__ out4)
+{
+    const uint64_t t = first + (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= slots) return;
+    const int2 h = res[t];
+    const int prim = h.y;
+    float* o = out4 + t * 4;      // 4-byte aligned: four stores
+    if (prim < 0) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; return; }
+    f3 org, dir; float tmax;
+    load_ray8(rays, t / k, org, dir, tmax);
+    hit_detail(sc, org, dir, tmax, h, o);
+}
+
+// ---- every hit: the fill of pt_trace_rays_list (pt_lists.h says which code sorts which segment) ----------------
+// The sink of the fill.  A lane owns the segment [b, b + m) of the records.  m <= kListLds: HitList itself, over the lane's LDS list with
+// k = m; the list goes out sorted after the walk.  m > kListLds: every member of H is appended to the segment in the order the walk
+// meets it, while fewer than m are stored, with HitCount's bound (tmax) and acceptance — so the members appended are the members
+// pt_count_hits counts —, and ptk_list_sort sorts the segment afterwards.
+struct HitSeg : HitList {
+    int2* seg;
+    int64_t m;
+    bool append;
+    PT_DEV bool wants(float t, int prim) const { return append ? !(t > bound) : HitList::wants(t, prim); }
+    PT_DEV void take(float t, int prim)
+    {
+        if (!append) { HitList::take(t, prim); return; }
+        if (cnt < m) { seg[cnt] = make_int2(__float_as_int(t), prim); cnt++; }
+    }
+};
+
+// One ray per lane, rays_k's shape with the list of class kListLds.  A lane whose segment is empty walks nothing.  Every record of the
+// segment is written once, by its lane: the members, then the miss record (0, -1) up to m.  Nothing outside [0, cap) is written:
+// list_segment clamps.
+template <bool QUAD, bool BOTH>
+__global__ __launch_bounds__(64)
+void rays_list(DevScene sc, const float4* __restrict__ rays, uint32_t n, const int64_t* __restrict__ off, int64_t cap, int2* __restrict__ out)
+{
+    __shared__ int lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    __shared__ int2 lds_list[kListLds * kHitRow];
+    const uint32_t lane = threadIdx.x, i = blockIdx.x * 64u + lane;
+    if (i >= n) return;
+    int64_t b, e;
+    list_segment(off, i, cap, b, e);
+    const int64_t m = e - b;
+    if (m == 0) return;
+    f3 org, dir; float tmax;
+    load_ray8(rays, i, org, dir, tmax);
+    int2* list = &lds_list[lane];
+    int2* dst = out + b;
+    HitSeg s;
+    s.list = list; s.k = m > kListLds ? 0 : (int)m; s.cnt = 0; s.bound = tmax; s.boundPrim = -1;
+    s.seg = dst; s.m = m; s.append = m > kListLds;
+    hits_ray<QUAD, BOTH>(sc, org, dir, tmax, &lds_stack[lane], s);
+    int64_t j = 0;
+    if (!s.append)
+        for (; j < s.cnt; j++) dst[j] = list[j * kHitRow];
+    else
+        j = s.cnt;
+    for (; j < m; j++) dst[j] = make_int2(0, -1);
+}
+
+// The detail records of every segment, after the sort: hit_detail per member slot, zeros per miss slot.  A short segment by its query's
+// thread, a long one by the whole workgroup (pt_lists.h: for_each_segment).
+__global__ __launch_bounds__(kSegThreads)
+void rays_list_detail(DevScene sc, const float4* __restrict__ rays, uint32_t n, uint32_t per, const int64_t* __restrict__ off, int64_t cap,
+                      const int2* __restrict__ res, float* __restrict__ out4)
+{
+    auto slot = [&](const f3& org, const f3& dir, float tmax, int64_t t) {
+        const int2 h = res[t];
+        float* o = out4 + t * 4;
+        if (h.y < 0) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; return; }
+        hit_detail(sc, org, dir, tmax, h, o);
+    };
+    for_each_segment(off, n, per, cap,
+                     [&](uint32_t i, int64_t b, int64_t e) {
+                         f3 org, dir; float tmax;
+                         load_ray8(rays, i, org, dir, tmax);
+                         for (int64_t t = b; t < e; t++) slot(org, dir, tmax, t);
+                     },
+                     [&](uint32_t i, int64_t b, int64_t e) {
+                         f3 org, dir; float tmax;
+                         load_ray8(rays, i, org, dir, tmax);
+                         for (int64_t t = b + threadIdx.x; t < e; t += kSegThreads) slot(org, dir, tmax, t);
+                     });
 }
 
 }  // namespace ptd
@@ -355,7 +436,49 @@ static hipError_t launch_count_hits(const ptd::DevScene& sc, const float* d_rays
     return hipGetLastError();
 }
 
+// Enqueues one batch of n <= 2^30 rays of pt_trace_rays_list on `stream`: the fill, the sort of the segments longer than kListLds,
+// then the detail records if asked for.  off: the batch's first offset; the records are addressed from d_hits whatever the batch.
+static hipError_t launch_rays_list(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, bool quad, bool both, const int64_t* off, int64_t cap,
+                                   PtRayHit* d_hits, float* d_detail4, hipStream_t stream)
+{
+    const dim3 blocks((n + 63u) / 64u);
+    const float4* rays = (const float4*)d_rays8;
+    int2* out = (int2*)d_hits;
+    if (quad) {
+        if (both) hipLaunchKernelGGL((ptd::rays_list<true, true>), blocks, dim3(64), 0, stream, sc, rays, n, off, cap, out);
+        else hipLaunchKernelGGL((ptd::rays_list<true, false>), blocks, dim3(64), 0, stream, sc, rays, n, off, cap, out);
+    } else {
+        if (both) hipLaunchKernelGGL((ptd::rays_list<false, true>), blocks, dim3(64), 0, stream, sc, rays, n, off, cap, out);
+        else hipLaunchKernelGGL((ptd::rays_list<false, false>), blocks, dim3(64), 0, stream, sc, rays, n, off, cap, out);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = ptk_list_sort(off, n, cap, out, true, stream)) != hipSuccess) return e;
+    if (d_detail4) {
+        uint32_t per, grid;
+        pt_list_grid(n, per, grid);
+        hipLaunchKernelGGL(ptd::rays_list_detail, dim3(grid), dim3(ptd::kSegThreads), 0, stream, sc, rays, n, per, off, cap, (const int2*)out, d_detail4);
+    }
+    return hipGetLastError();
+}
+
 // ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
+// pt_trace_rays_list and its host variant.  device: the pointers are device pointers (alignment checked, hits required); on the host
+// variant hits may be NULL (the sizing call).
+static int list_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, int32_t flags, const int64_t* offsets, int64_t cap,
+                        const void* hits, const float* detail, bool device)
+{
+    const char* bad = !s ? "NULL scene" : !rays ? "NULL rays" : !offsets ? "NULL offsets" : (device && !hits) ? "NULL hits" : n < 0 ? "n < 0" :
+                      cap < 0 ? "cap < 0" :
+                      (flags != PT_HITS_FRONT && flags != PT_HITS_BOTH_SIDES) ? "flags must be PT_HITS_FRONT or PT_HITS_BOTH_SIDES" :
+                      (device && ((uintptr_t)rays & 15)) ? "rays must be 16-byte aligned" :
+                      (device && ((uintptr_t)offsets & 7)) ? "offsets must be 8-byte aligned" :
+                      (device && ((uintptr_t)hits & 7)) ? "hits must be 8-byte aligned" :
+                      (device && ((uintptr_t)detail & 3)) ? "detail must be 4-byte aligned" : nullptr;
+    if (bad) { pt_set_error("%s: %s", who, bad); return PT_ERR_INVALID; }
+    return PT_OK;
+}
+
 // out_align: 8 for PtRayHit records, 4 for counts.  has_k: pt_trace_rays_k and its host variant.
 static int hits_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, bool has_k, int32_t k, int32_t flags, const void* out, int out_align,
                         const float* detail, bool device)
@@ -434,6 +557,51 @@ int pt_count_hits_host(PtScene* s, const float* h_rays8, int64_t n, int32_t flag
     if ((rc = pt_count_hits(s, d_rays.as<float>(), n, flags, d_count.as<int32_t>(), nullptr)) != PT_OK) return rc;
     HIPCHK(hipStreamSynchronize(nullptr));
     HIPCHK(hipMemcpy(h_count, d_count.as<>(), (size_t)n * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_trace_rays_list(PtScene* s, const float* d_rays8, int64_t n, int32_t flags, const int64_t* d_offsets, int64_t cap, PtRayHit* d_hits,
+                       float* d_detail4, void* hip_stream)
+{
+    int rc;
+    if ((rc = list_args_ok("pt_trace_rays_list", s, d_rays8, n, flags, d_offsets, cap, d_hits, d_detail4, true)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s), both = flags == PT_HITS_BOTH_SIDES;
+    for (int64_t off = 0; off < n; off += kHitsBatch) {
+        const uint32_t m = (uint32_t)(n - off < kHitsBatch ? n - off : kHitsBatch);
+        HIPCHK(launch_rays_list(s->dev, d_rays8 + off * 8, m, quad, both, d_offsets + off, cap, d_hits, d_detail4, (hipStream_t)hip_stream));
+    }
+    return PT_OK;
+}
+
+int pt_trace_rays_list_host(PtScene* s, const float* h_rays8, int64_t n, int32_t flags, int64_t* h_offsets, int64_t cap, PtRayHit* h_hits,
+                            float* h_detail4)
+{
+    int rc;
+    if ((rc = list_args_ok("pt_trace_rays_list_host", s, h_rays8, n, flags, h_offsets, cap, h_hits, h_detail4, false)) != PT_OK) return rc;
+    if (n == 0) { h_offsets[0] = 0; return PT_OK; }
+    HIPCHK(hipSetDevice(s->device));
+    DevBuf d_rays, d_count, d_off, d_scratch, d_hits, d_det;      // d_det stays null when the caller asked for no detail records
+    HIPCHK(d_rays.alloc((size_t)n * 32));
+    HIPCHK(d_count.alloc((size_t)n * 4));
+    HIPCHK(d_off.alloc((size_t)(n + 1) * 8));
+    HIPCHK(d_scratch.alloc((size_t)pt_list_offsets_scratch_bytes(n)));
+    HIPCHK(hipMemcpy(d_rays.as<>(), h_rays8, (size_t)n * 32, hipMemcpyHostToDevice));
+    if ((rc = pt_count_hits(s, d_rays.as<float>(), n, flags, d_count.as<int32_t>(), nullptr)) != PT_OK) return rc;
+    if ((rc = pt_list_offsets(d_count.as<int32_t>(), n, d_off.as<int64_t>(), d_scratch.as<>(), nullptr)) != PT_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(h_offsets, d_off.as<>(), (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
+    if (!h_hits) return PT_OK;      // the sizing call
+    const int64_t total = h_offsets[n];
+    if (cap < total) { pt_set_error("pt_trace_rays_list_host: cap %lld < %lld records", (long long)cap, (long long)total); return PT_ERR_INVALID; }
+    HIPCHK(d_hits.alloc((size_t)total * 8));
+    if (h_detail4) HIPCHK(d_det.alloc((size_t)total * 16));
+    if ((rc = pt_trace_rays_list(s, d_rays.as<float>(), n, flags, d_off.as<int64_t>(), total, d_hits.as<PtRayHit>(), d_det.as<float>(), nullptr)) != PT_OK)
+        return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(h_hits, d_hits.as<>(), (size_t)total * 8, hipMemcpyDeviceToHost));
+    if (h_detail4) HIPCHK(hipMemcpy(h_detail4, d_det.as<>(), (size_t)total * 16, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

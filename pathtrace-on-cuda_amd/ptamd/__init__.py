@@ -231,6 +231,12 @@ API = [
     ("pt_trace_rays_k_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     ("pt_count_hits", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     ("pt_count_hits_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
+    ("pt_list_offsets_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("pt_list_offsets", C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    ("pt_trace_rays_list", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P, _P]),
+    ("pt_within_radius_list", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
+    ("pt_trace_rays_list_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P]),
+    ("pt_within_radius_list_host", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("pt_rays_floats", C.c_int64, [C.c_int64]),
     ("pt_rays_work_bytes", C.c_int64, [C.POINTER(PtParams), C.c_int64]),
     ("pt_render_rays", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
@@ -1008,6 +1014,85 @@ class Scene:
         _check(lib().pt_count_hits(self._h, C.c_void_p(rays.data_ptr()), n, flags, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_count_hits")
         return cnt
 
+    def trace_rays_all(self, rays, both_sides=False, detail=False, stream_ptr=0):
+        """Every hit along each ray, sorted, in CSR form (include/pt_api.h: pt_trace_rays_list).  rays and both_sides as in trace_rays_k.
+        Returns (offsets, t, prim) — int64 of shape (n + 1,), the hits of ray i at [offsets[i], offsets[i + 1]) of the float32 and int32
+        arrays t and prim, nearest first, among equal t the larger prim first — and, with detail=True, the (total, 4) detail records
+        u/det v/det facing 0 as a fourth item.
+        A torch float32 tensor on the scene's device runs in place on stream_ptr: count_hits, list_offsets, one 8-byte read-back of the
+        total — which WAITS for the stream to pass the scan —, the allocation of the records, the fill.  The records are torch tensors on
+        that device, valid once the stream has passed the fill, and `rays` must stay alive until then.  A numpy array goes through
+        pt_trace_rays_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays."""
+        flags = HITS_BOTH_SIDES if both_sides else HITS_FRONT
+        if isinstance(rays, np.ndarray):
+            r = np.ascontiguousarray(rays, np.float32)
+            if r.ndim != 2 or r.shape[1] != 8:
+                raise PtError(f"trace_rays_all: rays has shape {r.shape}, want (n, 8)")
+            n = r.shape[0]
+            off = np.zeros(n + 1, np.int64)
+            _check(lib().pt_trace_rays_list_host(self._h, _ptr(r), n, flags, _ptr(off), 0, None, None), "pt_trace_rays_list_host")
+            total = int(off[n])
+            hits = np.zeros(total, HIT_DTYPE)
+            det = np.zeros((total, 4), np.float32) if detail else None
+            if total:
+                _check(lib().pt_trace_rays_list_host(self._h, _ptr(r), n, flags, _ptr(off), total, _ptr(hits), _ptr(det) if detail else None),
+                       "pt_trace_rays_list_host")
+            out = (off, np.ascontiguousarray(hits["t"]), np.ascontiguousarray(hits["prim"]))
+            return out + (det,) if detail else out
+        n = _device_rays("trace_rays_all", rays, self.device)
+        import torch
+        if n == 0:
+            off, total = torch.zeros(1, dtype=torch.int64, device=rays.device), 0
+        else:
+            off = list_offsets(self.count_hits(rays, both_sides=both_sides, stream_ptr=stream_ptr), stream_ptr=stream_ptr)
+            total = _read_total(off, stream_ptr)
+        hits = torch.empty((total, 2), dtype=torch.int32, device=rays.device)      # PtRayHit: t's bits | prim
+        det = torch.empty((total, 4), dtype=torch.float32, device=rays.device) if detail else None
+        if total:
+            _check(lib().pt_trace_rays_list(self._h, C.c_void_p(rays.data_ptr()), n, flags, C.c_void_p(off.data_ptr()), total, C.c_void_p(hits.data_ptr()),
+                                            C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_trace_rays_list")
+        out = (off, hits[:, 0].view(torch.float32), hits[:, 1])
+        return out + (det,) if detail else out
+
+    def within_radius(self, points, detail=False, stream_ptr=0):
+        """Every primitive within each point's radius, sorted, in CSR form (include/pt_api.h: pt_within_radius_list).  points as in
+        nearest_k; an infinite radius lists every primitive.  Returns (offsets, dist2, prim) — int64 of shape (n + 1,), the members of
+        point i at [offsets[i], offsets[i + 1]) of the float32 and int32 arrays dist2 and prim, nearest first, among equal dist2 the larger
+        prim first — and, with detail=True, the (total, 8) detail records c.xyz v w side feature 0 as a fourth item.
+        A torch float32 tensor on the scene's device runs in place on stream_ptr: count_within, list_offsets, one 8-byte read-back of the
+        total — which WAITS for the stream to pass the scan —, the allocation of the records, the fill.  The records are torch tensors on
+        that device, valid once the stream has passed the fill, and `points` must stay alive until then.  A numpy array goes through
+        pt_within_radius_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays."""
+        if isinstance(points, np.ndarray):
+            p = np.ascontiguousarray(points, np.float32)
+            if p.ndim != 2 or p.shape[1] != 4:
+                raise PtError(f"within_radius: points has shape {p.shape}, want (n, 4)")
+            n = p.shape[0]
+            off = np.zeros(n + 1, np.int64)
+            _check(lib().pt_within_radius_list_host(self._h, _ptr(p), n, _ptr(off), 0, None, None), "pt_within_radius_list_host")
+            total = int(off[n])
+            res = np.zeros(total, NEAREST_DTYPE)
+            det = np.zeros((total, 8), np.float32) if detail else None
+            if total:
+                _check(lib().pt_within_radius_list_host(self._h, _ptr(p), n, _ptr(off), total, _ptr(res), _ptr(det) if detail else None),
+                       "pt_within_radius_list_host")
+            out = (off, np.ascontiguousarray(res["dist2"]), np.ascontiguousarray(res["prim"]))
+            return out + (det,) if detail else out
+        n = _device_points("within_radius", points, self.device)
+        import torch
+        if n == 0:
+            off, total = torch.zeros(1, dtype=torch.int64, device=points.device), 0
+        else:
+            off = list_offsets(self.count_within(points, stream_ptr=stream_ptr), stream_ptr=stream_ptr)
+            total = _read_total(off, stream_ptr)
+        res = torch.empty((total, 2), dtype=torch.int32, device=points.device)      # PtNearest: dist2's bits | prim
+        det = torch.empty((total, 8), dtype=torch.float32, device=points.device) if detail else None
+        if total:
+            _check(lib().pt_within_radius_list(self._h, C.c_void_p(points.data_ptr()), n, C.c_void_p(off.data_ptr()), total, C.c_void_p(res.data_ptr()),
+                                               C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_within_radius_list")
+        out = (off, res[:, 0].view(torch.float32), res[:, 1])
+        return out + (det,) if detail else out
+
     def render_rays_device(self, d_rays_ptr, n_rays, prm, d_rgb_ptr, d_work_ptr, d_seed_ptr=0, seed_stride=None, stream_ptr=0):
         """Device-resident radiance along n_rays RAY8 records (raw device pointers: rays_floats(n) floats of output, rays_work_bytes(prm,
         n) bytes of scratch, d_seed_ptr 0 = ray i is seeded with i), enqueued on the given stream; blocks until the render has drained.
@@ -1072,6 +1157,47 @@ class Scene:
         prim = np.zeros(n, np.int32)
         _check(lib().pt_dbg_raycast(self._h, _ptr(rays8), n, _ptr(hits), _ptr(prim)), "pt_dbg_raycast")
         return hits, prim
+
+
+def list_offsets(count, stream_ptr=0):
+    """CSR offsets of per-query counts (include/pt_api.h: pt_list_offsets): (n + 1,) int64, offsets[0] = 0 and offsets[i + 1] =
+    offsets[i] + max(count[i], 0), without wrapping at 2^31.  count: a contiguous int32 torch tensor of shape (n,) on a GPU, used in
+    place: the scan is enqueued on stream_ptr on count's device and the offsets are a torch tensor there, valid once the stream has
+    passed the scan.  A numpy array is scanned on device 0 through the NULL stream, with a wait, and the offsets come back as numpy."""
+    import torch
+    if isinstance(count, np.ndarray):
+        c = np.ascontiguousarray(count)
+        if c.dtype != np.int32 or c.ndim != 1:
+            raise PtError(f"list_offsets: count must be int32 of shape (n,), got {c.dtype} {c.shape}")
+        off = list_offsets(torch.from_numpy(c).to("cuda:0"))
+        torch.cuda.synchronize(0)
+        return off.cpu().numpy()
+    if not (hasattr(count, "data_ptr") and hasattr(count, "is_contiguous")):
+        raise PtError("list_offsets: count must be a torch tensor or a numpy array")
+    if str(count.dtype) != "torch.int32" or not count.is_contiguous() or count.dim() != 1:
+        raise PtError(f"list_offsets: count must be contiguous int32 of shape (n,), got {count.dtype} {tuple(count.shape)}")
+    if count.device.type != "cuda":
+        raise PtError(f"list_offsets: count is on {count.device}, want a GPU")
+    n = count.shape[0]
+    sb = lib().pt_list_offsets_scratch_bytes(n)
+    with torch.cuda.device(count.device):
+        off = torch.empty(n + 1, dtype=torch.int64, device=count.device)
+        scratch = torch.empty(max(sb, 8), dtype=torch.uint8, device=count.device)
+        cptr = count.data_ptr() or scratch.data_ptr()      # an empty tensor has no address; n = 0 reads no count
+        _check(lib().pt_list_offsets(C.c_void_p(cptr), n, C.c_void_p(off.data_ptr()), C.c_void_p(scratch.data_ptr()), C.c_void_p(stream_ptr)),
+               "pt_list_offsets")
+        st = torch.cuda.ExternalStream(stream_ptr, device=count.device) if stream_ptr else torch.cuda.default_stream(count.device)
+        if st.cuda_stream != torch.cuda.current_stream().cuda_stream:      # the NULL stream included
+            scratch.record_stream(st)      # not reused before the stream the scan is on has passed it
+    return off
+
+
+def _read_total(off, stream_ptr):
+    """off[-1] as an int: one 8-byte read-back on stream_ptr (or the NULL stream), which waits for that stream."""
+    import torch
+    st = torch.cuda.ExternalStream(stream_ptr, device=off.device) if stream_ptr else torch.cuda.default_stream(off.device)
+    with torch.cuda.stream(st):
+        return int(off[-1].item())
 
 
 def tiles_floats(cam, prm):

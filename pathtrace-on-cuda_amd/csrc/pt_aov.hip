@@ -298,12 +298,10 @@ int pt_aov_rays(PtScene* s, const float* d_rays8, int64_t n_rays, float* d_aov, 
     if (rc) return rc;
     if (n_rays == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
-    const int64_t kBatch = (int64_t)1 << 30;      // rays per launch: ray numbers are 32-bit
-    for (int64_t off = 0; off < n_rays; off += kBatch) {
-        const uint32_t m = (uint32_t)(n_rays - off < kBatch ? n_rays - off : kBatch);
+    HIPCHK(pt_query_batches(n_rays, [&](int64_t off, uint32_t m) {
         const ptd::AovRays src{(const float4*)(d_rays8 + off * 8), m};
-        HIPCHK(launch_aov(s, src, (m + 63u) / 64u, d_aov + off * 8, d_prim ? d_prim + off : nullptr, (hipStream_t)hip_stream));
-    }
+        return launch_aov(s, src, (m + 63u) / 64u, d_aov + off * 8, d_prim ? d_prim + off : nullptr, (hipStream_t)hip_stream);
+    }));
     return PT_OK;
 }
 

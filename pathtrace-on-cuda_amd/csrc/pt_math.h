@@ -65,6 +65,13 @@ PT_DEV f3 refract(const f3& w, const f3& n, float inv_eta) {
     return (-w) * inv_eta + (inv_eta * c - __builtin_sqrtf(k)) * n;
 }
 
+// Ray i of the caller's RAY8 records (include/pt_api.h: org.xyz dir.xyz reserved tmax), as two 16-byte loads: the ray queries' loader
+PT_DEV void load_ray(const float4* __restrict__ rays, size_t i, f3& org, f3& dir, float& tmax)
+{
+    const float4 a = rays[2 * i], b = rays[2 * i + 1];
+    org = f3(a.x, a.y, a.z); dir = f3(a.w, b.x, b.y); tmax = b.w;
+}
+
 // ---- correctly rounded float transcendentals through fp64 ---------------------------
 PT_DEV float cr_sin(float x) { return (float)::sin((double)x); }
 PT_DEV float cr_cos(float x) { return (float)::cos((double)x); }

@@ -1,11 +1,12 @@
 // pt_nearest.h — what the distance queries share (pt_nearest.hip: pt_closest_points; pt_knearest.hip: pt_nearest_k, pt_count_within): the
 // ONE statement of the float32 function f of include/pt_api.h ("Closest-point queries"), of the box distance their walks prune with,
-// of the widening of the child boxes of either tree that the pruning's premise rests on, and of the detail record.
-// DESIGN.md sections 29 and 30.
+// of the widening of the child boxes of either tree that the pruning's premise rests on, of the detail record, and the point walk over
+// either tree that hands the candidates to a query's sink.  DESIGN.md sections 29, 30 and 38.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pt_device.h"
 #include "pt_math.h"
+#include "pt_trace.h"
 
 namespace ptd {
 
@@ -124,6 +125,113 @@ PT_DEV bool near_pop(const int2* stack, int& sp, float best, int& cur)
         if (!(__int_as_float(e.x) > best)) { cur = e.y; return true; }
     }
     return false;
+}
+
+// ---- the point walk of pt_knearest.hip's queries: candidates f(p, k) to a sink (pt_lists.h: SlotList has the interface) -----------
+// Sinks: the K list, the count and the fill.  s.offer(f, prim): the sink's acceptance and, if it accepts, its take.  SINK::kOrdered:
+// take the nearest child next (the bound falls sooner); else the children as they come.  pt_nearest.hip's closest query keeps its own
+// copy of the walk (through this template its kernel's code changed and measured slower).
+
+// The `cnt` triangles at tree position `first` (a leaf of either tree: ~ref = first << 3 | cnt)
+template <class SINK>
+PT_DEV void knear_leaf(const DevScene& sc, int ref, const f3& p, SINK& s)
+{
+    const int code = ~ref, first = code >> 3, cnt = code & 7;
+    for (int k = 0; k < cnt; k++) {
+        const float4* rec = sc.tri + 3 * (size_t)(first + k);
+        const float4 a = rec[0], b = rec[1], c = rec[2];
+        s.offer(tri_f(p, f3(a.x, a.y, a.z), f3(b.x, b.y, b.z), f3(c.x, c.y, c.z)), __float_as_int(a.w));
+    }
+}
+
+// The walk over the 4-wide quantised tree.  A node pushes at most three of its children and descends into the fourth, a leaf pushes
+// nothing: the stack never exceeds 3 entries per level (the caller has checked 3 * quad_depth + 2 <= kQueryStack), and the walk ends
+// whatever the floats are, as quad_step's does.  An ordered sink takes the nearest child next and pushes the others farthest first.
+template <class SINK>
+PT_DEV void knear_walk_quad(const DevScene& sc, const f3& p, int2* stack, SINK& s)
+{
+    int cur = 0, sp = 0;
+    for (;;) {
+        if (cur >= 0) {
+            const uint4* np = sc.quad + 4 * (size_t)cur;
+            const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
+            const int ref[4] = {(int)n1.x, (int)n1.y, (int)n1.z, (int)n1.w};
+            int key[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                f3 lo, hi;
+                near_quad_child_box(n0, n2, n3, k, lo, hi);
+                const float lb = boxdist2(p, lo, hi);
+                key[k] = ((ref[k] == -1) | (lb > s.bound)) ? kQuadMiss : __float_as_int(lb);      // strictly: an equal bound may hide a tie that enters
+            }
+            if constexpr (SINK::kOrdered) {
+                int k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3], r0 = ref[0], r1 = ref[1], r2 = ref[2], r3 = ref[3];
+#define PT_CE(ka, ra, kb, rb) { const bool sw = ka > kb; const int tk = sw ? kb : ka, tr = sw ? rb : ra; kb = sw ? ka : kb; rb = sw ? ra : rb; ka = tk; ra = tr; }
+                PT_CE(k0, r0, k1, r1) PT_CE(k2, r2, k3, r3) PT_CE(k0, r0, k2, r2) PT_CE(k1, r1, k3, r3) PT_CE(k1, r1, k2, r2)
+#undef PT_CE
+                if (k0 != kQuadMiss) {
+                    if (k3 != kQuadMiss) { stack[sp * 64] = make_int2(k3, r3); sp++; }
+                    if (k2 != kQuadMiss) { stack[sp * 64] = make_int2(k2, r2); sp++; }
+                    if (k1 != kQuadMiss) { stack[sp * 64] = make_int2(k1, r1); sp++; }
+                    cur = r0;
+                    continue;
+                }
+            } else {
+                bool have = false;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    if (key[k] == kQuadMiss) continue;
+                    if (have) { stack[sp * 64] = make_int2(key[k], ref[k]); sp++; }
+                    else { cur = ref[k]; have = true; }
+                }
+                if (have) continue;
+            }
+        } else {
+            knear_leaf(sc, cur, p, s);
+        }
+        if (!near_pop(stack, sp, s.bound, cur)) return;
+    }
+}
+
+// The walk over the binary tree, for a scene whose 4-wide walk would not fit kQueryStack (or PTAMD_QUERY_QUAD=0).  As in trace_closest a
+// leaf child is evaluated on the spot and an entry is pushed only where both children are interior: at most depth - 1 <= 31 entries.
+template <class SINK>
+PT_DEV void knear_walk_binary(const DevScene& sc, const f3& p, int2* stack, SINK& s)
+{
+    int cur = 0, sp = 0;
+    for (;;) {
+        const float4 q0 = sc.nodes[4 * (size_t)cur + 0], q1 = sc.nodes[4 * (size_t)cur + 1], q2 = sc.nodes[4 * (size_t)cur + 2], q3 = sc.nodes[4 * (size_t)cur + 3];
+        f3 loL(q0.x, q0.y, q0.z), hiL(q0.w, q1.x, q1.y), loR(q1.z, q1.w, q2.x), hiR(q2.y, q2.z, q2.w);
+        widen_binary(loL, hiL);
+        widen_binary(loR, hiR);
+        const float lbL = boxdist2(p, loL, hiL), lbR = boxdist2(p, loR, hiR);
+        const int refL = __float_as_int(q3.x), refR = __float_as_int(q3.y);
+        if (refL < 0 && !(lbL > s.bound)) knear_leaf(sc, refL, p, s);
+        if (refR < 0 && !(lbR > s.bound)) knear_leaf(sc, refR, p, s);
+        const bool okL = (refL >= 0) & !(lbL > s.bound), okR = (refR >= 0) & !(lbR > s.bound);      // against what the leaves left
+        if (okL & okR) {
+            const bool lNear = !SINK::kOrdered || lbL <= lbR;
+            stack[sp * 64] = lNear ? make_int2(__float_as_int(lbR), refR) : make_int2(__float_as_int(lbL), refL);
+            sp++;
+            cur = lNear ? refL : refR;
+        } else if (okL) {
+            cur = refL;
+        } else if (okR) {
+            cur = refR;
+        } else if (!near_pop(stack, sp, s.bound, cur)) {
+            return;
+        }
+    }
+}
+
+// Point q (p.xyz radius): the walk, then the spheres in order
+template <bool QUAD, class SINK>
+PT_DEV void knear_point(const DevScene& sc, const float4& q, int2* stack, SINK& s)
+{
+    const f3 p(q.x, q.y, q.z);
+    if (QUAD) knear_walk_quad(sc, p, stack, s);
+    else knear_walk_binary(sc, p, stack, s);
+    for (int j = 0; j < sc.n_spheres; j++) s.offer(sphere_f(p, sc.spheres[4 * j]), sc.n_tris + j);
 }
 
 }  // namespace ptd

@@ -178,14 +178,9 @@ static hipError_t launch_nearest(const ptd::DevScene& sc, const float* d_points4
 static int nearest_args_ok(const char* who, const PtScene* s, const float* points, int64_t n, int32_t mode, const PtNearest* out, const float* detail,
                            bool device)
 {
-    const char* bad = !s ? "NULL scene" : !points ? "NULL points" : !out ? "NULL out" : n < 0 ? "n < 0" :
-                      (mode != PT_NEAREST_CLOSEST && mode != PT_NEAREST_ANY) ? "mode must be PT_NEAREST_CLOSEST or PT_NEAREST_ANY" :
-                      (mode == PT_NEAREST_ANY && detail) ? "an any-within query has no detail record (d_detail8 must be NULL)" :
-                      (device && ((uintptr_t)points & 15)) ? "points must be 16-byte aligned" :
-                      (device && ((uintptr_t)out & 7)) ? "out must be 8-byte aligned" :
-                      (device && ((uintptr_t)detail & 3)) ? "detail must be 4-byte aligned" : nullptr;
-    if (bad) { pt_set_error("%s: %s", who, bad); return PT_ERR_INVALID; }
-    return PT_OK;
+    const char* param = (mode != PT_NEAREST_CLOSEST && mode != PT_NEAREST_ANY) ? "mode must be PT_NEAREST_CLOSEST or PT_NEAREST_ANY" :
+                        (mode == PT_NEAREST_ANY && detail) ? "an any-within query has no detail record (d_detail8 must be NULL)" : nullptr;
+    return pt_query_args(who, s, n, device, {"points", points, "out", out, "out", 8, "detail", detail, param, false, nullptr, 0});
 }
 
 extern "C" {
@@ -197,12 +192,10 @@ int pt_closest_points(PtScene* s, const float* d_points4, int64_t n, int32_t mod
     if (n == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
     const bool quad = pt_query_walks_quad(s);
-    const int64_t kBatch = (int64_t)1 << 30;      // points per launch: point numbers are 32-bit
-    for (int64_t off = 0; off < n; off += kBatch) {
-        const uint32_t m = (uint32_t)(n - off < kBatch ? n - off : kBatch);
-        HIPCHK(launch_nearest(s->dev, d_points4 + off * 4, m, mode == PT_NEAREST_ANY, quad, d_out + off, d_detail8 ? d_detail8 + off * 8 : nullptr,
-                              (hipStream_t)hip_stream));
-    }
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_nearest(s->dev, d_points4 + off * 4, m, mode == PT_NEAREST_ANY, quad, d_out + off, d_detail8 ? d_detail8 + off * 8 : nullptr,
+                              (hipStream_t)hip_stream);
+    }));
     return PT_OK;
 }
 
@@ -212,16 +205,9 @@ int pt_closest_points_host(PtScene* s, const float* h_points4, int64_t n, int32_
     if ((rc = nearest_args_ok("pt_closest_points_host", s, h_points4, n, mode, h_out, h_detail8, false)) != PT_OK) return rc;
     if (n == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
-    DevBuf d_pts, d_out, d_det;      // d_det stays null when the caller asked for no detail records
-    HIPCHK(d_pts.alloc((size_t)n * 16));
-    HIPCHK(d_out.alloc((size_t)n * 8));
-    if (h_detail8) HIPCHK(d_det.alloc((size_t)n * 32));
-    HIPCHK(hipMemcpy(d_pts.as<>(), h_points4, (size_t)n * 16, hipMemcpyHostToDevice));
-    if ((rc = pt_closest_points(s, d_pts.as<float>(), n, mode, d_out.as<PtNearest>(), d_det.as<float>(), nullptr)) != PT_OK) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipMemcpy(h_out, d_out.as<>(), (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (h_detail8) HIPCHK(hipMemcpy(h_detail8, d_det.as<>(), (size_t)n * 32, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return pt_host_query(h_points4, (size_t)n * 16, h_out, (size_t)n * 8, h_detail8, (size_t)n * 32, [&](float* d_pts, void* d_out, float* d_det) {
+        return pt_closest_points(s, d_pts, n, mode, (PtNearest*)d_out, d_det, nullptr);
+    });
 }
 
 }  // extern "C"

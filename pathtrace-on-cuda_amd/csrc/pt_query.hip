@@ -22,13 +22,6 @@
 
 namespace ptd {
 
-// RAY8: org.xyz dir.xyz reserved tmax, as two 16-byte loads
-PT_DEV void load_ray(const float4* __restrict__ rays, size_t i, f3& org, f3& dir, float& tmax)
-{
-    const float4 a = rays[2 * i], b = rays[2 * i + 1];
-    org = f3(a.x, a.y, a.z); dir = f3(a.w, b.x, b.y); tmax = b.w;
-}
-
 // The spheres, in order, against the triangles' result (pt_trace.h: spheres_closest), and the 8-byte record.  An any-hit query that has its
 // triangle needs no sphere; one that has none tests them against tmax exactly as the closest-hit query does, and stops at the first.
 template <bool ANY>
@@ -118,14 +111,9 @@ static hipError_t launch_query(const ptd::DevScene& sc, const float* uv, const f
 static int query_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, int32_t mode, const PtRayHit* hits, const float* surface,
                          bool device)
 {
-    const char* bad = !s ? "NULL scene" : !rays ? "NULL rays" : !hits ? "NULL hits" : n < 0 ? "n < 0" :
-                      (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_ANY) ? "mode must be PT_QUERY_CLOSEST or PT_QUERY_ANY" :
-                      (mode == PT_QUERY_ANY && surface) ? "an any-hit query has no surface record (d_surface29 must be NULL)" :
-                      (device && ((uintptr_t)rays & 15)) ? "rays must be 16-byte aligned" :
-                      (device && ((uintptr_t)hits & 7)) ? "hits must be 8-byte aligned" :
-                      (device && ((uintptr_t)surface & 3)) ? "surface must be 4-byte aligned" : nullptr;
-    if (bad) { pt_set_error("%s: %s", who, bad); return PT_ERR_INVALID; }
-    return PT_OK;
+    const char* param = (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_ANY) ? "mode must be PT_QUERY_CLOSEST or PT_QUERY_ANY" :
+                        (mode == PT_QUERY_ANY && surface) ? "an any-hit query has no surface record (d_surface29 must be NULL)" : nullptr;
+    return pt_query_args(who, s, n, device, {"rays", rays, "hits", hits, "hits", 8, "surface", surface, param, false, nullptr, 0});
 }
 
 extern "C" {
@@ -137,12 +125,10 @@ int pt_trace_rays(PtScene* s, const float* d_rays8, int64_t n, int32_t mode, PtR
     if (n == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
     const bool quad = pt_query_walks_quad(s);
-    const int64_t kBatch = (int64_t)1 << 30;      // rays per launch: ray numbers are 32-bit
-    for (int64_t off = 0; off < n; off += kBatch) {
-        const uint32_t m = (uint32_t)(n - off < kBatch ? n - off : kBatch);
-        HIPCHK(launch_query(s->dev, s->uv.as<float>(), d_rays8 + off * 8, m, mode == PT_QUERY_ANY, quad, d_hits + off,
-                              d_surface29 ? d_surface29 + off * 29 : nullptr, (hipStream_t)hip_stream));
-    }
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_query(s->dev, s->uv.as<float>(), d_rays8 + off * 8, m, mode == PT_QUERY_ANY, quad, d_hits + off,
+                            d_surface29 ? d_surface29 + off * 29 : nullptr, (hipStream_t)hip_stream);
+    }));
     return PT_OK;
 }
 
@@ -152,16 +138,9 @@ int pt_trace_rays_host(PtScene* s, const float* h_rays8, int64_t n, int32_t mode
     if ((rc = query_args_ok("pt_trace_rays_host", s, h_rays8, n, mode, h_hits, h_surface29, false)) != PT_OK) return rc;
     if (n == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
-    DevBuf d_rays, d_hits, d_surf;      // d_surf stays null when the caller asked for no surface records
-    HIPCHK(d_rays.alloc((size_t)n * 32));
-    HIPCHK(d_hits.alloc((size_t)n * 8));
-    if (h_surface29) HIPCHK(d_surf.alloc((size_t)n * 116));
-    HIPCHK(hipMemcpy(d_rays.as<>(), h_rays8, (size_t)n * 32, hipMemcpyHostToDevice));
-    if ((rc = pt_trace_rays(s, d_rays.as<float>(), n, mode, d_hits.as<PtRayHit>(), d_surf.as<float>(), nullptr)) != PT_OK) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipMemcpy(h_hits, d_hits.as<>(), (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (h_surface29) HIPCHK(hipMemcpy(h_surface29, d_surf.as<>(), (size_t)n * 116, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return pt_host_query(h_rays8, (size_t)n * 32, h_hits, (size_t)n * 8, h_surface29, (size_t)n * 116, [&](float* d_rays, void* d_hits, float* d_surf) {
+        return pt_trace_rays(s, d_rays, n, mode, (PtRayHit*)d_hits, d_surf, nullptr);
+    });
 }
 
 }  // extern "C"

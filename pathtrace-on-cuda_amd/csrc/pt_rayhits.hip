@@ -10,8 +10,8 @@
 // is still met and the tie rule decides.  As in pt_knearest.hip every triangle must sit below exactly ONE leaf of the tree walked.
 //
 // Shape: query_rays' (pt_query.hip) — one ray per lane, one-wave workgroups, the per-lane int stack in LDS with entry e at
-// stack[e * 64].  Beside it nearest_k's per-lane list, sorted, slot j at list[j * kHitRow + lane] as int2 (t's bits, prim).  t is
-// compared as a FLOAT (-0 equals +0, and its bits go out as pt_trace_rays would write them).  Facing is not stored: the detail kernel
+// stack[e * 64].  Beside it nearest_k's per-lane list, sorted, slot j at list[j * kSlotRow + lane] as int2 (t's bits, prim): pt_lists.h's
+// SlotList<true>, t compared as a FLOAT (-0 equals +0, and its bits go out as pt_trace_rays would write them).  Facing is not stored: the detail kernel
 // recomputes it from the sign of det (a triangle) or from which root the slot holds (a sphere).
 #include <hip/hip_runtime.h>
 #include "pt_device.h"
@@ -22,44 +22,13 @@
 
 namespace ptd {
 
-constexpr int kHitRow = 65;      // int2 entries from one slot of the list to the next: pt_knearest.hip's kListRow, for the same copy-out
-
-// What a walk hands its hits to.  `bound`: a box the ray enters beyond this holds nothing the sink would take.  wants(): the sink's
-// precondition, asked before the leaf box is fetched; take(): only after a wants() on the sink as it is now.
-// The list of the first K.  (bound, boundPrim) is (tmax, -1) while cnt < k and slot k - 1 from then on, so that ONE rule accepts:
-// t < bound, or t == bound and a larger prim — with fewer than k that is t <= tmax, with k it is "precedes the last slot".  A NaN t
-// passes neither comparison.  Every slot index is at most min(cnt, k - 1) <= k - 1, and the kernel has checked k <= KC.
-struct HitList {
-    int2* list;      // this lane's slot 0
-    int k, cnt;
-    float bound;
-    int boundPrim;
-    PT_DEV bool wants(float t, int prim) const { return (t < bound) | ((t == bound) & (prim > boundPrim)); }
-    PT_DEV void take(float t, int prim)
-    {
-        int j = (cnt < k) ? cnt : k - 1;      // the slot that opens: the next free one, or the last, whose hit drops out
-        while (j > 0) {                       // shift from the tail until the slot before precedes the hit
-            const int2 e = list[(j - 1) * kHitRow];
-            const float et = __int_as_float(e.x);
-            if ((et < t) | ((et == t) & (e.y > prim))) break;
-            list[j * kHitRow] = e;
-            j--;
-        }
-        list[j * kHitRow] = make_int2(__float_as_int(t), prim);
-        cnt += (cnt < k) ? 1 : 0;
-        if (cnt == k) {
-            const int2 last = list[(k - 1) * kHitRow];
-            bound = __int_as_float(last.x);
-            boundPrim = last.y;
-        }
-    }
-};
-
-// |H|: the bound stays tmax
+// What a walk hands its hits to (pt_lists.h: SlotList has the interface; wants() is asked before the leaf box is fetched).
+// |H|: the bound stays tmax.  counts(): its acceptance, and the fill's for a long segment (pt_lists.h: SlotSeg).
 struct HitCount {
     int cnt;
     float bound;
-    PT_DEV bool wants(float t, int) const { return !(t > bound); }
+    PT_DEV static bool counts(float t, float bound) { return !(t > bound); }
+    PT_DEV bool wants(float t, int) const { return counts(t, bound); }
     PT_DEV void take(float, int) { cnt++; }
 };
 
@@ -203,12 +172,6 @@ PT_DEV void sphere_hits(const DevScene& sc, const f3& org, const f3& dir, float 
     }
 }
 
-PT_DEV void load_ray8(const float4* __restrict__ rays, size_t i, f3& org, f3& dir, float& tmax)
-{
-    const float4 a = rays[2 * i], b = rays[2 * i + 1];
-    org = f3(a.x, a.y, a.z); dir = f3(a.w, b.x, b.y); tmax = b.w;
-}
-
 template <bool QUAD, bool BOTH, class SINK>
 PT_DEV void hits_ray(const DevScene& sc, const f3& org, const f3& dir, float tmax, int* stack, SINK& s)
 {
@@ -217,9 +180,9 @@ PT_DEV void hits_ray(const DevScene& sc, const f3& org, const f3& dir, float tma
     sphere_hits<BOTH>(sc, org, dir, tmax, s);
 }
 
-// KC: the capacity class of the list, the smallest of 4, 8, 16, 32 that holds k (launch_rays_k).  The wave's 64 rays own the 64 * k
-// consecutive records from out[blockIdx.x * 64 * k]; every lane pads its list with miss records and the wave copies the block out
-// of LDS in record order, 64 consecutive records (512 bytes) per store, exactly as nearest_k does.
+// KC: the capacity class of the list (pt_scene.h: pt_kc_dispatch).  The wave's 64 rays own the 64 * k consecutive records from
+// out[blockIdx.x * 64 * k]; every lane pads its list with miss records and the wave copies the block
+// out of LDS in record order, 64 consecutive records (512 bytes) per store, exactly as nearest_k's points do.
 // No waves-per-SIMD figure in the launch bounds, as in nearest_k: above KC = 4 the list's LDS, not the registers, decides how many
 // workgroups a CU holds (DESIGN.md section 34 has the table; the registers allow kQueryWaves in every instantiation).
 template <int KC, bool QUAD, bool BOTH>
@@ -227,26 +190,26 @@ __global__ __launch_bounds__(64)
 void rays_k(DevScene sc, const float4* __restrict__ rays, uint32_t n, int k, int2* __restrict__ out)
 {
     __shared__ int lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
-    __shared__ int2 lds_list[KC * kHitRow];
+    __shared__ int2 lds_list[KC * kSlotRow];
     if (k < 1 || k > KC) return;      // the launcher's choice of KC, restated where the list is indexed
     const uint32_t lane = threadIdx.x, base = blockIdx.x * 64u, i = base + lane;
     int2* list = &lds_list[lane];
     int cnt = 0;
     if (i < n) {
         f3 org, dir; float tmax;
-        load_ray8(rays, i, org, dir, tmax);
-        HitList s{list, k, 0, tmax, -1};
+        load_ray(rays, i, org, dir, tmax);
+        SlotList<true> s{list, k, 0, tmax, -1};
         hits_ray<QUAD, BOTH>(sc, org, dir, tmax, &lds_stack[lane], s);
         cnt = s.cnt;
     }
-    for (int j = cnt; j < k; j++) list[j * kHitRow] = make_int2(0, -1);      // a miss is (0, -1)
+    for (int j = cnt; j < k; j++) list[j * kSlotRow] = make_int2(0, -1);      // a miss is (0, -1)
     __syncthreads();
     const uint32_t live = (n - base < 64u) ? n - base : 64u, total = live * (uint32_t)k;
     int2* dst = out + (size_t)base * (size_t)k;
     const int q64 = 64 / k, m64 = 64 % k;
     int t = (int)lane / k, j = (int)lane % k;      // record r is slot j of ray t: r = t * k + j, t < live <= 64
     for (uint32_t r = lane; r < total; r += 64u) {
-        dst[r] = lds_list[j * kHitRow + t];
+        dst[r] = lds_list[j * kSlotRow + t];
         j += m64;
         t += q64;
         if (j >= k) { j -= k; t++; }
@@ -261,7 +224,7 @@ void count_hits(DevScene sc, const float4* __restrict__ rays, uint32_t n, int32_
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     if (i >= n) return;
     f3 org, dir; float tmax;
-    load_ray8(rays, i, org, dir, tmax);
+    load_ray(rays, i, org, dir, tmax);
     HitCount s{0, tmax};
     hits_ray<QUAD, BOTH>(sc, org, dir, tmax, &lds_stack[threadIdx.x], s);
     out[i] = s.cnt;
@@ -298,7 +261,7 @@ PT_DEV void hit_detail(const DevScene& sc, const f3& org, const f3& dir, float t
     o[0] = dot(P, T) * invDet; o[1] = dot(Q, dir) * invDet; o[2] = (det < kEps) ? -1.f : 1.f; o[3] = 0.f;
 }
 
-// A launch covers the slots from `first` on (launch_rays_k: at most kHitDetailSlots of them, so that no grid exceeds 2^31 threads).
+// A launch covers the slots from `first` on (pt_scene.h: pt_detail_chunks).
 __global__ __launch_bounds__(256)
 void rays_k_detail(DevScene sc, const float4* __restrict__ rays, uint64_t first, uint64_t slots, uint32_t k, const int2* __restrict__ res, float* __restrict__ out4)
 {
@@ -309,36 +272,19 @@ void rays_k_detail(DevScene sc, const float4* __restrict__ rays, uint64_t first,
     float* o = out4 + t * 4;      // 4-byte aligned: four stores
     if (prim < 0) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; return; }
     f3 org, dir; float tmax;
-    load_ray8(rays, t / k, org, dir, tmax);
+    load_ray(rays, t / k, org, dir, tmax);
     hit_detail(sc, org, dir, tmax, h, o);
 }
 
 // ---- every hit: the fill of pt_trace_rays_list (pt_lists.h says which code sorts which segment) ----------------
-// The sink of the fill.  A lane owns the segment [b, b + m) of the records.  m <= kListLds: HitList itself, over the lane's LDS list with
-// k = m; the list goes out sorted after the walk.  m > kListLds: every member of H is appended to the segment in the order the walk
-// meets it, while fewer than m are stored, with HitCount's bound (tmax) and acceptance — so the members appended are the members
-// pt_count_hits counts —, and ptk_list_sort sorts the segment afterwards.
-struct HitSeg : HitList {
-    int2* seg;
-    int64_t m;
-    bool append;
-    PT_DEV bool wants(float t, int prim) const { return append ? !(t > bound) : HitList::wants(t, prim); }
-    PT_DEV void take(float t, int prim)
-    {
-        if (!append) { HitList::take(t, prim); return; }
-        if (cnt < m) { seg[cnt] = make_int2(__float_as_int(t), prim); cnt++; }
-    }
-};
-
-// One ray per lane, rays_k's shape with the list of class kListLds.  A lane whose segment is empty walks nothing.  Every record of the
-// segment is written once, by its lane: the members, then the miss record (0, -1) up to m.  Nothing outside [0, cap) is written:
-// list_segment clamps.
+// One ray per lane, rays_k's shape with the list of class kListLds and the sink SlotSeg, whose long segments take HitCount's members.
+// A lane whose segment is empty walks nothing.  Nothing outside [0, cap) is written: list_segment clamps.
 template <bool QUAD, bool BOTH>
 __global__ __launch_bounds__(64)
 void rays_list(DevScene sc, const float4* __restrict__ rays, uint32_t n, const int64_t* __restrict__ off, int64_t cap, int2* __restrict__ out)
 {
     __shared__ int lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
-    __shared__ int2 lds_list[kListLds * kHitRow];
+    __shared__ int2 lds_list[kListLds * kSlotRow];
     const uint32_t lane = threadIdx.x, i = blockIdx.x * 64u + lane;
     if (i >= n) return;
     int64_t b, e;
@@ -346,79 +292,46 @@ void rays_list(DevScene sc, const float4* __restrict__ rays, uint32_t n, const i
     const int64_t m = e - b;
     if (m == 0) return;
     f3 org, dir; float tmax;
-    load_ray8(rays, i, org, dir, tmax);
+    load_ray(rays, i, org, dir, tmax);
     int2* list = &lds_list[lane];
     int2* dst = out + b;
-    HitSeg s;
-    s.list = list; s.k = m > kListLds ? 0 : (int)m; s.cnt = 0; s.bound = tmax; s.boundPrim = -1;
-    s.seg = dst; s.m = m; s.append = m > kListLds;
+    SlotSeg<true, HitCount> s(list, dst, m, tmax);
     hits_ray<QUAD, BOTH>(sc, org, dir, tmax, &lds_stack[lane], s);
-    int64_t j = 0;
-    if (!s.append)
-        for (; j < s.cnt; j++) dst[j] = list[j * kHitRow];
-    else
-        j = s.cnt;
-    for (; j < m; j++) dst[j] = make_int2(0, -1);
+    fill_write_out(list, dst, m, s.cnt, s.append);
 }
 
-// The detail records of every segment, after the sort: hit_detail per member slot, zeros per miss slot.  A short segment by its query's
-// thread, a long one by the whole workgroup (pt_lists.h: for_each_segment).
+// The detail records of every segment, after the sort: hit_detail per member slot (pt_lists.h: segments_detail)
 __global__ __launch_bounds__(kSegThreads)
 void rays_list_detail(DevScene sc, const float4* __restrict__ rays, uint32_t n, uint32_t per, const int64_t* __restrict__ off, int64_t cap,
                       const int2* __restrict__ res, float* __restrict__ out4)
 {
-    auto slot = [&](const f3& org, const f3& dir, float tmax, int64_t t) {
-        const int2 h = res[t];
-        float* o = out4 + t * 4;
-        if (h.y < 0) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; return; }
-        hit_detail(sc, org, dir, tmax, h, o);
-    };
-    for_each_segment(off, n, per, cap,
-                     [&](uint32_t i, int64_t b, int64_t e) {
-                         f3 org, dir; float tmax;
-                         load_ray8(rays, i, org, dir, tmax);
-                         for (int64_t t = b; t < e; t++) slot(org, dir, tmax, t);
-                     },
-                     [&](uint32_t i, int64_t b, int64_t e) {
-                         f3 org, dir; float tmax;
-                         load_ray8(rays, i, org, dir, tmax);
-                         for (int64_t t = b + threadIdx.x; t < e; t += kSegThreads) slot(org, dir, tmax, t);
-                     });
+    struct Ray { f3 org, dir; float tmax; };
+    segments_detail<4>(off, n, per, cap, res, out4,
+                       [&](uint32_t i) { Ray r; load_ray(rays, i, r.org, r.dir, r.tmax); return r; },
+                       [&](const Ray& r, int2 h, float* o) { hit_detail(sc, r.org, r.dir, r.tmax, h, o); });
 }
 
 }  // namespace ptd
-
-template <int KC>
-static void launch_rays_kc(const ptd::DevScene& sc, const float4* rays, uint32_t n, int k, bool quad, bool both, int2* out, hipStream_t stream)
-{
-    const dim3 blocks((n + 63u) / 64u);
-    if (quad) {
-        if (both) hipLaunchKernelGGL((ptd::rays_k<KC, true, true>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
-        else hipLaunchKernelGGL((ptd::rays_k<KC, true, false>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
-    } else {
-        if (both) hipLaunchKernelGGL((ptd::rays_k<KC, false, true>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
-        else hipLaunchKernelGGL((ptd::rays_k<KC, false, false>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
-    }
-}
-
-static const uint64_t kHitDetailSlots = (uint64_t)1 << 31;      // slots per launch of rays_k_detail (a multiple of its 256 threads)
 
 // Enqueues one batch of n <= 2^30 rays on `stream`: k records per ray, then the detail records if asked for
 static hipError_t launch_rays_k(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, int k, bool quad, bool both, PtRayHit* d_hits, float* d_detail4, hipStream_t stream)
 {
     const float4* rays = (const float4*)d_rays8;
     int2* out = (int2*)d_hits;
-    if (k <= 4) launch_rays_kc<4>(sc, rays, n, k, quad, both, out, stream);
-    else if (k <= 8) launch_rays_kc<8>(sc, rays, n, k, quad, both, out, stream);
-    else if (k <= 16) launch_rays_kc<16>(sc, rays, n, k, quad, both, out, stream);
-    else launch_rays_kc<32>(sc, rays, n, k, quad, both, out, stream);
-    if (d_detail4) {      // 2^30 rays are up to 2^35 slots: several launches, each of at most 2^31 threads
-        const uint64_t slots = (uint64_t)n * (uint64_t)k;
-        for (uint64_t first = 0; first < slots; first += kHitDetailSlots) {
-            const uint64_t m = slots - first < kHitDetailSlots ? slots - first : kHitDetailSlots;
-            hipLaunchKernelGGL(ptd::rays_k_detail, dim3((uint32_t)((m + 255u) / 256u)), dim3(256), 0, stream, sc, rays, first, slots, (uint32_t)k, (const int2*)out, d_detail4);
+    const dim3 blocks((n + 63u) / 64u);
+    pt_kc_dispatch(k, [&](auto kc) {
+        if (quad) {
+            if (both) hipLaunchKernelGGL((ptd::rays_k<kc, true, true>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
+            else hipLaunchKernelGGL((ptd::rays_k<kc, true, false>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
+        } else {
+            if (both) hipLaunchKernelGGL((ptd::rays_k<kc, false, true>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
+            else hipLaunchKernelGGL((ptd::rays_k<kc, false, false>), blocks, dim3(64), 0, stream, sc, rays, n, k, out);
         }
-    }
+    });
+    if (d_detail4)
+        pt_detail_chunks((uint64_t)n * (uint64_t)k, [&](uint64_t first, dim3 grid) {
+            hipLaunchKernelGGL(ptd::rays_k_detail, grid, dim3(256), 0, stream, sc, rays, first, (uint64_t)n * (uint64_t)k, (uint32_t)k, (const int2*)out, d_detail4);
+        });
     return hipGetLastError();
 }
 
@@ -463,101 +376,75 @@ static hipError_t launch_rays_list(const ptd::DevScene& sc, const float* d_rays8
 }
 
 // ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
-// pt_trace_rays_list and its host variant.  device: the pointers are device pointers (alignment checked, hits required); on the host
-// variant hits may be NULL (the sizing call).
+static const char* flags_bad(int32_t flags)
+{
+    return (flags != PT_HITS_FRONT && flags != PT_HITS_BOTH_SIDES) ? "flags must be PT_HITS_FRONT or PT_HITS_BOTH_SIDES" : nullptr;
+}
+
+// has_k: pt_trace_rays_k and its host variant (PtRayHit records), else the counts
+static int hits_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, bool has_k, int32_t k, int32_t flags, const void* out,
+                        const float* detail, bool device)
+{
+    const char* param = (has_k && (k < 1 || k > PT_RAY_HITS_KMAX)) ? "k must be in 1 .. PT_RAY_HITS_KMAX" : flags_bad(flags);
+    return pt_query_args(who, s, n, device, {"rays", rays, "out", out, has_k ? "hits" : "count", has_k ? 8 : 4, "detail", detail, param, false, nullptr, 0});
+}
+
+// pt_trace_rays_list and its host variant
 static int list_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, int32_t flags, const int64_t* offsets, int64_t cap,
                         const void* hits, const float* detail, bool device)
 {
-    const char* bad = !s ? "NULL scene" : !rays ? "NULL rays" : !offsets ? "NULL offsets" : (device && !hits) ? "NULL hits" : n < 0 ? "n < 0" :
-                      cap < 0 ? "cap < 0" :
-                      (flags != PT_HITS_FRONT && flags != PT_HITS_BOTH_SIDES) ? "flags must be PT_HITS_FRONT or PT_HITS_BOTH_SIDES" :
-                      (device && ((uintptr_t)rays & 15)) ? "rays must be 16-byte aligned" :
-                      (device && ((uintptr_t)offsets & 7)) ? "offsets must be 8-byte aligned" :
-                      (device && ((uintptr_t)hits & 7)) ? "hits must be 8-byte aligned" :
-                      (device && ((uintptr_t)detail & 3)) ? "detail must be 4-byte aligned" : nullptr;
-    if (bad) { pt_set_error("%s: %s", who, bad); return PT_ERR_INVALID; }
-    return PT_OK;
+    return pt_query_args(who, s, n, device, {"rays", rays, "hits", hits, "hits", 8, "detail", detail, flags_bad(flags), true, offsets, cap});
 }
-
-// out_align: 8 for PtRayHit records, 4 for counts.  has_k: pt_trace_rays_k and its host variant.
-static int hits_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, bool has_k, int32_t k, int32_t flags, const void* out, int out_align,
-                        const float* detail, bool device)
-{
-    const char* bad = !s ? "NULL scene" : !rays ? "NULL rays" : !out ? "NULL out" : n < 0 ? "n < 0" :
-                      (has_k && (k < 1 || k > PT_RAY_HITS_KMAX)) ? "k must be in 1 .. PT_RAY_HITS_KMAX" :
-                      (flags != PT_HITS_FRONT && flags != PT_HITS_BOTH_SIDES) ? "flags must be PT_HITS_FRONT or PT_HITS_BOTH_SIDES" :
-                      (device && ((uintptr_t)rays & 15)) ? "rays must be 16-byte aligned" :
-                      (device && ((uintptr_t)out & (uintptr_t)(out_align - 1))) ? (out_align == 8 ? "hits must be 8-byte aligned" : "count must be 4-byte aligned") :
-                      (device && ((uintptr_t)detail & 3)) ? "detail must be 4-byte aligned" : nullptr;
-    if (bad) { pt_set_error("%s: %s", who, bad); return PT_ERR_INVALID; }
-    return PT_OK;
-}
-
-static const int64_t kHitsBatch = (int64_t)1 << 30;      // rays per launch: ray numbers are 32-bit
 
 extern "C" {
 
 int pt_trace_rays_k(PtScene* s, const float* d_rays8, int64_t n, int32_t k, int32_t flags, PtRayHit* d_hits, float* d_detail4, void* hip_stream)
 {
     int rc;
-    if ((rc = hits_args_ok("pt_trace_rays_k", s, d_rays8, n, true, k, flags, d_hits, 8, d_detail4, true)) != PT_OK) return rc;
+    if ((rc = hits_args_ok("pt_trace_rays_k", s, d_rays8, n, true, k, flags, d_hits, d_detail4, true)) != PT_OK) return rc;
     if (n == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
     const bool quad = pt_query_walks_quad(s), both = flags == PT_HITS_BOTH_SIDES;
-    for (int64_t off = 0; off < n; off += kHitsBatch) {
-        const uint32_t m = (uint32_t)(n - off < kHitsBatch ? n - off : kHitsBatch);
-        HIPCHK(launch_rays_k(s->dev, d_rays8 + off * 8, m, k, quad, both, d_hits + off * k, d_detail4 ? d_detail4 + off * k * 4 : nullptr, (hipStream_t)hip_stream));
-    }
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_rays_k(s->dev, d_rays8 + off * 8, m, k, quad, both, d_hits + off * k, d_detail4 ? d_detail4 + off * k * 4 : nullptr, (hipStream_t)hip_stream);
+    }));
     return PT_OK;
 }
 
 int pt_trace_rays_k_host(PtScene* s, const float* h_rays8, int64_t n, int32_t k, int32_t flags, PtRayHit* h_hits, float* h_detail4)
 {
     int rc;
-    if ((rc = hits_args_ok("pt_trace_rays_k_host", s, h_rays8, n, true, k, flags, h_hits, 8, h_detail4, false)) != PT_OK) return rc;
+    if ((rc = hits_args_ok("pt_trace_rays_k_host", s, h_rays8, n, true, k, flags, h_hits, h_detail4, false)) != PT_OK) return rc;
     if (n == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
     const size_t slots = (size_t)n * (size_t)k;
-    DevBuf d_rays, d_hits, d_det;      // d_det stays null when the caller asked for no detail records
-    HIPCHK(d_rays.alloc((size_t)n * 32));
-    HIPCHK(d_hits.alloc(slots * 8));
-    if (h_detail4) HIPCHK(d_det.alloc(slots * 16));
-    HIPCHK(hipMemcpy(d_rays.as<>(), h_rays8, (size_t)n * 32, hipMemcpyHostToDevice));
-    if ((rc = pt_trace_rays_k(s, d_rays.as<float>(), n, k, flags, d_hits.as<PtRayHit>(), d_det.as<float>(), nullptr)) != PT_OK) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipMemcpy(h_hits, d_hits.as<>(), slots * 8, hipMemcpyDeviceToHost));
-    if (h_detail4) HIPCHK(hipMemcpy(h_detail4, d_det.as<>(), slots * 16, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return pt_host_query(h_rays8, (size_t)n * 32, h_hits, slots * 8, h_detail4, slots * 16, [&](float* d_rays, void* d_hits, float* d_det) {
+        return pt_trace_rays_k(s, d_rays, n, k, flags, (PtRayHit*)d_hits, d_det, nullptr);
+    });
 }
 
 int pt_count_hits(PtScene* s, const float* d_rays8, int64_t n, int32_t flags, int32_t* d_count, void* hip_stream)
 {
     int rc;
-    if ((rc = hits_args_ok("pt_count_hits", s, d_rays8, n, false, 0, flags, d_count, 4, nullptr, true)) != PT_OK) return rc;
+    if ((rc = hits_args_ok("pt_count_hits", s, d_rays8, n, false, 0, flags, d_count, nullptr, true)) != PT_OK) return rc;
     if (n == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
     const bool quad = pt_query_walks_quad(s), both = flags == PT_HITS_BOTH_SIDES;
-    for (int64_t off = 0; off < n; off += kHitsBatch) {
-        const uint32_t m = (uint32_t)(n - off < kHitsBatch ? n - off : kHitsBatch);
-        HIPCHK(launch_count_hits(s->dev, d_rays8 + off * 8, m, quad, both, d_count + off, (hipStream_t)hip_stream));
-    }
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_count_hits(s->dev, d_rays8 + off * 8, m, quad, both, d_count + off, (hipStream_t)hip_stream);
+    }));
     return PT_OK;
 }
 
 int pt_count_hits_host(PtScene* s, const float* h_rays8, int64_t n, int32_t flags, int32_t* h_count)
 {
     int rc;
-    if ((rc = hits_args_ok("pt_count_hits_host", s, h_rays8, n, false, 0, flags, h_count, 4, nullptr, false)) != PT_OK) return rc;
+    if ((rc = hits_args_ok("pt_count_hits_host", s, h_rays8, n, false, 0, flags, h_count, nullptr, false)) != PT_OK) return rc;
     if (n == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
-    DevBuf d_rays, d_count;
-    HIPCHK(d_rays.alloc((size_t)n * 32));
-    HIPCHK(d_count.alloc((size_t)n * 4));
-    HIPCHK(hipMemcpy(d_rays.as<>(), h_rays8, (size_t)n * 32, hipMemcpyHostToDevice));
-    if ((rc = pt_count_hits(s, d_rays.as<float>(), n, flags, d_count.as<int32_t>(), nullptr)) != PT_OK) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipMemcpy(h_count, d_count.as<>(), (size_t)n * 4, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return pt_host_query(h_rays8, (size_t)n * 32, h_count, (size_t)n * 4, nullptr, 0, [&](float* d_rays, void* d_count, float*) {
+        return pt_count_hits(s, d_rays, n, flags, (int32_t*)d_count, nullptr);
+    });
 }
 
 int pt_trace_rays_list(PtScene* s, const float* d_rays8, int64_t n, int32_t flags, const int64_t* d_offsets, int64_t cap, PtRayHit* d_hits,
@@ -568,10 +455,9 @@ int pt_trace_rays_list(PtScene* s, const float* d_rays8, int64_t n, int32_t flag
     if (n == 0) return PT_OK;
     HIPCHK(hipSetDevice(s->device));
     const bool quad = pt_query_walks_quad(s), both = flags == PT_HITS_BOTH_SIDES;
-    for (int64_t off = 0; off < n; off += kHitsBatch) {
-        const uint32_t m = (uint32_t)(n - off < kHitsBatch ? n - off : kHitsBatch);
-        HIPCHK(launch_rays_list(s->dev, d_rays8 + off * 8, m, quad, both, d_offsets + off, cap, d_hits, d_detail4, (hipStream_t)hip_stream));
-    }
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_rays_list(s->dev, d_rays8 + off * 8, m, quad, both, d_offsets + off, cap, d_hits, d_detail4, (hipStream_t)hip_stream);
+    }));
     return PT_OK;
 }
 
@@ -582,27 +468,11 @@ int pt_trace_rays_list_host(PtScene* s, const float* h_rays8, int64_t n, int32_t
     if ((rc = list_args_ok("pt_trace_rays_list_host", s, h_rays8, n, flags, h_offsets, cap, h_hits, h_detail4, false)) != PT_OK) return rc;
     if (n == 0) { h_offsets[0] = 0; return PT_OK; }
     HIPCHK(hipSetDevice(s->device));
-    DevBuf d_rays, d_count, d_off, d_scratch, d_hits, d_det;      // d_det stays null when the caller asked for no detail records
-    HIPCHK(d_rays.alloc((size_t)n * 32));
-    HIPCHK(d_count.alloc((size_t)n * 4));
-    HIPCHK(d_off.alloc((size_t)(n + 1) * 8));
-    HIPCHK(d_scratch.alloc((size_t)pt_list_offsets_scratch_bytes(n)));
-    HIPCHK(hipMemcpy(d_rays.as<>(), h_rays8, (size_t)n * 32, hipMemcpyHostToDevice));
-    if ((rc = pt_count_hits(s, d_rays.as<float>(), n, flags, d_count.as<int32_t>(), nullptr)) != PT_OK) return rc;
-    if ((rc = pt_list_offsets(d_count.as<int32_t>(), n, d_off.as<int64_t>(), d_scratch.as<>(), nullptr)) != PT_OK) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipMemcpy(h_offsets, d_off.as<>(), (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
-    if (!h_hits) return PT_OK;      // the sizing call
-    const int64_t total = h_offsets[n];
-    if (cap < total) { pt_set_error("pt_trace_rays_list_host: cap %lld < %lld records", (long long)cap, (long long)total); return PT_ERR_INVALID; }
-    HIPCHK(d_hits.alloc((size_t)total * 8));
-    if (h_detail4) HIPCHK(d_det.alloc((size_t)total * 16));
-    if ((rc = pt_trace_rays_list(s, d_rays.as<float>(), n, flags, d_off.as<int64_t>(), total, d_hits.as<PtRayHit>(), d_det.as<float>(), nullptr)) != PT_OK)
-        return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipMemcpy(h_hits, d_hits.as<>(), (size_t)total * 8, hipMemcpyDeviceToHost));
-    if (h_detail4) HIPCHK(hipMemcpy(h_detail4, d_det.as<>(), (size_t)total * 16, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return pt_host_list("pt_trace_rays_list_host", h_rays8, n, 32, h_offsets, cap, h_hits, h_detail4, 16,
+                        [&](float* d_rays, int32_t* d_count) { return pt_count_hits(s, d_rays, n, flags, d_count, nullptr); },
+                        [&](float* d_rays, int64_t* d_off, int64_t total, void* d_hits, float* d_det) {
+                            return pt_trace_rays_list(s, d_rays, n, flags, d_off, total, (PtRayHit*)d_hits, d_det, nullptr);
+                        });
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // Everything the scene owns is released by its destructor, whichever path deletes it.
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "pt_internal.h"
@@ -84,6 +85,122 @@ struct PtScene {
 // Which walk pt_trace_rays and the feature-buffer kernel of pt_aov.hip take: the 4-wide tree when its walk fits their per-lane stack
 // (and PTAMD_QUERY_QUAD=0 does not force the other), else the binary tree with trace_closest
 inline bool pt_query_walks_quad(const PtScene* s) { return s->query_quad && 3 * s->dev.quad_depth + 2 <= ptd::kQueryStack; }
+
+// ---- what the query entry points share (pt_query.hip, pt_nearest.hip, pt_knearest.hip, pt_rayhits.hip; pt_aov.hip: pt_aov_rays) ----
+// The argument checks, in the order every query makes them: scene, input, a list's offsets, output (a list's host variant may leave it
+// NULL: the sizing call), n, a list's cap, the query's own parameters (`param`: the message of the first one that fails, nullptr = none),
+// then on the device the alignment of input (16), offsets (8), output (outAlign bytes, named outName) and detail (4, named detName).
+// PT_OK, or PT_ERR_INVALID with "who: message" set.
+struct QueryArgs {
+    const char* in; const void* inPtr;                                   // "rays" or "points"
+    const char* outNull; const void* outPtr;                             // the name "NULL ..." gives the output
+    const char* outName; int outAlign;
+    const char* detName; const void* detPtr;
+    const char* param;
+    bool list; const int64_t* offsets; int64_t cap;
+};
+inline int pt_query_args(const char* who, const PtScene* s, int64_t n, bool device, const QueryArgs& a)
+{
+    const auto fail = [&](const char* fmt, const char* what) { pt_set_error(fmt, who, what); return PT_ERR_INVALID; };
+    if (!s) return fail("%s: NULL %s", "scene");
+    if (!a.inPtr) return fail("%s: NULL %s", a.in);
+    if (a.list && !a.offsets) return fail("%s: NULL %s", "offsets");
+    if ((device || !a.list) && !a.outPtr) return fail("%s: NULL %s", a.outNull);
+    if (n < 0) return fail("%s: %s", "n < 0");
+    if (a.list && a.cap < 0) return fail("%s: %s", "cap < 0");
+    if (a.param) return fail("%s: %s", a.param);
+    if (!device) return PT_OK;
+    if ((uintptr_t)a.inPtr & 15) return fail("%s: %s must be 16-byte aligned", a.in);
+    if (a.list && ((uintptr_t)a.offsets & 7)) return fail("%s: %s must be 8-byte aligned", "offsets");
+    if ((uintptr_t)a.outPtr & (uintptr_t)(a.outAlign - 1)) return fail(a.outAlign == 8 ? "%s: %s must be 8-byte aligned" : "%s: %s must be 4-byte aligned", a.outName);
+    if ((uintptr_t)a.detPtr & 3) return fail("%s: %s must be 4-byte aligned", a.detName);
+    return PT_OK;
+}
+
+constexpr int64_t kQueryBatch = (int64_t)1 << 30;      // queries per launch: query numbers are 32-bit
+
+// launch(off, m) for each batch of m <= kQueryBatch queries from off, in order; the first error ends the loop
+template <class LAUNCH>
+inline hipError_t pt_query_batches(int64_t n, LAUNCH launch)
+{
+    for (int64_t off = 0; off < n; off += kQueryBatch) {
+        const hipError_t e = launch(off, (uint32_t)(n - off < kQueryBatch ? n - off : kQueryBatch));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// f(std::integral_constant<int, KC>()) with KC the capacity class of a K query's list: the smallest of 4, 8, 16, 32 that holds k, so that
+// k = 2 does not pay the LDS of k = 32
+template <class F>
+inline void pt_kc_dispatch(int k, F f)
+{
+    if (k <= 4) f(std::integral_constant<int, 4>());
+    else if (k <= 8) f(std::integral_constant<int, 8>());
+    else if (k <= 16) f(std::integral_constant<int, 16>());
+    else f(std::integral_constant<int, 32>());
+}
+
+// The detail kernels of the K queries, one 256-thread workgroup per 256 slots: 2^30 queries are up to 2^35 slots, so launch(first,
+// blocks) enqueues the slots from `first` on, at most kDetailSlots of them (a multiple of 256), so that no grid exceeds 2^31 threads
+constexpr uint64_t kDetailSlots = (uint64_t)1 << 31;
+template <class LAUNCH>
+inline void pt_detail_chunks(uint64_t slots, LAUNCH launch)
+{
+    for (uint64_t first = 0; first < slots; first += kDetailSlots) {
+        const uint64_t m = slots - first < kDetailSlots ? slots - first : kDetailSlots;
+        launch(first, dim3((uint32_t)((m + 255u) / 256u)));
+    }
+}
+
+// The body of a query's _host variant, after its checks and hipSetDevice: the inBytes of h_in and room for the outBytes of h_out and, if
+// h_det is given, the detBytes of h_det on the device; run(d_in, d_out, d_det) — the device entry point on the null stream, d_det null
+// when h_det is —, a synchronisation, the results copied back.
+template <class RUN>
+inline int pt_host_query(const void* h_in, size_t inBytes, void* h_out, size_t outBytes, void* h_det, size_t detBytes, RUN run)
+{
+    DevBuf d_in, d_out, d_det;
+    HIPCHK(d_in.alloc(inBytes));
+    HIPCHK(d_out.alloc(outBytes));
+    if (h_det) HIPCHK(d_det.alloc(detBytes));
+    HIPCHK(hipMemcpy(d_in.as<>(), h_in, inBytes, hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = run(d_in.as<float>(), d_out.as<>(), d_det.as<float>())) != PT_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(h_out, d_out.as<>(), outBytes, hipMemcpyDeviceToHost));
+    if (h_det) HIPCHK(hipMemcpy(h_det, d_det.as<>(), detBytes, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// The body of a list's _host variant (pt_trace_rays_list_host, pt_within_radius_list_host), after its checks and hipSetDevice: n > 0
+// queries of inRec bytes each; count(d_in, d_count) and offsets into h_offsets; without h_out the sizing call ends there; else cap must
+// hold the total, and fill(d_in, d_offsets, total, d_out, d_det) writes records of 8 bytes and, if h_det is given, detRec bytes.
+template <class COUNT, class FILL>
+inline int pt_host_list(const char* who, const void* h_in, int64_t n, size_t inRec, int64_t* h_offsets, int64_t cap, void* h_out, void* h_det,
+                        size_t detRec, COUNT count, FILL fill)
+{
+    DevBuf d_in, d_count, d_off, d_scratch, d_out, d_det;      // d_det stays null when the caller asked for no detail records
+    HIPCHK(d_in.alloc((size_t)n * inRec));
+    HIPCHK(d_count.alloc((size_t)n * 4));
+    HIPCHK(d_off.alloc((size_t)(n + 1) * 8));
+    HIPCHK(d_scratch.alloc((size_t)pt_list_offsets_scratch_bytes(n)));
+    HIPCHK(hipMemcpy(d_in.as<>(), h_in, (size_t)n * inRec, hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = count(d_in.as<float>(), d_count.as<int32_t>())) != PT_OK) return rc;
+    if ((rc = pt_list_offsets(d_count.as<int32_t>(), n, d_off.as<int64_t>(), d_scratch.as<>(), nullptr)) != PT_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(h_offsets, d_off.as<>(), (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
+    if (!h_out) return PT_OK;      // the sizing call
+    const int64_t total = h_offsets[n];
+    if (cap < total) { pt_set_error("%s: cap %lld < %lld records", who, (long long)cap, (long long)total); return PT_ERR_INVALID; }
+    HIPCHK(d_out.alloc((size_t)total * 8));
+    if (h_det) HIPCHK(d_det.alloc((size_t)total * detRec));
+    if ((rc = fill(d_in.as<float>(), d_off.as<int64_t>(), total, d_out.as<>(), d_det.as<float>())) != PT_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(h_out, d_out.as<>(), (size_t)total * 8, hipMemcpyDeviceToHost));
+    if (h_det) HIPCHK(hipMemcpy(h_det, d_det.as<>(), (size_t)total * detRec, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
 
 // pt_api.hip: the table of a batch of views in the scene's buffer `views` (grown on demand; the caller knows that nothing on the device
 // still reads the old one): origins | cameras | first passes, packed by way of the host image h_views and copied in stream order.

@@ -295,6 +295,60 @@ def _device_rays(who, rays, device):
     return rays.shape[0]
 
 
+def _host_rows(who, a, name, width):
+    """The numpy path of a query: `a` as contiguous float32 rows of `width` floats; returns (array, n)."""
+    x = np.ascontiguousarray(a, np.float32)
+    if x.ndim != 2 or x.shape[1] != width:
+        raise PtError(f"{who}: {name} has shape {x.shape}, want (n, {width})")
+    return x, x.shape[0]
+
+
+def _host_out(shape, dtype, detail, det_width):
+    """The numpy outputs of a query: zeroed records of the tuple `shape` and, if detail, zeroed float32 detail records of
+    shape + (det_width,), else None."""
+    return np.zeros(shape, dtype), (np.zeros(shape + (det_width,), np.float32) if detail else None)
+
+
+def _records(res, det):
+    """A query's result from its 8-byte records: (key, prim), float32 and int32, and det as a third item unless it is None.  res: a
+    numpy structured array (HIT_DTYPE, NEAREST_DTYPE) or an int32 torch tensor of shape (..., 2) (key's bits | prim)."""
+    if isinstance(res, np.ndarray):
+        out = tuple(np.ascontiguousarray(res[f]) for f in res.dtype.names)
+    else:
+        import torch
+        out = (res[..., 0].view(torch.float32), res[..., 1])
+    return out if det is None else out + (det,)
+
+
+def _csr(who, a, name, width, dtype, det_width, detail, stream_ptr, device, device_rows, count, host_list, device_list):
+    """The CSR routine of Scene.trace_rays_all and Scene.within_radius on the scene on `device`.  a: the queries, rows of `width`
+    floats (device_rows: their device-side checks); count(a): the per-query counts on the device; host_list / device_list(a, n,
+    offsets, cap, records, detail): the list's _host and device entry points, checked, with pointers.  The numpy path makes the
+    sizing call, then the fill; the device path counts, scans, reads the total back and fills, on stream_ptr."""
+    if isinstance(a, np.ndarray):
+        x, n = _host_rows(who, a, name, width)
+        off = np.zeros(n + 1, np.int64)
+        host_list(_ptr(x), n, _ptr(off), 0, None, None)
+        total = int(off[n])
+        res, det = _host_out((total,), dtype, detail, det_width)
+        if total:
+            host_list(_ptr(x), n, _ptr(off), total, _ptr(res), _ptr(det) if detail else None)
+        return (off,) + _records(res, det)
+    n = device_rows(who, a, device)
+    import torch
+    if n == 0:
+        off, total = torch.zeros(1, dtype=torch.int64, device=a.device), 0
+    else:
+        off = list_offsets(count(a), stream_ptr=stream_ptr)
+        total = _read_total(off, stream_ptr)
+    res = torch.empty((total, 2), dtype=torch.int32, device=a.device)      # PtRayHit / PtNearest: key's bits | prim
+    det = torch.empty((total, det_width), dtype=torch.float32, device=a.device) if detail else None
+    if total:
+        device_list(C.c_void_p(a.data_ptr()), n, C.c_void_p(off.data_ptr()), total, C.c_void_p(res.data_ptr()),
+                    C.c_void_p(det.data_ptr()) if detail else None)
+    return (off,) + _records(res, det)
+
+
 def _rebuild_params(depth_budget, large_fraction):
     """PtRebuildParams of the two optional arguments of Scene.rebuild_tree / rebuild_tree_optimized: a None takes its default."""
     prm = PtRebuildParams()
@@ -857,29 +911,17 @@ class Scene:
             raise PtError("trace_rays: an any-hit query has no surface record")
         mode = QUERY_ANY if any_hit else QUERY_CLOSEST
         if isinstance(rays, np.ndarray):
-            r = np.ascontiguousarray(rays, np.float32)
-            if r.ndim != 2 or r.shape[1] != 8:
-                raise PtError(f"trace_rays: rays has shape {r.shape}, want (n, 8)")
-            n = r.shape[0]
-            hits = np.zeros(n, HIT_DTYPE)
-            surf = np.zeros((n, 29), np.float32) if surface else None
+            r, n = _host_rows("trace_rays", rays, "rays", 8)
+            hits, surf = _host_out((n,), HIT_DTYPE, surface, 29)
             _check(lib().pt_trace_rays_host(self._h, _ptr(r), n, mode, _ptr(hits), _ptr(surf) if surface else None), "pt_trace_rays_host")
-            out = (np.ascontiguousarray(hits["t"]), np.ascontiguousarray(hits["prim"]))
-            return out + (surf,) if surface else out
-        if not (hasattr(rays, "data_ptr") and hasattr(rays, "is_contiguous")):
-            raise PtError("trace_rays: rays must be a torch tensor or a numpy array")
-        if str(rays.dtype) != "torch.float32" or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 8:
-            raise PtError(f"trace_rays: rays must be contiguous float32 of shape (n, 8), got {rays.dtype} {tuple(rays.shape)}")
-        if rays.device.type != "cuda" or rays.device.index != self.device:
-            raise PtError(f"trace_rays: rays is on {rays.device}, the scene is on device {self.device}")
+            return _records(hits, surf)
+        n = _device_rays("trace_rays", rays, self.device)
         import torch
-        n = rays.shape[0]
         hits = torch.empty((n, 2), dtype=torch.int32, device=rays.device)      # PtRayHit: t's bits | prim
         surf = torch.empty((n, 29), dtype=torch.float32, device=rays.device) if surface else None
         _check(lib().pt_trace_rays(self._h, C.c_void_p(rays.data_ptr()), n, mode, C.c_void_p(hits.data_ptr()),
                                    C.c_void_p(surf.data_ptr()) if surface else None, C.c_void_p(stream_ptr)), "pt_trace_rays")
-        out = (hits[:, 0].view(torch.float32), hits[:, 1])
-        return out + (surf,) if surface else out
+        return _records(hits, surf)
 
     def closest_points(self, points, any_within=False, detail=False, stream_ptr=0):
         """The primitive nearest to each of the caller's points (include/pt_api.h: pt_closest_points).  points: (n, 4) float32 POINT4
@@ -893,29 +935,17 @@ class Scene:
             raise PtError("closest_points: an any-within query has no detail record")
         mode = NEAREST_ANY if any_within else NEAREST_CLOSEST
         if isinstance(points, np.ndarray):
-            p = np.ascontiguousarray(points, np.float32)
-            if p.ndim != 2 or p.shape[1] != 4:
-                raise PtError(f"closest_points: points has shape {p.shape}, want (n, 4)")
-            n = p.shape[0]
-            res = np.zeros(n, NEAREST_DTYPE)
-            det = np.zeros((n, 8), np.float32) if detail else None
+            p, n = _host_rows("closest_points", points, "points", 4)
+            res, det = _host_out((n,), NEAREST_DTYPE, detail, 8)
             _check(lib().pt_closest_points_host(self._h, _ptr(p), n, mode, _ptr(res), _ptr(det) if detail else None), "pt_closest_points_host")
-            out = (np.ascontiguousarray(res["dist2"]), np.ascontiguousarray(res["prim"]))
-            return out + (det,) if detail else out
-        if not (hasattr(points, "data_ptr") and hasattr(points, "is_contiguous")):
-            raise PtError("closest_points: points must be a torch tensor or a numpy array")
-        if str(points.dtype) != "torch.float32" or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 4:
-            raise PtError(f"closest_points: points must be contiguous float32 of shape (n, 4), got {points.dtype} {tuple(points.shape)}")
-        if points.device.type != "cuda" or points.device.index != self.device:
-            raise PtError(f"closest_points: points is on {points.device}, the scene is on device {self.device}")
+            return _records(res, det)
+        n = _device_points("closest_points", points, self.device)
         import torch
-        n = points.shape[0]
         res = torch.empty((n, 2), dtype=torch.int32, device=points.device)      # PtNearest: dist2's bits | prim
         det = torch.empty((n, 8), dtype=torch.float32, device=points.device) if detail else None
         _check(lib().pt_closest_points(self._h, C.c_void_p(points.data_ptr()), n, mode, C.c_void_p(res.data_ptr()),
                                        C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_closest_points")
-        out = (res[:, 0].view(torch.float32), res[:, 1])
-        return out + (det,) if detail else out
+        return _records(res, det)
 
     def nearest_k(self, points, k, detail=False, stream_ptr=0):
         """The k nearest primitives within each point's radius, sorted (include/pt_api.h: pt_nearest_k).  points: (n, 4) float32 POINT4
@@ -929,34 +959,26 @@ class Scene:
         if not 1 <= k <= NEAREST_KMAX:
             raise PtError(f"nearest_k: k = {k}, want 1 .. {NEAREST_KMAX}")
         if isinstance(points, np.ndarray):
-            p = np.ascontiguousarray(points, np.float32)
-            if p.ndim != 2 or p.shape[1] != 4:
-                raise PtError(f"nearest_k: points has shape {p.shape}, want (n, 4)")
-            n = p.shape[0]
-            res = np.zeros((n, k), NEAREST_DTYPE)
-            det = np.zeros((n, k, 8), np.float32) if detail else None
+            p, n = _host_rows("nearest_k", points, "points", 4)
+            res, det = _host_out((n, k), NEAREST_DTYPE, detail, 8)
             _check(lib().pt_nearest_k_host(self._h, _ptr(p), n, k, _ptr(res), _ptr(det) if detail else None), "pt_nearest_k_host")
-            out = (np.ascontiguousarray(res["dist2"]), np.ascontiguousarray(res["prim"]))
-            return out + (det,) if detail else out
+            return _records(res, det)
         n = _device_points("nearest_k", points, self.device)
         import torch
         res = torch.empty((n, k, 2), dtype=torch.int32, device=points.device)      # PtNearest: dist2's bits | prim
         det = torch.empty((n, k, 8), dtype=torch.float32, device=points.device) if detail else None
         _check(lib().pt_nearest_k(self._h, C.c_void_p(points.data_ptr()), n, k, C.c_void_p(res.data_ptr()),
                                   C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_nearest_k")
-        out = (res[:, :, 0].view(torch.float32), res[:, :, 1])
-        return out + (det,) if detail else out
+        return _records(res, det)
 
     def count_within(self, points, stream_ptr=0):
         """How many primitives lie within each point's radius (include/pt_api.h: pt_count_within), uncapped: (n,) int32.  points as in
         nearest_k; an infinite radius counts every primitive, by walking the whole tree.  A torch tensor on the scene's device is
         used in place and the count is a torch tensor there, in stream order; a numpy array goes through pt_count_within_host."""
         if isinstance(points, np.ndarray):
-            p = np.ascontiguousarray(points, np.float32)
-            if p.ndim != 2 or p.shape[1] != 4:
-                raise PtError(f"count_within: points has shape {p.shape}, want (n, 4)")
-            cnt = np.zeros(p.shape[0], np.int32)
-            _check(lib().pt_count_within_host(self._h, _ptr(p), p.shape[0], _ptr(cnt)), "pt_count_within_host")
+            p, n = _host_rows("count_within", points, "points", 4)
+            cnt = np.zeros(n, np.int32)
+            _check(lib().pt_count_within_host(self._h, _ptr(p), n, _ptr(cnt)), "pt_count_within_host")
             return cnt
         n = _device_points("count_within", points, self.device)
         import torch
@@ -978,23 +1000,17 @@ class Scene:
             raise PtError(f"trace_rays_k: k = {k}, want 1 .. {RAY_HITS_KMAX}")
         flags = HITS_BOTH_SIDES if both_sides else HITS_FRONT
         if isinstance(rays, np.ndarray):
-            r = np.ascontiguousarray(rays, np.float32)
-            if r.ndim != 2 or r.shape[1] != 8:
-                raise PtError(f"trace_rays_k: rays has shape {r.shape}, want (n, 8)")
-            n = r.shape[0]
-            hits = np.zeros((n, k), HIT_DTYPE)
-            det = np.zeros((n, k, 4), np.float32) if detail else None
+            r, n = _host_rows("trace_rays_k", rays, "rays", 8)
+            hits, det = _host_out((n, k), HIT_DTYPE, detail, 4)
             _check(lib().pt_trace_rays_k_host(self._h, _ptr(r), n, k, flags, _ptr(hits), _ptr(det) if detail else None), "pt_trace_rays_k_host")
-            out = (np.ascontiguousarray(hits["t"]), np.ascontiguousarray(hits["prim"]))
-            return out + (det,) if detail else out
+            return _records(hits, det)
         n = _device_rays("trace_rays_k", rays, self.device)
         import torch
         hits = torch.empty((n, k, 2), dtype=torch.int32, device=rays.device)      # PtRayHit: t's bits | prim
         det = torch.empty((n, k, 4), dtype=torch.float32, device=rays.device) if detail else None
         _check(lib().pt_trace_rays_k(self._h, C.c_void_p(rays.data_ptr()), n, k, flags, C.c_void_p(hits.data_ptr()),
                                      C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_trace_rays_k")
-        out = (hits[:, :, 0].view(torch.float32), hits[:, :, 1])
-        return out + (det,) if detail else out
+        return _records(hits, det)
 
     def count_hits(self, rays, both_sides=False, stream_ptr=0):
         """How many hits each ray has in [0, tmax] (include/pt_api.h: pt_count_hits), uncapped: (n,) int32.  rays and both_sides as in
@@ -1002,11 +1018,9 @@ class Scene:
         numpy array goes through pt_count_hits_host."""
         flags = HITS_BOTH_SIDES if both_sides else HITS_FRONT
         if isinstance(rays, np.ndarray):
-            r = np.ascontiguousarray(rays, np.float32)
-            if r.ndim != 2 or r.shape[1] != 8:
-                raise PtError(f"count_hits: rays has shape {r.shape}, want (n, 8)")
-            cnt = np.zeros(r.shape[0], np.int32)
-            _check(lib().pt_count_hits_host(self._h, _ptr(r), r.shape[0], flags, _ptr(cnt)), "pt_count_hits_host")
+            r, n = _host_rows("count_hits", rays, "rays", 8)
+            cnt = np.zeros(n, np.int32)
+            _check(lib().pt_count_hits_host(self._h, _ptr(r), n, flags, _ptr(cnt)), "pt_count_hits_host")
             return cnt
         n = _device_rays("count_hits", rays, self.device)
         import torch
@@ -1024,35 +1038,12 @@ class Scene:
         that device, valid once the stream has passed the fill, and `rays` must stay alive until then.  A numpy array goes through
         pt_trace_rays_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays."""
         flags = HITS_BOTH_SIDES if both_sides else HITS_FRONT
-        if isinstance(rays, np.ndarray):
-            r = np.ascontiguousarray(rays, np.float32)
-            if r.ndim != 2 or r.shape[1] != 8:
-                raise PtError(f"trace_rays_all: rays has shape {r.shape}, want (n, 8)")
-            n = r.shape[0]
-            off = np.zeros(n + 1, np.int64)
-            _check(lib().pt_trace_rays_list_host(self._h, _ptr(r), n, flags, _ptr(off), 0, None, None), "pt_trace_rays_list_host")
-            total = int(off[n])
-            hits = np.zeros(total, HIT_DTYPE)
-            det = np.zeros((total, 4), np.float32) if detail else None
-            if total:
-                _check(lib().pt_trace_rays_list_host(self._h, _ptr(r), n, flags, _ptr(off), total, _ptr(hits), _ptr(det) if detail else None),
-                       "pt_trace_rays_list_host")
-            out = (off, np.ascontiguousarray(hits["t"]), np.ascontiguousarray(hits["prim"]))
-            return out + (det,) if detail else out
-        n = _device_rays("trace_rays_all", rays, self.device)
-        import torch
-        if n == 0:
-            off, total = torch.zeros(1, dtype=torch.int64, device=rays.device), 0
-        else:
-            off = list_offsets(self.count_hits(rays, both_sides=both_sides, stream_ptr=stream_ptr), stream_ptr=stream_ptr)
-            total = _read_total(off, stream_ptr)
-        hits = torch.empty((total, 2), dtype=torch.int32, device=rays.device)      # PtRayHit: t's bits | prim
-        det = torch.empty((total, 4), dtype=torch.float32, device=rays.device) if detail else None
-        if total:
-            _check(lib().pt_trace_rays_list(self._h, C.c_void_p(rays.data_ptr()), n, flags, C.c_void_p(off.data_ptr()), total, C.c_void_p(hits.data_ptr()),
-                                            C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_trace_rays_list")
-        out = (off, hits[:, 0].view(torch.float32), hits[:, 1])
-        return out + (det,) if detail else out
+        return _csr("trace_rays_all", rays, "rays", 8, HIT_DTYPE, 4, detail, stream_ptr, self.device, _device_rays,
+                         lambda d: self.count_hits(d, both_sides=both_sides, stream_ptr=stream_ptr),
+                         lambda r, n, off, cap, out, det: _check(lib().pt_trace_rays_list_host(self._h, r, n, flags, off, cap, out, det),
+                                                                 "pt_trace_rays_list_host"),
+                         lambda r, n, off, cap, out, det: _check(lib().pt_trace_rays_list(self._h, r, n, flags, off, cap, out, det,
+                                                                                          C.c_void_p(stream_ptr)), "pt_trace_rays_list"))
 
     def within_radius(self, points, detail=False, stream_ptr=0):
         """Every primitive within each point's radius, sorted, in CSR form (include/pt_api.h: pt_within_radius_list).  points as in
@@ -1063,35 +1054,12 @@ class Scene:
         total — which WAITS for the stream to pass the scan —, the allocation of the records, the fill.  The records are torch tensors on
         that device, valid once the stream has passed the fill, and `points` must stay alive until then.  A numpy array goes through
         pt_within_radius_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays."""
-        if isinstance(points, np.ndarray):
-            p = np.ascontiguousarray(points, np.float32)
-            if p.ndim != 2 or p.shape[1] != 4:
-                raise PtError(f"within_radius: points has shape {p.shape}, want (n, 4)")
-            n = p.shape[0]
-            off = np.zeros(n + 1, np.int64)
-            _check(lib().pt_within_radius_list_host(self._h, _ptr(p), n, _ptr(off), 0, None, None), "pt_within_radius_list_host")
-            total = int(off[n])
-            res = np.zeros(total, NEAREST_DTYPE)
-            det = np.zeros((total, 8), np.float32) if detail else None
-            if total:
-                _check(lib().pt_within_radius_list_host(self._h, _ptr(p), n, _ptr(off), total, _ptr(res), _ptr(det) if detail else None),
-                       "pt_within_radius_list_host")
-            out = (off, np.ascontiguousarray(res["dist2"]), np.ascontiguousarray(res["prim"]))
-            return out + (det,) if detail else out
-        n = _device_points("within_radius", points, self.device)
-        import torch
-        if n == 0:
-            off, total = torch.zeros(1, dtype=torch.int64, device=points.device), 0
-        else:
-            off = list_offsets(self.count_within(points, stream_ptr=stream_ptr), stream_ptr=stream_ptr)
-            total = _read_total(off, stream_ptr)
-        res = torch.empty((total, 2), dtype=torch.int32, device=points.device)      # PtNearest: dist2's bits | prim
-        det = torch.empty((total, 8), dtype=torch.float32, device=points.device) if detail else None
-        if total:
-            _check(lib().pt_within_radius_list(self._h, C.c_void_p(points.data_ptr()), n, C.c_void_p(off.data_ptr()), total, C.c_void_p(res.data_ptr()),
-                                               C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_within_radius_list")
-        out = (off, res[:, 0].view(torch.float32), res[:, 1])
-        return out + (det,) if detail else out
+        return _csr("within_radius", points, "points", 4, NEAREST_DTYPE, 8, detail, stream_ptr, self.device, _device_points,
+                         lambda d: self.count_within(d, stream_ptr=stream_ptr),
+                         lambda p, n, off, cap, out, det: _check(lib().pt_within_radius_list_host(self._h, p, n, off, cap, out, det),
+                                                                 "pt_within_radius_list_host"),
+                         lambda p, n, off, cap, out, det: _check(lib().pt_within_radius_list(self._h, p, n, off, cap, out, det,
+                                                                                             C.c_void_p(stream_ptr)), "pt_within_radius_list"))
 
     def render_rays_device(self, d_rays_ptr, n_rays, prm, d_rgb_ptr, d_work_ptr, d_seed_ptr=0, seed_stride=None, stream_ptr=0):
         """Device-resident radiance along n_rays RAY8 records (raw device pointers: rays_floats(n) floats of output, rays_work_bytes(prm,

@@ -379,17 +379,24 @@ PT_API int  pt_window_expand(const PtCamera* cam, const int32_t window[4], int32
  * pt_error_estimate: whole-buffer figures over the pixels of this rank's tiles that lie inside the frame (hence cam and
  *   prm->rank / world; prm->passes is not read) and whose S and M2 are all finite.  Per-pixel terms in float32 as written below, summed
  *   in float64 in a fixed order (per-block partial sums in d_scratch, added up on the host; no atomics): two calls return the
- *   same bits.  The only call here that waits for the stream (it reads the partial sums back).
- * Buffers are caller-owned; 16-byte aligned ones are read and written with 16-byte accesses (others work, slower).  Everything is
- * enqueued on `hip_stream` on the current device.  Bad arguments (NULL, n_before < 0, n_passes < 2, camera / params that
- * pt_tiles_floats rejects) return PT_ERR_INVALID before any HIP call.
+ *   same bits.  The only call here that waits for the stream (it reads the partial sums back).  The order, restated in
+ *   tests/stats_ref.py (estimate32): min(1024, ceil(floats / 3072)) blocks of 256 threads, each thread its groups of 4 pixels at the
+ *   stride of the grid, the lanes of a wave in a shuffle tree, the four waves in order, the blocks in order on the host.
+ *   Two degenerate outcomes, as the formulas give them: a buffer whose used pixels all have S = 0 and M2 = 0 (an all-black frame)
+ *   has rel_rms = NaN (0 / 0) and mean_rel_se = 0; a buffer with no used pixel (pixels == 0: every in-frame pixel skipped) has NaN
+ *   in both.  A caller that compares rel_rms with a target must decide what NaN means to it.
+ * Buffers are caller-owned; float buffers must be 4-byte aligned and d_scratch 8-byte aligned; 16-byte aligned ones are read and
+ * written with 16-byte accesses (others work, slower, and give the same bits).  Everything is enqueued on `hip_stream` on the
+ * current device.  Bad arguments (NULL, a misaligned buffer, n_before < 0, n_passes < 2, camera / params that pt_tiles_floats
+ * rejects) return PT_ERR_INVALID before any HIP call.
  *
  * pt_render_converge: host convenience like pt_render (whole frame, world = 1, synchronous).  Renders batches of prm->passes
  *   passes (first_pass advancing from prm->first_pass), folds each batch, estimates after each batch once two passes are in,
  *   and stops after the first batch whose rel_rms <= target_rel_rms, or at max_passes (>= 2; the last batch is shortened to
  *   fit, and prm->first_pass + max_passes must respect the seed limit of pt_render).  h_accum_rgb[W*H*3] = S, bit for bit what
  *   pt_render returns for passes = *passes_done (divide by it: pt_tonemap_u8(out, *passes_done)); h_var_rgb (may be NULL) =
- *   pt_variance of it; *est = the last estimate.  A batch costs a pipeline drain and a 40 KB read-back: measured at
+ *   pt_variance of it; *est = the last estimate.  On an all-black frame rel_rms is NaN (above), NaN <= target is false, and the call
+ *   runs to max_passes.  A batch costs a pipeline drain and a 40 KB read-back: measured at
  *   1080p on 8 passes x 256 spp, batches of 1 / 4 / 8 passes take 1.48 / 1.10 / 1.00 x the time of one pt_render call (DESIGN.md
  *   section 10) — use batches of 8 (4 if the finer stopping grain is worth 10 %), never 1; a tile-split version would need the
  *   ranks to agree on when to stop and is not provided (the three calls above take any rank / world).
@@ -1117,7 +1124,9 @@ PT_API int  pt_render_rays_host(PtScene* s, const float* h_rays8, const int32_t*
  * pt_render_tile_list, so the passes go where the noise is (csrc/pt_stats.hip).
  *
  * "Frame tile layout" below = the layout of pt_render_tiles with rank 0 of world 1: tile t (row-major over the full frame) owns
- *   floats 192 t .. 192 t + 191, pt_tiles_floats(cam, world 1) floats in all.  All buffers 16-byte aligned.
+ *   floats 192 t .. 192 t + 191, pt_tiles_floats(cam, world 1) floats in all.  The float buffers of pt_accumulate_tile_list (d_work,
+ *   d_sum, d_m2) and of pt_finish_tiles (d_sum, d_m2, d_mean, d_var) must be 16-byte aligned: their kernels move float4 only.
+ *   pt_tile_errors takes 4-byte aligned moments and writes d_err 8-byte aligned; int32 buffers are 4-byte aligned.
  * pt_accumulate_tile_list: the list variant of pt_accumulate_passes.  d_work is the work buffer a pt_render_tile_list(cam, prm, list of
  *   n_tiles) left behind (prm->passes x n_tiles x 192 means, pass-major, list order); entry i is folded into tile d_list[i] of d_sum /
  *   d_m2 (frame tile layout), per float exactly the fold of pt_accumulate_passes with k = n_before + 1, ...: a tile's result is bit for
@@ -1135,7 +1144,7 @@ PT_API int  pt_render_rays_host(PtScene* s, const float* h_rays8, const int32_t*
  *   float32, n converted to float once:  d_mean = S / n;  d_var = (max(M2, 0) * n) / (n - 1) (a NaN M2 stays NaN; n == 1 gives what
  *   the formula gives).  A tile with n == 0 gets +0 in both.  Either output may be NULL, not both.
  * The three calls take DEVICE pointers, are asynchronous on `hip_stream`, allocate nothing and read nothing back.  Checked before the
- *   first HIP call, else PT_ERR_INVALID: NULL pointers, n_tiles < 1 or more than the frame has, n_before < 0, n_passes < 2,
+ *   first HIP call, else PT_ERR_INVALID: NULL pointers, a buffer short of the alignment above, n_tiles < 1 or more than the frame has, n_before < 0, n_passes < 2,
  *   prm->rank != 0 || prm->world != 1, a camera or params that pt_tiles_floats rejects, both outputs of pt_finish_tiles NULL.
  *   The ENTRIES of d_list are the caller's responsibility, as the contents of any device buffer are: each must be a tile of the frame
  *   and none may appear twice (an entry outside the frame is skipped by the fold and yields a zero record; a tile listed twice is

@@ -20,7 +20,9 @@
 // over the in-frame pixels whose S and M2 are all finite.  Deterministic: a fixed grid, each thread a fixed stride of pixels,
 // each block a fixed shuffle + LDS tree, one partial per block; the host adds the partials in block order.  No atomics.
 // Kernels: pure streams, 256-thread blocks, one float4 per thread where the buffers are 16-byte aligned (a render's tile
-// buffers always are: pt_tiles_floats() is a multiple of 192), plain 16-byte loads and stores.
+// buffers always are: pt_tiles_floats() is a multiple of 192), plain 16-byte loads and stores; the scalar twins (st_fold<float>,
+// st_variance1, st_estimate<false>) give the same bits for buffers that are only 4-byte aligned.  tests/stats_ref.py: estimate32
+// restates st_estimate and the host sum in their order; tests/test_stats_exact.py holds every kernel here to its restatement.
 //
 // Adaptive sampling (pt_accumulate_tile_list, pt_tile_errors, pt_finish_tiles, pt_render_adaptive) builds on the same fold and variance:
 // st_fold_list folds the staging slab of a tile-LIST render into frame-layout moments (entry i -> tile list[i]), st_tile_errors reduces the
@@ -159,6 +161,12 @@ void st_estimate(const float* __restrict__ sum, const float* __restrict__ m2, lo
 static inline bool st_aligned16(const void* a, const void* b, const void* c)
 {
     return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+// what the entry points require of their buffers: 4 bytes for float / int32, 8 for the records that hold a double, 16 where a kernel
+// has no scalar twin (the list calls).  NULL passes: whether a pointer may be NULL is its own check.
+static inline bool st_aligned(unsigned bytes, const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr)
+{
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & (bytes - 1)) == 0;
 }
 
 // ---- adaptive sampling: the moments of a tile LIST, an error figure per tile, the frame of tiles with unequal pass counts ----------
@@ -304,6 +312,7 @@ int pt_accumulate_passes(const void* d_work, const PtCamera* cam, const PtParams
                          void* hip_stream)
 {
     if (!d_work || !d_sum || !d_m2) { pt_set_error("pt_accumulate_passes: NULL argument"); return PT_ERR_INVALID; }
+    if (!ptd::st_aligned(4, d_work, d_sum, d_m2)) { pt_set_error("pt_accumulate_passes: a float buffer is not 4-byte aligned"); return PT_ERR_INVALID; }
     if (n_before < 0 || (prm && (long long)n_before + prm->passes > 0x7fffffffLL)) { pt_set_error("pt_accumulate_passes: bad n_before %d", n_before); return PT_ERR_INVALID; }
     ptd::DevParams d;
     const int rc = pt_fill_params(cam, prm, d);
@@ -317,6 +326,7 @@ int pt_accumulate_passes(const void* d_work, const PtCamera* cam, const PtParams
 int pt_variance(const float* d_m2, int64_t n_floats, int32_t n_passes, float* d_var, void* hip_stream)
 {
     if (!d_m2 || !d_var || n_floats < 1 || n_passes < 2) { pt_set_error("pt_variance: NULL buffer, n_floats < 1 or n_passes < 2"); return PT_ERR_INVALID; }
+    if (!ptd::st_aligned(4, d_m2, d_var)) { pt_set_error("pt_variance: a float buffer is not 4-byte aligned"); return PT_ERR_INVALID; }
     HIPCHK(launch_variance(d_m2, n_floats, n_passes, d_var, (hipStream_t)hip_stream));
     return PT_OK;
 }
@@ -332,6 +342,7 @@ int pt_error_estimate(const float* d_sum, const float* d_m2, const PtCamera* cam
                       void* d_scratch, PtErrorEstimate* h_out, void* hip_stream)
 {
     if (!d_sum || !d_m2 || !d_scratch || !h_out) { pt_set_error("pt_error_estimate: NULL argument"); return PT_ERR_INVALID; }
+    if (!ptd::st_aligned(4, d_sum, d_m2) || !ptd::st_aligned(8, d_scratch)) { pt_set_error("pt_error_estimate: d_sum / d_m2 not 4-byte or d_scratch not 8-byte aligned"); return PT_ERR_INVALID; }
     if (n_passes < 2) { pt_set_error("pt_error_estimate: n_passes %d < 2", n_passes); return PT_ERR_INVALID; }
     if (!cam || !prm) { pt_set_error("NULL camera/params"); return PT_ERR_INVALID; }
     PtParams p = *prm; p.passes = 1; p.first_pass = 0;      // only the geometry of the split is read
@@ -422,6 +433,9 @@ int pt_accumulate_tile_list(const void* d_work, const PtCamera* cam, const PtPar
                             int32_t n_before, float* d_sum, float* d_m2, int32_t* d_tile_passes, void* hip_stream)
 {
     if (!d_work || !d_list || !d_sum || !d_m2) { pt_set_error("pt_accumulate_tile_list: NULL argument"); return PT_ERR_INVALID; }
+    if (!ptd::st_aligned(16, d_work, d_sum, d_m2) || !ptd::st_aligned(4, d_list, d_tile_passes)) {      // st_fold_list has no scalar twin
+        pt_set_error("pt_accumulate_tile_list: d_work / d_sum / d_m2 not 16-byte or d_list / d_tile_passes not 4-byte aligned"); return PT_ERR_INVALID;
+    }
     if (n_before < 0 || (prm && (long long)n_before + prm->passes > 0x7fffffffLL)) { pt_set_error("pt_accumulate_tile_list: bad n_before %d", n_before); return PT_ERR_INVALID; }
     ptd::DevParams d;
     const int rc = pt_fill_params(cam, prm, d);
@@ -440,6 +454,7 @@ int pt_tile_errors(const float* d_sum, const float* d_m2, const PtCamera* cam, c
                    PtTileError* d_err, void* hip_stream)
 {
     if (!d_sum || !d_m2 || !d_err) { pt_set_error("pt_tile_errors: NULL argument"); return PT_ERR_INVALID; }
+    if (!ptd::st_aligned(4, d_sum, d_m2, d_list) || !ptd::st_aligned(8, d_err)) { pt_set_error("pt_tile_errors: d_sum / d_m2 / d_list not 4-byte or d_err not 8-byte aligned"); return PT_ERR_INVALID; }
     if (n_passes < 2) { pt_set_error("pt_tile_errors: n_passes %d < 2", n_passes); return PT_ERR_INVALID; }
     ptd::DevParams d;
     const int rc = whole_frame_grid(cam, d);
@@ -456,6 +471,9 @@ int pt_finish_tiles(const float* d_sum, const float* d_m2, const int32_t* d_tile
 {
     if (!d_sum || !d_m2 || !d_tile_passes) { pt_set_error("pt_finish_tiles: NULL argument"); return PT_ERR_INVALID; }
     if (!d_mean && !d_var) { pt_set_error("pt_finish_tiles: neither a mean nor a variance buffer"); return PT_ERR_INVALID; }
+    if (!ptd::st_aligned(16, d_sum, d_m2, d_mean, d_var) || !ptd::st_aligned(4, d_tile_passes)) {      // st_finish_tiles has no scalar twin
+        pt_set_error("pt_finish_tiles: d_sum / d_m2 / d_mean / d_var not 16-byte or d_tile_passes not 4-byte aligned"); return PT_ERR_INVALID;
+    }
     ptd::DevParams d;
     const int rc = whole_frame_grid(cam, d);
     if (rc) return rc;

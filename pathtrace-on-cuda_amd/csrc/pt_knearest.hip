@@ -26,10 +26,13 @@ namespace ptd {
 // counts(): its acceptance, and the fill's for a long segment (pt_lists.h: SlotSeg).
 struct KCount {
     static constexpr bool kOrdered = false;     // every child within r2 is visited whatever the order
+    static constexpr bool kStops = false;
     int cnt;
     float bound;
     PT_DEV static bool counts(float f, float bound) { return f <= bound; }
     PT_DEV void offer(float f, int) { cnt += counts(f, bound) ? 1 : 0; }
+    PT_DEV bool wants(float f, int) const { return counts(f, bound); }      // the two halves of offer(), for pt_lists.h's Filtered
+    PT_DEV void take(float, int) { cnt++; }
 };
 
 // KC: the capacity class of the list (pt_scene.h: pt_kc_dispatch).  The wave's 64 points own the 64 * k consecutive records from
@@ -124,6 +127,80 @@ void near_list_detail(DevScene sc, const float4* __restrict__ points, uint32_t n
                        [&](const float4& q, int2 h, float* o) { near_detail(sc, q, h.y, o); });
 }
 
+// ---- the filtered forms (include/pt_api.h: "Query filters") ----------------------------------------------------
+// The kernels above with their sink behind pt_lists.h's Filtered: the same walk, the same one-wave workgroups and LDS layouts, the
+// same capacity classes.  A point query has no near bound.
+
+// pt_closest_points_f: the first member of C' — the shared point walk over the one-slot sink —, or (ANY) some member
+template <bool ANY, bool QUAD>
+__global__ __launch_bounds__(64)
+void near_one_f(DevScene sc, const float4* __restrict__ points, uint32_t n, QFilter flt, float2* __restrict__ out)
+{
+    __shared__ int2 lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const float4 q = points[i];
+    Filtered<SlotOne<ANY>> s{{q.w * q.w, -1, 0.f, -1}, lane_filter(flt, i, 0.f)};
+    knear_point<QUAD>(sc, q, &lds_stack[threadIdx.x], s);
+    out[i] = make_float2(s.key, __int_as_float(s.prim));      // a miss is (0, -1)
+}
+
+template <int KC, bool QUAD>
+__global__ __launch_bounds__(64)
+void nearest_k_f(DevScene sc, const float4* __restrict__ points, uint32_t n, int k, QFilter flt, int2* __restrict__ out)
+{
+    __shared__ int2 lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    __shared__ int2 lds_list[KC * kSlotRow];
+    if (k < 1 || k > KC) return;      // the launcher's choice of KC, restated where the list is indexed
+    const uint32_t lane = threadIdx.x, base = blockIdx.x * 64u, i = base + lane;
+    int2* list = &lds_list[lane];
+    int cnt = 0;
+    if (i < n) {
+        const float4 q = points[i];
+        Filtered<SlotList<false>> s{{list, k, 0, q.w * q.w, -1}, lane_filter(flt, i, 0.f)};
+        knear_point<QUAD>(sc, q, &lds_stack[lane], s);
+        cnt = s.cnt;
+    }
+    for (int j = cnt; j < k; j++) list[j * kSlotRow] = make_int2(0, -1);      // a miss is (0, -1)
+    __syncthreads();
+    klist_copy_out(lds_list, out, base, n, k);
+}
+
+template <bool QUAD>
+__global__ __launch_bounds__(64)
+void count_within_f(DevScene sc, const float4* __restrict__ points, uint32_t n, QFilter flt, int32_t* __restrict__ out)
+{
+    __shared__ int2 lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const float4 q = points[i];
+    Filtered<KCount> s{{0, q.w * q.w}, lane_filter(flt, i, 0.f)};
+    knear_point<QUAD>(sc, q, &lds_stack[threadIdx.x], s);
+    out[i] = s.cnt;
+}
+
+// The fill: a long segment's appended members are Filtered<KCount>'s members, the filtered count's
+template <bool QUAD>
+__global__ __launch_bounds__(64)
+void near_list_f(DevScene sc, const float4* __restrict__ points, uint32_t n, QFilter flt, const int64_t* __restrict__ off, int64_t cap,
+                 int2* __restrict__ out)
+{
+    __shared__ int2 lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    __shared__ int2 lds_list[kListLds * kSlotRow];
+    const uint32_t lane = threadIdx.x, i = blockIdx.x * 64u + lane;
+    if (i >= n) return;
+    int64_t b, e;
+    list_segment(off, i, cap, b, e);
+    const int64_t m = e - b;
+    if (m == 0) return;
+    const float4 q = points[i];
+    int2* list = &lds_list[lane];
+    int2* dst = out + b;
+    Filtered<SlotSeg<false, KCount>> s{SlotSeg<false, KCount>(list, dst, m, q.w * q.w), lane_filter(flt, i, 0.f)};
+    knear_point<QUAD>(sc, q, &lds_stack[lane], s);
+    fill_write_out(list, dst, m, s.cnt, s.append);
+}
+
 }  // namespace ptd
 
 // Enqueues one batch of n <= 2^30 points on `stream`: k records per point, then the detail records if asked for
@@ -172,20 +249,84 @@ static hipError_t launch_near_list(const ptd::DevScene& sc, const float* d_point
     return hipGetLastError();
 }
 
+// ---- the filtered forms' launchers: as the ones above, over the _f kernels ---------------------------------------------------------
+// pt_nearest.hip's pt_closest_points_f: (dist2, prim) per point; its detail records are that file's
+hipError_t ptk_near_one_f(const ptd::DevScene& sc, const float* d_points4, uint32_t n, bool any, bool quad, const ptd::QFilter& flt, PtNearest* d_out,
+                          hipStream_t stream)
+{
+    const dim3 blocks((n + 63u) / 64u);
+    const float4* pts = (const float4*)d_points4;
+    float2* out = (float2*)d_out;
+    if (quad) {
+        if (any) hipLaunchKernelGGL((ptd::near_one_f<true, true>), blocks, dim3(64), 0, stream, sc, pts, n, flt, out);
+        else hipLaunchKernelGGL((ptd::near_one_f<false, true>), blocks, dim3(64), 0, stream, sc, pts, n, flt, out);
+    } else {
+        if (any) hipLaunchKernelGGL((ptd::near_one_f<true, false>), blocks, dim3(64), 0, stream, sc, pts, n, flt, out);
+        else hipLaunchKernelGGL((ptd::near_one_f<false, false>), blocks, dim3(64), 0, stream, sc, pts, n, flt, out);
+    }
+    return hipGetLastError();
+}
+
+static hipError_t launch_nearest_k_f(const ptd::DevScene& sc, const float* d_points4, uint32_t n, int k, bool quad, const ptd::QFilter& flt, PtNearest* d_out,
+                                     float* d_detail8, hipStream_t stream)
+{
+    const float4* pts = (const float4*)d_points4;
+    int2* out = (int2*)d_out;
+    const dim3 blocks((n + 63u) / 64u);
+    pt_kc_dispatch(k, [&](auto kc) {
+        if (quad) hipLaunchKernelGGL((ptd::nearest_k_f<kc, true>), blocks, dim3(64), 0, stream, sc, pts, n, k, flt, out);
+        else hipLaunchKernelGGL((ptd::nearest_k_f<kc, false>), blocks, dim3(64), 0, stream, sc, pts, n, k, flt, out);
+    });
+    if (d_detail8)
+        pt_detail_chunks((uint64_t)n * (uint64_t)k, [&](uint64_t first, dim3 grid) {
+            hipLaunchKernelGGL(ptd::nearest_k_detail, grid, dim3(256), 0, stream, sc, pts, first, (uint64_t)n * (uint64_t)k, (uint32_t)k, (const int2*)out, d_detail8);
+        });
+    return hipGetLastError();
+}
+
+static hipError_t launch_count_within_f(const ptd::DevScene& sc, const float* d_points4, uint32_t n, bool quad, const ptd::QFilter& flt, int32_t* d_count,
+                                        hipStream_t stream)
+{
+    const dim3 blocks((n + 63u) / 64u);
+    if (quad) hipLaunchKernelGGL((ptd::count_within_f<true>), blocks, dim3(64), 0, stream, sc, (const float4*)d_points4, n, flt, d_count);
+    else hipLaunchKernelGGL((ptd::count_within_f<false>), blocks, dim3(64), 0, stream, sc, (const float4*)d_points4, n, flt, d_count);
+    return hipGetLastError();
+}
+
+static hipError_t launch_near_list_f(const ptd::DevScene& sc, const float* d_points4, uint32_t n, bool quad, const ptd::QFilter& flt, const int64_t* off,
+                                     int64_t cap, PtNearest* d_out, float* d_detail8, hipStream_t stream)
+{
+    const dim3 blocks((n + 63u) / 64u);
+    const float4* pts = (const float4*)d_points4;
+    int2* out = (int2*)d_out;
+    if (quad) hipLaunchKernelGGL((ptd::near_list_f<true>), blocks, dim3(64), 0, stream, sc, pts, n, flt, off, cap, out);
+    else hipLaunchKernelGGL((ptd::near_list_f<false>), blocks, dim3(64), 0, stream, sc, pts, n, flt, off, cap, out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = ptk_list_sort(off, n, cap, out, false, stream)) != hipSuccess) return e;
+    if (d_detail8) {
+        uint32_t per, grid;
+        pt_list_grid(n, per, grid);
+        hipLaunchKernelGGL(ptd::near_list_detail, dim3(grid), dim3(ptd::kSegThreads), 0, stream, sc, pts, n, per, off, cap, (const int2*)out, d_detail8);
+    }
+    return hipGetLastError();
+}
+
 // ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
 // has_k: pt_nearest_k and its host variant (PtNearest records), else the counts
 static int knear_args_ok(const char* who, const PtScene* s, const float* points, int64_t n, bool has_k, int32_t k, const void* out,
-                         const float* detail, bool device)
+                         const float* detail, bool device, const PtQueryFilter* filter = nullptr)
 {
     const char* param = (has_k && (k < 1 || k > PT_NEAREST_KMAX)) ? "k must be in 1 .. PT_NEAREST_KMAX" : nullptr;
-    return pt_query_args(who, s, n, device, {"points", points, "out", out, has_k ? "out" : "count", has_k ? 8 : 4, "detail", detail, param, false, nullptr, 0});
+    return pt_query_args(who, s, n, device, {"points", points, "out", out, has_k ? "out" : "count", has_k ? 8 : 4, "detail", detail, param, false, nullptr, 0,
+                                             filter, false});
 }
 
 // pt_within_radius_list and its host variant
 static int near_list_args_ok(const char* who, const PtScene* s, const float* points, int64_t n, const int64_t* offsets, int64_t cap,
-                             const void* out, const float* detail, bool device)
+                             const void* out, const float* detail, bool device, const PtQueryFilter* filter = nullptr)
 {
-    return pt_query_args(who, s, n, device, {"points", points, "out", out, "out", 8, "detail", detail, nullptr, true, offsets, cap});
+    return pt_query_args(who, s, n, device, {"points", points, "out", out, "out", 8, "detail", detail, nullptr, true, offsets, cap, filter, false});
 }
 
 extern "C" {
@@ -264,6 +405,53 @@ int pt_within_radius_list_host(PtScene* s, const float* h_points4, int64_t n, in
                         [&](float* d_pts, int64_t* d_off, int64_t total, void* d_out, float* d_det) {
                             return pt_within_radius_list(s, d_pts, n, d_off, total, (PtNearest*)d_out, d_det, nullptr);
                         });
+}
+
+// ---- the filtered forms: the twin's checks, then the filter's; a neutral filter enqueues the twin itself ---------------------------
+int pt_nearest_k_f(PtScene* s, const float* d_points4, int64_t n, int32_t k, const PtQueryFilter* filter, PtNearest* d_out, float* d_detail8,
+                   void* hip_stream)
+{
+    int rc;
+    if ((rc = knear_args_ok("pt_nearest_k_f", s, d_points4, n, true, k, d_out, d_detail8, true, filter)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    if (pt_filter_neutral(filter)) return pt_nearest_k(s, d_points4, n, k, d_out, d_detail8, hip_stream);
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s);
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_nearest_k_f(s->dev, d_points4 + off * 4, m, k, quad, pt_filter_dev(filter, off), d_out + off * k,
+                                  d_detail8 ? d_detail8 + off * k * 8 : nullptr, (hipStream_t)hip_stream);
+    }));
+    return PT_OK;
+}
+
+int pt_count_within_f(PtScene* s, const float* d_points4, int64_t n, const PtQueryFilter* filter, int32_t* d_count, void* hip_stream)
+{
+    int rc;
+    if ((rc = knear_args_ok("pt_count_within_f", s, d_points4, n, false, 0, d_count, nullptr, true, filter)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    if (pt_filter_neutral(filter)) return pt_count_within(s, d_points4, n, d_count, hip_stream);
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s);
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_count_within_f(s->dev, d_points4 + off * 4, m, quad, pt_filter_dev(filter, off), d_count + off, (hipStream_t)hip_stream);
+    }));
+    return PT_OK;
+}
+
+int pt_within_radius_list_f(PtScene* s, const float* d_points4, int64_t n, const int64_t* d_offsets, int64_t cap, const PtQueryFilter* filter,
+                            PtNearest* d_out, float* d_detail8, void* hip_stream)
+{
+    int rc;
+    if ((rc = near_list_args_ok("pt_within_radius_list_f", s, d_points4, n, d_offsets, cap, d_out, d_detail8, true, filter)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    if (pt_filter_neutral(filter)) return pt_within_radius_list(s, d_points4, n, d_offsets, cap, d_out, d_detail8, hip_stream);
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s);
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_near_list_f(s->dev, d_points4 + off * 4, m, quad, pt_filter_dev(filter, off), d_offsets + off, cap, d_out, d_detail8,
+                                  (hipStream_t)hip_stream);
+    }));
+    return PT_OK;
 }
 
 }  // extern "C"

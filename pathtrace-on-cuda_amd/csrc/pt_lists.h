@@ -2,6 +2,8 @@
 // pt_within_radius_list; DESIGN.md sections 30, 34 and 37): the order of the records, the per-lane LDS list of the K kernels and of the
 // fill, the fill's sink and its write-out, the clamped segment of a query, the pass over the segments that hands a short one to one
 // thread and a long one to the whole workgroup, the detail kernels' body over it, and the launcher of the sort (pt_lists.hip).
+// And the query filters (section 40): the wrapper that puts any of these sinks behind a filter, and the one-slot sink of the filtered
+// closest and any forms.
 //
 // Which code sorts a segment of m slots:
 //   m <= kListLds          the fill keeps it sorted in the K kernels' per-lane LDS list, with that lane's k = m
@@ -11,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include "pt_device.h"
 #include "pt_math.h"
+#include "../../include/pt_api.h"
 
 namespace ptd {
 
@@ -67,6 +70,7 @@ constexpr int kSlotRow = 65;
 template <bool FKEY>
 struct SlotList {
     static constexpr bool kOrdered = true;      // a point walk visits the nearer child first: the bound falls sooner
+    static constexpr bool kStops = false;       // a walk need not ask done(): the sink wants candidates to the end
     int2* list;                                 // this lane's slot 0
     int k, cnt;
     float bound;
@@ -120,6 +124,103 @@ struct SlotSeg : SlotList<FKEY> {
         if (COUNT::counts(key, this->bound) & (this->cnt < m)) { seg[this->cnt] = make_int2(__float_as_int(key), prim); this->cnt++; }
     }
 };
+
+// ---- query filters (include/pt_api.h: "Query filters") --------------------------------------------------------
+// A filtered query answers over H' = the members of its twin's set H that the filter keeps, a pure selection.  The whole correctness
+// argument: a sink's bound is only ever moved by take(), and Filtered calls the inner take() for members of H' alone — A FILTERED-OUT
+// PRIMITIVE NEVER TIGHTENS A BOUND.  So the inner sink sees exactly the walk of a scene that holds H' only, with a bound that is at
+// every moment the bound of that walk: whatever the walks' culls prove for H they prove for H'.  The inner sink's own test comes
+// first — registers only —, so that only a candidate the sink would take pays the filter's one 4-byte gather.
+//
+// The filter as a kernel takes it (by value): the three arrays of PtQueryFilter, each null or a device pointer, already advanced to
+// the launch's first query where they are per query.
+struct QFilter {
+    const uint32_t* prim_bits;      // per primitive; null: every bit set
+    const uint32_t* query_bits;     // per query; null: `bits`
+    const int32_t* skip;            // per query; null: none
+    uint32_t bits;
+    uint32_t tmin;                  // PT_FILTER_TMIN given: the ray's 7th float is its near bound
+};
+
+// One query's filter, in registers.  skip = -1 and tmin = -inf keep everything: no primitive has number -1, no key is below -inf.
+struct LaneFilter {
+    const uint32_t* prim_bits;
+    uint32_t m;
+    int skip;
+    float tmin;
+    // skip, tmin, then the gather; a null prim_bits costs no load (the pointer is uniform: a scalar branch)
+    PT_DEV bool keeps(float key, int prim) const
+    {
+        if (prim == skip) return false;
+        if (key < tmin) return false;
+        if (!prim_bits) return m != 0u;
+        return (prim_bits[prim] & m) != 0u;
+    }
+};
+
+// Query i's filter.  tmin: the ray's near bound as read by the caller (ignored unless f.tmin).
+PT_DEV LaneFilter lane_filter(const QFilter& f, uint32_t i, float tmin)
+{
+    LaneFilter l;
+    l.prim_bits = f.prim_bits;
+    l.m = f.query_bits ? f.query_bits[i] : f.bits;
+    l.skip = f.skip ? f.skip[i] : -1;
+    l.tmin = f.tmin ? tmin : -__builtin_inff();
+    return l;
+}
+
+// Any sink behind a filter: wants() and offer() are the inner sink's test, then the filter's; take(), bound and kOrdered are the inner
+// sink's.  SINK has wants() and take() (a point walk's offer() is the two in a row).
+template <class SINK>
+struct Filtered : SINK {
+    LaneFilter f;
+    PT_DEV bool wants(float key, int prim) const { return SINK::wants(key, prim) && f.keeps(key, prim); }
+    PT_DEV void offer(float key, int prim)
+    {
+        if (wants(key, prim)) SINK::take(key, prim);
+    }
+};
+
+// The sink of the filtered closest and any forms: one slot of SlotList's rule, in registers, no LDS list.  Empty: (bound, boundPrim) =
+// (tmax or r2, -1), (key, prim) = (0, -1), the miss record.  ANY: after the first member nothing is wanted any more — bound 0 and the
+// largest prim fail both halves of the rule for every key >= 0 —, and the sink says so: kStops makes the walks ask done() before they
+// take the next node off their stack (a compile-time choice: a walk over any other sink has no such test).
+template <bool ANY>
+struct SlotOne {
+    static constexpr bool kOrdered = true;
+    static constexpr bool kStops = ANY;
+    PT_DEV bool done() const { return ANY && prim >= 0; }
+    float bound;
+    int boundPrim;
+    float key;
+    int prim;
+    PT_DEV bool wants(float k, int p) const { return (k < bound) | ((k == bound) & (p > boundPrim)); }
+    PT_DEV void take(float k, int p)
+    {
+        key = k;
+        prim = p;
+        bound = ANY ? 0.f : k;
+        boundPrim = ANY ? 0x7fffffff : p;
+    }
+};
+
+// The end of a K kernel: the wave's lists, padded with miss records by their lanes, go out of LDS in record order — record r of the
+// block is slot r % k of query r / k —, 64 consecutive records (512 bytes) per store.  base: the wave's first query; the __syncthreads
+// between the lanes' last list writes and these reads is the caller's.
+PT_DEV void klist_copy_out(const int2* lds_list, int2* __restrict__ out, uint32_t base, uint32_t n, int k)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint32_t live = (n - base < 64u) ? n - base : 64u, total = live * (uint32_t)k;
+    int2* dst = out + (size_t)base * (size_t)k;
+    const int q64 = 64 / k, m64 = 64 % k;
+    int t = (int)lane / k, j = (int)lane % k;      // record r is slot j of query t: r = t * k + j, t < live <= 64
+    for (uint32_t r = lane; r < total; r += 64u) {
+        dst[r] = lds_list[j * kSlotRow + t];
+        j += m64;
+        t += q64;
+        if (j >= k) { j -= k; t++; }
+    }
+}
 
 // The end of a list fill, in the lane that owns the segment dst = &out[b] of m records: every record written once — the lane's list of
 // cnt sorted members (slot 0 at list), or the cnt members appended, then the miss record (0, -1) up to m
@@ -205,6 +306,26 @@ inline void pt_list_grid(uint32_t n, uint32_t& per, uint32_t& blocks)
     blocks = chunks < ptd::kSegGrid ? chunks : ptd::kSegGrid;
 }
 
+// A launch's filter from the caller's (checked by pt_query_args; null: the neutral one), for the batch whose first query is `first`
+inline ptd::QFilter pt_filter_dev(const PtQueryFilter* f, int64_t first)
+{
+    if (!f) return ptd::QFilter{nullptr, nullptr, nullptr, 0xFFFFFFFFu, 0u};
+    return ptd::QFilter{f->d_prim_bits, f->d_query_bits ? f->d_query_bits + first : nullptr, f->d_skip_prim ? f->d_skip_prim + first : nullptr, f->bits,
+                        f->flags & PT_FILTER_TMIN};
+}
+
+// Does the filter keep every member of every query?  Then a _f entry point enqueues its twin's own kernels.
+inline bool pt_filter_neutral(const PtQueryFilter* f)
+{
+    return !f || (!f->d_prim_bits && !f->d_query_bits && !f->d_skip_prim && f->bits == 0xFFFFFFFFu && f->flags == 0u);
+}
+
 // pt_lists.hip: enqueues the sort of every segment of more than kListLds slots of the n (<= 2^30) queries whose n + 1 offsets start at
 // `off` (clamped to cap), records at `rec`.  floatKey: t (the ray lists), else f (the point lists).
 hipError_t ptk_list_sort(const int64_t* off, uint32_t n, int64_t cap, int2* rec, bool floatKey, hipStream_t stream);
+// pt_rayhits.hip / pt_knearest.hip: enqueue the filtered closest (or `any`) form for n <= 2^30 queries, (key, prim) per query, for
+// pt_query.hip's pt_trace_rays_f and pt_nearest.hip's pt_closest_points_f, whose surface and detail kernels live in those files
+hipError_t ptk_rays_one_f(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, bool any, bool quad, const ptd::QFilter& flt, PtRayHit* d_hits,
+                          hipStream_t stream);
+hipError_t ptk_near_one_f(const ptd::DevScene& sc, const float* d_points4, uint32_t n, bool any, bool quad, const ptd::QFilter& flt, PtNearest* d_out,
+                          hipStream_t stream);

@@ -219,4 +219,15 @@ int pt_list_offsets(const int32_t* d_count, int64_t n, int64_t* d_offsets, void*
     return PT_OK;
 }
 
+// The neutral filter of the _f queries (include/pt_api.h: "Query filters")
+void pt_query_filter_default(PtQueryFilter* f)
+{
+    if (!f) return;
+    f->d_prim_bits = nullptr;
+    f->d_query_bits = nullptr;
+    f->d_skip_prim = nullptr;
+    f->bits = 0xFFFFFFFFu;
+    f->flags = 0u;
+}
+
 }  // extern "C"

@@ -129,7 +129,8 @@ PT_DEV bool near_pop(const int2* stack, int& sp, float best, int& cur)
 
 // ---- the point walk of pt_knearest.hip's queries: candidates f(p, k) to a sink (pt_lists.h: SlotList has the interface) -----------
 // Sinks: the K list, the count and the fill.  s.offer(f, prim): the sink's acceptance and, if it accepts, its take.  SINK::kOrdered:
-// take the nearest child next (the bound falls sooner); else the children as they come.  pt_nearest.hip's closest query keeps its own
+// take the nearest child next (the bound falls sooner); else the children as they come.  SINK::kStops: the walk ends once s.done()
+// (pt_lists.h: the any form's sink; false for every other sink, whose walks hold no such test).  pt_nearest.hip's closest query keeps its own
 // copy of the walk (through this template its kernel's code changed and measured slower).
 
 // The `cnt` triangles at tree position `first` (a leaf of either tree: ~ref = first << 3 | cnt)
@@ -188,6 +189,7 @@ PT_DEV void knear_walk_quad(const DevScene& sc, const f3& p, int2* stack, SINK& 
             }
         } else {
             knear_leaf(sc, cur, p, s);
+            if constexpr (SINK::kStops) { if (s.done()) return; }
         }
         if (!near_pop(stack, sp, s.bound, cur)) return;
     }
@@ -200,6 +202,7 @@ PT_DEV void knear_walk_binary(const DevScene& sc, const f3& p, int2* stack, SINK
 {
     int cur = 0, sp = 0;
     for (;;) {
+        if constexpr (SINK::kStops) { if (s.done()) return; }
         const float4 q0 = sc.nodes[4 * (size_t)cur + 0], q1 = sc.nodes[4 * (size_t)cur + 1], q2 = sc.nodes[4 * (size_t)cur + 2], q3 = sc.nodes[4 * (size_t)cur + 3];
         f3 loL(q0.x, q0.y, q0.z), hiL(q0.w, q1.x, q1.y), loR(q1.z, q1.w, q2.x), hiR(q2.y, q2.z, q2.w);
         widen_binary(loL, hiL);

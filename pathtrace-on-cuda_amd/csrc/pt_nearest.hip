@@ -19,6 +19,7 @@
 #include "pt_trace.h"
 #include "pt_scene.h"
 #include "pt_nearest.h"
+#include "pt_lists.h"
 
 namespace ptd {
 
@@ -176,11 +177,11 @@ static hipError_t launch_nearest(const ptd::DevScene& sc, const float* d_points4
 
 // ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
 static int nearest_args_ok(const char* who, const PtScene* s, const float* points, int64_t n, int32_t mode, const PtNearest* out, const float* detail,
-                           bool device)
+                           bool device, const PtQueryFilter* filter = nullptr)
 {
     const char* param = (mode != PT_NEAREST_CLOSEST && mode != PT_NEAREST_ANY) ? "mode must be PT_NEAREST_CLOSEST or PT_NEAREST_ANY" :
                         (mode == PT_NEAREST_ANY && detail) ? "an any-within query has no detail record (d_detail8 must be NULL)" : nullptr;
-    return pt_query_args(who, s, n, device, {"points", points, "out", out, "out", 8, "detail", detail, param, false, nullptr, 0});
+    return pt_query_args(who, s, n, device, {"points", points, "out", out, "out", 8, "detail", detail, param, false, nullptr, 0, filter, false});
 }
 
 extern "C" {
@@ -208,6 +209,29 @@ int pt_closest_points_host(PtScene* s, const float* h_points4, int64_t n, int32_
     return pt_host_query(h_points4, (size_t)n * 16, h_out, (size_t)n * 8, h_detail8, (size_t)n * 32, [&](float* d_pts, void* d_out, float* d_det) {
         return pt_closest_points(s, d_pts, n, mode, (PtNearest*)d_out, d_det, nullptr);
     });
+}
+
+// The filtered form (section "Query filters"): the twin's checks, then the filter's; a neutral filter enqueues the twin itself.  Else
+// the shared point walk (pt_knearest.hip) over the one-slot sink writes the records, and the detail records come from nearest_detail.
+int pt_closest_points_f(PtScene* s, const float* d_points4, int64_t n, int32_t mode, const PtQueryFilter* filter, PtNearest* d_out, float* d_detail8,
+                        void* hip_stream)
+{
+    int rc;
+    if ((rc = nearest_args_ok("pt_closest_points_f", s, d_points4, n, mode, d_out, d_detail8, true, filter)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    if (pt_filter_neutral(filter)) return pt_closest_points(s, d_points4, n, mode, d_out, d_detail8, hip_stream);
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        const float* pts = d_points4 + off * 4;
+        const hipError_t e = ptk_near_one_f(s->dev, pts, m, mode == PT_NEAREST_ANY, quad, pt_filter_dev(filter, off), d_out + off, stream);
+        if (e != hipSuccess || !d_detail8) return e;
+        hipLaunchKernelGGL(ptd::nearest_detail, dim3((m + 255u) / 256u), dim3(256), 0, stream, s->dev, (const float4*)pts, m, (const float2*)(d_out + off),
+                           d_detail8 + off * 8);
+        return hipGetLastError();
+    }));
+    return PT_OK;
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include "pt_trace.h"
 #include "pt_shade.h"
 #include "pt_scene.h"
+#include "pt_lists.h"
 
 namespace ptd {
 
@@ -109,11 +110,11 @@ static hipError_t launch_query(const ptd::DevScene& sc, const float* uv, const f
 
 // ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
 static int query_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, int32_t mode, const PtRayHit* hits, const float* surface,
-                         bool device)
+                         bool device, const PtQueryFilter* filter = nullptr)
 {
     const char* param = (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_ANY) ? "mode must be PT_QUERY_CLOSEST or PT_QUERY_ANY" :
                         (mode == PT_QUERY_ANY && surface) ? "an any-hit query has no surface record (d_surface29 must be NULL)" : nullptr;
-    return pt_query_args(who, s, n, device, {"rays", rays, "hits", hits, "hits", 8, "surface", surface, param, false, nullptr, 0});
+    return pt_query_args(who, s, n, device, {"rays", rays, "hits", hits, "hits", 8, "surface", surface, param, false, nullptr, 0, filter, true});
 }
 
 extern "C" {
@@ -141,6 +142,29 @@ int pt_trace_rays_host(PtScene* s, const float* h_rays8, int64_t n, int32_t mode
     return pt_host_query(h_rays8, (size_t)n * 32, h_hits, (size_t)n * 8, h_surface29, (size_t)n * 116, [&](float* d_rays, void* d_hits, float* d_surf) {
         return pt_trace_rays(s, d_rays, n, mode, (PtRayHit*)d_hits, d_surf, nullptr);
     });
+}
+
+// The filtered form (section "Query filters"): the twin's checks, then the filter's; a neutral filter enqueues the twin itself.  Else
+// pt_rayhits.hip's walk over the one-slot sink writes the records, and the surface records come from query_surface as above.
+int pt_trace_rays_f(PtScene* s, const float* d_rays8, int64_t n, int32_t mode, const PtQueryFilter* filter, PtRayHit* d_hits, float* d_surface29,
+                    void* hip_stream)
+{
+    int rc;
+    if ((rc = query_args_ok("pt_trace_rays_f", s, d_rays8, n, mode, d_hits, d_surface29, true, filter)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    if (pt_filter_neutral(filter)) return pt_trace_rays(s, d_rays8, n, mode, d_hits, d_surface29, hip_stream);
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        const float* rays = d_rays8 + off * 8;
+        const hipError_t e = ptk_rays_one_f(s->dev, rays, m, mode == PT_QUERY_ANY, quad, pt_filter_dev(filter, off), d_hits + off, stream);
+        if (e != hipSuccess || !d_surface29) return e;
+        hipLaunchKernelGGL(ptd::query_surface, dim3((m + 255u) / 256u), dim3(256), 0, stream, s->dev, s->uv.as<float>(), (const float4*)rays, m,
+                           (const float2*)(d_hits + off), d_surface29 + off * 29);
+        return hipGetLastError();
+    }));
+    return PT_OK;
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@ namespace ptd {
 // What a walk hands its hits to (pt_lists.h: SlotList has the interface; wants() is asked before the leaf box is fetched).
 // |H|: the bound stays tmax.  counts(): its acceptance, and the fill's for a long segment (pt_lists.h: SlotSeg).
 struct HitCount {
+    static constexpr bool kStops = false;
     int cnt;
     float bound;
     PT_DEV static bool counts(float t, float bound) { return !(t > bound); }
@@ -82,6 +83,7 @@ PT_DEV void hits_walk_quad(const DevScene& sc, const f3& org, const f3& dir, int
             const int code = ~cur;
             int first = code >> 3, cnt = code & 7;
             while (cnt > 0) { tri_hits_pairrec<BOTH>(sc, first, cnt > 1, org, dir, inv, degenerate, s); first += 2; cnt -= 2; }
+            if constexpr (SINK::kStops) { if (s.done()) return; }
         }
         if (sp == 0) return;
         sp--;
@@ -103,6 +105,7 @@ PT_DEV void hits_walk_binary(const DevScene& sc, const f3& org, const f3& dir, i
     float cullB = s.bound * kcull;
     int sp = 0, cur = 0;
     for (;;) {
+        if constexpr (SINK::kStops) { if (s.done()) return; }
         const float4 q0 = sc.nodes[4 * (size_t)cur + 0], q1 = sc.nodes[4 * (size_t)cur + 1], q2 = sc.nodes[4 * (size_t)cur + 2], q3 = sc.nodes[4 * (size_t)cur + 3];
         float tnL, tnR;
         bool okL, okR;
@@ -311,7 +314,98 @@ void rays_list_detail(DevScene sc, const float4* __restrict__ rays, uint32_t n, 
                        [&](const Ray& r, int2 h, float* o) { hit_detail(sc, r.org, r.dir, r.tmax, h, o); });
 }
 
+// ---- the filtered forms (include/pt_api.h: "Query filters") ----------------------------------------------------
+// The kernels above with their sink behind pt_lists.h's Filtered: the same walks, the same one-wave workgroups and LDS layouts, the
+// same capacity classes.  The ray's near bound is the 7th float of its record, which no other kernel reads.
+PT_DEV LaneFilter load_ray_f(const float4* __restrict__ rays, uint32_t i, const QFilter& flt, f3& org, f3& dir, float& tmax)
+{
+    load_ray(rays, i, org, dir, tmax);
+    return lane_filter(flt, i, rays[2 * (size_t)i + 1].z);      // the float4 load_ray has just fetched
+}
+
+// pt_trace_rays_f: the first member of H' under PT_HITS_FRONT, or (ANY) some member.  query_rays' shape and record.
+template <bool ANY, bool QUAD>
+__global__ __launch_bounds__(64, kQueryWaves)
+void rays_one_f(DevScene sc, const float4* __restrict__ rays, uint32_t n, QFilter flt, float2* __restrict__ hits)
+{
+    __shared__ int lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    f3 org, dir; float tmax;
+    const LaneFilter lf = load_ray_f(rays, i, flt, org, dir, tmax);
+    Filtered<SlotOne<ANY>> s{{tmax, -1, 0.f, -1}, lf};
+    hits_ray<QUAD, false>(sc, org, dir, tmax, &lds_stack[threadIdx.x], s);
+    hits[i] = make_float2(s.key, __int_as_float(s.prim));      // a miss is (0, -1)
+}
+
+template <int KC, bool QUAD, bool BOTH>
+__global__ __launch_bounds__(64)
+void rays_k_f(DevScene sc, const float4* __restrict__ rays, uint32_t n, int k, QFilter flt, int2* __restrict__ out)
+{
+    __shared__ int lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    __shared__ int2 lds_list[KC * kSlotRow];
+    if (k < 1 || k > KC) return;      // the launcher's choice of KC, restated where the list is indexed
+    const uint32_t lane = threadIdx.x, base = blockIdx.x * 64u, i = base + lane;
+    int2* list = &lds_list[lane];
+    int cnt = 0;
+    if (i < n) {
+        f3 org, dir; float tmax;
+        const LaneFilter lf = load_ray_f(rays, i, flt, org, dir, tmax);
+        Filtered<SlotList<true>> s{{list, k, 0, tmax, -1}, lf};
+        hits_ray<QUAD, BOTH>(sc, org, dir, tmax, &lds_stack[lane], s);
+        cnt = s.cnt;
+    }
+    for (int j = cnt; j < k; j++) list[j * kSlotRow] = make_int2(0, -1);      // a miss is (0, -1)
+    __syncthreads();
+    klist_copy_out(lds_list, out, base, n, k);
+}
+
+template <bool QUAD, bool BOTH>
+__global__ __launch_bounds__(64, kQueryWaves)
+void count_hits_f(DevScene sc, const float4* __restrict__ rays, uint32_t n, QFilter flt, int32_t* __restrict__ out)
+{
+    __shared__ int lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    f3 org, dir; float tmax;
+    const LaneFilter lf = load_ray_f(rays, i, flt, org, dir, tmax);
+    Filtered<HitCount> s{{0, tmax}, lf};
+    hits_ray<QUAD, BOTH>(sc, org, dir, tmax, &lds_stack[threadIdx.x], s);
+    out[i] = s.cnt;
+}
+
+// The fill: a long segment's appended members are Filtered<HitCount>'s members, the filtered count's
+template <bool QUAD, bool BOTH>
+__global__ __launch_bounds__(64)
+void rays_list_f(DevScene sc, const float4* __restrict__ rays, uint32_t n, QFilter flt, const int64_t* __restrict__ off, int64_t cap,
+                 int2* __restrict__ out)
+{
+    __shared__ int lds_stack[(QUAD ? kQueryStack : kStackDepth) * 64];
+    __shared__ int2 lds_list[kListLds * kSlotRow];
+    const uint32_t lane = threadIdx.x, i = blockIdx.x * 64u + lane;
+    if (i >= n) return;
+    int64_t b, e;
+    list_segment(off, i, cap, b, e);
+    const int64_t m = e - b;
+    if (m == 0) return;
+    f3 org, dir; float tmax;
+    const LaneFilter lf = load_ray_f(rays, i, flt, org, dir, tmax);
+    int2* list = &lds_list[lane];
+    int2* dst = out + b;
+    Filtered<SlotSeg<true, HitCount>> s{SlotSeg<true, HitCount>(list, dst, m, tmax), lf};
+    hits_ray<QUAD, BOTH>(sc, org, dir, tmax, &lds_stack[lane], s);
+    fill_write_out(list, dst, m, s.cnt, s.append);
+}
+
 }  // namespace ptd
+
+// f(std::bool_constant<QUAD>(), std::bool_constant<BOTH>()): the walk and the sides of a launch as compile-time values
+template <class F>
+static void quad_both_dispatch(bool quad, bool both, F f)
+{
+    if (quad) { if (both) f(std::true_type(), std::true_type()); else f(std::true_type(), std::false_type()); }
+    else { if (both) f(std::false_type(), std::true_type()); else f(std::false_type(), std::false_type()); }
+}
 
 // Enqueues one batch of n <= 2^30 rays on `stream`: k records per ray, then the detail records if asked for
 static hipError_t launch_rays_k(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, int k, bool quad, bool both, PtRayHit* d_hits, float* d_detail4, hipStream_t stream)
@@ -375,6 +469,68 @@ static hipError_t launch_rays_list(const ptd::DevScene& sc, const float* d_rays8
     return hipGetLastError();
 }
 
+// ---- the filtered forms' launchers: as the ones above, over the _f kernels ---------------------------------------------------------
+hipError_t ptk_rays_one_f(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, bool any, bool quad, const ptd::QFilter& flt, PtRayHit* d_hits,
+                          hipStream_t stream)
+{
+    const dim3 blocks((n + 63u) / 64u);
+    const float4* rays = (const float4*)d_rays8;
+    float2* hits = (float2*)d_hits;
+    quad_both_dispatch(quad, any, [&](auto q, auto a) {
+        hipLaunchKernelGGL((ptd::rays_one_f<decltype(a)::value, decltype(q)::value>), blocks, dim3(64), 0, stream, sc, rays, n, flt, hits);
+    });
+    return hipGetLastError();
+}
+
+static hipError_t launch_rays_k_f(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, int k, bool quad, bool both, const ptd::QFilter& flt,
+                                  PtRayHit* d_hits, float* d_detail4, hipStream_t stream)
+{
+    const float4* rays = (const float4*)d_rays8;
+    int2* out = (int2*)d_hits;
+    const dim3 blocks((n + 63u) / 64u);
+    pt_kc_dispatch(k, [&](auto kc) {
+        quad_both_dispatch(quad, both, [&](auto q, auto b) {
+            hipLaunchKernelGGL((ptd::rays_k_f<decltype(kc)::value, decltype(q)::value, decltype(b)::value>), blocks, dim3(64), 0, stream, sc, rays, n, k, flt, out);
+        });
+    });
+    if (d_detail4)
+        pt_detail_chunks((uint64_t)n * (uint64_t)k, [&](uint64_t first, dim3 grid) {
+            hipLaunchKernelGGL(ptd::rays_k_detail, grid, dim3(256), 0, stream, sc, rays, first, (uint64_t)n * (uint64_t)k, (uint32_t)k, (const int2*)out, d_detail4);
+        });
+    return hipGetLastError();
+}
+
+static hipError_t launch_count_hits_f(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, bool quad, bool both, const ptd::QFilter& flt,
+                                      int32_t* d_count, hipStream_t stream)
+{
+    const dim3 blocks((n + 63u) / 64u);
+    const float4* rays = (const float4*)d_rays8;
+    quad_both_dispatch(quad, both, [&](auto q, auto b) {
+        hipLaunchKernelGGL((ptd::count_hits_f<decltype(q)::value, decltype(b)::value>), blocks, dim3(64), 0, stream, sc, rays, n, flt, d_count);
+    });
+    return hipGetLastError();
+}
+
+static hipError_t launch_rays_list_f(const ptd::DevScene& sc, const float* d_rays8, uint32_t n, bool quad, bool both, const ptd::QFilter& flt,
+                                     const int64_t* off, int64_t cap, PtRayHit* d_hits, float* d_detail4, hipStream_t stream)
+{
+    const dim3 blocks((n + 63u) / 64u);
+    const float4* rays = (const float4*)d_rays8;
+    int2* out = (int2*)d_hits;
+    quad_both_dispatch(quad, both, [&](auto q, auto b) {
+        hipLaunchKernelGGL((ptd::rays_list_f<decltype(q)::value, decltype(b)::value>), blocks, dim3(64), 0, stream, sc, rays, n, flt, off, cap, out);
+    });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = ptk_list_sort(off, n, cap, out, true, stream)) != hipSuccess) return e;
+    if (d_detail4) {
+        uint32_t per, grid;
+        pt_list_grid(n, per, grid);
+        hipLaunchKernelGGL(ptd::rays_list_detail, dim3(grid), dim3(ptd::kSegThreads), 0, stream, sc, rays, n, per, off, cap, (const int2*)out, d_detail4);
+    }
+    return hipGetLastError();
+}
+
 // ---- entry points (include/pt_api.h): every argument check comes before the first HIP call ----------------------------------------
 static const char* flags_bad(int32_t flags)
 {
@@ -383,17 +539,18 @@ static const char* flags_bad(int32_t flags)
 
 // has_k: pt_trace_rays_k and its host variant (PtRayHit records), else the counts
 static int hits_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, bool has_k, int32_t k, int32_t flags, const void* out,
-                        const float* detail, bool device)
+                        const float* detail, bool device, const PtQueryFilter* filter = nullptr)
 {
     const char* param = (has_k && (k < 1 || k > PT_RAY_HITS_KMAX)) ? "k must be in 1 .. PT_RAY_HITS_KMAX" : flags_bad(flags);
-    return pt_query_args(who, s, n, device, {"rays", rays, "out", out, has_k ? "hits" : "count", has_k ? 8 : 4, "detail", detail, param, false, nullptr, 0});
+    return pt_query_args(who, s, n, device, {"rays", rays, "out", out, has_k ? "hits" : "count", has_k ? 8 : 4, "detail", detail, param, false, nullptr, 0,
+                                                   filter, true});
 }
 
 // pt_trace_rays_list and its host variant
 static int list_args_ok(const char* who, const PtScene* s, const float* rays, int64_t n, int32_t flags, const int64_t* offsets, int64_t cap,
-                        const void* hits, const float* detail, bool device)
+                        const void* hits, const float* detail, bool device, const PtQueryFilter* filter = nullptr)
 {
-    return pt_query_args(who, s, n, device, {"rays", rays, "hits", hits, "hits", 8, "detail", detail, flags_bad(flags), true, offsets, cap});
+    return pt_query_args(who, s, n, device, {"rays", rays, "hits", hits, "hits", 8, "detail", detail, flags_bad(flags), true, offsets, cap, filter, true});
 }
 
 extern "C" {
@@ -473,6 +630,53 @@ int pt_trace_rays_list_host(PtScene* s, const float* h_rays8, int64_t n, int32_t
                         [&](float* d_rays, int64_t* d_off, int64_t total, void* d_hits, float* d_det) {
                             return pt_trace_rays_list(s, d_rays, n, flags, d_off, total, (PtRayHit*)d_hits, d_det, nullptr);
                         });
+}
+
+// ---- the filtered forms: the twin's checks, then the filter's; a neutral filter enqueues the twin itself ---------------------------
+int pt_trace_rays_k_f(PtScene* s, const float* d_rays8, int64_t n, int32_t k, int32_t flags, const PtQueryFilter* filter, PtRayHit* d_hits,
+                      float* d_detail4, void* hip_stream)
+{
+    int rc;
+    if ((rc = hits_args_ok("pt_trace_rays_k_f", s, d_rays8, n, true, k, flags, d_hits, d_detail4, true, filter)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    if (pt_filter_neutral(filter)) return pt_trace_rays_k(s, d_rays8, n, k, flags, d_hits, d_detail4, hip_stream);
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s), both = flags == PT_HITS_BOTH_SIDES;
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_rays_k_f(s->dev, d_rays8 + off * 8, m, k, quad, both, pt_filter_dev(filter, off), d_hits + off * k,
+                               d_detail4 ? d_detail4 + off * k * 4 : nullptr, (hipStream_t)hip_stream);
+    }));
+    return PT_OK;
+}
+
+int pt_count_hits_f(PtScene* s, const float* d_rays8, int64_t n, int32_t flags, const PtQueryFilter* filter, int32_t* d_count, void* hip_stream)
+{
+    int rc;
+    if ((rc = hits_args_ok("pt_count_hits_f", s, d_rays8, n, false, 0, flags, d_count, nullptr, true, filter)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    if (pt_filter_neutral(filter)) return pt_count_hits(s, d_rays8, n, flags, d_count, hip_stream);
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s), both = flags == PT_HITS_BOTH_SIDES;
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_count_hits_f(s->dev, d_rays8 + off * 8, m, quad, both, pt_filter_dev(filter, off), d_count + off, (hipStream_t)hip_stream);
+    }));
+    return PT_OK;
+}
+
+int pt_trace_rays_list_f(PtScene* s, const float* d_rays8, int64_t n, int32_t flags, const int64_t* d_offsets, int64_t cap, const PtQueryFilter* filter,
+                         PtRayHit* d_hits, float* d_detail4, void* hip_stream)
+{
+    int rc;
+    if ((rc = list_args_ok("pt_trace_rays_list_f", s, d_rays8, n, flags, d_offsets, cap, d_hits, d_detail4, true, filter)) != PT_OK) return rc;
+    if (n == 0) return PT_OK;
+    if (pt_filter_neutral(filter)) return pt_trace_rays_list(s, d_rays8, n, flags, d_offsets, cap, d_hits, d_detail4, hip_stream);
+    HIPCHK(hipSetDevice(s->device));
+    const bool quad = pt_query_walks_quad(s), both = flags == PT_HITS_BOTH_SIDES;
+    HIPCHK(pt_query_batches(n, [&](int64_t off, uint32_t m) {
+        return launch_rays_list_f(s->dev, d_rays8 + off * 8, m, quad, both, pt_filter_dev(filter, off), d_offsets + off, cap, d_hits, d_detail4,
+                                  (hipStream_t)hip_stream);
+    }));
+    return PT_OK;
 }
 
 }  // extern "C"

@@ -90,7 +90,9 @@ inline bool pt_query_walks_quad(const PtScene* s) { return s->query_quad && 3 * 
 // The argument checks, in the order every query makes them: scene, input, a list's offsets, output (a list's host variant may leave it
 // NULL: the sizing call), n, a list's cap, the query's own parameters (`param`: the message of the first one that fails, nullptr = none),
 // then on the device the alignment of input (16), offsets (8), output (outAlign bytes, named outName) and detail (4, named detName).
-// PT_OK, or PT_ERR_INVALID with "who: message" set.
+// A filtered query (`filter`; NULL, the neutral one, has nothing to check) adds, after all of its twin's: unknown filter flags,
+// PT_FILTER_TMIN on a point query, the alignment (4) of the filter's three arrays.  The filter is a host struct and is read; its
+// arrays are not.  PT_OK, or PT_ERR_INVALID with "who: message" set.
 struct QueryArgs {
     const char* in; const void* inPtr;                                   // "rays" or "points"
     const char* outNull; const void* outPtr;                             // the name "NULL ..." gives the output
@@ -98,6 +100,7 @@ struct QueryArgs {
     const char* detName; const void* detPtr;
     const char* param;
     bool list; const int64_t* offsets; int64_t cap;
+    const PtQueryFilter* filter; bool filterRays;                        // the _f entry points; filterRays: a ray query (it may take PT_FILTER_TMIN)
 };
 inline int pt_query_args(const char* who, const PtScene* s, int64_t n, bool device, const QueryArgs& a)
 {
@@ -114,6 +117,14 @@ inline int pt_query_args(const char* who, const PtScene* s, int64_t n, bool devi
     if (a.list && ((uintptr_t)a.offsets & 7)) return fail("%s: %s must be 8-byte aligned", "offsets");
     if ((uintptr_t)a.outPtr & (uintptr_t)(a.outAlign - 1)) return fail(a.outAlign == 8 ? "%s: %s must be 8-byte aligned" : "%s: %s must be 4-byte aligned", a.outName);
     if ((uintptr_t)a.detPtr & 3) return fail("%s: %s must be 4-byte aligned", a.detName);
+    if (a.filter) {
+        const PtQueryFilter& f = *a.filter;
+        if (f.flags & ~PT_FILTER_TMIN) return fail("%s: %s", "unknown filter flags");
+        if ((f.flags & PT_FILTER_TMIN) && !a.filterRays) return fail("%s: %s", "PT_FILTER_TMIN applies to ray queries only");
+        if ((uintptr_t)f.d_prim_bits & 3) return fail("%s: %s must be 4-byte aligned", "filter d_prim_bits");
+        if ((uintptr_t)f.d_query_bits & 3) return fail("%s: %s must be 4-byte aligned", "filter d_query_bits");
+        if ((uintptr_t)f.d_skip_prim & 3) return fail("%s: %s must be 4-byte aligned", "filter d_skip_prim");
+    }
     return PT_OK;
 }
 

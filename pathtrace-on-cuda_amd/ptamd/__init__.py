@@ -8,6 +8,7 @@ torch.distributed only.
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -96,6 +97,13 @@ NEAREST_CLOSEST, NEAREST_ANY = 0, 1
 NEAREST_KMAX = 32      # PT_NEAREST_KMAX: the most slots per point of pt_nearest_k
 RAY_HITS_KMAX = 32     # PT_RAY_HITS_KMAX: the most slots per ray of pt_trace_rays_k
 HITS_FRONT, HITS_BOTH_SIDES = 0, 1
+FILTER_TMIN = 1       # PT_FILTER_TMIN: a ray's 7th float is its near bound
+
+
+class PtQueryFilter(C.Structure):
+    _fields_ = [("d_prim_bits", C.c_void_p), ("d_query_bits", C.c_void_p), ("d_skip_prim", C.c_void_p), ("bits", C.c_uint32), ("flags", C.c_uint32)]
+
+
 AOV_FLOATS = 8        # floats per pixel of pt_render_aov: albedo.rgb | normal.xyz | depth | coverage
 
 _lib = None
@@ -237,6 +245,15 @@ API = [
     ("pt_within_radius_list", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("pt_trace_rays_list_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P]),
     ("pt_within_radius_list_host", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("pt_query_filter_default", None, [C.POINTER(PtQueryFilter)]),
+    ("pt_trace_rays_f", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(PtQueryFilter), _P, _P, _P]),
+    ("pt_trace_rays_k_f", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(PtQueryFilter), _P, _P, _P]),
+    ("pt_count_hits_f", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(PtQueryFilter), _P, _P]),
+    ("pt_trace_rays_list_f", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(PtQueryFilter), _P, _P, _P]),
+    ("pt_closest_points_f", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(PtQueryFilter), _P, _P, _P]),
+    ("pt_nearest_k_f", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(PtQueryFilter), _P, _P, _P]),
+    ("pt_count_within_f", C.c_int, [_P, _P, C.c_int64, C.POINTER(PtQueryFilter), _P, _P]),
+    ("pt_within_radius_list_f", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(PtQueryFilter), _P, _P, _P]),
     ("pt_rays_floats", C.c_int64, [C.c_int64]),
     ("pt_rays_work_bytes", C.c_int64, [C.POINTER(PtParams), C.c_int64]),
     ("pt_render_rays", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
@@ -255,6 +272,17 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise PtError(f"{LIB_PATH} is missing: build it with `make -C {PKG_ROOT}` "
                           "(there is no CPU fallback for the render path)")
+        # torch, where it is installed, has to meet the HIP runtime first.  Its libtorch_hip.so asks for "libamdhip64.so" by that bare
+        # name, with an RPATH to the copy torch ships, whose SONAME is libamdhip64.so.N; libptamd.so asks for libamdhip64.so.N.  With
+        # torch loaded first the loader satisfies libptamd.so by SONAME from torch's copy: one runtime in the process.  The other way
+        # round ROCm's copy is loaded, the bare name matches no loaded SONAME, torch opens its own copy beside it, and that second
+        # runtime finds no GPU ("No HIP GPUs are available") — in every call that stages numpy through torch (QueryFilter,
+        # list_offsets) after a Scene exists.  Importing torch initialises no device.
+        if "torch" not in sys.modules:
+            try:
+                import torch      # noqa: F401
+            except ImportError:
+                pass              # no torch: the C-ABI paths need none, and the ones that do say so when they import it
         l = C.CDLL(LIB_PATH)
         for name, res, args in API:
             fn = getattr(l, name)       # AttributeError if the library does not export it
@@ -347,6 +375,70 @@ def _csr(who, a, name, width, dtype, det_width, detail, stream_ptr, device, devi
         device_list(C.c_void_p(a.data_ptr()), n, C.c_void_p(off.data_ptr()), total, C.c_void_p(res.data_ptr()),
                     C.c_void_p(det.data_ptr()) if detail else None)
     return (off,) + _records(res, det)
+
+
+class QueryFilter:
+    """Which primitives a query may answer with (include/pt_api.h: "Query filters"): the `filter=` argument of Scene.trace_rays,
+    trace_rays_k, count_hits, trace_rays_all, closest_points, nearest_k, count_within and within_radius.
+      prim_bits   one 32-bit word per primitive (triangles in the order of `tris`, then spheres); None: every bit set
+      query_bits  one word per ray / point; None: `bits` for every query
+      skip        one int32 per ray / point, the primitive that query ignores (-1, or anything that is no primitive: none); None: none
+      tmin        True (ray queries only): the 7th float of each ray is its near bound; a hit at exactly tmin is kept
+    A primitive is a member for query i iff (prim_bits[prim] & query_bits[i]) != 0 and prim != skip[i].  The arrays are contiguous 1-D
+    torch tensors (int32 or uint32) on the scene's device, used in place, or numpy arrays (uint32 / int32), which are uploaded with
+    torch to the scene's device at their first use and kept.  The filter keeps its arrays alive; they must not change while a query
+    that reads them is in flight."""
+
+    def __init__(self, prim_bits=None, bits=0xFFFFFFFF, query_bits=None, skip=None, tmin=False):
+        bits = int(bits)
+        if not 0 <= bits <= 0xFFFFFFFF:
+            raise PtError(f"QueryFilter: bits = {bits:#x} is not a 32-bit word")
+        self.bits, self.tmin = bits, bool(tmin)
+        self._given = {"prim_bits": self._checked("prim_bits", prim_bits, ("uint32", "int32")),
+                       "query_bits": self._checked("query_bits", query_bits, ("uint32", "int32")),
+                       "skip": self._checked("skip", skip, ("int32",))}
+        self._on = {}      # device -> {name: torch tensor there}
+
+    @staticmethod
+    def _checked(name, a, dtypes):
+        if a is None:
+            return None
+        if isinstance(a, np.ndarray):
+            if a.ndim != 1 or a.dtype.name not in dtypes:
+                raise PtError(f"QueryFilter: {name} must be a 1-D array of {' or '.join(dtypes)}, got {a.dtype} {a.shape}")
+            return np.ascontiguousarray(a)
+        if not (hasattr(a, "data_ptr") and hasattr(a, "is_contiguous")):
+            raise PtError(f"QueryFilter: {name} must be a torch tensor or a numpy array")
+        if str(a.dtype).replace("torch.", "") not in dtypes or a.dim() != 1 or not a.is_contiguous():
+            raise PtError(f"QueryFilter: {name} must be a contiguous 1-D tensor of {' or '.join(dtypes)}, got {a.dtype} {tuple(a.shape)}")
+        return a
+
+    def _checks(self, who, device, n, n_prims, rays):
+        """This filter's checks for n queries of the scene on `device` with n_prims primitives: no device call."""
+        if self.tmin and not rays:
+            raise PtError(f"{who}: tmin applies to ray queries only")
+        for name, want in (("prim_bits", n_prims), ("query_bits", n), ("skip", n)):      # every check before the first upload
+            a = self._given[name]
+            if a is None:
+                continue
+            if a.shape[0] != want:
+                raise PtError(f"{who}: filter {name} has {a.shape[0]} entries, want {want}")
+            if not isinstance(a, np.ndarray) and (a.device.type != "cuda" or a.device.index != device):
+                raise PtError(f"{who}: filter {name} is on {a.device}, the scene is on device {device}")
+
+    def _bind(self, who, device, n, n_prims, rays):
+        """The PtQueryFilter of this filter, after _checks of the same arguments; uploads what is numpy."""
+        self._checks(who, device, n, n_prims, rays)
+        on = self._on.setdefault(device, {})
+        ptr = {}
+        for name, a in self._given.items():
+            if isinstance(a, np.ndarray):
+                if name not in on:
+                    import torch
+                    on[name] = torch.from_numpy(a.view(np.int32)).to(f"cuda:{device}")
+                a = on[name]
+            ptr[name] = (a.data_ptr() or None) if a is not None else None
+        return PtQueryFilter(ptr["prim_bits"], ptr["query_bits"], ptr["skip"], self.bits, FILTER_TMIN if self.tmin else 0)
 
 
 def _rebuild_params(depth_budget, large_fraction):
@@ -456,6 +548,7 @@ class Scene:
         spheres = np.ascontiguousarray(spheres, np.float32).reshape(-1, SPHERE_FLOATS)
         self.device = device
         self.n_tris = tris.shape[0]
+        self.n_spheres = spheres.shape[0]
         self._h = C.c_void_p()
         _check(lib().pt_scene_create(_ptr(nodes), nodes.shape[0], _ptr(tris), tris.shape[0],
                                      _ptr(spheres) if spheres.shape[0] else None, spheres.shape[0], device, C.byref(self._h)),
@@ -900,16 +993,52 @@ class Scene:
         _check(lib().pt_scene_tree_info(self._h, C.byref(info)), "pt_scene_tree_info")
         return {name: int(getattr(info, name)) for name, _ in PtTreeInfo._fields_}
 
-    def trace_rays(self, rays, any_hit=False, surface=False, stream_ptr=0):
+    def _filtered(self, who, a, rays, filter, run, unfiltered):
+        """A query method's path with filter=: `a` (rays if `rays` else points; numpy is moved to the scene's device with torch, a torch
+        tensor is used in place) and the filter's struct go to run(tensor, n, byref(struct)), the device path over the _f entry point,
+        which returns torch tensors; numpy input gets numpy arrays back, after a wait.  An empty numpy input has nothing to filter and
+        no device address: after the filter's checks it takes unfiltered(), the method's own numpy path, which returns the empty arrays."""
+        if not isinstance(filter, QueryFilter):
+            raise PtError(f"{who}: filter must be a ptamd.QueryFilter")
+        host = isinstance(a, np.ndarray)
+        if host:
+            x, n = _host_rows(who, a, "rays" if rays else "points", 8 if rays else 4)
+        else:
+            n = (_device_rays if rays else _device_points)(who, a, self.device)
+        if host and n == 0:
+            filter._checks(who, self.device, n, self.n_tris + self.n_spheres, rays)
+            return unfiltered()
+        fs = filter._bind(who, self.device, n, self.n_tris + self.n_spheres, rays)
+        import torch
+        if host:
+            a = torch.from_numpy(x).to(f"cuda:{self.device}")
+            torch.cuda.synchronize(self.device)      # the uploads, whatever stream the query goes to
+        out = run(a, n, C.byref(fs))
+        if not host:
+            return out
+        torch.cuda.synchronize(self.device)
+        return tuple(np.ascontiguousarray(o.cpu().numpy()) for o in out) if isinstance(out, tuple) else out.cpu().numpy()
+
+    def trace_rays(self, rays, any_hit=False, surface=False, stream_ptr=0, filter=None):
         """Cast the caller's rays (include/pt_api.h: pt_trace_rays).  rays: (n, 8) float32 RAY8 records, org.xyz dir.xyz 0 tmax.
         Returns (t, prim) — float32 and int32 of length n, a miss is (0, -1) — and, with surface=True (closest hit only), the (n, 29)
         HIT records of raycast() as a third item.  any_hit=True: prim >= 0 iff the closest-hit query hits; which hit is unspecified.
         A torch float32 tensor on the scene's device is used in place (data_ptr()): the query is enqueued on stream_ptr, the results
         are torch tensors on that device, valid once the stream has passed the query, and `rays` must stay alive until then.
-        A numpy array goes through pt_trace_rays_host (synchronous) and returns numpy arrays."""
+        A numpy array goes through pt_trace_rays_host (synchronous) and returns numpy arrays.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
         if any_hit and surface:
             raise PtError("trace_rays: an any-hit query has no surface record")
         mode = QUERY_ANY if any_hit else QUERY_CLOSEST
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                hits = torch.empty((n, 2), dtype=torch.int32, device=d.device)
+                surf = torch.empty((n, 29), dtype=torch.float32, device=d.device) if surface else None
+                _check(lib().pt_trace_rays_f(self._h, C.c_void_p(d.data_ptr()), n, mode, f, C.c_void_p(hits.data_ptr()),
+                                             C.c_void_p(surf.data_ptr()) if surface else None, C.c_void_p(stream_ptr)), "pt_trace_rays_f")
+                return _records(hits, surf)
+            return self._filtered("trace_rays", rays, True, filter, run, lambda: self.trace_rays(rays, any_hit, surface, stream_ptr))
         if isinstance(rays, np.ndarray):
             r, n = _host_rows("trace_rays", rays, "rays", 8)
             hits, surf = _host_out((n,), HIT_DTYPE, surface, 29)
@@ -923,17 +1052,27 @@ class Scene:
                                    C.c_void_p(surf.data_ptr()) if surface else None, C.c_void_p(stream_ptr)), "pt_trace_rays")
         return _records(hits, surf)
 
-    def closest_points(self, points, any_within=False, detail=False, stream_ptr=0):
+    def closest_points(self, points, any_within=False, detail=False, stream_ptr=0, filter=None):
         """The primitive nearest to each of the caller's points (include/pt_api.h: pt_closest_points).  points: (n, 4) float32 POINT4
         records, p.xyz radius (>= 0, inf allowed).  Returns (dist2, prim) — float32 and int32 of length n, a miss is (0, -1) — and, with
         detail=True (closest only), the (n, 8) detail records c.xyz v w side feature 0 as a third item.  any_within=True: prim >= 0 iff
         the closest query finds something within the radius; which primitive is unspecified.
         A torch float32 tensor on the scene's device is used in place (data_ptr()): the query is enqueued on stream_ptr, the results
         are torch tensors on that device, valid once the stream has passed the query, and `points` must stay alive until then.
-        A numpy array goes through pt_closest_points_host (synchronous) and returns numpy arrays."""
+        A numpy array goes through pt_closest_points_host (synchronous) and returns numpy arrays.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
         if any_within and detail:
             raise PtError("closest_points: an any-within query has no detail record")
         mode = NEAREST_ANY if any_within else NEAREST_CLOSEST
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                res = torch.empty((n, 2), dtype=torch.int32, device=d.device)
+                det = torch.empty((n, 8), dtype=torch.float32, device=d.device) if detail else None
+                _check(lib().pt_closest_points_f(self._h, C.c_void_p(d.data_ptr()), n, mode, f, C.c_void_p(res.data_ptr()),
+                                                 C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_closest_points_f")
+                return _records(res, det)
+            return self._filtered("closest_points", points, False, filter, run, lambda: self.closest_points(points, any_within, detail, stream_ptr))
         if isinstance(points, np.ndarray):
             p, n = _host_rows("closest_points", points, "points", 4)
             res, det = _host_out((n,), NEAREST_DTYPE, detail, 8)
@@ -947,17 +1086,27 @@ class Scene:
                                        C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_closest_points")
         return _records(res, det)
 
-    def nearest_k(self, points, k, detail=False, stream_ptr=0):
+    def nearest_k(self, points, k, detail=False, stream_ptr=0, filter=None):
         """The k nearest primitives within each point's radius, sorted (include/pt_api.h: pt_nearest_k).  points: (n, 4) float32 POINT4
         records, p.xyz radius (>= 0, inf allowed); 1 <= k <= NEAREST_KMAX.  Returns (dist2, prim) — float32 and int32 of shape (n, k),
         nearest first, among equal dist2 the larger prim first, the slots past the last candidate (0, -1) — and, with detail=True, the
         (n, k, 8) detail records c.xyz v w side feature 0 as a third item (zeros in a miss slot).
         A torch float32 tensor on the scene's device is used in place (data_ptr()): the query is enqueued on stream_ptr, the results
         are torch tensors on that device, valid once the stream has passed the query, and `points` must stay alive until then.
-        A numpy array goes through pt_nearest_k_host (synchronous) and returns numpy arrays."""
+        A numpy array goes through pt_nearest_k_host (synchronous) and returns numpy arrays.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
         k = int(k)
         if not 1 <= k <= NEAREST_KMAX:
             raise PtError(f"nearest_k: k = {k}, want 1 .. {NEAREST_KMAX}")
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                res = torch.empty((n, k, 2), dtype=torch.int32, device=d.device)
+                det = torch.empty((n, k, 8), dtype=torch.float32, device=d.device) if detail else None
+                _check(lib().pt_nearest_k_f(self._h, C.c_void_p(d.data_ptr()), n, k, f, C.c_void_p(res.data_ptr()),
+                                            C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_nearest_k_f")
+                return _records(res, det)
+            return self._filtered("nearest_k", points, False, filter, run, lambda: self.nearest_k(points, k, detail, stream_ptr))
         if isinstance(points, np.ndarray):
             p, n = _host_rows("nearest_k", points, "points", 4)
             res, det = _host_out((n, k), NEAREST_DTYPE, detail, 8)
@@ -971,10 +1120,19 @@ class Scene:
                                   C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_nearest_k")
         return _records(res, det)
 
-    def count_within(self, points, stream_ptr=0):
+    def count_within(self, points, stream_ptr=0, filter=None):
         """How many primitives lie within each point's radius (include/pt_api.h: pt_count_within), uncapped: (n,) int32.  points as in
         nearest_k; an infinite radius counts every primitive, by walking the whole tree.  A torch tensor on the scene's device is
-        used in place and the count is a torch tensor there, in stream order; a numpy array goes through pt_count_within_host."""
+        used in place and the count is a torch tensor there, in stream order; a numpy array goes through pt_count_within_host.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                cnt = torch.empty(n, dtype=torch.int32, device=d.device)
+                _check(lib().pt_count_within_f(self._h, C.c_void_p(d.data_ptr()), n, f, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)),
+                       "pt_count_within_f")
+                return cnt
+            return self._filtered("count_within", points, False, filter, run, lambda: self.count_within(points, stream_ptr))
         if isinstance(points, np.ndarray):
             p, n = _host_rows("count_within", points, "points", 4)
             cnt = np.zeros(n, np.int32)
@@ -986,7 +1144,7 @@ class Scene:
         _check(lib().pt_count_within(self._h, C.c_void_p(points.data_ptr()), n, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_count_within")
         return cnt
 
-    def trace_rays_k(self, rays, k, both_sides=False, detail=False, stream_ptr=0):
+    def trace_rays_k(self, rays, k, both_sides=False, detail=False, stream_ptr=0, filter=None):
         """The first k hits along each ray, sorted (include/pt_api.h: pt_trace_rays_k).  rays: (n, 8) float32 RAY8 records, org.xyz
         dir.xyz 0 tmax, as trace_rays takes them; 1 <= k <= RAY_HITS_KMAX.  Returns (t, prim) — float32 and int32 of shape (n, k), nearest
         first, among equal t the larger prim first, the slots past the last hit (0, -1) — and, with detail=True, the (n, k, 4) detail
@@ -994,11 +1152,21 @@ class Scene:
         count too (HITS_BOTH_SIDES); with False column 0 is trace_rays' closest hit.
         A torch float32 tensor on the scene's device is used in place (data_ptr()): the query is enqueued on stream_ptr, the results
         are torch tensors on that device, valid once the stream has passed the query, and `rays` must stay alive until then.
-        A numpy array goes through pt_trace_rays_k_host (synchronous) and returns numpy arrays."""
+        A numpy array goes through pt_trace_rays_k_host (synchronous) and returns numpy arrays.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
         k = int(k)
         if not 1 <= k <= RAY_HITS_KMAX:
             raise PtError(f"trace_rays_k: k = {k}, want 1 .. {RAY_HITS_KMAX}")
         flags = HITS_BOTH_SIDES if both_sides else HITS_FRONT
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                hits = torch.empty((n, k, 2), dtype=torch.int32, device=d.device)
+                det = torch.empty((n, k, 4), dtype=torch.float32, device=d.device) if detail else None
+                _check(lib().pt_trace_rays_k_f(self._h, C.c_void_p(d.data_ptr()), n, k, flags, f, C.c_void_p(hits.data_ptr()),
+                                               C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_trace_rays_k_f")
+                return _records(hits, det)
+            return self._filtered("trace_rays_k", rays, True, filter, run, lambda: self.trace_rays_k(rays, k, both_sides, detail, stream_ptr))
         if isinstance(rays, np.ndarray):
             r, n = _host_rows("trace_rays_k", rays, "rays", 8)
             hits, det = _host_out((n, k), HIT_DTYPE, detail, 4)
@@ -1012,11 +1180,20 @@ class Scene:
                                      C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_trace_rays_k")
         return _records(hits, det)
 
-    def count_hits(self, rays, both_sides=False, stream_ptr=0):
+    def count_hits(self, rays, both_sides=False, stream_ptr=0, filter=None):
         """How many hits each ray has in [0, tmax] (include/pt_api.h: pt_count_hits), uncapped: (n,) int32.  rays and both_sides as in
         trace_rays_k.  A torch tensor on the scene's device is used in place and the count is a torch tensor there, in stream order; a
-        numpy array goes through pt_count_hits_host."""
+        numpy array goes through pt_count_hits_host.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
         flags = HITS_BOTH_SIDES if both_sides else HITS_FRONT
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                cnt = torch.empty(n, dtype=torch.int32, device=d.device)
+                _check(lib().pt_count_hits_f(self._h, C.c_void_p(d.data_ptr()), n, flags, f, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)),
+                       "pt_count_hits_f")
+                return cnt
+            return self._filtered("count_hits", rays, True, filter, run, lambda: self.count_hits(rays, both_sides, stream_ptr))
         if isinstance(rays, np.ndarray):
             r, n = _host_rows("count_hits", rays, "rays", 8)
             cnt = np.zeros(n, np.int32)
@@ -1028,7 +1205,7 @@ class Scene:
         _check(lib().pt_count_hits(self._h, C.c_void_p(rays.data_ptr()), n, flags, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_count_hits")
         return cnt
 
-    def trace_rays_all(self, rays, both_sides=False, detail=False, stream_ptr=0):
+    def trace_rays_all(self, rays, both_sides=False, detail=False, stream_ptr=0, filter=None):
         """Every hit along each ray, sorted, in CSR form (include/pt_api.h: pt_trace_rays_list).  rays and both_sides as in trace_rays_k.
         Returns (offsets, t, prim) — int64 of shape (n + 1,), the hits of ray i at [offsets[i], offsets[i + 1]) of the float32 and int32
         arrays t and prim, nearest first, among equal t the larger prim first — and, with detail=True, the (total, 4) detail records
@@ -1036,8 +1213,16 @@ class Scene:
         A torch float32 tensor on the scene's device runs in place on stream_ptr: count_hits, list_offsets, one 8-byte read-back of the
         total — which WAITS for the stream to pass the scan —, the allocation of the records, the fill.  The records are torch tensors on
         that device, valid once the stream has passed the fill, and `rays` must stay alive until then.  A numpy array goes through
-        pt_trace_rays_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays."""
+        pt_trace_rays_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
         flags = HITS_BOTH_SIDES if both_sides else HITS_FRONT
+        if filter is not None:
+            def run(d, n, f):
+                return _csr("trace_rays_all", d, "rays", 8, HIT_DTYPE, 4, detail, stream_ptr, self.device, _device_rays,
+                            lambda t: self.count_hits(t, both_sides=both_sides, stream_ptr=stream_ptr, filter=filter), None,
+                            lambda r, n, off, cap, out, det: _check(lib().pt_trace_rays_list_f(self._h, r, n, flags, off, cap, f, out, det,
+                                                                                               C.c_void_p(stream_ptr)), "pt_trace_rays_list_f"))
+            return self._filtered("trace_rays_all", rays, True, filter, run, lambda: self.trace_rays_all(rays, both_sides, detail, stream_ptr))
         return _csr("trace_rays_all", rays, "rays", 8, HIT_DTYPE, 4, detail, stream_ptr, self.device, _device_rays,
                          lambda d: self.count_hits(d, both_sides=both_sides, stream_ptr=stream_ptr),
                          lambda r, n, off, cap, out, det: _check(lib().pt_trace_rays_list_host(self._h, r, n, flags, off, cap, out, det),
@@ -1045,7 +1230,7 @@ class Scene:
                          lambda r, n, off, cap, out, det: _check(lib().pt_trace_rays_list(self._h, r, n, flags, off, cap, out, det,
                                                                                           C.c_void_p(stream_ptr)), "pt_trace_rays_list"))
 
-    def within_radius(self, points, detail=False, stream_ptr=0):
+    def within_radius(self, points, detail=False, stream_ptr=0, filter=None):
         """Every primitive within each point's radius, sorted, in CSR form (include/pt_api.h: pt_within_radius_list).  points as in
         nearest_k; an infinite radius lists every primitive.  Returns (offsets, dist2, prim) — int64 of shape (n + 1,), the members of
         point i at [offsets[i], offsets[i + 1]) of the float32 and int32 arrays dist2 and prim, nearest first, among equal dist2 the larger
@@ -1053,7 +1238,15 @@ class Scene:
         A torch float32 tensor on the scene's device runs in place on stream_ptr: count_within, list_offsets, one 8-byte read-back of the
         total — which WAITS for the stream to pass the scan —, the allocation of the records, the fill.  The records are torch tensors on
         that device, valid once the stream has passed the fill, and `points` must stay alive until then.  A numpy array goes through
-        pt_within_radius_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays."""
+        pt_within_radius_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
+        if filter is not None:
+            def run(d, n, f):
+                return _csr("within_radius", d, "points", 4, NEAREST_DTYPE, 8, detail, stream_ptr, self.device, _device_points,
+                            lambda t: self.count_within(t, stream_ptr=stream_ptr, filter=filter), None,
+                            lambda p, n, off, cap, out, det: _check(lib().pt_within_radius_list_f(self._h, p, n, off, cap, f, out, det,
+                                                                                                  C.c_void_p(stream_ptr)), "pt_within_radius_list_f"))
+            return self._filtered("within_radius", points, False, filter, run, lambda: self.within_radius(points, detail, stream_ptr))
         return _csr("within_radius", points, "points", 4, NEAREST_DTYPE, 8, detail, stream_ptr, self.device, _device_points,
                          lambda d: self.count_within(d, stream_ptr=stream_ptr),
                          lambda p, n, off, cap, out, det: _check(lib().pt_within_radius_list_host(self._h, p, n, off, cap, out, det),

@@ -1145,6 +1145,102 @@ PT_API int  pt_within_radius_list_f(PtScene* s, const float* d_points4, int64_t 
                                     const PtQueryFilter* filter, PtNearest* d_out /* cap */, float* d_detail8 /* cap * 8, may be NULL */, void* hip_stream);
 
 /* ----------------------------------------------------------------------------------
+ * Box queries (new: the reference has no such query).  Opt-in: every call above is as it was.
+ * The third shape of a BVH query set: after what lies along a RAY and what lies near a POINT, what lies in a REGION, an axis-aligned
+ * box of the caller's (csrc/pt_box.hip, csrc/pt_box.h): voxelising the resident (and moving) scene into an occupancy grid, selecting
+ * every triangle in a box or above a plane, the broad phase "does anything reach into this cell".  DESIGN.md section 41.
+ *
+ * Boxes are BOX8 records: lo.xyz | reserved | hi.xyz | reserved, 32 bytes, 16-byte aligned; the two reserved floats are not read.
+ *   Primitives are numbered as in pt_trace_rays: triangles first, in the order of `tris`, spheres after them.
+ * Arithmetic: IEEE float32, every operation below rounded once and none contracted, in the order written; dot, cross, min, max and
+ *   boxdist2 are those of the section "Closest-point queries".
+ * The class key g(Q, k) of box Q = (lo, hi) and primitive k takes one of three values: 0 = inside, 1 = touching, +inf = no member.
+ *   valid = lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z.  An invalid box has no member: g = +inf for every k.  That covers an inverted
+ *   box and any NaN coordinate (a comparison with NaN is false).  lo == hi on an axis is allowed: a slice, a point.
+ * g(Q, k) for triangle k, V0 E1 E2 as in the closest-point section:  a = V0, ab = E1, ac = E2, b = a + ab, c = a + ac
+ *     1. tlo, thi = component-wise min(min(a, b), c), max(max(a, b), c)      (exactly the box f's last line computes)
+ *     2. unless tlo <= hi && thi >= lo on every axis:  g = +inf
+ *     3. if tlo >= lo && thi <= hi on every axis:  g = 0
+ *     4. if any of the six coordinates of Q is infinite:  g = 1, and step 5 is skipped.  A box bounded on ONE axis only — a half-space,
+ *        a slab — is then answered exactly (a triangle's extent on one axis is an interval).  A box that is bounded on two or three
+ *        axes and infinite elsewhere — a COLUMN, infinite on one axis only; a quadrant — is answered CONSERVATIVELY: a triangle whose
+ *        own box overlaps Q but which passes Q by diagonally is reported as touching.
+ *     5. the separating axes, with bc = ac - ab:
+ *          ctr = (lo + hi) * 0.5;  h = max(hi - ctr, ctr - lo) per axis;  v0 = a - ctr, v1 = b - ctr, v2 = c - ctr
+ *          plane:  n = cross(ab, ac);  d = dot(n, v0);  r = (h.x*|n.x| + h.y*|n.y|) + h.z*|n.z|;  separates when |d| > r
+ *          edges:  for e in the order ab, ac, bc and for axis i in x, y, z, with (j, k) the next two axes cyclically:
+ *                    p_m = v_m[k]*e[j] - v_m[j]*e[k]  for m = 0, 1, 2;   rr = h[j]*|e[k]| + h[k]*|e[j]|
+ *                    separates when min(min(p0, p1), p2) > rr || max(max(p0, p1), p2) < -rr
+ *          g = +inf if any of the ten separates, else 1
+ *   Every comparison is inclusive: touching counts.  A zero-area triangle has n = 0, so its plane never separates: it is judged by
+ *   the boxes and the edge axes.  Step 2 is a FLOOR, as the last line of f is: a member's own box overlaps Q, compared without any
+ *   rounding in between, and every widened box of either tree contains the boxes of the records below it — so
+ *   a walk that culls by the same per-axis overlap test never disagrees with this definition, and the answer is the same bits before
+ *   and after a refit or any rebuild.
+ * g(Q, k) for sphere j (k = number of triangles + j), center c, radius rad; membership refers to the sphere's SURFACE, as
+ *   pt_closest_points measures to the surface:
+ *     if c - rad >= lo && c + rad <= hi on every axis:  g = 0
+ *     else  near2 = boxdist2(c, lo, hi);  far2 = (gx*gx + gy*gy) + gz*gz with g_axis = max(|lo - c|, |hi - c|);  rr = rad * rad
+ *           g = 1 if near2 <= rr && far2 >= rr, else +inf      (a box strictly inside the ball touches no surface)
+ * Members: B(Q) = { k : g(Q, k) <= bound }, bound = 1 for PT_BOX_TOUCHING (flags 0: inside or touching), 0 for PT_BOX_INSIDE (flags 1).
+ *   Order: g ascending — inside first —, among equal g the larger primitive index first: the one order of the lists above.
+ * Overflow: coordinates so large that a product or sum of step 5 overflows float32 leave THAT pair's class unspecified; every prim
+ *   stays in [-1, number of primitives) and every count in [0, number of primitives].
+ * pt_box_count: d_count[i] = |B(Q_i)|.
+ * pt_box_any:   d_out[i].prim >= 0 exactly when pt_box_count of the same box, flags and filter is above 0; the record is then SOME
+ *   member, (g(Q, prim), prim) with its own cls bits; which member is unspecified and may change between versions (the walk stops at
+ *   the first).  No member: the miss record (0, -1).
+ * pt_box_list:  the segment of box i is [b, e) with b = clamp(d_offsets[i], 0, cap) and e = clamp(d_offsets[i + 1], b, cap), as
+ *   pt_trace_rays_list states it: no record outside the segments is written, whatever the offsets hold, never one outside [0, cap).
+ *   With m = e - b:  m >= |B|: slots 0 .. |B| - 1 hold B in order, the later slots the miss record (0, -1);  m < |B|: the m slots hold
+ *   m distinct members of B, sorted among themselves; which members is unspecified.
+ *   The CSR route: pt_box_count, pt_list_offsets, pt_box_list with the SAME flags and filter — the records are then the concatenation
+ *   of every B, bit for bit brute force over the scene's current positions.
+ * filter (may be NULL): a PtQueryFilter exactly as the section above takes it — primitive masks, per-query masks, one skipped
+ *   primitive per box; a filtered-out primitive is no member.  PT_FILTER_TMIN does not apply.  A filter that keeps everything runs the
+ *   unfiltered kernels.
+ * pt_box_count, pt_box_any, pt_box_list: d_boxes8 (16-byte aligned), d_out (8-byte aligned), d_offsets (8-byte aligned) and d_count
+ *   (4-byte aligned) are DEVICE pointers on the scene's device.  Everything is enqueued on `hip_stream`: no host wait, nothing is read
+ *   back, nothing is allocated (pt_scene_device_bytes stays what it was); batches of at most 2^30 boxes go per launch.  A query
+ *   enqueued after pt_scene_update_vertices, pt_scene_rebuild_tree, pt_scene_rebuild_tree_ex or pt_scene_rebuild_tree_opt on the same
+ *   stream sees their result.  The buffers must stay valid until the stream has passed the query.  A query leaves every render state
+ *   alone: frames, pt_last_iterations, pt_last_counters, pt_last_render_ms.  Concurrency: ONE query, update or render at a time per
+ *   scene.
+ * pt_box_count_host, pt_box_any_host, pt_box_list_host: the same on HOST arrays, without a filter (as the section above rules for
+ *   _host variants): upload, query on the NULL stream, wait and download.  pt_box_list_host follows pt_within_radius_list_host:
+ *   h_offsets (n + 1) is always written; with h_out NULL the call stops there (the sizing call); with cap < h_offsets[n] it returns
+ *   PT_ERR_INVALID, the offsets written.
+ * Argument checks, in the order of every query: NULL scene / boxes / offsets / out / count, n < 0, cap < 0, unknown flags, then the
+ *   alignments, then the filter's (unknown filter flags, PT_FILTER_TMIN, a misaligned filter array) return PT_ERR_INVALID before any
+ *   HIP call, no pointer dereferenced, the message naming the entry point.  n = 0 returns PT_OK without a HIP call.
+ * The walk ends whatever the floats are, by the argument of quad_step (csrc/pt_trace.h): depth-first over a finite tree, its stack
+ *   bounded by the depth of the tree.
+ * Cost: a box's cost is the number of tree nodes its box overlaps plus one key per triangle below an
+ *   overlapping leaf; every lane walks alone, so one box that holds thousands of primitives holds its wave for that long — the
+ *   caller's cost, as an infinite radius is.  A box query is the right call when the region IS a box (a voxel, a cell, a selection
+ *   rectangle, a half-space): pt_count_within on the bounding ball over-reports by the ball's corners, overlaps more of the tree and
+ *   needs a host pass to tell; when the region is a ball, pt_count_within is.  Measured on an MI355X (69,576 triangles, 2 M boxes): the
+ *   voxels of a 128^3 grid over the scene, 95 % of them empty, count in 0.52 ms (pt_count_within on their bounding balls: 0.68 ms, and
+ *   1.65 times as many primitives reported), any in 0.12 ms, count + offsets + fill in 1.3 ms; voxel-sized boxes ON the surface, 21
+ *   members each, count in 3.7 ms, any in 0.30 ms, count + offsets + fill (45 M records) in 12.4 ms.
+ * Out of scope: oriented boxes, frusta and general convex regions; detail records per member; a wave-cooperative walk for boxes that
+ *   hold thousands of members; node-level mask culling; _host variants with filters; a multi-GPU split; a CLI option.
+ * -------------------------------------------------------------------------------- */
+typedef struct PtBoxMember { float cls; int32_t prim; } PtBoxMember;   /* 8 bytes; a miss is (0, -1) */
+#define PT_BOX_TOUCHING 0
+#define PT_BOX_INSIDE   1
+PT_API int  pt_box_count(PtScene* s, const float* d_boxes8, int64_t n, int32_t flags, const PtQueryFilter* filter /* may be NULL */,
+                         int32_t* d_count, void* hip_stream);
+PT_API int  pt_box_any(PtScene* s, const float* d_boxes8, int64_t n, int32_t flags, const PtQueryFilter* filter /* may be NULL */,
+                       PtBoxMember* d_out /* n */, void* hip_stream);
+PT_API int  pt_box_list(PtScene* s, const float* d_boxes8, int64_t n, int32_t flags, const int64_t* d_offsets /* n + 1 */, int64_t cap,
+                        const PtQueryFilter* filter /* may be NULL */, PtBoxMember* d_out /* cap */, void* hip_stream);
+PT_API int  pt_box_count_host(PtScene* s, const float* h_boxes8, int64_t n, int32_t flags, int32_t* h_count);
+PT_API int  pt_box_any_host(PtScene* s, const float* h_boxes8, int64_t n, int32_t flags, PtBoxMember* h_out);
+PT_API int  pt_box_list_host(PtScene* s, const float* h_boxes8, int64_t n, int32_t flags, int64_t* h_offsets /* n + 1, written */, int64_t cap,
+                             PtBoxMember* h_out /* may be NULL */);
+
+/* ----------------------------------------------------------------------------------
  * Radiance along the caller's own rays (new: the reference reaches its integrator through a pinhole camera only).
  * Opt-in: every call above is as it was.  pt_trace_rays opened the geometry of an uploaded scene to the caller's rays; this opens
  * the light transport: a panorama, fisheye, orthographic or thin-lens camera, a light probe at a point, a lightmap texel, the

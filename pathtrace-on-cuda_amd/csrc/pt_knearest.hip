@@ -22,18 +22,7 @@
 
 namespace ptd {
 
-// The list of the K nearest: pt_lists.h's SlotList<false> (f's bits order as ints).  The count of C(p): the bound stays r2.
-// counts(): its acceptance, and the fill's for a long segment (pt_lists.h: SlotSeg).
-struct KCount {
-    static constexpr bool kOrdered = false;     // every child within r2 is visited whatever the order
-    static constexpr bool kStops = false;
-    int cnt;
-    float bound;
-    PT_DEV static bool counts(float f, float bound) { return f <= bound; }
-    PT_DEV void offer(float f, int) { cnt += counts(f, bound) ? 1 : 0; }
-    PT_DEV bool wants(float f, int) const { return counts(f, bound); }      // the two halves of offer(), for pt_lists.h's Filtered
-    PT_DEV void take(float, int) { cnt++; }
-};
+// The list of the K nearest: pt_lists.h's SlotList<false> (f's bits order as ints).  The count of C(p): pt_lists.h's KCount, the bound r2.
 
 // KC: the capacity class of the list (pt_scene.h: pt_kc_dispatch).  The wave's 64 points own the 64 * k consecutive records from
 // out[blockIdx.x * 64 * k]; every lane pads its list with miss records and the wave copies the block

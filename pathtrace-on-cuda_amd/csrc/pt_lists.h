@@ -101,6 +101,19 @@ struct SlotList {
     }
 };
 
+// The count of the members of a point query's C(p) or a box query's B(Q): the bound stays what it was set to (r2; a box's class bound).
+// counts(): its acceptance, and the fill's for a long segment (SlotSeg).
+struct KCount {
+    static constexpr bool kOrdered = false;     // every child within r2 is visited whatever the order
+    static constexpr bool kStops = false;
+    int cnt;
+    float bound;
+    PT_DEV static bool counts(float f, float bound) { return f <= bound; }
+    PT_DEV void offer(float f, int) { cnt += counts(f, bound) ? 1 : 0; }
+    PT_DEV bool wants(float f, int) const { return counts(f, bound); }      // the two halves of offer(), for pt_lists.h's Filtered
+    PT_DEV void take(float, int) { cnt++; }
+};
+
 // The sink of a list fill.  A lane owns the segment [b, b + m) of the records, seg = &out[b].  m <= kListLds:
 // SlotList itself, over the lane's LDS list with k = m; the list goes out sorted.  m > kListLds: every member is appended to the segment
 // in the order the walk meets it, while fewer than m are stored, with COUNT's acceptance (COUNT::counts(key, bound), the bound staying

@@ -100,6 +100,14 @@ HITS_FRONT, HITS_BOTH_SIDES = 0, 1
 FILTER_TMIN = 1       # PT_FILTER_TMIN: a ray's 7th float is its near bound
 
 
+class PtBoxMember(C.Structure):
+    _fields_ = [("cls", C.c_float), ("prim", C.c_int32)]
+
+
+BOX_DTYPE = np.dtype([("cls", "<f4"), ("prim", "<i4")])      # PtBoxMember as a numpy record: cls 0 = inside, 1 = touching
+BOX_TOUCHING, BOX_INSIDE = 0, 1
+
+
 class PtQueryFilter(C.Structure):
     _fields_ = [("d_prim_bits", C.c_void_p), ("d_query_bits", C.c_void_p), ("d_skip_prim", C.c_void_p), ("bits", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -254,6 +262,12 @@ API = [
     ("pt_nearest_k_f", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(PtQueryFilter), _P, _P, _P]),
     ("pt_count_within_f", C.c_int, [_P, _P, C.c_int64, C.POINTER(PtQueryFilter), _P, _P]),
     ("pt_within_radius_list_f", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(PtQueryFilter), _P, _P, _P]),
+    ("pt_box_count", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(PtQueryFilter), _P, _P]),
+    ("pt_box_any", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(PtQueryFilter), _P, _P]),
+    ("pt_box_list", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(PtQueryFilter), _P, _P]),
+    ("pt_box_count_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
+    ("pt_box_any_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
+    ("pt_box_list_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
     ("pt_rays_floats", C.c_int64, [C.c_int64]),
     ("pt_rays_work_bytes", C.c_int64, [C.POINTER(PtParams), C.c_int64]),
     ("pt_render_rays", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
@@ -321,6 +335,17 @@ def _device_rays(who, rays, device):
     if rays.device.type != "cuda" or rays.device.index != device:
         raise PtError(f"{who}: rays is on {rays.device}, the scene is on device {device}")
     return rays.shape[0]
+
+
+def _device_boxes(who, boxes, device):
+    """The host-side checks of a BOX8 tensor for the scene on `device`; returns n."""
+    if not (hasattr(boxes, "data_ptr") and hasattr(boxes, "is_contiguous")):
+        raise PtError(f"{who}: boxes must be a torch tensor or a numpy array")
+    if str(boxes.dtype) != "torch.float32" or not boxes.is_contiguous() or boxes.dim() != 2 or boxes.shape[1] != 8:
+        raise PtError(f"{who}: boxes must be contiguous float32 of shape (n, 8), got {boxes.dtype} {tuple(boxes.shape)}")
+    if boxes.device.type != "cuda" or boxes.device.index != device:
+        raise PtError(f"{who}: boxes is on {boxes.device}, the scene is on device {device}")
+    return boxes.shape[0]
 
 
 def _host_rows(who, a, name, width):
@@ -439,6 +464,12 @@ class QueryFilter:
                 a = on[name]
             ptr[name] = (a.data_ptr() or None) if a is not None else None
         return PtQueryFilter(ptr["prim_bits"], ptr["query_bits"], ptr["skip"], self.bits, FILTER_TMIN if self.tmin else 0)
+
+    def struct(self, scene, n, rays=False):
+        """The PtQueryFilter of this filter for n queries (rays, else points or boxes) of `scene`, for a caller who passes it to the
+        C-ABI directly (C.byref(...)): checked as the Scene methods check it; numpy arrays are uploaded at their first use.  The filter
+        must outlive the calls that read the struct."""
+        return self._bind("QueryFilter.struct", scene.device, int(n), scene.n_tris + scene.n_spheres, bool(rays))
 
 
 def _rebuild_params(depth_budget, large_fraction):
@@ -993,8 +1024,8 @@ class Scene:
         _check(lib().pt_scene_tree_info(self._h, C.byref(info)), "pt_scene_tree_info")
         return {name: int(getattr(info, name)) for name, _ in PtTreeInfo._fields_}
 
-    def _filtered(self, who, a, rays, filter, run, unfiltered):
-        """A query method's path with filter=: `a` (rays if `rays` else points; numpy is moved to the scene's device with torch, a torch
+    def _filtered(self, who, a, rays, filter, run, unfiltered, boxes=False):
+        """A query method's path with filter=: `a` (rays if `rays`, BOX8 records if `boxes`, else points; numpy is moved to the scene's device with torch, a torch
         tensor is used in place) and the filter's struct go to run(tensor, n, byref(struct)), the device path over the _f entry point,
         which returns torch tensors; numpy input gets numpy arrays back, after a wait.  An empty numpy input has nothing to filter and
         no device address: after the filter's checks it takes unfiltered(), the method's own numpy path, which returns the empty arrays."""
@@ -1002,9 +1033,9 @@ class Scene:
             raise PtError(f"{who}: filter must be a ptamd.QueryFilter")
         host = isinstance(a, np.ndarray)
         if host:
-            x, n = _host_rows(who, a, "rays" if rays else "points", 8 if rays else 4)
+            x, n = _host_rows(who, a, "boxes" if boxes else "rays" if rays else "points", 8 if rays or boxes else 4)
         else:
-            n = (_device_rays if rays else _device_points)(who, a, self.device)
+            n = (_device_boxes if boxes else _device_rays if rays else _device_points)(who, a, self.device)
         if host and n == 0:
             filter._checks(who, self.device, n, self.n_tris + self.n_spheres, rays)
             return unfiltered()
@@ -1254,6 +1285,85 @@ class Scene:
                          lambda p, n, off, cap, out, det: _check(lib().pt_within_radius_list(self._h, p, n, off, cap, out, det,
                                                                                              C.c_void_p(stream_ptr)), "pt_within_radius_list"))
 
+    def box_count(self, boxes, inside=False, stream_ptr=0, filter=None):
+        """How many primitives lie inside or touch each of the caller's axis-aligned boxes (include/pt_api.h: pt_box_count): (n,) int32.
+        boxes: (n, 8) float32 BOX8 records, lo.xyz 0 hi.xyz 0 (grid_boxes makes those of a regular grid).  inside=True: only the
+        primitives wholly inside.  An inverted box or one with a NaN holds nothing.  A torch tensor on the scene's device is used in
+        place and the count is a torch tensor there, in stream order; a numpy array goes through pt_box_count_host.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
+        flags = BOX_INSIDE if inside else BOX_TOUCHING
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                cnt = torch.empty(n, dtype=torch.int32, device=d.device)
+                _check(lib().pt_box_count(self._h, C.c_void_p(d.data_ptr()), n, flags, f, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_box_count")
+                return cnt
+            return self._filtered("box_count", boxes, False, filter, run, lambda: self.box_count(boxes, inside, stream_ptr), boxes=True)
+        if isinstance(boxes, np.ndarray):
+            b, n = _host_rows("box_count", boxes, "boxes", 8)
+            cnt = np.zeros(n, np.int32)
+            _check(lib().pt_box_count_host(self._h, _ptr(b), n, flags, _ptr(cnt)), "pt_box_count_host")
+            return cnt
+        n = _device_boxes("box_count", boxes, self.device)
+        import torch
+        cnt = torch.empty(n, dtype=torch.int32, device=boxes.device)
+        _check(lib().pt_box_count(self._h, C.c_void_p(boxes.data_ptr()), n, flags, None, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_box_count")
+        return cnt
+
+    def box_any(self, boxes, inside=False, stream_ptr=0, filter=None):
+        """Does anything lie inside or touch each box (include/pt_api.h: pt_box_any)?  Returns (cls, prim) — float32 and int32 of length
+        n: prim >= 0 exactly when box_count of the same box is above 0, and then some member with its class, 0 = inside, 1 = touching
+        (which member is unspecified); else the miss (0, -1).  boxes, inside, stream_ptr and filter as in box_count."""
+        flags = BOX_INSIDE if inside else BOX_TOUCHING
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                res = torch.empty((n, 2), dtype=torch.int32, device=d.device)
+                _check(lib().pt_box_any(self._h, C.c_void_p(d.data_ptr()), n, flags, f, C.c_void_p(res.data_ptr()), C.c_void_p(stream_ptr)), "pt_box_any")
+                return _records(res, None)
+            return self._filtered("box_any", boxes, False, filter, run, lambda: self.box_any(boxes, inside, stream_ptr), boxes=True)
+        if isinstance(boxes, np.ndarray):
+            b, n = _host_rows("box_any", boxes, "boxes", 8)
+            res = np.zeros(n, BOX_DTYPE)
+            _check(lib().pt_box_any_host(self._h, _ptr(b), n, flags, _ptr(res)), "pt_box_any_host")
+            return _records(res, None)
+        n = _device_boxes("box_any", boxes, self.device)
+        import torch
+        res = torch.empty((n, 2), dtype=torch.int32, device=boxes.device)      # PtBoxMember: cls's bits | prim
+        _check(lib().pt_box_any(self._h, C.c_void_p(boxes.data_ptr()), n, flags, None, C.c_void_p(res.data_ptr()), C.c_void_p(stream_ptr)), "pt_box_any")
+        return _records(res, None)
+
+    def in_boxes(self, boxes, inside=False, stream_ptr=0, filter=None):
+        """Every primitive inside or touching each box, in CSR form (include/pt_api.h: pt_box_list).  Returns (offsets, cls, prim) — int64
+        of shape (n + 1,), the members of box i at [offsets[i], offsets[i + 1]) of the float32 and int32 arrays cls and prim: the
+        primitives inside (cls 0) first, then the touching ones (cls 1), within a class the larger prim first.  boxes and inside as in
+        box_count.  A torch float32 tensor on the scene's device runs in place on stream_ptr: box_count, list_offsets, one 8-byte
+        read-back of the total — which WAITS for the stream to pass the scan —, the allocation of the records, the fill.  A numpy array
+        goes through pt_box_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
+        flags = BOX_INSIDE if inside else BOX_TOUCHING
+        if filter is not None:
+            def run(d, n, f):
+                return _csr("in_boxes", d, "boxes", 8, BOX_DTYPE, 0, False, stream_ptr, self.device, _device_boxes,
+                            lambda t: self.box_count(t, inside, stream_ptr=stream_ptr, filter=filter), None,
+                            lambda b, n, off, cap, out, det: _check(lib().pt_box_list(self._h, b, n, flags, off, cap, f, out, C.c_void_p(stream_ptr)),
+                                                                    "pt_box_list"))
+            return self._filtered("in_boxes", boxes, False, filter, run, lambda: self.in_boxes(boxes, inside, stream_ptr), boxes=True)
+        return _csr("in_boxes", boxes, "boxes", 8, BOX_DTYPE, 0, False, stream_ptr, self.device, _device_boxes,
+                    lambda d: self.box_count(d, inside, stream_ptr=stream_ptr),
+                    lambda b, n, off, cap, out, det: _check(lib().pt_box_list_host(self._h, b, n, flags, off, cap, out), "pt_box_list_host"),
+                    lambda b, n, off, cap, out, det: _check(lib().pt_box_list(self._h, b, n, flags, off, cap, None, out, C.c_void_p(stream_ptr)),
+                                                            "pt_box_list"))
+
+    def voxelize(self, lo, hi, shape, inside=False, filter=None):
+        """The scene as an occupancy grid: the (nz, ny, nx) int32 counts of box_count over grid_boxes(lo, hi, shape) on the scene's
+        device, a torch tensor there (NULL stream).  Neighbouring voxels share their faces bit for bit and touching counts, so a
+        primitive that touches a shared face counts in BOTH voxels: the counts do not sum to the number of primitives.  inside and
+        filter as in box_count."""
+        boxes = grid_boxes(lo, hi, shape, device=self.device)
+        nx, ny, nz = (int(v) for v in shape)
+        return self.box_count(boxes, inside=inside, filter=filter).view(nz, ny, nx)
+
     def render_rays_device(self, d_rays_ptr, n_rays, prm, d_rgb_ptr, d_work_ptr, d_seed_ptr=0, seed_stride=None, stream_ptr=0):
         """Device-resident radiance along n_rays RAY8 records (raw device pointers: rays_floats(n) floats of output, rays_work_bytes(prm,
         n) bytes of scratch, d_seed_ptr 0 = ray i is seeded with i), enqueued on the given stream; blocks until the render has drained.
@@ -1318,6 +1428,42 @@ class Scene:
         prim = np.zeros(n, np.int32)
         _check(lib().pt_dbg_raycast(self._h, _ptr(rays8), n, _ptr(hits), _ptr(prim)), "pt_dbg_raycast")
         return hits, prim
+
+
+def _grid_edges(lo, hi, shape):
+    """The per-axis edges of grid_boxes: three float32 arrays of n + 1 edges, lo + (hi - lo) * (i / n) in float32, the last one hi."""
+    lo, hi = np.asarray(lo, np.float32).reshape(-1), np.asarray(hi, np.float32).reshape(-1)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all()):
+        raise PtError(f"grid_boxes: lo and hi must be 3 finite floats each with lo <= hi, got {lo} {hi}")
+    try:
+        n = [int(v) for v in shape]
+    except (TypeError, ValueError):
+        raise PtError(f"grid_boxes: shape must be three ints (nx, ny, nz), got {shape!r}")
+    if len(n) != 3 or min(n) < 1 or n[0] * n[1] * n[2] >= 1 << 31:
+        raise PtError(f"grid_boxes: shape must be three ints >= 1 (nx, ny, nz) with fewer than 2^31 voxels, got {shape!r}")
+    edges = []
+    for a in range(3):
+        e = (lo[a] + (hi[a] - lo[a]) * (np.arange(n[a] + 1, dtype=np.float32) / np.float32(n[a]))).astype(np.float32)
+        e[n[a]] = hi[a]
+        edges.append(e)
+    return edges, n
+
+
+def grid_boxes(lo, hi, shape, device=0):
+    """The BOX8 records of the nx * ny * nz voxels of a regular grid over [lo, hi], x fastest (voxel (ix, iy, iz) is row
+    (iz * ny + iy) * nx + ix): an (n, 8) float32 torch tensor on cuda:`device`; device=None: a numpy array.  Each axis's n + 1 edges are
+    computed ONCE in float32, lo + (hi - lo) * (i / n), and the last is set to hi exactly: neighbouring voxels share a face bit for
+    bit, so no primitive falls between two voxels, and one that touches a shared face is a member of both."""
+    (ex, ey, ez), (nx, ny, nz) = _grid_edges(lo, hi, shape)
+    b = np.zeros((nz, ny, nx, 8), np.float32)
+    b[..., 0], b[..., 4] = ex[None, None, :-1], ex[None, None, 1:]
+    b[..., 1], b[..., 5] = ey[None, :-1, None], ey[None, 1:, None]
+    b[..., 2], b[..., 6] = ez[:-1, None, None], ez[1:, None, None]
+    b = b.reshape(-1, 8)
+    if device is None:
+        return b
+    import torch
+    return torch.from_numpy(b).to(f"cuda:{int(device)}")
 
 
 def list_offsets(count, stream_ptr=0):

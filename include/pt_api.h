@@ -1223,7 +1223,7 @@ PT_API int  pt_within_radius_list_f(PtScene* s, const float* d_points4, int64_t 
  *   voxels of a 128^3 grid over the scene, 95 % of them empty, count in 0.52 ms (pt_count_within on their bounding balls: 0.68 ms, and
  *   1.65 times as many primitives reported), any in 0.12 ms, count + offsets + fill in 1.3 ms; voxel-sized boxes ON the surface, 21
  *   members each, count in 3.7 ms, any in 0.30 ms, count + offsets + fill (45 M records) in 12.4 ms.
- * Out of scope: oriented boxes, frusta and general convex regions; detail records per member; a wave-cooperative walk for boxes that
+ * Out of scope: oriented boxes, frusta and general convex regions (the next section); detail records per member; a wave-cooperative walk for boxes that
  *   hold thousands of members; node-level mask culling; _host variants with filters; a multi-GPU split; a CLI option.
  * -------------------------------------------------------------------------------- */
 typedef struct PtBoxMember { float cls; int32_t prim; } PtBoxMember;   /* 8 bytes; a miss is (0, -1) */
@@ -1239,6 +1239,114 @@ PT_API int  pt_box_count_host(PtScene* s, const float* h_boxes8, int64_t n, int3
 PT_API int  pt_box_any_host(PtScene* s, const float* h_boxes8, int64_t n, int32_t flags, PtBoxMember* h_out);
 PT_API int  pt_box_list_host(PtScene* s, const float* h_boxes8, int64_t n, int32_t flags, int64_t* h_offsets /* n + 1, written */, int64_t cap,
                              PtBoxMember* h_out /* may be NULL */);
+
+/* ----------------------------------------------------------------------------------
+ * Convex-region queries (new: the reference has no such query).  Opt-in: every call above is as it was.
+ * The regions a caller who also renders actually has: the frustum of a pixel window of a camera (a marquee selection, view-frustum
+ * culling of the resident, moving scene per camera, per 8 x 8 tile, per view of a batch), an oriented bounding box of a tool, a
+ * vehicle or a sensor, a light's or a portal's pyramid (csrc/pt_convex.hip, csrc/pt_convex.h).  DESIGN.md section 42.
+ *
+ * A region is the intersection of m half-spaces, m = n_planes, ONE value per call in 1 .. PT_CONVEX_MAX_PLANES (8).  Region i reads m
+ *   PLANE4 records n.xyz | d at d_planes4 + (i * m + j) * 4 floats, j = 0 .. m - 1; the array is 16-byte aligned.  A point x is inside
+ *   plane j when s_j(x) <= d_j with  s_j(x) = (n.x*x.x + n.y*x.y) + n.z*x.z.
+ *   Primitives are numbered as in pt_trace_rays: triangles first, in the order of `tris`, spheres after them.
+ * Arithmetic: IEEE float32, every operation below rounded once and none contracted, in the order written.
+ * Normals need not be unit.  A plane (0, 0, 0, d >= 0) is neutral (a region of fewer planes is padded with it), as is d = +inf;
+ *   (0, 0, 0, d < 0) and d = -inf make the region empty.
+ *   valid = every normal component of the region's m planes is finite.  An invalid region has no member: h = +inf for every k.  A NaN d
+ *   needs no rule: s <= NaN is false, so everything is outside.
+ * The class key h(Q, k) of region Q and primitive k takes one of three values: 0 = inside, 1 = touching, +inf = no member.
+ * h(Q, k) for triangle k, V0 E1 E2 as in the closest-point section:  a = V0, b = a + E1, c = a + E2 (the record's own floats, exactly
+ *   as the box section forms them);  in_j(v) = s_j(v) <= d_j
+ *     1. if some j has none of in_j(a), in_j(b), in_j(c):  h = +inf
+ *     2. else if every j has all three:  h = 0
+ *     3. else h = 1
+ * h(Q, k) for sphere j (k = number of triangles + j), center c, radius rad; membership refers to the sphere's SURFACE:
+ *     len_j = sqrtf((n.x*n.x + n.y*n.y) + n.z*n.z);  r_j = rad * len_j;  sc_j = s_j(c)
+ *     1. if some j has !(sc_j - r_j <= d_j):  h = +inf
+ *     2. else if every j has sc_j + r_j <= d_j:  h = 0
+ *     3. else h = 1
+ *   Class 1 is CONSERVATIVE: a triangle that straddles two planes near an edge or a corner of the region, yet passes the region by,
+ *   is reported as touching (no plane of the region separates it; an edge-edge axis would), and a region wholly inside a ball is
+ *   reported as touching that sphere — as the box section's column case over-reports.  Class 0 is exact.  A region of one plane (a
+ *   half-space) or of two parallel planes (a slab) is answered exactly.  DESIGN.md section 42 has the measured share of over-reports.
+ *   Rule 1 is a FLOOR: s_j at the corner of a box that minimises it — per axis lo where n >= 0, hi otherwise — is, in float32 and with
+ *   no slack, at most s_j of every float point of the box, because rounding to nearest is monotone; every widened box of either tree
+ *   contains the boxes of the records below it.  So a walk that culls a node by that corner never disagrees
+ *   with this definition, and the answer is the same bits before and after a refit or any rebuild.
+ * Members: C(Q) = { k : h(Q, k) <= bound }, bound = 1 for PT_CONVEX_TOUCHING (flags 0: inside or touching), 0 for PT_CONVEX_INSIDE
+ *   (flags 1).  Order: h ascending — inside first —, among equal h the larger primitive index first: the one order of the lists above.
+ *   Records are PtBoxMember.
+ * Overflow: coordinates so large that a product or sum overflows float32 leave THAT pair's class unspecified; every prim stays in
+ *   [-1, number of primitives) and every count in [0, number of primitives].
+ * pt_convex_count: d_count[i] = |C(Q_i)|.
+ * pt_convex_any:   d_out[i].prim >= 0 exactly when pt_convex_count of the same region, flags and filter is above 0; the record is then
+ *   SOME member, (h(Q, prim), prim) with its own cls bits; which member is unspecified and may change between versions (the walk stops
+ *   at the first).  No member: the miss record (0, -1).
+ * pt_convex_list:  the segment of region i is [b, e) with b = clamp(d_offsets[i], 0, cap) and e = clamp(d_offsets[i + 1], b, cap), as
+ *   pt_trace_rays_list states it: no record outside the segments is written, whatever the offsets hold, never one outside [0, cap).
+ *   With len = e - b:  len >= |C|: slots 0 .. |C| - 1 hold C in order, the later slots the miss record (0, -1);  len < |C|: the len
+ *   slots hold len distinct members of C, sorted among themselves; which members is unspecified.
+ *   The CSR route: pt_convex_count, pt_list_offsets, pt_convex_list with the SAME n_planes, flags and filter — the records are then the
+ *   concatenation of every C, bit for bit brute force over the scene's current positions.
+ * filter (may be NULL): a PtQueryFilter exactly as the section "Query filters" takes it — primitive masks, per-query masks, one skipped
+ *   primitive per region; a filtered-out primitive is no member.  PT_FILTER_TMIN does not apply.  A filter that keeps everything runs
+ *   the unfiltered kernels.
+ * pt_convex_count, pt_convex_any, pt_convex_list: d_planes4 (16-byte aligned), d_out (8-byte aligned), d_offsets (8-byte aligned) and
+ *   d_count (4-byte aligned) are DEVICE pointers on the scene's device.  Everything is enqueued on `hip_stream`: no host wait, nothing is
+ *   read back, nothing is allocated (pt_scene_device_bytes stays what it was); batches of at most 2^30 regions go per launch.  A query
+ *   enqueued after pt_scene_update_vertices, pt_scene_rebuild_tree, pt_scene_rebuild_tree_ex or pt_scene_rebuild_tree_opt on the same
+ *   stream sees their result.  The buffers must stay valid until the stream has passed the query.  A query leaves every render state
+ *   alone: frames, pt_last_iterations, pt_last_counters, pt_last_render_ms.  Concurrency: ONE query, update or render at a time per
+ *   scene.
+ * pt_convex_count_host, pt_convex_any_host, pt_convex_list_host: the same on HOST arrays, without a filter (as the _host variants of
+ *   the box section): upload, query on the NULL stream, wait and download.  pt_convex_list_host follows pt_box_list_host: h_offsets
+ *   (n + 1) is always written; with h_out NULL the call stops there (the sizing call); with cap < h_offsets[n] it returns
+ *   PT_ERR_INVALID, the offsets written.
+ * Argument checks, in the order of every query: NULL scene / planes / offsets / out / count, n < 0, cap < 0, n_planes outside 1 .. 8,
+ *   unknown flags, then the alignments (planes 16, offsets 8, out 8, count 4), then the filter's (unknown filter flags,
+ *   PT_FILTER_TMIN, a misaligned filter array) return PT_ERR_INVALID before any HIP call, no pointer dereferenced, the message naming
+ *   the entry point.  n = 0 returns PT_OK without a HIP call, but does not excuse a NULL.
+ * The walk ends whatever the floats are, by the argument of quad_step (csrc/pt_trace.h): depth-first over a finite tree, its stack
+ *   bounded by the depth of the tree.
+ * pt_camera_frustum (host only, no HIP call): the six planes of the half-open pixel window [x0, x1) x [y0, y1) of `cam`, in the order
+ *   left, right, top, bottom, near, far, as 24 floats for n_planes = 6.  0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H; the four are floats, so
+ *   that a caller can widen a window by a fraction of a pixel; the sample of pixel (px, py) at offset (u1, u2) is the screen position
+ *   (px + u1, py + u2).  Computed in float64 from the camera's float32 fields and rounded once to float32:
+ *     the direction at screen position (fx, fy) is  F + (2 (fx/(W-1) - 0.5) tx) R + (-2 (fy/(H-1) - 0.5) ty) U  with tx, ty the float32
+ *     half-angle tangents of a render of `cam` (the device's pixel_direction uses the same); a side plane contains cam->pos and the two
+ *     corner directions of its side, its normal (not unit) oriented so that the direction at the window's centre is inside,
+ *     d = n . pos; near is (-F^, -(F^ . pos + near)) and far (F^, F^ . pos + far) with F^ = F / |F|; near < 0 or far = +inf gives the
+ *     neutral plane (0, 0, 0, +inf) in that place.
+ *   Two windows that share a side (x1 of one is x0 of the other, the same y0, y1) get that plane with the same bits up to sign.
+ *   PT_ERR_INVALID: a NULL, a bad window, W or H below 2, a NaN near or far, near > far, a camera field that is not finite, a zero
+ *   forward vector, a degenerate side.
+ * Cost: as a box's — the nodes the region may reach plus one key per triangle below such a leaf —, a node test
+ *   and a key each costing m plane evaluations; every lane walks alone, so one region that holds thousands of primitives holds its
+ *   wave for that long: the whole-frame frustum is a query for one lane, the caller's cost.  Measured on an MI355X (69,576
+ *   triangles): the 32,400 frusta of the 8 x 8 tiles of a 1080p camera count in 2.05 ms, any in 0.14 ms, count + offsets + fill
+ *   (196,147 records) in 4.4 ms; the 2 M voxels of a 128^3 grid as six planes each count in 0.68 ms, where pt_box_count of the same
+ *   boxes takes 0.50 ms and reports 0.69 times as many members (when the region IS an axis-aligned box, pt_box_count is the call);
+ *   2 M voxel-sized oriented boxes on the surface, 25 members each, count in 7.7 ms, any in 1.2 ms, count + offsets + fill (52.5 M
+ *   records) in 22.5 ms.
+ * Out of scope: an exact class 1 (clipping the triangle against the region, or the remaining separating axes); more than 8 planes; a
+ *   per-query plane count; non-convex regions; detail records per member; a wave-cooperative walk for regions that hold thousands of
+ *   members; node-level mask culling; _host variants with filters; a multi-GPU split; a ptrender option.
+ * -------------------------------------------------------------------------------- */
+#define PT_CONVEX_TOUCHING   0
+#define PT_CONVEX_INSIDE     1
+#define PT_CONVEX_MAX_PLANES 8
+PT_API int  pt_convex_count(PtScene* s, const float* d_planes4, int64_t n, int32_t n_planes, int32_t flags, const PtQueryFilter* filter /* may be NULL */,
+                            int32_t* d_count, void* hip_stream);
+PT_API int  pt_convex_any(PtScene* s, const float* d_planes4, int64_t n, int32_t n_planes, int32_t flags, const PtQueryFilter* filter /* may be NULL */,
+                          PtBoxMember* d_out /* n */, void* hip_stream);
+PT_API int  pt_convex_list(PtScene* s, const float* d_planes4, int64_t n, int32_t n_planes, int32_t flags, const int64_t* d_offsets /* n + 1 */,
+                           int64_t cap, const PtQueryFilter* filter /* may be NULL */, PtBoxMember* d_out /* cap */, void* hip_stream);
+PT_API int  pt_convex_count_host(PtScene* s, const float* h_planes4, int64_t n, int32_t n_planes, int32_t flags, int32_t* h_count);
+PT_API int  pt_convex_any_host(PtScene* s, const float* h_planes4, int64_t n, int32_t n_planes, int32_t flags, PtBoxMember* h_out);
+PT_API int  pt_convex_list_host(PtScene* s, const float* h_planes4, int64_t n, int32_t n_planes, int32_t flags, int64_t* h_offsets /* n + 1, written */,
+                                int64_t cap, PtBoxMember* h_out /* may be NULL */);
+PT_API int  pt_camera_frustum(const PtCamera* cam, float x0, float y0, float x1, float y1, float near_dist, float far_dist, float* planes24 /* 24, written */);
 
 /* ----------------------------------------------------------------------------------
  * Radiance along the caller's own rays (new: the reference reaches its integrator through a pinhole camera only).

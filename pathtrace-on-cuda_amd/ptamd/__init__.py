@@ -106,6 +106,8 @@ class PtBoxMember(C.Structure):
 
 BOX_DTYPE = np.dtype([("cls", "<f4"), ("prim", "<i4")])      # PtBoxMember as a numpy record: cls 0 = inside, 1 = touching
 BOX_TOUCHING, BOX_INSIDE = 0, 1
+CONVEX_TOUCHING, CONVEX_INSIDE = 0, 1      # PT_CONVEX_TOUCHING, PT_CONVEX_INSIDE
+CONVEX_MAX_PLANES = 8                      # PT_CONVEX_MAX_PLANES
 
 
 class PtQueryFilter(C.Structure):
@@ -268,6 +270,13 @@ API = [
     ("pt_box_count_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     ("pt_box_any_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     ("pt_box_list_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
+    ("pt_convex_count", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(PtQueryFilter), _P, _P]),
+    ("pt_convex_any", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(PtQueryFilter), _P, _P]),
+    ("pt_convex_list", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(PtQueryFilter), _P, _P]),
+    ("pt_convex_count_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    ("pt_convex_any_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    ("pt_convex_list_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    ("pt_camera_frustum", C.c_int, [C.POINTER(PtCamera), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     ("pt_rays_floats", C.c_int64, [C.c_int64]),
     ("pt_rays_work_bytes", C.c_int64, [C.POINTER(PtParams), C.c_int64]),
     ("pt_render_rays", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
@@ -1024,16 +1033,19 @@ class Scene:
         _check(lib().pt_scene_tree_info(self._h, C.byref(info)), "pt_scene_tree_info")
         return {name: int(getattr(info, name)) for name, _ in PtTreeInfo._fields_}
 
-    def _filtered(self, who, a, rays, filter, run, unfiltered, boxes=False):
+    def _filtered(self, who, a, rays, filter, run, unfiltered, boxes=False, rows=None):
         """A query method's path with filter=: `a` (rays if `rays`, BOX8 records if `boxes`, else points; numpy is moved to the scene's device with torch, a torch
         tensor is used in place) and the filter's struct go to run(tensor, n, byref(struct)), the device path over the _f entry point,
         which returns torch tensors; numpy input gets numpy arrays back, after a wait.  An empty numpy input has nothing to filter and
-        no device address: after the filter's checks it takes unfiltered(), the method's own numpy path, which returns the empty arrays."""
+        no device address: after the filter's checks it takes unfiltered(), the method's own numpy path, which returns the empty arrays.
+        rows = (name, width): `a` is rows of `width` floats that the caller has checked already (the convex regions' planes)."""
         if not isinstance(filter, QueryFilter):
             raise PtError(f"{who}: filter must be a ptamd.QueryFilter")
         host = isinstance(a, np.ndarray)
         if host:
-            x, n = _host_rows(who, a, "boxes" if boxes else "rays" if rays else "points", 8 if rays or boxes else 4)
+            x, n = _host_rows(who, a, *rows) if rows else _host_rows(who, a, "boxes" if boxes else "rays" if rays else "points", 8 if rays or boxes else 4)
+        elif rows:
+            n = a.shape[0]
         else:
             n = (_device_boxes if boxes else _device_rays if rays else _device_points)(who, a, self.device)
         if host and n == 0:
@@ -1364,6 +1376,85 @@ class Scene:
         nx, ny, nz = (int(v) for v in shape)
         return self.box_count(boxes, inside=inside, filter=filter).view(nz, ny, nx)
 
+    def convex_count(self, planes, inside=False, stream_ptr=0, filter=None):
+        """How many primitives lie inside or touch each of the caller's convex regions (include/pt_api.h: pt_convex_count): (n,) int32.
+        planes: (n, m, 4) float32 PLANE4 records n.xyz | d, 1 <= m <= CONVEX_MAX_PLANES, region i the points x with n . x <= d for
+        all m of its planes (frustum_planes, obb_planes and aabb_planes make them; pad a region of fewer planes with (0, 0, 0, 0)).
+        inside=True: only the primitives wholly inside.  A region with a NaN or an infinite normal holds nothing.  A torch tensor on
+        the scene's device is used in place and the count is a torch tensor there, in stream order; a numpy array goes through
+        pt_convex_count_host.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
+        flags = CONVEX_INSIDE if inside else CONVEX_TOUCHING
+        x, n, m = _convex_planes("convex_count", planes, self.device)
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                cnt = torch.empty(n, dtype=torch.int32, device=d.device)
+                _check(lib().pt_convex_count(self._h, C.c_void_p(d.data_ptr()), n, m, flags, f, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_convex_count")
+                return cnt
+            return self._filtered("convex_count", x, False, filter, run, lambda: self.convex_count(planes, inside, stream_ptr), rows=("planes", 4 * m))
+        if isinstance(x, np.ndarray):
+            cnt = np.zeros(n, np.int32)
+            _check(lib().pt_convex_count_host(self._h, _ptr(x), n, m, flags, _ptr(cnt)), "pt_convex_count_host")
+            return cnt
+        import torch
+        cnt = torch.empty(n, dtype=torch.int32, device=x.device)
+        _check(lib().pt_convex_count(self._h, C.c_void_p(x.data_ptr()), n, m, flags, None, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_convex_count")
+        return cnt
+
+    def convex_any(self, planes, inside=False, stream_ptr=0, filter=None):
+        """Does anything lie inside or touch each region (include/pt_api.h: pt_convex_any)?  Returns (cls, prim) — float32 and int32 of
+        length n: prim >= 0 exactly when convex_count of the same region is above 0, and then some member with its class, 0 = inside,
+        1 = touching (which member is unspecified); else the miss (0, -1).  planes, inside, stream_ptr and filter as in convex_count."""
+        flags = CONVEX_INSIDE if inside else CONVEX_TOUCHING
+        x, n, m = _convex_planes("convex_any", planes, self.device)
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                res = torch.empty((n, 2), dtype=torch.int32, device=d.device)
+                _check(lib().pt_convex_any(self._h, C.c_void_p(d.data_ptr()), n, m, flags, f, C.c_void_p(res.data_ptr()), C.c_void_p(stream_ptr)), "pt_convex_any")
+                return _records(res, None)
+            return self._filtered("convex_any", x, False, filter, run, lambda: self.convex_any(planes, inside, stream_ptr), rows=("planes", 4 * m))
+        if isinstance(x, np.ndarray):
+            res = np.zeros(n, BOX_DTYPE)
+            _check(lib().pt_convex_any_host(self._h, _ptr(x), n, m, flags, _ptr(res)), "pt_convex_any_host")
+            return _records(res, None)
+        import torch
+        res = torch.empty((n, 2), dtype=torch.int32, device=x.device)      # PtBoxMember: cls's bits | prim
+        _check(lib().pt_convex_any(self._h, C.c_void_p(x.data_ptr()), n, m, flags, None, C.c_void_p(res.data_ptr()), C.c_void_p(stream_ptr)), "pt_convex_any")
+        return _records(res, None)
+
+    def in_convex(self, planes, inside=False, stream_ptr=0, filter=None):
+        """Every primitive inside or touching each region, in CSR form (include/pt_api.h: pt_convex_list).  Returns (offsets, cls, prim)
+        — int64 of shape (n + 1,), the members of region i at [offsets[i], offsets[i + 1]) of the float32 and int32 arrays cls and prim:
+        the primitives inside (cls 0) first, then the touching ones (cls 1), within a class the larger prim first.  planes and inside as
+        in convex_count.  A torch float32 tensor on the scene's device runs in place on stream_ptr: convex_count, list_offsets, one
+        8-byte read-back of the total — which WAITS for the stream to pass the scan —, the allocation of the records, the fill.  A
+        numpy array goes through pt_convex_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
+        flags = CONVEX_INSIDE if inside else CONVEX_TOUCHING
+        x, n, m = _convex_planes("in_convex", planes, self.device)
+        checked = lambda who, a, device: a.shape[0]      # noqa: E731  (the rows of x are checked)
+        if filter is not None:
+            def run(d, n, f):
+                return _csr("in_convex", d, "planes", 4 * m, BOX_DTYPE, 0, False, stream_ptr, self.device, checked,
+                            lambda t: self.convex_count(t.view(-1, m, 4), inside, stream_ptr=stream_ptr, filter=filter), None,
+                            lambda b, n, off, cap, out, det: _check(lib().pt_convex_list(self._h, b, n, m, flags, off, cap, f, out, C.c_void_p(stream_ptr)),
+                                                                    "pt_convex_list"))
+            return self._filtered("in_convex", x, False, filter, run, lambda: self.in_convex(planes, inside, stream_ptr), rows=("planes", 4 * m))
+        return _csr("in_convex", x, "planes", 4 * m, BOX_DTYPE, 0, False, stream_ptr, self.device, checked,
+                    lambda d: self.convex_count(d.view(-1, m, 4), inside, stream_ptr=stream_ptr),
+                    lambda b, n, off, cap, out, det: _check(lib().pt_convex_list_host(self._h, b, n, m, flags, off, cap, out), "pt_convex_list_host"),
+                    lambda b, n, off, cap, out, det: _check(lib().pt_convex_list(self._h, b, n, m, flags, off, cap, None, out, C.c_void_p(stream_ptr)),
+                                                            "pt_convex_list"))
+
+    def select_window(self, cam, window, inside=False, filter=None):
+        """The marquee selection: the indices, ascending (int32 numpy), of the primitives that touch (inside=True: lie wholly inside)
+        the frustum of the pixel window (x0, y0, x1, y1) of `cam`, half-open and unbounded in depth (frustum_planes).  Touching is
+        conservative near the frustum's edges, as convex_count states; filter as in convex_count."""
+        _, _, prim = self.in_convex(frustum_planes(cam, window)[None], inside=inside, filter=filter)
+        return np.sort(prim)
+
     def render_rays_device(self, d_rays_ptr, n_rays, prm, d_rgb_ptr, d_work_ptr, d_seed_ptr=0, seed_stride=None, stream_ptr=0):
         """Device-resident radiance along n_rays RAY8 records (raw device pointers: rays_floats(n) floats of output, rays_work_bytes(prm,
         n) bytes of scratch, d_seed_ptr 0 = ray i is seeded with i), enqueued on the given stream; blocks until the render has drained.
@@ -1464,6 +1555,69 @@ def grid_boxes(lo, hi, shape, device=0):
         return b
     import torch
     return torch.from_numpy(b).to(f"cuda:{int(device)}")
+
+
+def _convex_planes(who, planes, device):
+    """The host-side checks of a convex query's planes, (n, m, 4) float32 with 1 <= m <= CONVEX_MAX_PLANES, for the scene on `device`:
+    a torch tensor there, or a numpy array.  Returns (the planes as n rows of 4 m floats, n, m)."""
+    if isinstance(planes, np.ndarray):
+        x = np.ascontiguousarray(planes, np.float32)
+        shape = x.shape
+    elif hasattr(planes, "data_ptr") and hasattr(planes, "is_contiguous"):
+        x, shape = planes, tuple(planes.shape)
+        if str(x.dtype) != "torch.float32" or not x.is_contiguous():
+            raise PtError(f"{who}: planes must be contiguous float32 of shape (n, m, 4), got {x.dtype} {shape}")
+    else:
+        raise PtError(f"{who}: planes must be a torch tensor or a numpy array")
+    if len(shape) != 3 or shape[2] != 4 or not 1 <= shape[1] <= CONVEX_MAX_PLANES:
+        raise PtError(f"{who}: planes has shape {tuple(shape)}, want (n, m, 4) with 1 <= m <= {CONVEX_MAX_PLANES}")
+    if not isinstance(x, np.ndarray) and (x.device.type != "cuda" or x.device.index != device):
+        raise PtError(f"{who}: planes is on {x.device}, the scene is on device {device}")
+    return x.reshape(shape[0], 4 * shape[1]), shape[0], shape[1]
+
+
+def frustum_planes(cam, window=None, near=-1.0, far=float("inf")):
+    """The six planes (left, right, top, bottom, near, far) of the frustum of a pixel window of `cam` (include/pt_api.h:
+    pt_camera_frustum): (6, 4) float32 for Scene.convex_count and its kin.  window: (x0, y0, x1, y1), half-open, floats allowed, None:
+    the whole frame; a list of windows gives (n, 6, 4).  near < 0: no near plane; far = inf: no far plane (the neutral plane
+    (0, 0, 0, inf) stands in their place)."""
+    if window is None:
+        window = (0, 0, cam.W, cam.H)
+    w = np.asarray(window, np.float32)
+    if w.ndim not in (1, 2) or w.shape[-1] != 4:
+        raise PtError(f"frustum_planes: window must be (x0, y0, x1, y1) or a list of such, got shape {w.shape}")
+    out = np.zeros((len(w.reshape(-1, 4)), 6, 4), np.float32)
+    for i, (x0, y0, x1, y1) in enumerate(w.reshape(-1, 4).tolist()):
+        _check(lib().pt_camera_frustum(C.byref(cam), x0, y0, x1, y1, near, far, _ptr(out[i])), "pt_camera_frustum")
+    return out[0] if w.ndim == 1 else out
+
+
+def _planes64(normals, d):
+    """(k, 4) float32 PLANE4 records from float64 normals and offsets, each rounded once"""
+    return np.concatenate([normals, d[:, None]], 1).astype(np.float32)
+
+
+def obb_planes(center, axes, half):
+    """The six planes of an oriented box: (6, 4) float32, +axis_0, -axis_0, +axis_1, ...  axes: the three rows of a rotation; the planes
+    are +-axis_k with d = +-axis_k . center + half_k, computed in float64 and rounded once."""
+    c, a, h = np.asarray(center, np.float64).reshape(-1), np.asarray(axes, np.float64), np.asarray(half, np.float64).reshape(-1)
+    if c.shape != (3,) or a.shape != (3, 3) or h.shape != (3,):
+        raise PtError(f"obb_planes: want a center of 3, axes of (3, 3) and half sizes of 3, got {c.shape} {a.shape} {h.shape}")
+    n = np.stack([a[0], -a[0], a[1], -a[1], a[2], -a[2]])
+    return _planes64(n, n @ c + np.repeat(h, 2))
+
+
+def aabb_planes(lo, hi):
+    """The six planes of the axis-aligned box [lo, hi]: (6, 4) float32, normals +e_k, -e_k per axis, d = hi_k, -lo_k: the coordinates
+    themselves, so that a float32 box gives its own faces."""
+    lo, hi = np.asarray(lo, np.float32).reshape(-1), np.asarray(hi, np.float32).reshape(-1)
+    if lo.shape != (3,) or hi.shape != (3,):
+        raise PtError(f"aabb_planes: want lo and hi of 3 floats each, got {lo.shape} {hi.shape}")
+    out = np.zeros((6, 4), np.float32)
+    for k in range(3):
+        out[2 * k, k], out[2 * k, 3] = 1, hi[k]
+        out[2 * k + 1, k], out[2 * k + 1, 3] = -1, -lo[k]
+    return out
 
 
 def list_offsets(count, stream_ptr=0):

@@ -1349,6 +1349,99 @@ PT_API int  pt_convex_list_host(PtScene* s, const float* h_planes4, int64_t n, i
 PT_API int  pt_camera_frustum(const PtCamera* cam, float x0, float y0, float x1, float y1, float near_dist, float far_dist, float* planes24 /* 24, written */);
 
 /* ----------------------------------------------------------------------------------
+ * Sphere casts (new: the reference has no such query).  Opt-in: every call above is as it was.
+ * The query a collision user needs first: how far a body of some size can travel before it touches the scene (csrc/pt_sweep.hip,
+ * csrc/pt_sweep.h) — the end cap of a character's capsule, a camera boom, a tool tip, a LiDAR beam with divergence, clearance along a
+ * path — against a mesh that pt_scene_update_vertices moves.  A ray has no thickness, pt_closest_points no motion, and points stepped
+ * along the segment tunnel through thin geometry.  DESIGN.md section 43.
+ *
+ * Sweeps are SWEEP8 records: org.xyz | radius | dir.xyz | tmax, 32 bytes, the array 16-byte aligned.  The sphere of that radius has its
+ *   centre at o + t d for t in [0, tmax]; the direction is used as given and is NOT normalised, t is the parameter along it.
+ *   radius >= 0, and 0 is a two-sided thin ray; tmax >= 0, +inf allowed.  A zero direction is a sphere that stands still: only the
+ *   overlap rule (step 1) can make a member.  Results are PtRayHit (t, prim); primitives are numbered as in pt_trace_rays: triangles
+ *   first, in the order of `tris`, spheres after them; a miss is (0, -1).  Nothing is culled by facing, and the reference's leaf boxes
+ *   play no part.
+ * Arithmetic: IEEE float32, every operation below rounded once and none contracted, in the order written.  dot, cross, f, sphere_f
+ *   (the f of a sphere) and boxdist2 are those of the section "Closest-point queries".  min and max are selects,
+ *     min(a, b) = (b < a) ? b : a      max(a, b) = (b > a) ? b : a
+ *   with several arguments from the left, min(min(a, b), c): one answer for a NaN and for zeros of either sign.
+ *   o, d, r, tmax are the record's fields, r2 = r * r, NOW = 2^-126 (the smallest positive normal float).
+ * first(m, dv, R2): the first touch of the line m + t dv with the ball of squared radius R2 about 0, by the closest approach:
+ *     A = dot(dv, dv);  t0 = -dot(m, dv) / A;  w = m + t0 * dv;  k = R2 - dot(w, w);  t = t0 - sqrt(k / A)
+ *     first = max(NOW, t) when A > 0 && k >= 0 && t0 >= 0, else +inf
+ *   (Not the textbook b^2 - a c form: in float32 that left a residual |dist - r| of 3 * 10^-4 at coordinates of magnitude 4 and radius
+ *   0.01, this form 1.6 * 10^-6.)  A line that is inside the ball already by these floats and still approaches its middle touches NOW.
+ * tau(S, k) for triangle k, V0 E1 E2 as in the closest-point section:  a = V0, ab = E1, ac = E2, b = a + ab, c = a + ac, bc = ac - ab
+ *     1. Overlap.  If f(o, k) <= r2:  tau = 0, and steps 2 to 4 play no part.  So tau = 0 for exactly the primitives pt_count_within
+ *        counts for the point (o, r), bit for bit — and for no other: every contact below is at NOW or later.
+ *     2. Floor.  tlo, thi = the record's own box as f's last line forms it; lo' = tlo - r, hi' = thi + r.  Per axis with d != 0:
+ *        inv = 1 / d, t1 = (lo' - o) * inv, t2 = (hi' - o) * inv, near = min(t1, t2), far = max(t1, t2).  An axis with d == 0 passes
+ *        iff lo' <= o && o <= hi' and has no near or far.  tn = max(0, near_x, near_y, near_z), tf = min(tmax, far_x, far_y, far_z)
+ *        over the axes that have them.  Unless every d == 0 axis passes and tn <= tf:  tau = +inf.
+ *     3. Candidates.
+ *        Face:  n = cross(ab, ac), nn = dot(n, n), h = dot(o - a, n), dn = dot(d, n), s = (h >= 0) ? 1 : -1, ln = sqrt(nn),
+ *          g = s*h - r*ln.  When nn > 0 && s*dn < 0:  t = max(NOW, g > 0 ? g / -(s*dn) : 0),  q = (o + t*d) - ((s*r)/ln) * n; the
+ *          candidate t is taken if q passes the three edge-function tests >= 0 of f's `inside` (ap = q - a).  Only the near face:
+ *          a sphere that starts outside cannot reach the far offset face without first passing an edge cylinder.
+ *        Edges:  for (v, e) in (a, ab), (a, ac), (b, bc) with ee = dot(e, e) > 0:  m = o - v, um = dot(m, e) / ee, ud = dot(d, e) / ee,
+ *          t = first(m - um*e, d - ud*e, r2); taken if 0 <= um + t*ud && um + t*ud <= 1.
+ *        Vertices:  for v in a, b, c:  first(o - v, d, r2).
+ *        tau_raw = min over the at most seven, in this order from +inf.
+ *     4. tau = max(tau_raw, tn) when that is <= tmax, else +inf.
+ *   The floor only moves tau towards the true value: the centre at true contact lies inside the inflated box.  It is what lets a tree
+ *   walk prune without ever disagreeing with this definition (below).
+ * tau(S, k) for sphere j (k = number of triangles + j), center ctr, radius rad:  pc = o - ctr, l = sqrt(dot(pc, pc)), g = l - rad
+ *     if g * g <= r2:  tau = 0 (contact with the SURFACE, as everywhere; this is sphere_f <= r2)
+ *     else if l > rad:  R = rad + r;  tau = first(pc, d, R * R)
+ *     else (deep inside the ball):  R = rad - r;  A, t0, k of first(pc, d, R * R);  tau = max(NOW, t0 + sqrt(k / A)) when A > 0 && k >= 0,
+ *       else +inf
+ *     tau = +inf when it exceeds tmax.
+ *   tau = +inf is no member, also when tmax = +inf.
+ * PT_SWEEP_CLOSEST: defined without reference to any tree.  Among the primitives k with tau(S_i, k) <= tmax, d_hits[i] = (tau, k) of the
+ *   smallest tau; among equal tau the largest k (ties at tau = 0 are ordinary).  No such primitive: a miss, (0, -1).  The result is
+ *   therefore bit for bit the same before and after a refit or any rebuild, and equals a brute-force evaluation over the scene's
+ *   current positions.
+ *   d_detail8 (may be NULL): the 8-float record of the closest-point section, c.xyz | v | w | side | feature | 0, for the winning
+ *   primitive and the point  centre = o + tau * d  (one multiply and one add per axis, float32): the sphere's centre at contact.
+ *   A miss gives zeros.  The contact normal is centre - c, for the caller to normalise.
+ * PT_SWEEP_ANY: prim >= 0 exactly when the closest form of the same record (and filter) hits.  The record is SOME member k with
+ *   tau(S, k) <= tmax and t = tau(S, k) bit for bit; which member is unspecified and may change between versions (the walk stops at
+ *   the first).  d_detail8 must be NULL.
+ * Why a tree walk is exact: a child box (lo, hi), decoded and widened as the closest-point walks widen it, is entered iff
+ *   boxdist2(o, lo, hi) <= r2, or the test of step 2 on [lo - r, hi + r] passes with its tn not above the best tau so far (strictly:
+ *   an equal tn may hide a tie).  Every operation of both is monotone in lo and hi under rounding to nearest, for fixed o, inv and r,
+ *   and every widened box contains the boxes of the records below it: a parent's interval contains a child's
+ *   with no slack, and a culled node holds no member that could win or tie.
+ * filter (may be NULL): a PtQueryFilter exactly as the section "Query filters" takes it — primitive masks, per-query masks, one skipped
+ *   primitive per sweep (the body's own triangle, say); a filtered-out primitive is no member.  PT_FILTER_TMIN does not apply and is
+ *   rejected.  A filter that keeps everything runs the unfiltered kernels.
+ * pt_sweep_spheres: d_sweeps8 (16-byte aligned), d_hits (8-byte aligned) and d_detail8 (4-byte aligned) are DEVICE pointers on the
+ *   scene's device holding n records.  Everything is enqueued on `hip_stream`: no host wait, nothing is read back, nothing is allocated
+ *   (pt_scene_device_bytes stays what it was); batches of at most 2^30 sweeps go per launch.  A query enqueued after
+ *   pt_scene_update_vertices, pt_scene_rebuild_tree, pt_scene_rebuild_tree_ex or pt_scene_rebuild_tree_opt on the same stream sees
+ *   their result.  The buffers must stay valid until the stream has passed the query.  A query leaves every render state alone:
+ *   frames, pt_last_iterations, pt_last_counters, pt_last_render_ms.  Concurrency: ONE query, update or render at a time per scene.
+ * pt_sweep_spheres_host: the same on HOST arrays, without a filter: uploads, queries on the NULL stream, waits and downloads.
+ * Argument checks, in the order of every query: NULL scene / sweeps / hits, n < 0, an unknown mode, a detail buffer given with
+ *   PT_SWEEP_ANY, then the alignments (sweeps 16, hits 8, detail 4), then the filter's (unknown filter flags, PT_FILTER_TMIN, a
+ *   misaligned filter array) return PT_ERR_INVALID before any HIP call, no pointer dereferenced, the message naming the entry point.
+ *   n = 0 returns PT_OK without a HIP call, but does not excuse a NULL.
+ * A record with a non-finite coordinate, a negative or NaN radius or tmax, or a direction component that is denormal (its inverse
+ *   overflows): the result for THAT record is unspecified (prim stays in [-1, number of primitives)), the other records of the batch are
+ *   unaffected, and the call ends by the argument of quad_step (csrc/pt_trace.h): a depth-first walk over a finite tree, its stack
+ *   bounded by the depth of the tree whatever the floats are.
+ * Known limit: on a needle triangle the float32 normal is tilted (the kappa of the ray section's note), and the face candidate with
+ *   it; the error of tau grows with kappa as f's does.  DESIGN.md section 43 has the measured bound per family.
+ * Out of scope: contact counts, lists and the first K contacts along a sweep; capsule and box sweeps; rotation; a scene that moves
+ *   during the sweep; sorting sweeps for coherence; a wave-cooperative walk; a multi-GPU split; a ptrender option.
+ * -------------------------------------------------------------------------------- */
+#define PT_SWEEP_CLOSEST 0
+#define PT_SWEEP_ANY     1
+PT_API int  pt_sweep_spheres(PtScene* s, const float* d_sweeps8, int64_t n, int32_t mode, const PtQueryFilter* filter /* may be NULL */,
+                             PtRayHit* d_hits, float* d_detail8 /* may be NULL */, void* hip_stream);
+PT_API int  pt_sweep_spheres_host(PtScene* s, const float* h_sweeps8, int64_t n, int32_t mode, PtRayHit* h_hits, float* h_detail8 /* may be NULL */);
+
+/* ----------------------------------------------------------------------------------
  * Radiance along the caller's own rays (new: the reference reaches its integrator through a pinhole camera only).
  * Opt-in: every call above is as it was.  pt_trace_rays opened the geometry of an uploaded scene to the caller's rays; this opens
  * the light transport: a panorama, fisheye, orthographic or thin-lens camera, a light probe at a point, a lightmap texel, the

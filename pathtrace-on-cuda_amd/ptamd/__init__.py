@@ -108,6 +108,7 @@ BOX_DTYPE = np.dtype([("cls", "<f4"), ("prim", "<i4")])      # PtBoxMember as a 
 BOX_TOUCHING, BOX_INSIDE = 0, 1
 CONVEX_TOUCHING, CONVEX_INSIDE = 0, 1      # PT_CONVEX_TOUCHING, PT_CONVEX_INSIDE
 CONVEX_MAX_PLANES = 8                      # PT_CONVEX_MAX_PLANES
+SWEEP_CLOSEST, SWEEP_ANY = 0, 1            # PT_SWEEP_CLOSEST, PT_SWEEP_ANY
 
 
 class PtQueryFilter(C.Structure):
@@ -277,6 +278,8 @@ API = [
     ("pt_convex_any_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     ("pt_convex_list_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     ("pt_camera_frustum", C.c_int, [C.POINTER(PtCamera), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    ("pt_sweep_spheres", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(PtQueryFilter), _P, _P, _P]),
+    ("pt_sweep_spheres_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     ("pt_rays_floats", C.c_int64, [C.c_int64]),
     ("pt_rays_work_bytes", C.c_int64, [C.POINTER(PtParams), C.c_int64]),
     ("pt_render_rays", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
@@ -344,6 +347,17 @@ def _device_rays(who, rays, device):
     if rays.device.type != "cuda" or rays.device.index != device:
         raise PtError(f"{who}: rays is on {rays.device}, the scene is on device {device}")
     return rays.shape[0]
+
+
+def _device_sweeps(who, sweeps, device):
+    """The host-side checks of a SWEEP8 tensor for the scene on `device`; returns n."""
+    if not (hasattr(sweeps, "data_ptr") and hasattr(sweeps, "is_contiguous")):
+        raise PtError(f"{who}: sweeps must be a torch tensor or a numpy array")
+    if str(sweeps.dtype) != "torch.float32" or not sweeps.is_contiguous() or sweeps.dim() != 2 or sweeps.shape[1] != 8:
+        raise PtError(f"{who}: sweeps must be contiguous float32 of shape (n, 8), got {sweeps.dtype} {tuple(sweeps.shape)}")
+    if sweeps.device.type != "cuda" or sweeps.device.index != device:
+        raise PtError(f"{who}: sweeps is on {sweeps.device}, the scene is on device {device}")
+    return sweeps.shape[0]
 
 
 def _device_boxes(who, boxes, device):
@@ -1455,6 +1469,39 @@ class Scene:
         _, _, prim = self.in_convex(frustum_planes(cam, window)[None], inside=inside, filter=filter)
         return np.sort(prim)
 
+    def sweep_spheres(self, sweeps, any_hit=False, detail=False, stream_ptr=0, filter=None):
+        """How far each of the caller's spheres travels before it touches the scene (include/pt_api.h: pt_sweep_spheres).  sweeps: (n, 8)
+        float32 SWEEP8 records, org.xyz radius dir.xyz tmax (sweep_records makes them); the direction is not normalised, t is the
+        parameter along it.  Returns (t, prim) — float32 and int32 of length n, a miss is (0, -1) — and, with detail=True (closest
+        only), the (n, 8) detail records c.xyz v w side feature 0 of closest_points at the sphere's centre at contact as a third item.
+        any_hit=True: prim >= 0 iff the closest form hits; which contact is unspecified.
+        A torch float32 tensor on the scene's device is used in place (data_ptr()): the query is enqueued on stream_ptr, the results
+        are torch tensors on that device, valid once the stream has passed the query, and `sweeps` must stay alive until then.
+        A numpy array goes through pt_sweep_spheres_host (synchronous) and returns numpy arrays.
+        filter: a QueryFilter without tmin (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
+        if any_hit and detail:
+            raise PtError("sweep_spheres: an any-contact sweep has no detail record")
+        mode = SWEEP_ANY if any_hit else SWEEP_CLOSEST
+
+        def device_call(d, n, f):
+            import torch
+            hits = torch.empty((n, 2), dtype=torch.int32, device=d.device)      # PtRayHit: t's bits | prim
+            det = torch.empty((n, 8), dtype=torch.float32, device=d.device) if detail else None
+            _check(lib().pt_sweep_spheres(self._h, C.c_void_p(d.data_ptr()), n, mode, f, C.c_void_p(hits.data_ptr()),
+                                          C.c_void_p(det.data_ptr()) if detail else None, C.c_void_p(stream_ptr)), "pt_sweep_spheres")
+            return _records(hits, det)
+        if filter is not None:
+            if not isinstance(sweeps, np.ndarray):
+                _device_sweeps("sweep_spheres", sweeps, self.device)
+            return self._filtered("sweep_spheres", sweeps, False, filter, device_call, lambda: self.sweep_spheres(sweeps, any_hit, detail, stream_ptr),
+                                  rows=("sweeps", 8))
+        if isinstance(sweeps, np.ndarray):
+            x, n = _host_rows("sweep_spheres", sweeps, "sweeps", 8)
+            hits, det = _host_out((n,), HIT_DTYPE, detail, 8)
+            _check(lib().pt_sweep_spheres_host(self._h, _ptr(x), n, mode, _ptr(hits), _ptr(det) if detail else None), "pt_sweep_spheres_host")
+            return _records(hits, det)
+        return device_call(sweeps, _device_sweeps("sweep_spheres", sweeps, self.device), None)
+
     def render_rays_device(self, d_rays_ptr, n_rays, prm, d_rgb_ptr, d_work_ptr, d_seed_ptr=0, seed_stride=None, stream_ptr=0):
         """Device-resident radiance along n_rays RAY8 records (raw device pointers: rays_floats(n) floats of output, rays_work_bytes(prm,
         n) bytes of scratch, d_seed_ptr 0 = ray i is seeded with i), enqueued on the given stream; blocks until the render has drained.
@@ -1605,6 +1652,24 @@ def obb_planes(center, axes, half):
         raise PtError(f"obb_planes: want a center of 3, axes of (3, 3) and half sizes of 3, got {c.shape} {a.shape} {h.shape}")
     n = np.stack([a[0], -a[0], a[1], -a[1], a[2], -a[2]])
     return _planes64(n, n @ c + np.repeat(h, 2))
+
+
+def sweep_records(org, dir, radius, tmax):
+    """SWEEP8 records for Scene.sweep_spheres: (n, 8) float32, org.xyz | radius | dir.xyz | tmax.  org and dir: (n, 3) or 3 floats;
+    radius and tmax: n floats or one.  The four broadcast against each other; a negative or NaN radius or tmax is refused."""
+    o, d = np.asarray(org, np.float32), np.asarray(dir, np.float32)
+    r, t = np.asarray(radius, np.float32), np.asarray(tmax, np.float32)
+    if o.ndim not in (1, 2) or o.shape[-1] != 3 or d.ndim not in (1, 2) or d.shape[-1] != 3 or r.ndim > 1 or t.ndim > 1:
+        raise PtError(f"sweep_records: want org and dir of shape (n, 3) or (3,), radius and tmax of n floats or one, got {o.shape} {d.shape} {r.shape} {t.shape}")
+    if not ((r >= 0).all() and (t >= 0).all()):
+        raise PtError("sweep_records: radius and tmax must be >= 0")
+    try:
+        n = np.broadcast_shapes(o.shape[:-1], d.shape[:-1], r.shape, t.shape)
+    except ValueError:
+        raise PtError(f"sweep_records: the lengths do not agree: {o.shape} {d.shape} {r.shape} {t.shape}") from None
+    out = np.zeros(tuple(n or (1,)) + (8,), np.float32)
+    out[:, 0:3], out[:, 3], out[:, 4:7], out[:, 7] = o, r, d, t
+    return out
 
 
 def aabb_planes(lo, hi):

@@ -1442,6 +1442,104 @@ PT_API int  pt_sweep_spheres(PtScene* s, const float* d_sweeps8, int64_t n, int3
 PT_API int  pt_sweep_spheres_host(PtScene* s, const float* h_sweeps8, int64_t n, int32_t mode, PtRayHit* h_hits, float* h_detail8 /* may be NULL */);
 
 /* ----------------------------------------------------------------------------------
+ * Triangle queries (new: the reference has no such query).  Opt-in: every call above is as it was.
+ * The fourth shape of a query: after rays, points and regions, the caller's own TRIANGLES (csrc/pt_tri.hip, csrc/pt_tri.h): which
+ * primitives of the resident, moving scene the triangles of a tool, a robot link or a character mesh actually cut, and along which
+ * segments — the contact curve; and the plane section of the scene (a slicer layer, a floor plan, a section view) as the segments cut
+ * by a large quad of two query triangles.  pt_convex_count on a triangle written as five half-spaces is conservative near its edges
+ * and returns no geometry; this is exact triangle against triangle, and returns the segments.  DESIGN.md section 44.
+ *
+ * Queries are TRI12 records: a.xyz | - | b.xyz | - | c.xyz | -, 48 bytes, the array 16-byte aligned; the three reserved floats are not
+ *   read.  Primitives are numbered as in pt_trace_rays: triangles first, in the order of `tris`, spheres after them.  Results are
+ *   PtBoxMember records (cls, prim): every member's cls is 1, a miss is (0, -1).
+ * Arithmetic: IEEE float32, every operation below rounded once and none contracted, in the order written.  dot and cross are those of
+ *   the section "Closest-point queries"; min and max are the selects of the section "Sphere casts", several arguments from the left.
+ * Of the query T = (qa, qb, qc):  n = cross(qb - qa, qc - qa);  qlo, qhi = component-wise min(min(qa, qb), qc), max(max(qa, qb), qc);
+ *   the plane function  d(v) = (n.x*(v.x - qa.x) + n.y*(v.y - qa.y)) + n.z*(v.z - qa.z);  the inward edge normals
+ *   m0 = cross(n, qb - qa), m1 = cross(n, qc - qb), m2 = cross(n, qa - qc) and the edge functions
+ *   w0(x) = dot(m0, x - qa), w1(x) = dot(m1, x - qb), w2(x) = dot(m2, x - qa)      (edges 0 and 2 pass through qa, edge 1 through qb).
+ * Membership of triangle k, V0 E1 E2 as in the closest-point section:  a = V0, b = a + E1, c = a + E2 (the record's own floats)
+ *     1. Box floor.  tlo, thi = component-wise min(min(a, b), c), max(max(a, b), c).  Unless tlo <= qhi && thi >= qlo on every axis:
+ *        no member.
+ *     2. Plane floor.  da = d(a), db = d(b), dc = d(c); a vertex is ABOVE when its d >= 0 (half-open: a vertex on the plane is above).
+ *        Unless one vertex is above and one is not: no member.
+ *     3. Section.  The lone vertex L is the one whose side differs from the other two's; (v1, v2) are the other two in cyclic order:
+ *        L = a: (b, c), L = b: (c, a), L = c: (a, b).  t1 = d(L) / (d(L) - d(v1)), t2 = d(L) / (d(L) - d(v2));
+ *        P = L + t1*(v1 - L), Q = L + t2*(v2 - L)      (the subtraction, then one multiply and one add per axis).
+ *     4. Clip.  [s0, s1] = [0, 1].  For i = 0, 1, 2 in order:  wp = w_i(P), wq = w_i(Q).  If neither is >= 0: no member.  If exactly
+ *        one is:  s = wp / (wp - wq);  wp >= 0: s1 = min(s1, s), else s0 = max(s0, s).  After the three: member iff s0 <= s1, and then
+ *        PQ = Q - P,  p = P + s0*PQ,  q = P + s1*PQ,  kind = 1.
+ *   Consequences of the half-open rule: a triangle lying in T's plane has every vertex above and is no member (coplanar overlap is not
+ *   reported); a zero-area query has n = 0, every d = 0, every vertex above: no triangle member; a query with a NaN has every d NaN,
+ *   no vertex above: no triangle member, and the other records of the batch are unaffected.  A zero-area scene triangle that pierces
+ *   T is a member with p == q.  In real arithmetic steps 2 to 4 are exactly T intersected with triangle k for pairs that are not
+ *   coplanar: symmetric in the two triangles, not conservative.  The section points of an edge that two scene triangles share agree
+ *   within rounding, NOT bit for bit: a record stores a, E1, E2, and a + E1 is rounded, so the two records hold the shared vertices
+ *   with different last bits and walk the edge from different ends.
+ * Membership of sphere j (k = number of triangles + j), centre ctr, radius rad, by the SURFACE as everywhere:  with f and its closest
+ *   point c of the closest-point section (the detail record's c) taken for the point ctr and the triangle (qa, qb - qa, qc - qa), min
+ *   and max as selects;  far2 = max(max(|qa - ctr|^2, |qb - ctr|^2), |qc - ctr|^2), each dot(v, v);  rr = rad * rad:
+ *     member iff f <= rr && far2 >= rr      (T comes within rad of the centre and is not wholly inside the ball);  p = q = c, kind = 2.
+ * Members: M(T) = the members above.  Order: the larger primitive index first (every key is 1: the one order of the lists above).
+ * Overflow: coordinates so large that a product or sum overflows float32 leave THAT pair unspecified; every prim stays in
+ *   [-1, number of primitives) and every count in [0, number of primitives].
+ * pt_tri_count: d_count[i] = |M(T_i)|.
+ * pt_tri_any:   d_out[i].prim >= 0 exactly when pt_tri_count of the same record and filter is above 0; the record is then SOME member,
+ *   (1, prim); which member is unspecified and may change between versions (the walk stops at the first).  No member: (0, -1).
+ * pt_tri_list:  the segment of query i is [b, e) with b = clamp(d_offsets[i], 0, cap) and e = clamp(d_offsets[i + 1], b, cap), as
+ *   pt_box_list states it: no record outside the segments is written, whatever the offsets hold, never one outside [0, cap).  With
+ *   m = e - b:  m >= |M|: slots 0 .. |M| - 1 hold M in order, the later slots the miss record (0, -1);  m < |M|: the m slots hold m
+ *   distinct members, sorted among themselves; which members is unspecified.
+ *   d_detail8 (may be NULL): 8 floats per slot of every segment, p.xyz | q.xyz | kind | 0, for the member in that slot; a miss slot
+ *   holds zeros.  Written by a second pass over the filled slots that evaluates the same function on the scene's current records:
+ *   the same bits.  Slots outside the segments are not written.
+ *   The CSR route: pt_tri_count, pt_list_offsets, pt_tri_list with the SAME filter — the records are then the concatenation of every
+ *   M, bit for bit brute force over the scene's current positions.
+ * Why a tree walk is exact: a child box (lo, hi), decoded and widened as the box walks widen it, is entered iff it overlaps (qlo, qhi)
+ *   on every axis (inclusive) AND straddles the plane: d at the corner that minimises it — per axis lo where n >= 0, hi otherwise — is
+ *   < 0 and d at the opposite corner is >= 0.  d's subtraction, three products and two sums are monotone in each coordinate under
+ *   rounding to nearest; a record's vertices lie in its box; every widened box contains the boxes of the records below it (DESIGN.md
+ *   section 29).  So a culled node holds no member, and the answer is the same bits before and after a refit or any rebuild.  The
+ *   plane test makes a large slanted triangle — a slicing quad — walk a slab of the tree, not its whole bounding box.
+ * filter (may be NULL): a PtQueryFilter exactly as the section "Query filters" takes it — primitive masks, per-query masks, one skipped
+ *   primitive per query (the body's own triangle, say); a filtered-out primitive is no member.  PT_FILTER_TMIN does not apply and is
+ *   rejected.  A filter that keeps everything runs the unfiltered kernels.
+ * pt_tri_count, pt_tri_any, pt_tri_list: d_tris12 (16-byte aligned), d_out (8-byte aligned), d_offsets (8-byte aligned), d_count and
+ *   d_detail8 (4-byte aligned) are DEVICE pointers on the scene's device.  Everything is enqueued on `hip_stream`: no host wait, nothing
+ *   is read back, nothing is allocated (pt_scene_device_bytes stays what it was); batches of at most 2^30 queries go per launch.  A
+ *   query enqueued after pt_scene_update_vertices, pt_scene_rebuild_tree, pt_scene_rebuild_tree_ex or pt_scene_rebuild_tree_opt on the
+ *   same stream sees their result.  The buffers must stay valid until the stream has passed the query.  A query leaves every render
+ *   state alone: frames, pt_last_iterations, pt_last_counters, pt_last_render_ms.  Concurrency: ONE query, update or render at a time
+ *   per scene.
+ * pt_tri_count_host, pt_tri_any_host, pt_tri_list_host: the same on HOST arrays, without a filter: upload, query on the NULL stream,
+ *   wait and download.  pt_tri_list_host follows pt_box_list_host: h_offsets (n + 1) is always written; with h_out NULL the call stops
+ *   there (the sizing call); with cap < h_offsets[n] it returns PT_ERR_INVALID, the offsets written.  h_detail8 (may be NULL): cap * 8
+ *   floats, of which h_offsets[n] * 8 are written.
+ * Argument checks, in the order of every query: NULL scene / tris / offsets / out / count, n < 0, cap < 0, then the alignments (tris
+ *   16, offsets 8, out 8, count 4, detail 4), then the filter's (unknown filter flags, PT_FILTER_TMIN, a misaligned filter array)
+ *   return PT_ERR_INVALID before any HIP call, no pointer dereferenced, the message naming the entry point.  n = 0 returns PT_OK
+ *   without a HIP call, but does not excuse a NULL.  Only pt_tri_list and pt_tri_list_host take a detail buffer.
+ * The walk ends whatever the floats are, by the argument of quad_step (csrc/pt_trace.h): depth-first over a finite tree, its stack
+ *   bounded by the depth of the tree.
+ * Cost: the tree nodes whose boxes the query's box overlaps and its plane crosses, plus one key per triangle
+ *   below such a leaf; every lane walks alone, so one large query — a slicing quad through the whole scene — holds its wave for as
+ *   long as its slab of the tree takes: the caller's cost, as a whole-frame frustum is.
+ * Out of scope: self-intersection of the scene's own mesh (neighbours share edges: it needs an adjacency-aware rule); coplanar
+ *   overlap; the circle of a sphere section; K-limited lists; a wave-cooperative walk; _host variants with filters; a multi-GPU
+ *   split; a CLI option.
+ * -------------------------------------------------------------------------------- */
+PT_API int  pt_tri_count(PtScene* s, const float* d_tris12, int64_t n, const PtQueryFilter* filter /* may be NULL */, int32_t* d_count, void* hip_stream);
+PT_API int  pt_tri_any(PtScene* s, const float* d_tris12, int64_t n, const PtQueryFilter* filter /* may be NULL */, PtBoxMember* d_out /* n */,
+                       void* hip_stream);
+PT_API int  pt_tri_list(PtScene* s, const float* d_tris12, int64_t n, const int64_t* d_offsets /* n + 1 */, int64_t cap,
+                        const PtQueryFilter* filter /* may be NULL */, PtBoxMember* d_out /* cap */, float* d_detail8 /* cap * 8, may be NULL */,
+                        void* hip_stream);
+PT_API int  pt_tri_count_host(PtScene* s, const float* h_tris12, int64_t n, int32_t* h_count);
+PT_API int  pt_tri_any_host(PtScene* s, const float* h_tris12, int64_t n, PtBoxMember* h_out);
+PT_API int  pt_tri_list_host(PtScene* s, const float* h_tris12, int64_t n, int64_t* h_offsets /* n + 1, written */, int64_t cap,
+                             PtBoxMember* h_out /* may be NULL */, float* h_detail8 /* may be NULL */);
+
+/* ----------------------------------------------------------------------------------
  * Radiance along the caller's own rays (new: the reference reaches its integrator through a pinhole camera only).
  * Opt-in: every call above is as it was.  pt_trace_rays opened the geometry of an uploaded scene to the caller's rays; this opens
  * the light transport: a panorama, fisheye, orthographic or thin-lens camera, a light probe at a point, a lightmap texel, the

@@ -280,6 +280,12 @@ API = [
     ("pt_camera_frustum", C.c_int, [C.POINTER(PtCamera), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     ("pt_sweep_spheres", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(PtQueryFilter), _P, _P, _P]),
     ("pt_sweep_spheres_host", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
+    ("pt_tri_count", C.c_int, [_P, _P, C.c_int64, C.POINTER(PtQueryFilter), _P, _P]),
+    ("pt_tri_any", C.c_int, [_P, _P, C.c_int64, C.POINTER(PtQueryFilter), _P, _P]),
+    ("pt_tri_list", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(PtQueryFilter), _P, _P, _P]),
+    ("pt_tri_count_host", C.c_int, [_P, _P, C.c_int64, _P]),
+    ("pt_tri_any_host", C.c_int, [_P, _P, C.c_int64, _P]),
+    ("pt_tri_list_host", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("pt_rays_floats", C.c_int64, [C.c_int64]),
     ("pt_rays_work_bytes", C.c_int64, [C.POINTER(PtParams), C.c_int64]),
     ("pt_render_rays", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(PtParams), _P, _P, _P]),
@@ -358,6 +364,17 @@ def _device_sweeps(who, sweeps, device):
     if sweeps.device.type != "cuda" or sweeps.device.index != device:
         raise PtError(f"{who}: sweeps is on {sweeps.device}, the scene is on device {device}")
     return sweeps.shape[0]
+
+
+def _device_tris(who, tris, device):
+    """The checks of a query's device path on TRI12 records, (n, 12) float32: n."""
+    if not (hasattr(tris, "data_ptr") and hasattr(tris, "is_contiguous")):
+        raise PtError(f"{who}: tris must be a torch tensor or a numpy array")
+    if str(tris.dtype) != "torch.float32" or not tris.is_contiguous() or tris.dim() != 2 or tris.shape[1] != 12:
+        raise PtError(f"{who}: tris must be contiguous float32 of shape (n, 12), got {tris.dtype} {tuple(tris.shape)}")
+    if tris.device.type != "cuda" or tris.device.index != device:
+        raise PtError(f"{who}: tris is on {tris.device}, the scene is on device {device}")
+    return tris.shape[0]
 
 
 def _device_boxes(who, boxes, device):
@@ -1502,6 +1519,95 @@ class Scene:
             return _records(hits, det)
         return device_call(sweeps, _device_sweeps("sweep_spheres", sweeps, self.device), None)
 
+    def tri_count(self, tris, stream_ptr=0, filter=None, detail=False):
+        """How many primitives each of the caller's triangles cuts (include/pt_api.h: pt_tri_count): (n,) int32.  tris: (n, 12) float32
+        TRI12 records, a.xyz - b.xyz - c.xyz - (tri_records makes them).  A zero-area triangle or one with a NaN cuts no triangle.  A
+        torch tensor on the scene's device is used in place and the count is a torch tensor there, in stream order; a numpy array
+        goes through pt_tri_count_host.  Only cut_by_triangles returns segments: detail must stay False.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
+        if detail:
+            raise PtError("tri_count: a detail buffer is allowed only on the list call (cut_by_triangles)")
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                cnt = torch.empty(n, dtype=torch.int32, device=d.device)
+                _check(lib().pt_tri_count(self._h, C.c_void_p(d.data_ptr()), n, f, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_tri_count")
+                return cnt
+            if not isinstance(tris, np.ndarray):
+                _device_tris("tri_count", tris, self.device)
+            return self._filtered("tri_count", tris, False, filter, run, lambda: self.tri_count(tris, stream_ptr), rows=("tris", 12))
+        if isinstance(tris, np.ndarray):
+            x, n = _host_rows("tri_count", tris, "tris", 12)
+            cnt = np.zeros(n, np.int32)
+            _check(lib().pt_tri_count_host(self._h, _ptr(x), n, _ptr(cnt)), "pt_tri_count_host")
+            return cnt
+        n = _device_tris("tri_count", tris, self.device)
+        import torch
+        cnt = torch.empty(n, dtype=torch.int32, device=tris.device)
+        _check(lib().pt_tri_count(self._h, C.c_void_p(tris.data_ptr()), n, None, C.c_void_p(cnt.data_ptr()), C.c_void_p(stream_ptr)), "pt_tri_count")
+        return cnt
+
+    def tri_any(self, tris, stream_ptr=0, filter=None, detail=False):
+        """Does each triangle cut anything (include/pt_api.h: pt_tri_any)?  Returns (cls, prim) — float32 and int32 of length n: prim >= 0
+        exactly when tri_count of the same record is above 0, and then some member with cls 1 (which member is unspecified); else the
+        miss (0, -1).  tris, stream_ptr, filter and detail as in tri_count."""
+        if detail:
+            raise PtError("tri_any: a detail buffer is allowed only on the list call (cut_by_triangles)")
+        if filter is not None:
+            def run(d, n, f):
+                import torch
+                res = torch.empty((n, 2), dtype=torch.int32, device=d.device)
+                _check(lib().pt_tri_any(self._h, C.c_void_p(d.data_ptr()), n, f, C.c_void_p(res.data_ptr()), C.c_void_p(stream_ptr)), "pt_tri_any")
+                return _records(res, None)
+            if not isinstance(tris, np.ndarray):
+                _device_tris("tri_any", tris, self.device)
+            return self._filtered("tri_any", tris, False, filter, run, lambda: self.tri_any(tris, stream_ptr), rows=("tris", 12))
+        if isinstance(tris, np.ndarray):
+            x, n = _host_rows("tri_any", tris, "tris", 12)
+            res = np.zeros(n, BOX_DTYPE)
+            _check(lib().pt_tri_any_host(self._h, _ptr(x), n, _ptr(res)), "pt_tri_any_host")
+            return _records(res, None)
+        n = _device_tris("tri_any", tris, self.device)
+        import torch
+        res = torch.empty((n, 2), dtype=torch.int32, device=tris.device)      # PtBoxMember: cls's bits | prim
+        _check(lib().pt_tri_any(self._h, C.c_void_p(tris.data_ptr()), n, None, C.c_void_p(res.data_ptr()), C.c_void_p(stream_ptr)), "pt_tri_any")
+        return _records(res, None)
+
+    def cut_by_triangles(self, tris, segments=False, stream_ptr=0, filter=None):
+        """Every primitive each triangle cuts, in CSR form (include/pt_api.h: pt_tri_list).  Returns (offsets, cls, prim) — int64 of shape
+        (n + 1,), the members of triangle i at [offsets[i], offsets[i + 1]) of the float32 and int32 arrays cls (all 1) and prim, the
+        larger prim first — and, with segments=True, the (total, 8) records p.xyz q.xyz kind 0 as a fourth item: the segment along
+        which the two triangles cut (kind 1), or the query's point closest to a sphere's centre twice (kind 2).
+        A torch float32 tensor on the scene's device runs in place on stream_ptr: tri_count, list_offsets, one 8-byte read-back of the
+        total — which WAITS for the stream to pass the scan —, the allocation of the records, the fill.  A numpy array goes through
+        pt_tri_list_host (synchronous: a sizing call, then the fill) and returns numpy arrays.
+        filter: a QueryFilter (numpy input is then moved to the device with torch and comes back as numpy); None: no filter."""
+        if filter is not None:
+            def run(d, n, f):
+                return _csr("cut_by_triangles", d, "tris", 12, BOX_DTYPE, 8, segments, stream_ptr, self.device, _device_tris,
+                            lambda t: self.tri_count(t, stream_ptr=stream_ptr, filter=filter), None,
+                            lambda b, n, off, cap, out, det: _check(lib().pt_tri_list(self._h, b, n, off, cap, f, out, det, C.c_void_p(stream_ptr)),
+                                                                    "pt_tri_list"))
+            if not isinstance(tris, np.ndarray):
+                _device_tris("cut_by_triangles", tris, self.device)
+            return self._filtered("cut_by_triangles", tris, False, filter, run, lambda: self.cut_by_triangles(tris, segments, stream_ptr),
+                                  rows=("tris", 12))
+        return _csr("cut_by_triangles", tris, "tris", 12, BOX_DTYPE, 8, segments, stream_ptr, self.device, _device_tris,
+                    lambda d: self.tri_count(d, stream_ptr=stream_ptr),
+                    lambda b, n, off, cap, out, det: _check(lib().pt_tri_list_host(self._h, b, n, off, cap, out, det), "pt_tri_list_host"),
+                    lambda b, n, off, cap, out, det: _check(lib().pt_tri_list(self._h, b, n, off, cap, None, out, det, C.c_void_p(stream_ptr)),
+                                                            "pt_tri_list"))
+
+    def slice(self, point, normal, half_extent):
+        """The plane section of the scene: the segments along which a square of the given half-extent, centred on `point` in the plane
+        with that normal, cuts the scene's triangles (two query triangles that share the square's diagonal: quad_triangles).  Returns
+        (segments, prim): (m, 2, 3) float32 end points and (m,) int32, the members of the first triangle and then of the second, each
+        with the larger prim first; spheres are left out (their section is a circle, not a segment).  Synchronous, numpy."""
+        quad = slice_triangles(point, normal, half_extent)      # its checks come before any device call
+        _, _, prim, seg = self.cut_by_triangles(quad, segments=True)
+        keep = seg[:, 6] == 1
+        return np.ascontiguousarray(seg[keep, 0:6]).reshape(-1, 2, 3), np.ascontiguousarray(prim[keep])
+
     def render_rays_device(self, d_rays_ptr, n_rays, prm, d_rgb_ptr, d_work_ptr, d_seed_ptr=0, seed_stride=None, stream_ptr=0):
         """Device-resident radiance along n_rays RAY8 records (raw device pointers: rays_floats(n) floats of output, rays_work_bytes(prm,
         n) bytes of scratch, d_seed_ptr 0 = ray i is seeded with i), enqueued on the given stream; blocks until the render has drained.
@@ -1670,6 +1776,43 @@ def sweep_records(org, dir, radius, tmax):
     out = np.zeros(tuple(n or (1,)) + (8,), np.float32)
     out[:, 0:3], out[:, 3], out[:, 4:7], out[:, 7] = o, r, d, t
     return out
+
+
+def tri_records(a, b, c):
+    """TRI12 records for Scene.tri_count, tri_any and cut_by_triangles: (n, 12) float32, a.xyz 0 b.xyz 0 c.xyz 0.  a, b, c: (n, 3) or 3
+    floats each."""
+    v = [np.atleast_2d(np.asarray(x, np.float32)) for x in (a, b, c)]
+    if any(x.ndim != 2 or x.shape[1] != 3 for x in v):
+        raise PtError(f"tri_records: want a, b and c of shape (n, 3) or (3,), got {[x.shape for x in v]}")
+    try:
+        v = np.broadcast_arrays(*v)
+    except ValueError:
+        raise PtError(f"tri_records: the lengths do not agree: {[x.shape for x in v]}") from None
+    out = np.zeros((v[0].shape[0], 12), np.float32)
+    out[:, 0:3], out[:, 4:7], out[:, 8:11] = v
+    return out
+
+
+def quad_triangles(center, u, v):
+    """The parallelogram center +- u +- v as two TRI12 records that share its diagonal: (2, 12) float32, (c - u - v, c + u - v, c + u + v)
+    and (c - u - v, c + u + v, c - u + v), the corners computed in float64 and rounded once, both wound about cross(u, v)."""
+    c, u, v = (np.asarray(x, np.float64).reshape(-1) for x in (center, u, v))
+    if c.shape != (3,) or u.shape != (3,) or v.shape != (3,) or not (np.isfinite(c).all() and np.isfinite(u).all() and np.isfinite(v).all()):
+        raise PtError(f"quad_triangles: want three finite vectors of 3 floats, got {center!r} {u!r} {v!r}")
+    p00, p10, p11, p01 = c - u - v, c + u - v, c + u + v, c - u + v
+    return tri_records([p00, p00], [p10, p11], [p11, p01])
+
+
+def slice_triangles(point, normal, half_extent):
+    """The two TRI12 records Scene.slice cuts the scene with: the square of that half-extent centred on `point` in the plane with that
+    normal, its sides along u = normalize(cross(n, e)), e the axis on which n is smallest, and cross(n, u) (float64, rounded once)."""
+    n = np.asarray(normal, np.float64).reshape(-1)
+    if n.shape != (3,) or not np.isfinite(n).all() or not (n * n).sum() > 0 or not (np.isfinite(half_extent) and half_extent > 0):
+        raise PtError(f"slice: want a finite non-zero normal of 3 floats and a half_extent > 0, got {normal!r} {half_extent!r}")
+    n = n / np.sqrt((n * n).sum())
+    u = np.cross(n, np.eye(3)[int(np.argmin(np.abs(n)))])
+    u /= np.sqrt((u * u).sum())
+    return quad_triangles(point, u * half_extent, np.cross(n, u) * half_extent)
 
 
 def aabb_planes(lo, hi):
